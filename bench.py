@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: batch exact top-k search over the ICD corpus on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload replicated|rowshard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--workload replicated|rowshard]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,19 +18,27 @@ Workload `replicated` (default; BASELINE.json configs[1]), per GPU
     exact fallback for uncertified queries), k = 10. Results are bit-identical to the exact kernel.
 With N > 1 every rank holds a corpus replica and its own query batch (data-parallel, no collective on
 the data path: weak scaling); `value` is the whole-job rate = N * nq * K / max-over-ranks time: the HEADLINE workload
-replicated, labelled so. BASELINE configs[3] proper - 1 M queries over the node, 125 000 per GPU - is measured next to it
-and reported under "config3" (run_config3: the per-GPU share in slices of the index's batch size, every 100th query
-checked against the oracle).
+replicated, labelled so. With --full, BASELINE configs[3] proper - 1 M queries over the node, 125 000 per GPU - is measured
+next to it and reported under "config3" (run_config3: the per-GPU share in slices of the index's batch size, every 100th
+query checked against the oracle).
+
+A plain run (no --full) does what the headline needs and nothing else: it sets up, warms up (--settle-ms of untimed steps
+between W warm-up steps), times exactly K steps, writes the last step's outputs when --dump-outputs DIR is given
+(dump_outputs: DIR/adjusted_scores.npy, raw_scores.npy, ids.npy, levels.npy; the inputs are seeded, so two builds given the
+same arguments can be compared file for file) and prints one JSON line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (the milliseconds of one timed step), the configuration and the step's fallback counters. Everything below -
+the parity check, the kernel times and roofline, the repeated windows, the side workloads, the CPU baseline and the N > 1
+legs - runs with --full only, and --full reports it exactly as before, in the same line.
 
 Workload `rowshard` (BASELINE.json configs[4]; SURVEY.md 8d "Config 5"): every rank generates a shard of
 1 250 000 x 768 rows ON THE DEVICE (seed 1234 + rank; N = 8 -> the 10 M-row corpus), the query batch (100 000 x 768,
 seed 4321, replicated) is searched in slices: local top-k of the shard -> ONE RCCL all_gather of (score f32, id i64,
 level i32) per hit -> merge kernel + level reweight on every rank (rag_project_icd10_amd.sharded.ShardedSearch, ROW).
 One STEP = one pass of the whole query batch; per-GPU work is fixed as N grows (weak scaling: the corpus grows).
-With N > 1 the default run also measures this workload and reports it under "rowshard" in the same JSON line, so the
-driver's scaling run (bench.py --gpus 1/2/4/8) yields both curves.
+With N > 1 a --full run also measures this workload and reports it under "rowshard" in the same JSON line, so a
+scaling run (bench.py --full --gpus 1/2/4/8) yields both curves.
 
-At N = 1 the default line also carries, under "extra" (never the headline): the same step on the real CSV's size
+At N = 1 a --full line also carries, under "extra" (never the headline): the same step on the real CSV's size
 (40 474 rows), on SURVEY 8d's clustered data (512 centroids, x = normalise(c_j + 0.5 eps)), on the headline data at the
 serving path's k = 20 (/query searches top_k * 2, services/multi_diagnosis_service.py:153) and on an ICD-SHAPED corpus
 ("family": 300 families x 124 near-identical rows in code order, mutual cosine 0.99 - the reference's semantic_text repeats
@@ -39,7 +47,7 @@ ms_per_step, fallback_queries, last_second_pass and ids_exact against the oracle
 headline workload against its own 157.3 TFLOP/s peak; "windows" = the K-step window repeated (min / median / max) and
 the first window of the process, before the clock has settled.
 
-The JSON line also carries
+A --full line also carries
     roofline      dominant kernel (coarse_flat_kernel): algorithmic FLOPs 2*nq*n*dim per launch / its mean
                   duration over the timed steps (hipEvents recorded by the library on the search
                   stream), against the dense fp16/bf16 MFMA peak (2.5 PFLOP/s) and against the bare MFMA stream
@@ -303,13 +311,14 @@ class Ctx:
         self.barrier()
         return self.max_over_ranks(time.perf_counter() - t0), out
 
-    def timed(self, fn, steps, warmup, before_timing=None, after_timing=None, settle_s=0.0, repeats=0):
+    def timed(self, fn, steps, warmup, before_timing=None, after_timing=None, settle_s=0.0, repeats=0, first_window=True):
         """W untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; max over ranks:
         THE measurement (first return value). Around it, reported next to it and never instead of it:
         settle_s > 0: a fresh process needs ~20 steps until the chip holds its steady clock (scripts/probe/clock_settle.py:
           0.90, 0.77, then 0.745 ms per step in chunks of ten), so before the W warm-up steps of the measurement the device
-          is kept busy with the same step for that long (untimed setup, like building the index) - and the window a plain
-          "W warm-up steps, K timed steps" gives in a fresh process is measured FIRST and returned as info["first_window_s"];
+          is kept busy with the same step for that long (untimed setup, like building the index) - and, with first_window, the
+          window a plain "W warm-up steps, K timed steps" gives in a fresh process is measured FIRST and returned as
+          info["first_window_s"];
         repeats: the K-step window is repeated that many times after the measurement (info["repeat_s"])."""
         out = None
         info = {"first_window_s": None, "repeat_s": []}
@@ -317,7 +326,8 @@ class Ctx:
             for _ in range(warmup):
                 fn()
             self.sync()
-            info["first_window_s"], _ = self.window(fn, steps)
+            if first_window:
+                info["first_window_s"], _ = self.window(fn, steps)
             t_end = time.perf_counter() + settle_s
             while time.perf_counter() < t_end:
                 for _ in range(4):
@@ -359,6 +369,29 @@ def oracle_check(corpus, levels, queries, k, out, world=1):
             "adjusted_scores_exact": bool(adj.tobytes() == want[0].tobytes()),
             "max_abs_dscore": float(np.max(np.abs(raw.astype(np.float64) - want[1].astype(np.float64)))),
             "parity_checked_queries": int(len(queries)), "parity_check_s": round(time.perf_counter() - t0, 2)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+OUTPUT_NAMES = ("adjusted_scores", "raw_scores", "ids", "levels")
+
+
+def dump_outputs(path, out):
+    """--dump-outputs DIR: what the timed path returned in its last step - search_reweighted's (adjusted scores, raw scores,
+    ids, levels), one row per query - as DIR/<name>.npy: float32 and float64 arrays as they are, integer arrays in float64
+    (exact). Above DUMP_LIMIT_BYTES in all, a fixed sample of the query rows (default_rng(0), ascending) is written, and
+    DIR/rows.npy names those rows. The inputs are seeded, so two builds given the same arguments can be compared file for file."""
+    arrs = [x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in out]
+    arrs = [a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for a in arrs]
+    nrows = len(arrs[0])
+    row_bytes = sum(a.nbytes for a in arrs) // max(1, nrows)
+    os.makedirs(path, exist_ok=True)
+    if row_bytes * nrows > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(nrows, keep, replace=False))
+        arrs = [a[rows] for a in arrs]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for name, a in zip(OUTPUT_NAMES, arrs):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def side_workload(*a, **kw):
@@ -828,13 +861,37 @@ def run_replicated(ctx, args, index_factory=hip_index_factory):
         prof.update(index.profile_summary())
         index.set_profiling(False)
 
-    elapsed, out, info = ctx.timed(lambda: index.search_reweighted(dq, k, mode), args.steps, args.warmup, before, after,
-                                   settle_s=args.settle_ms / 1e3, repeats=args.repeats)
+    # a plain run is the measurement alone: no hipEvents in the timed region, no first or repeated windows (--full adds them)
+    full = args.full
+    elapsed, out, info = ctx.timed(lambda: index.search_reweighted(dq, k, mode), args.steps, args.warmup,
+                                   before if full else None, after if full else None,
+                                   settle_s=args.settle_ms / 1e3, repeats=args.repeats if full else 0, first_window=full)
     stats = index.stats()
+    if ctx.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     line = None
     if ctx.rank == 0:
-        parity = oracle_check(corpus, levels, queries, k, out, ctx.world)
         fast = mode == MODE_AUTO and stats["last_mode"] == MODE_AUTO
+        line = {
+            "metric": "queries_per_sec", "value": ctx.world * nq * args.steps / elapsed, "unit": "queries/s",
+            "n_gpus": ctx.world, "steps": args.steps, "warmup": args.warmup, "settle_ms_before_warmup": args.settle_ms,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f16" if fast else "f32",
+            "data": "synthetic",
+            "full": full,
+            "config": {"workload": (f"BASELINE configs[1]: {nq} random fp32 768-d queries x {n}x768 corpus, " if ctx.world == 1 else
+                                    f"BASELINE configs[1] replicated on every GPU (the headline workload, {nq} random fp32 768-d queries per GPU x {n}x768 corpus; "
+                                    f"configs[3] at its stated size is the `config3` object of a --full run), ")
+                                   + f"top_k={k}, search only (pre-embedded, HBM-resident inputs), level reweight fused",
+                       "nq_per_gpu": nq, "corpus_rows": n, "dim": dim, "top_k": k, "mode": args.mode,
+                       "parallelism": f"query-sharded x{ctx.world}, corpus replicated" if ctx.world > 1 else "single GPU",
+                       "collective_ranks": ctx.dist.get_world_size() if ctx.world > 1 else 1,
+                       "result_arithmetic": "fp32 canonical chain (bit-identical to the CPU oracle)"},
+            "fallback_queries": int(stats["last_fallback"]), "coarse_chunks": int(stats["last_chunks"]),
+        }
+    if ctx.rank == 0 and full:
+        line.update(oracle_check(corpus, levels, queries, k, out, ctx.world))
         dom_ms = prof["ms_coarse"] if fast else prof["ms_exact"]
         flops = 2.0 * nq * n * dim
         achieved = flops / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
@@ -843,23 +900,7 @@ def run_replicated(ctx, args, index_factory=hip_index_factory):
         traffic, traffic_src = pmc_traffic(kern, nq, n)
         ref_tf, ref_src = reference_gemm() if fast else (None, None)
         per_step = sorted(x / args.steps * 1e3 for x in [elapsed] + info["repeat_s"])
-        line = {
-            "metric": "queries_per_sec", "value": ctx.world * nq * args.steps / elapsed, "unit": "queries/s",
-            "n_gpus": ctx.world, "steps": args.steps, "warmup": args.warmup, "settle_ms_before_warmup": args.settle_ms,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f16" if fast else "f32",
-            "data": "synthetic",
-            "config": {"workload": (f"BASELINE configs[1]: {nq} random fp32 768-d queries x {n}x768 corpus, " if ctx.world == 1 else
-                                    f"BASELINE configs[1] replicated on every GPU (the headline workload, {nq} random fp32 768-d queries per GPU x {n}x768 corpus; "
-                                    f"configs[3] at its stated size is the `config3` object), ")
-                                   + f"top_k={k}, search only (pre-embedded, HBM-resident inputs), level reweight fused",
-                       "nq_per_gpu": nq, "corpus_rows": n, "dim": dim, "top_k": k, "mode": args.mode,
-                       "parallelism": f"query-sharded x{ctx.world}, corpus replicated" if ctx.world > 1 else "single GPU",
-                       "collective_ranks": ctx.dist.get_world_size() if ctx.world > 1 else 1,
-                       "result_arithmetic": "fp32 canonical chain (bit-identical to the CPU oracle)"},
-            **parity,
-            "fallback_queries": int(stats["last_fallback"]), "coarse_chunks": int(stats["last_chunks"]),
+        line.update({
             "kernel_ms": {kname: round(v, 5) for kname, v in prof.items() if kname != "count"},
             "roofline": {"bound": "mfma", "kernel": kern,
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
@@ -879,9 +920,11 @@ def run_replicated(ctx, args, index_factory=hip_index_factory):
             "extra": {"windows": {"what": f"the {args.steps}-step window repeated {1 + len(info['repeat_s'])} times back to back (the first is `value`), ms per step",
                                   "min": per_step[0], "median": per_step[len(per_step) // 2], "max": per_step[-1],
                                   "first_window_of_the_process": (info["first_window_s"] / args.steps * 1e3) if info["first_window_s"] else None}},
-        }
+        })
     index.close()
     del index, dq
+    if not full:
+        return line
     if ctx.world == 1 and not args.no_extras:
         # (every rank would run these; they are N = 1 lines: other data and sizes next to the Gaussian headline)
         steps_x = max(5, min(args.steps, 20))
@@ -1071,8 +1114,9 @@ def exact_merge_torch(torch, scores, ids, k):
     return torch.gather(s, 1, o2)[:, :k].to(torch.float32), torch.gather(i, 1, o2)[:, :k]
 
 
-def run_rowshard(ctx, args, index_factory=hip_index_factory, sharded_factory=None, native_trial=None):
-    """BASELINE configs[4]: the corpus row-sharded over the ranks (1.25 M rows per GPU), the query batch replicated"""
+def run_rowshard(ctx, args, index_factory=hip_index_factory, sharded_factory=None, native_trial=None, dump_dir=None):
+    """BASELINE configs[4]: the corpus row-sharded over the ranks (1.25 M rows per GPU), the query batch replicated.
+    dump_dir: --dump-outputs of `--workload rowshard` (the last pass's slices, concatenated)"""
     from rag_project_icd10_amd.sharded import ROW_SHARD, ShardedSearch
     torch, dist = ctx.torch, ctx.dist
     n, dim, k = args.rows_per_gpu, 768, args.k
@@ -1102,6 +1146,8 @@ def run_rowshard(ctx, args, index_factory=hip_index_factory, sharded_factory=Non
             index.profile_summary()
 
     elapsed, outs, _ = ctx.timed(one_pass, steps, warmup, before)
+    if dump_dir and ctx.rank == 0:
+        dump_outputs(dump_dir, [torch.cat([o[c] for o in outs]) for c in range(4)])
     prof = index.profile_summary() if hasattr(index, "profile_summary") else {"ms_coarse": 0.0, "count": 0}
     if hasattr(index, "set_profiling"):
         index.set_profiling(False)
@@ -1350,8 +1396,13 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps of the measurement")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity against the CPU oracle, kernel times and roofline, repeated windows, the side "
+                         "workloads and the CPU baseline (N = 1), the configs[3] and row-sharded legs (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (rank 0's batch; dump_outputs)")
     ap.add_argument("--settle-ms", type=float, default=60.0,
                     help="untimed: keep the device busy with the step for this long before the warm-up steps (clock ramp of a fresh process)")
     ap.add_argument("--profile-every", type=int, default=5, help="hipEvents around the kernels of every N-th step of the timed region")
@@ -1398,14 +1449,14 @@ def main(argv=None):
     if "native_trial" in eng:
         eng = {k: v for k, v in eng.items() if k != "native_trial"}
     if args.workload == "rowshard":
-        line = run_rowshard(ctx, args, **rs_eng)
+        line = run_rowshard(ctx, args, dump_dir=args.dump_outputs, **rs_eng)
     else:
         line = run_replicated(ctx, args, **({"index_factory": eng["index_factory"]} if eng else {}))
-        if ctx.world > 1 and not args.no_config3:
+        if ctx.world > 1 and args.full and not args.no_config3:
             c3 = run_config3(ctx, args, **({"index_factory": eng["index_factory"]} if eng else {}))
             if line is not None:
                 line["config3"] = c3
-        if ctx.world > 1 and not args.no_rowshard:
+        if ctx.world > 1 and args.full and not args.no_rowshard:
             rs = run_rowshard(ctx, args, **rs_eng)
             if line is not None:
                 line["rowshard"] = rs

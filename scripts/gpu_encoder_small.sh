@@ -1,12 +1,12 @@
 #!/bin/bash
-# The small-input encoder's evidence -> gpurun_out/${TAG}_encoder_small.log and ${TAG}_query_latency.log:
+# The small-input encoder's evidence -> out/${TAG}_encoder_small.log and ${TAG}_query_latency.log:
 # latencies against the replayed framework graph, clock stamps inside the GEMM kernels (diagnostic build csrc/abe:
 # make -C rag_project_icd10_amd/csrc ABLATE=1 OUT=abe EXTRA='-DICD_FV_LIST="ICD_FV_CASE(6326427)"'), rocprofv3 kernel
 # durations of 200 forwards at 15 and 98 tokens, one /query-shaped request at a time.   usage: scripts/gpu_encoder_small.sh r05
 TAG=${1:-r05}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-O=$R/gpurun_out/${TAG}_encoder_small.log
-mkdir -p $R/gpurun_out
+O=$R/out/${TAG}_encoder_small.log
+mkdir -p $R/out
 {
 echo "# scripts/gpu_encoder_small.sh $TAG: one MI355X, synthetic BERT-base weights (the shapes of shibing624/text2vec-base-chinese)"
 echo "# (1) scripts/probe/encoder_small_probe.py: small = csrc/encoder_small.hpp through icd_encoder_encode; graph = the framework's forward replayed from a HIP graph (rounds 1-4)"
@@ -26,5 +26,5 @@ for r in csv.DictReader(open(sys.argv[1])):
   cd $R
 done
 } > $O 2>&1
-(echo "# scripts/probe/query_latency.py: ONE /query-shaped request at a time (MultiDiagnosisService.match_multiple_diagnoses, top_k = 5), 40 474-row corpus, synthetic encoder / NER weights"; timeout -k 10 300 python3 $R/scripts/probe/query_latency.py 2>&1 | grep -v "not resolvable\|amdgpu.ids") > $R/gpurun_out/${TAG}_query_latency.log
-tail -5 $O; cat $R/gpurun_out/${TAG}_query_latency.log
+(echo "# scripts/probe/query_latency.py: ONE /query-shaped request at a time (MultiDiagnosisService.match_multiple_diagnoses, top_k = 5), 40 474-row corpus, synthetic encoder / NER weights"; timeout -k 10 300 python3 $R/scripts/probe/query_latency.py 2>&1 | grep -v "not resolvable\|amdgpu.ids") > $R/out/${TAG}_query_latency.log
+tail -5 $O; cat $R/out/${TAG}_query_latency.log

@@ -6,11 +6,11 @@
 TAG=${1:-r05}
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
-(timeout 900 python3 scripts/probe/gemm_reference.py 2>&1 | grep -v amdgpu.ids) > gpurun_out/${TAG}_gemm_reference.log
+mkdir -p $R/out
+(timeout 900 python3 scripts/probe/gemm_reference.py 2>&1 | grep -v amdgpu.ids) > out/${TAG}_gemm_reference.log
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_gemmref -- python3 $R/scripts/probe/gemm_reference.py --trace-only > $R/gpurun_out/rocprof_gemmref_$TAG.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/out/prof_${TAG}_gemmref -- python3 $R/scripts/probe/gemm_reference.py --trace-only > $R/out/rocprof_gemmref_$TAG.log 2>&1
 cd $R
-echo "## rocprofv3 --kernel-trace --stats of the three vendor GEMMs (12 launches each; name, calls, average ns)" >> gpurun_out/${TAG}_gemm_reference.log
-for f in $(find gpurun_out/prof_${TAG}_gemmref -name "*kernel_stats.csv"); do head -8 $f | cut -c1-400 >> gpurun_out/${TAG}_gemm_reference.log; done
-cat gpurun_out/${TAG}_gemm_reference.log
+echo "## rocprofv3 --kernel-trace --stats of the three vendor GEMMs (12 launches each; name, calls, average ns)" >> out/${TAG}_gemm_reference.log
+for f in $(find out/prof_${TAG}_gemmref -name "*kernel_stats.csv"); do head -8 $f | cut -c1-400 >> out/${TAG}_gemm_reference.log; done
+cat out/${TAG}_gemm_reference.log

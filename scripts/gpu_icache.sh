@@ -4,7 +4,7 @@ rocprofv3 -L 2>/dev/null | grep -i -E "icache|ifetch|inst_cache|SQC_" | head -40
 cat $R/gpurun_out/icache_counters.txt | cut -c1-200
 for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_INSTS_BRANCH SQ_WAVE_CYCLES"; do
   d=$R/gpurun_out/pmc_icache_$(echo $set | cut -d' ' -f1)
-  timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $d -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $d.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $d -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $d.log 2>&1
   tail -2 $d.log | cut -c1-200
 done
 cd $R

@@ -1,7 +1,7 @@
-# copy what scripts/gpu_final.sh TAG a|b left under gpurun_out/ (scratch) into profiles/ (tracked) under the names profiles/README.md lists
+# copy what scripts/gpu_final.sh TAG a|b left under out/ (scratch) into profiles/ (tracked) under the names profiles/README.md lists
 # usage: bash scripts/install_evidence.sh r06
 TAG=${1:-r06}
-G=gpurun_out; P=profiles
+G=out; P=profiles
 cpif() { [ -s "$1" ] && cp "$1" "$2"; }
 cpif $G/bench.log $P/${TAG}_bench_n1.json
 cpif $G/bench_rowshard.log $P/${TAG}_bench_rowshard_n1.json

@@ -223,9 +223,9 @@ def main():
             tf = flop / (ms * 1e-3) / 1e12
             print(f'{name}: {ms:.4f} ms = {tf:.0f} TFLOP/s = {tf / PEAK:.3f}; x {tf / ref["tflops"]:.3f} of the vendor GEMM at the coarse shape, '
                   f'x {tf / light["tflops"]:.3f} of the output-light one')
-    json.dump(res, open(os.path.join(ROOT, 'gpurun_out/gemm_reference.json'), 'w'), indent=1, default=str)
+    json.dump(res, open(os.path.join(ROOT, 'out/gemm_reference.json'), 'w'), indent=1, default=str)
 
 
 if __name__ == '__main__':
-    os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
+    os.makedirs(os.path.join(ROOT, 'out'), exist_ok=True)
     main()

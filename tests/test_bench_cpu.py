@@ -33,7 +33,7 @@ def _worker_body(rank, world, port, q):
     assert ctx.world == world and ctx.dist.get_world_size() == world
     args = argparse.Namespace(steps=2, warmup=1, settle_ms=0.0, repeats=1, profile_every=1, nq=40, n=900, k=5, mode="auto", rows_per_gpu=700, rowshard_queries=50,
                               rowshard_slice=32, rowshard_steps=2, no_cpu_baseline=True, no_extras=True, no_family=True,
-                              config3_queries=70, config3_steps=1)
+                              config3_queries=70, config3_steps=1, full=True, dump_outputs=None)
     rs = bench.run_rowshard(ctx, args, index_factory=eng.index_factory, sharded_factory=eng.sharded_factory)
     rp = bench.run_replicated(ctx, args, index_factory=eng.index_factory)
     c3 = bench.run_config3(ctx, args, index_factory=eng.index_factory)
@@ -99,7 +99,7 @@ def _run_bench(extra_args, extra_env=None, timeout=420):
 
 
 def test_bench_gpus_2_starts_two_ranks_itself():
-    p = _run_bench(["--gpus", "2"])
+    p = _run_bench(["--gpus", "2", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout     # ONE JSON line on stdout
@@ -127,7 +127,7 @@ def test_bench_under_torch_distributed_run_exactly_as_the_driver_launches_n_gt_1
                 "ICD_BENCH_TEST_ENGINE": os.path.join(ROOT, "tests", "bench_cpu_engine.py")})
     port = 29890 + (os.getpid() % 40)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2"] + ["--corpus-rows" if a == "--n" else a for a in SMALL]   # (the launcher's parser rejects `--n` as an ambiguous prefix of its own options)
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + ["--corpus-rows" if a == "--n" else a for a in SMALL]   # (the launcher's parser rejects `--n` as an ambiguous prefix of its own options)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
@@ -140,7 +140,7 @@ def test_bench_under_torch_distributed_run_exactly_as_the_driver_launches_n_gt_1
 
 
 def test_bench_gpus_1_is_a_single_process_line_with_the_extras():
-    p = _run_bench(["--gpus", "1"])
+    p = _run_bench(["--gpus", "1", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     assert line["n_gpus"] == 1 and line["config"]["collective_ranks"] == 1 and "rowshard" not in line
@@ -175,7 +175,7 @@ def test_bench_gpus_8_dry_run_on_cpu():
     with value / config3 / rowshard whose collectives span 8 ranks, parent and ranks gone inside the limit"""
     import time
     t0 = time.time()
-    p = _run_bench(["--gpus", "8", "--rank-timeout", "400"], timeout=500)
+    p = _run_bench(["--gpus", "8", "--full", "--rank-timeout", "400"], timeout=500)
     took = time.time() - t0
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -197,7 +197,7 @@ def test_bench_rank_with_a_hung_native_trial_does_not_strand_the_others():
     --rank-timeout"""
     import time
     t0 = time.time()
-    p = _run_bench(["--gpus", "2", "--no-config3", "--rank-timeout", "120"], {"ICD_BENCH_TEST_TRIAL_HUNG_RANK": "1"}, timeout=300)
+    p = _run_bench(["--gpus", "2", "--full", "--no-config3", "--rank-timeout", "120"], {"ICD_BENCH_TEST_TRIAL_HUNG_RANK": "1"}, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert time.time() - t0 < 100
     line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
@@ -263,16 +263,84 @@ def test_bench_adopts_the_c_abi_group_only_when_every_ranks_trial_passed():
     """round 6: the row-sharded leg reports the C-ABI group's number (config.engine says so, the torch engine's stays next to it)
     when the trial passed on EVERY rank - agreed over the CPU side channel; one rank whose output differed keeps all of them on
     the torch.distributed number. The trial itself is the test engine's stand-in (tests/bench_cpu_engine.py native_trial)."""
-    p = _run_bench(["--gpus", "2", "--no-config3", "--rank-timeout", "200"], {"ICD_BENCH_TEST_NATIVE_TRIAL": "ok"}, timeout=400)
+    p = _run_bench(["--gpus", "2", "--full", "--no-config3", "--rank-timeout", "200"], {"ICD_BENCH_TEST_NATIVE_TRIAL": "ok"}, timeout=400)
     assert p.returncode == 0, p.stderr[-2000:]
     rs = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])["rowshard"]
     assert rs["config"]["engine"] == "icd_group (C ABI)" and "icd_group_search" in rs["config"]["collective"]
     assert rs["native_group_trial"]["status"] == "ok" and rs["native_group_trial"]["adopted_as_the_legs_engine"] is True
     assert rs["value"] == rs["native_group_trial"]["value"] and rs["ms_per_step"] == 2.0
     assert rs["torch_distributed_engine"]["value"] > 0 and rs["ids_exact_on_sample"]
-    p = _run_bench(["--gpus", "2", "--no-config3", "--rank-timeout", "200"], {"ICD_BENCH_TEST_NATIVE_TRIAL": "rank1_differs"}, timeout=400)
+    p = _run_bench(["--gpus", "2", "--full", "--no-config3", "--rank-timeout", "200"], {"ICD_BENCH_TEST_NATIVE_TRIAL": "rank1_differs"}, timeout=400)
     assert p.returncode == 0, p.stderr[-2000:]
     rs = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])["rowshard"]
     assert rs["config"]["engine"] == "torch.distributed" and rs["torch_distributed_engine"] is None
     assert rs["native_group_trial"]["status"] == "ok" and rs["native_group_trial"]["adopted_as_the_legs_engine"] is False   # (rank 0's own trial passed; rank 1's did not)
     assert rs["value"] != rs["native_group_trial"]["value"] and rs["ids_exact_on_sample"]
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """a plain `bench.py --gpus 1 --steps K --warmup W`: the headline fields, K timed steps, none of what --full adds; with
+    --dump-outputs the last step's outputs, the same bytes from run to run and what the CPU oracle computes"""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        p = _run_bench(["--gpus", "1", "--dump-outputs", str(d)])   # (SMALL: --steps 2 --warmup 1)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout
+        line = json.loads(lines[0])
+        assert line["metric"] == "queries_per_sec" and line["unit"] == "queries/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f16" and line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+        assert abs(line["value"] - 40 * 2 / (line["ms_per_step"] * 2 / 1e3)) / line["value"] < 1e-6
+        for key in ("extra", "roofline", "kernel_ms", "ids_exact", "cpu_baseline", "config3", "rowshard"):
+            assert key not in line, key
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("adjusted_scores", "raw_scores", "ids", "levels")})
+    a, b = dumps
+    assert a["adjusted_scores"].dtype == np.float64 and a["raw_scores"].dtype == np.float32   # (as the path returns them)
+    assert a["ids"].dtype == np.float64 and a["levels"].dtype == np.float64
+    for n in a:
+        assert a[n].shape == (40, 5) and a[n].tobytes() == b[n].tobytes(), n
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import bench
+    import oracle as orc
+    corpus, levels, queries = bench.unit_rows(900, 768, 1234), bench.icd_levels(900, 1235), bench.unit_rows(40, 768, 4321)
+    os_, oi = orc.flat_ip_topk(corpus, queries, 5)
+    want = orc.reweight(os_, oi, levels)
+    assert np.array_equal(a["ids"], want[2].astype(np.float64)) and a["adjusted_scores"].tobytes() == want[0].tobytes()
+
+
+def test_bench_steps_sets_the_timed_steps(monkeypatch):
+    """--steps K runs exactly K steps between the clocks (and W before them), whatever the mode"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setenv("ICD_BENCH_DEVICE", "cpu")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    ctx = bench.Ctx()
+    real_window = ctx.window
+    timed = []
+
+    def window(fn, steps):
+        timed.append(steps)
+        return real_window(fn, steps)
+    monkeypatch.setattr(ctx, "window", window)
+    for full in (False, True):
+        timed.clear()
+        ctx.timed(lambda: None, 7, 2, settle_s=0.001, repeats=2 if full else 0, first_window=full)
+        assert timed == [7] * (4 if full else 1)   # (--full: the first window, the measurement, two repeats)
+
+
+def test_dump_outputs_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    rng = np.random.default_rng(3)
+    out = (rng.random((300, 4), dtype=np.float32), rng.random((300, 4), dtype=np.float32),
+           rng.integers(0, 10 ** 6, (300, 4)), rng.integers(1, 4, (300, 4)).astype(np.int32))
+    bench.dump_outputs(str(tmp_path), out)
+    rows = np.load(tmp_path / "rows.npy")
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in bench.OUTPUT_NAMES}
+    assert sum(v.nbytes for v in got.values()) <= 4000 and len(rows) == len(got["ids"]) > 0
+    assert np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["ids"], out[2][rows.astype(np.int64)].astype(np.float64))
+    assert got["raw_scores"].tobytes() == out[1][rows.astype(np.int64)].tobytes()

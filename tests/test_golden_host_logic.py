@@ -16,7 +16,8 @@ from rag_project_icd10_amd.services.uncertainty_diagnosis_service import Uncerta
 from rag_project_icd10_amd.tools.build_database import DatabaseBuilder
 from rag_project_icd10_amd.tools.text_processor import DiagnosisTextProcessor
 
-REF_CSV = "/root/reference/data/ICD_10v601.csv"
+# the reference's full data file (data/ICD_10v601.csv, byte for byte), stored compressed; csv_full_digest.json pins its content
+FULL_CSV_XZ = os.path.join(GOLDEN, "ICD_10v601.csv.xz")
 
 
 def _load(name):
@@ -37,11 +38,14 @@ def test_csv_slice_records_match_reference():
     assert any(r["code"].startswith("M8") and r["level"] == 1 for r in recs)   # morphology codes: no dot -> level 1
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CSV), reason="full reference CSV only exists in the build container")
-def test_full_csv_digest_matches_reference():
+def test_full_csv_digest_matches_reference(tmp_path):
+    import lzma
     d = _load("csv_full_digest.json")
+    csv_path = tmp_path / "ICD_10v601.csv"
+    with lzma.open(FULL_CSV_XZ) as src:
+        csv_path.write_bytes(src.read())
     b = DatabaseBuilder()
-    full = b.load_csv_data(REF_CSV)
+    full = b.load_csv_data(str(csv_path))
     assert len(full) == d["count"] == 40474
     hist = {}
     for r in full:
