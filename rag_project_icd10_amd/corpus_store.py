@@ -46,6 +46,7 @@ class CorpusStore:
         self._vectors: List[np.ndarray] = []   # chunks not yet concatenated
         self._matrix: Optional[np.ndarray] = None
         self._meta_bytes = 0   # committed length of meta.jsonl
+        self._code_title = None   # code_title_columns(): dropped by every change of `records`
         self.closed = False
 
     # ---- paths ------------------------------------------------------------------------------------
@@ -95,6 +96,7 @@ class CorpusStore:
         self.count = 0
         self._meta_bytes = 0
         self.records = []
+        self._code_title = None
         self._vectors = []
         self._matrix = np.zeros((0, self.dim), dtype=np.float32)
         for name in ("corpus.f32", "levels.i32", "meta.jsonl"):
@@ -107,6 +109,7 @@ class CorpusStore:
         self.count = 0
         self._meta_bytes = 0
         self.records = []
+        self._code_title = None
         self._vectors = []
         self._matrix = None
 
@@ -167,6 +170,7 @@ class CorpusStore:
         self._matrix = mat.reshape(self.count, self.dim)
         self._vectors = []
         self.records = []
+        self._code_title = None
         with open(self._file("meta.jsonl"), encoding="utf-8") as f:
             for i, line in enumerate(f):
                 if i >= self.count:
@@ -203,6 +207,7 @@ class CorpusStore:
             self._fsync_dir()
             self._meta_bytes += len(meta)
             self.records.extend(rows)
+            self._code_title = None
             self._vectors.append(vectors)
             self.count += len(rows)
             self._write_manifest()
@@ -217,14 +222,13 @@ class CorpusStore:
         return self._matrix
 
     def code_title_columns(self):
-        """(codes, titles): the two payload fields a Candidate is made of, as plain lists by row - rebuilt when rows were added
-        (the batched request path builds 10 000 Candidates per 1 000 strings: list indexing, not two dict lookups per object)"""
-        cached = getattr(self, "_code_title", None)
-        if cached is None or cached[0] != len(self.records):
-            codes = [r.get("code", "") for r in self.records]
-            titles = [r.get("preferred_zh", "") for r in self.records]
-            self._code_title = cached = (len(self.records), codes, titles)
-        return cached[1], cached[2]
+        """(codes, titles): the two payload fields a Candidate is made of, as plain lists by row - rebuilt after any change
+        of the rows: append, create, drop or load (the batched request path builds 10 000 Candidates per 1 000 strings: list
+        indexing, not two dict lookups per object). Not keyed by the row count: a store dropped and refilled with as many
+        rows holds other codes."""
+        if self._code_title is None:
+            self._code_title = ([r.get("code", "") for r in self.records], [r.get("preferred_zh", "") for r in self.records])
+        return self._code_title
 
     def levels(self) -> np.ndarray:
         """levels of the rows, from the metadata (levels.i32 is the same column as a flat file for external readers;

@@ -301,6 +301,32 @@ def test_corpus_store_stale_handle_never_truncates_committed_rows(tmp_path):
     assert os.path.exists(os.path.join(str(tmp_path), "icd10", ".lock"))
 
 
+def test_code_title_columns_follow_a_rebuild_with_the_same_row_count(tmp_path):
+    """the (codes, titles) columns the batched request path builds Candidates from: after a drop and a rebuild with as many
+    rows, and after a load of another store of the same size, they are the new rows' (the cache was once keyed by the row
+    count alone, and /query returned the dropped rows' codes and titles)"""
+    def rows(p):
+        return [{"code": f"{p}{i:02d}", "preferred_zh": f"{p}病{i}", "level": 1} for i in range(3)]
+
+    vec = np.zeros((3, 4), np.float32)
+    st = CorpusStore.open(str(tmp_path), "icd10", 4)
+    st.create()
+    st.append(rows("A"), vec)
+    assert st.code_title_columns() == (["A00", "A01", "A02"], ["A病0", "A病1", "A病2"])
+    st.drop()
+    st.create()
+    st.append(rows("B"), vec)
+    assert st.code_title_columns() == (["B00", "B01", "B02"], ["B病0", "B病1", "B病2"])
+    other = CorpusStore.open(str(tmp_path), "icd10_c", 4)
+    other.append(rows("C"), vec)
+    st.collection = "icd10_c"                                   # the same handle loads another store of 3 rows
+    with st._locked():
+        st._load()
+    assert st.code_title_columns() == (["C00", "C01", "C02"], ["C病0", "C病1", "C病2"])
+    st.append(rows("D")[:1], vec[:1])
+    assert st.code_title_columns()[0] == ["C00", "C01", "C02", "D00"]
+
+
 
 
 def test_trusted_candidate_equals_the_validated_constructor():
