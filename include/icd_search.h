@@ -233,6 +233,20 @@ int icd_hier_rescore(int32_t device, const double *adj, const int64_t *ids, int6
                      int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
                      double *out_boost, void *stream);
 
+/* icd_hier_rescore for queries that carry NER entities (the same arguments, checks and outputs). On live-shaped hits every
+ * factor the entities feed depends on the query and the first letter of the hit's code only, so it arrives per query:
+ *   q_params        [nq][22]: [0..11] as icd_hier_rescore's, the nine chapter boosts with the disease-entity term
+ *                   (_calculate_category_semantic_boost, services/hierarchical_similarity_service.py:293-328), [12] the
+ *                   entity match score against a live hit's empty title (:341-385), [13..21] the category alignment of each
+ *                   chapter of the table (:411-446; 0 for letters outside it)
+ * With every entity list empty (entries 12..21 zero) the outputs are byte-identical to icd_hier_rescore's. Bit-identical to
+ * batch_calculate_similarities(query, entities, hits) (tests/test_entity_rescoring_gpu.py).
+ */
+int icd_hier_rescore_entities(int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
+                              int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
+                              int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
+                              double *out_boost, void *stream);
+
 /* SURVEY.md row N3, score statistics. Replaces np.mean / np.std / np.var / max over the candidates' scores in
  * MultiDimensionalConfidenceService._assess_model_uncertainty (services/multidimensional_confidence_service.py:936-963)
  * and ._calculate_prediction_variance (:1087-1099), for nq queries at once, bit-identical to numpy's float64 results.

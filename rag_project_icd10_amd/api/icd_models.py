@@ -127,15 +127,20 @@ except ImportError:   # pragma: no cover - a tree without the built module
     _fastobj = None
 
 
-def bulk_candidates(codes, titles, factors_cls, ids, scores, originals, vs, hb, sc: float, cr: float) -> List["Candidate"]:
+def bulk_candidates(codes, titles, factors_cls, ids, scores, originals, vs, hb, sc: float, cr: float, em: float = 0.0,
+                    ca=None) -> List["Candidate"]:
     """The Candidate objects of ONE query's winners with their SimilarityFactors, in one loop without a call per object (row N2:
     the batched request path makes 10 000 of each per 1 000 strings - this loop is most of what that path costs the host).
     codes / titles: the corpus' columns by row; ids / scores / originals / vs / hb: the winners' parallel sequences (live hits:
-    level 1, parent "", no entity match, no category alignment - SURVEY F8). The caller has checked trusted_matches_ready().
+    level 1, parent "", no entity match, no category alignment - SURVEY F8). Queries with NER entities pass em (the query's entity
+    match score) and ca (the winners' category alignments, parallel to ids). The caller has checked trusted_matches_ready().
     A negative or NaN score raises the validated constructor's ValidationError (reference models/icd_models.py:71)."""
     if _fastobj is not None:
         try:
-            return _fastobj.bulk_candidates(Candidate, factors_cls, _SHARED_CAND_FIELDS, codes, titles, ids, scores, originals, vs, hb, sc, cr)
+            if ca is None:
+                return _fastobj.bulk_candidates(Candidate, factors_cls, _SHARED_CAND_FIELDS, codes, titles, ids, scores, originals, vs, hb, sc, cr)
+            return _fastobj.bulk_candidates(Candidate, factors_cls, _SHARED_CAND_FIELDS, codes, titles, ids, scores, originals, vs, hb, sc, cr,
+                                            em, ca)
         except ValueError:   # (a negative / NaN score: the loop below lets the validated constructor raise what the reference raises)
             pass
         except TypeError:    # (sequences that are not lists: the Python loop takes anything indexable)
@@ -147,8 +152,8 @@ def bulk_candidates(codes, titles, factors_cls, ids, scores, originals, vs, hb, 
         if not s >= 0.0:
             Candidate(code="", title="", score=s)   # raises
         f = onew(factors_cls)
-        f.__dict__ = {"vector_similarity": vs[j], "hierarchy_boost": hb[j], "entity_match_score": 0.0, "semantic_coherence": sc,
-                      "category_alignment": 0.0, "context_relevance": cr}
+        f.__dict__ = {"vector_similarity": vs[j], "hierarchy_boost": hb[j], "entity_match_score": em, "semantic_coherence": sc,
+                      "category_alignment": 0.0 if ca is None else ca[j], "context_relevance": cr}
         i = ids[j]
         c = new(Candidate)
         setattr_(c, "__dict__", {"code": codes[i], "title": titles[i], "score": s, "level": 1, "parent_code": "",

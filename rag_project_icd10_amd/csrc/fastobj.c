@@ -26,17 +26,21 @@ static PyObject *instance_with_dict(PyTypeObject *tp, PyObject *d) {
     return o;
 }
 
-/* bulk_candidates(candidate_type, factors_type, fields_set, codes, titles, ids, scores, originals, vs, hb, sc, cr) -> list
- * ids / scores / originals / vs / hb: lists (the first len(ids) entries of the others are used). Raises ValueError on a score
- * that is negative or NaN (the caller lets the validated constructor raise the reference's ValidationError). */
+/* bulk_candidates(candidate_type, factors_type, fields_set, codes, titles, ids, scores, originals, vs, hb, sc, cr[, em, ca]) -> list
+ * ids / scores / originals / vs / hb: lists (the first len(ids) entries of the others are used). em / ca (queries with NER
+ * entities): the query's entity match score and a list of the winners' category alignments; without them both factors are 0.0.
+ * Raises ValueError on a score that is negative or NaN (the caller lets the validated constructor raise the reference's
+ * ValidationError). */
 static PyObject *bulk_candidates(PyObject *self, PyObject *args) {
-    PyObject *ctype, *ftype, *fields, *codes, *titles, *ids, *scores, *origs, *vs, *hb, *sc, *cr;
-    if (!PyArg_ParseTuple(args, "OOOO!O!O!O!O!O!O!OO", &ctype, &ftype, &fields, &PyList_Type, &codes, &PyList_Type, &titles, &PyList_Type, &ids,
-                          &PyList_Type, &scores, &PyList_Type, &origs, &PyList_Type, &vs, &PyList_Type, &hb, &sc, &cr))
+    PyObject *ctype, *ftype, *fields, *codes, *titles, *ids, *scores, *origs, *vs, *hb, *sc, *cr, *em = NULL, *ca = NULL;
+    if (!PyArg_ParseTuple(args, "OOOO!O!O!O!O!O!O!OO|OO!", &ctype, &ftype, &fields, &PyList_Type, &codes, &PyList_Type, &titles, &PyList_Type, &ids,
+                          &PyList_Type, &scores, &PyList_Type, &origs, &PyList_Type, &vs, &PyList_Type, &hb, &sc, &cr, &em, &PyList_Type, &ca))
         return NULL;
     if (!PyType_Check(ctype) || !PyType_Check(ftype)) { PyErr_SetString(PyExc_TypeError, "types expected"); return NULL; }
+    if (!em) em = v_zero;
     const Py_ssize_t n = PyList_GET_SIZE(ids), nrows = PyList_GET_SIZE(codes);
-    if (PyList_GET_SIZE(scores) < n || PyList_GET_SIZE(origs) < n || PyList_GET_SIZE(vs) < n || PyList_GET_SIZE(hb) < n || PyList_GET_SIZE(titles) != nrows) {
+    if (PyList_GET_SIZE(scores) < n || PyList_GET_SIZE(origs) < n || PyList_GET_SIZE(vs) < n || PyList_GET_SIZE(hb) < n || PyList_GET_SIZE(titles) != nrows ||
+        (ca && PyList_GET_SIZE(ca) < n)) {
         PyErr_SetString(PyExc_ValueError, "parallel lists are shorter than ids");
         return NULL;
     }
@@ -51,8 +55,8 @@ static PyObject *bulk_candidates(PyObject *self, PyObject *args) {
         if (row < 0 || row >= nrows) { if (!PyErr_Occurred()) PyErr_SetString(PyExc_IndexError, "row id outside the corpus"); goto fail; }
         PyObject *fd = _PyDict_NewPresized(6);
         if (!fd) goto fail;
-        if (PyDict_SetItem(fd, k_vs, PyList_GET_ITEM(vs, j)) || PyDict_SetItem(fd, k_hb, PyList_GET_ITEM(hb, j)) || PyDict_SetItem(fd, k_em, v_zero) ||
-            PyDict_SetItem(fd, k_sc, sc) || PyDict_SetItem(fd, k_ca, v_zero) || PyDict_SetItem(fd, k_cr, cr)) { Py_DECREF(fd); goto fail; }
+        if (PyDict_SetItem(fd, k_vs, PyList_GET_ITEM(vs, j)) || PyDict_SetItem(fd, k_hb, PyList_GET_ITEM(hb, j)) || PyDict_SetItem(fd, k_em, em) ||
+            PyDict_SetItem(fd, k_sc, sc) || PyDict_SetItem(fd, k_ca, ca ? PyList_GET_ITEM(ca, j) : v_zero) || PyDict_SetItem(fd, k_cr, cr)) { Py_DECREF(fd); goto fail; }
         PyObject *f = instance_with_dict((PyTypeObject *)ftype, fd);
         if (!f) goto fail;
         PyObject *cd = _PyDict_NewPresized(8);

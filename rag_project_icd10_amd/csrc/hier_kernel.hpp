@@ -11,6 +11,9 @@
 //   services/hierarchical_similarity_service.py:575     stable sort by the enhanced score
 // Everything that reads strings (uncertainty markers, chapter keywords in the query, context relevance) is computed once
 // per QUERY on the host and arrives in q_params; per-ROW string facts (chapter letter, ".9" code) arrive as one tag byte.
+// With NER entities (q_params HIER_QP_ENT wide) the three factors they feed still depend on the query and the hit's
+// chapter letter only: the chapter boosts include the disease-entity term (:293-328), the entity match score is one value
+// per query (a live hit's haystack is " ", :341-385), the category alignment one value per (query, chapter) (:411-446).
 // The arithmetic is IEEE double, one rounding per Python operator (no contraction), in the reference's evaluation order:
 // results are bit-identical to the Python doubles (tests/test_gpu_parity.py).
 #pragma once
@@ -20,6 +23,7 @@
 namespace icd {
 
 constexpr int HIER_QP = 12;        // per query: [0] uncertainty weight (0: none) [1] context relevance [2] exact-match flag [3..11] chapter boosts
+constexpr int HIER_QP_ENT = 22;    // with entities: [0..11] as above (boosts with the entity term) [12] entity match score [13..21] category alignment by chapter
 constexpr int HIER_NCHAP = 9;
 constexpr int HIER_MAX_K = 128;
 
@@ -29,7 +33,7 @@ struct HierArgs {
     int nq, k;
     long long id_base, n_rows;
     const unsigned char *row_tags;   // [n_rows]: bits 0-3 chapter index (15 = none), bit 7 = code matches \.9\d*$
-    const double *q_params;          // [nq][HIER_QP]
+    const double *q_params;          // [nq][QP] (the kernel's template argument: HIER_QP or HIER_QP_ENT)
     double w_hb, w_em, w_sc, w_ca, w_cr, sc_value, level_term;
     int *out_order;          // [nq][k] position -> index of the hit in search order (-1 past the hits)
     double *out_enhanced;    // [nq][k] final score, best first
@@ -40,7 +44,9 @@ struct HierArgs {
 };
 
 #pragma clang fp contract(off)
+template <int QP>
 __global__ __launch_bounds__(256) void hier_rescore_kernel(HierArgs a) {
+    static_assert(QP == HIER_QP || QP == HIER_QP_ENT, "q_params are 12 or 22 wide");
     __shared__ double sh_key[4][HIER_MAX_K];
     __shared__ double sh_val[4][HIER_MAX_K][4];
     __shared__ int sh_idx[4][HIER_MAX_K];
@@ -48,7 +54,7 @@ __global__ __launch_bounds__(256) void hier_rescore_kernel(HierArgs a) {
     const int q = blockIdx.x * 4 + wave;
     if (q >= a.nq) return;
     const int k = a.k;
-    const double *qp = a.q_params + (size_t)q * HIER_QP;
+    const double *qp = a.q_params + (size_t)q * QP;
     const double uw = qp[0], cr = qp[1];
     const bool exact = qp[2] != 0.0;
     double *key = sh_key[wave];
@@ -132,9 +138,16 @@ __global__ __launch_bounds__(256) void hier_rescore_kernel(HierArgs a) {
             const bool hp = v > 0.95;
             double extra = 0.0;
             extra = extra + h * a.w_hb / 0.2 * (hp ? 0.5 : 1.0);
-            extra = extra + 0.0 * a.w_em / 0.15;                        // entity_match_score is 0 without entities
-            if (a.sc_value > v) extra = extra + (a.sc_value - v) * a.w_sc / 0.08;
-            extra = extra + 0.0 * a.w_ca / 0.04;                        // category_alignment is 0 without entities
+            if constexpr (QP == HIER_QP_ENT) {
+                extra = extra + qp[12] * a.w_em / 0.15;                 // entity_match_score: one value per query
+                if (a.sc_value > v) extra = extra + (a.sc_value - v) * a.w_sc / 0.08;
+                const double ca = c < HIER_NCHAP ? qp[13 + c] : 0.0;    // category_alignment: 0 outside the chapter table
+                extra = extra + ca * a.w_ca / 0.04;
+            } else {
+                extra = extra + 0.0 * a.w_em / 0.15;                    // entity_match_score is 0 without entities
+                if (a.sc_value > v) extra = extra + (a.sc_value - v) * a.w_sc / 0.08;
+                extra = extra + 0.0 * a.w_ca / 0.04;                    // category_alignment is 0 without entities
+            }
             extra = extra + cr * a.w_cr / 0.03;
             if (hp) extra = extra + 0.15;
             double s = v + extra;

@@ -1517,10 +1517,11 @@ int icd_merge_topk(int32_t device, const float *scores, const int64_t *ids, cons
     return ICD_OK;
 }
 
-int icd_hier_rescore(int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
-                     int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
-                     int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
-                     double *out_boost, void *stream) {
+// the two entry points share their checks and arguments; qp_width is the width of a query's row of q_params
+static int hier_rescore_launch(int qp_width, int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
+                               int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
+                               int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
+                               double *out_boost, void *stream) {
     if (!adj || !ids || !row_tags || !q_params || !weights) return fail(ICD_ERR_INVALID, "input pointer is NULL");
     if (!out_order || !out_enhanced || !out_score || !out_vs || !out_hb || !out_boost) return fail(ICD_ERR_INVALID, "output pointer is NULL");
     if (k <= 0 || k > HIER_MAX_K) return fail(ICD_ERR_INVALID, "k=%d (1..%d)", k, HIER_MAX_K);
@@ -1534,9 +1535,28 @@ int icd_hier_rescore(int32_t device, const double *adj, const int64_t *ids, int6
     a.sc_value = weights[5]; a.level_term = weights[6];
     a.out_order = out_order; a.out_enhanced = out_enhanced; a.out_score = out_score; a.out_vs = out_vs; a.out_hb = out_hb;
     a.out_boost = out_boost;
-    hipLaunchKernelGGL(hier_rescore_kernel, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    if (qp_width == HIER_QP_ENT)
+        hipLaunchKernelGGL(hier_rescore_kernel<HIER_QP_ENT>, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    else
+        hipLaunchKernelGGL(hier_rescore_kernel<HIER_QP>, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     HIP_TRY(hipGetLastError());
     return ICD_OK;
+}
+
+int icd_hier_rescore(int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
+                     int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
+                     int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
+                     double *out_boost, void *stream) {
+    return hier_rescore_launch(HIER_QP, device, adj, ids, nq, k, id_base, n_rows, row_tags, q_params, weights, out_order,
+                               out_enhanced, out_score, out_vs, out_hb, out_boost, stream);
+}
+
+int icd_hier_rescore_entities(int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
+                              int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
+                              int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
+                              double *out_boost, void *stream) {
+    return hier_rescore_launch(HIER_QP_ENT, device, adj, ids, nq, k, id_base, n_rows, row_tags, q_params, weights, out_order,
+                               out_enhanced, out_score, out_vs, out_hb, out_boost, stream);
 }
 
 int icd_pack_winners(int32_t device, const int32_t *order, const int64_t *ids, const float *raw, const double *adj, const double *enhanced,

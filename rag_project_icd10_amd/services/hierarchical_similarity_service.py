@@ -43,14 +43,17 @@ def trusted_factors(vs: float, hb: float, em: float, sc: float, ca: float, cr: f
     return f
 
 
-def trusted_factors_row(vs_row, hb_row, sc: float, cr: float) -> list:
-    """trusted_factors for one query's winners in one call (live hits: no entity match, no category alignment)"""
+def trusted_factors_row(vs_row, hb_row, sc: float, cr: float, em: float = 0.0, ca_row=None) -> list:
+    """trusted_factors for one query's winners in one call (live hits without entities: no entity match, no category
+    alignment; with entities: the query's entity match score em and the winners' category alignments ca_row)"""
     new, cls = object.__new__, SimilarityFactors
     out = []
-    for vs, hb in zip(vs_row, hb_row):
+    if ca_row is None:
+        ca_row = (0.0,) * len(vs_row)
+    for vs, hb, ca in zip(vs_row, hb_row, ca_row):
         f = new(cls)
-        f.__dict__ = {"vector_similarity": vs, "hierarchy_boost": hb, "entity_match_score": 0.0, "semantic_coherence": sc,
-                      "category_alignment": 0.0, "context_relevance": cr}
+        f.__dict__ = {"vector_similarity": vs, "hierarchy_boost": hb, "entity_match_score": em, "semantic_coherence": sc,
+                      "category_alignment": ca, "context_relevance": cr}
         out.append(f)
     return out
 
@@ -348,20 +351,71 @@ class HierarchicalSimilarityService:
                     cats[ci] = float(min(0.0 + (hits / len(kws)) * 0.3 * info.get("semantic_weight", 1.0), 0.4))
         return [weight, float(cr), exact] + cats
 
+    QP_ENTITIES = 22   # width of query_params_entities' table
+
+    def query_params_entities(self, query_text: str, query_entities: Dict[str, List[Dict]]) -> List[float]:
+        """The 22 per-query numbers of the device-side rescoring of a query WITH its NER entities (icd_hier_rescore_entities):
+        on live-shaped hits every factor the entities feed depends on the query and the first letter of the hit's code only.
+        [0..2] as query_params; [3..11] the chapter boosts of _calculate_category_semantic_boost with the entities (its
+        disease-entity term); [12] _calculate_entity_match_score against a live hit (no title, no semantic text); [13..21]
+        _calculate_category_alignment of each chapter in CHAPTER_ORDER. Every entry is what the per-candidate method returns
+        on the clean query batch_calculate_similarities uses - the methods themselves are called (np.float32 or missing
+        confidences, their try / degrade rules) - except where the method's result is 0.0 with certainty: a chapter none of
+        whose keywords occurs in the text it scans. With no entities the first 12 entries are query_params and the rest 0."""
+        base = self.query_params(query_text)
+        if type(query_entities) is not dict:   # (the methods' own try blocks decide, as on the host path)
+            return self._query_params_entities_slow(query_text, query_entities, base, False)
+        plain = all(type(ents) is list and all(type(e) is dict and type(e.get("text", "")) is str for e in ents)
+                    for ents in query_entities.values())
+        if plain and not any(query_entities.values()):
+            return base + [0.0] * 10          # the common case: NER found nothing
+        return self._query_params_entities_slow(query_text, query_entities, base, plain)
+
+    def _query_params_entities_slow(self, query_text, query_entities, base, plain):
+        import re
+        cls = type(self)
+        if getattr(cls, "_kw_chapter", None) is None:
+            cls._kw_chapter = [re.compile("|".join(re.escape(k) for k in _CHAPTERS[c][1])) for c in self.CHAPTER_ORDER]
+        clean = self.uncertainty_service.clean_and_weight(query_text)[0]
+        boosts, align = [0.0] * len(self.CHAPTER_ORDER), [0.0] * len(self.CHAPTER_ORDER)
+        if plain:
+            # a chapter's boost / alignment is 0.0 unless one of its keywords occurs in the text the method scans (the query
+            # and the disease entities / every entity; "\n" occurs in no keyword, so joined texts give no false match)
+            lowered_q = clean.lower()
+            disease = "\n".join(e.get("text", "").lower() for e in query_entities.get("disease", []))
+            every = "\n".join(e.get("text", "").lower() for ents in query_entities.values() for e in ents)
+            for ci, rx in enumerate(cls._kw_chapter):
+                info = self.main_categories[self.CHAPTER_ORDER[ci]]
+                if rx.search(lowered_q) or rx.search(disease):
+                    boosts[ci] = self._calculate_category_semantic_boost(clean, query_entities, info)
+                if rx.search(every):
+                    align[ci] = self._calculate_category_alignment(query_entities, {"code": self.CHAPTER_ORDER[ci]})
+        else:
+            for ci, c in enumerate(self.CHAPTER_ORDER):
+                boosts[ci] = self._calculate_category_semantic_boost(clean, query_entities, self.main_categories[c])
+                align[ci] = self._calculate_category_alignment(query_entities, {"code": c})
+        em = self._calculate_entity_match_score(query_entities, {})
+        return base[:3] + boosts + [em] + align
+
     def device_weights(self) -> List[float]:
         w = self.factor_weights
         return [w["hierarchy_boost"], w["entity_match_score"], w["semantic_coherence"], w["category_alignment"],
                 w["context_relevance"], 0.3 if self.embedding_service else 0.5, self._get_level_boost_factor(1) * 0.3]
 
-    def rescore_live_hits_batch(self, queries: List[str], adj, ids, row_tags, id_base: int = 0, q_params=None):
+    def rescore_live_hits_batch(self, queries: List[str], adj, ids, row_tags, id_base: int = 0, q_params=None, entities=None):
         """batch_calculate_similarities(q, {}, hits) for every query of a batch whose hits are still device tensors
         (adj f64 [nq, k] and ids i64 [nq, k] from MilvusService.search_batch; row_tags from MilvusService.row_tags()).
         Returns device tensors [nq, k] in the final order: (order, enhanced, score, vector_similarity, hierarchy_boost,
-        uncertainty_boost) - see include/icd_search.h icd_hier_rescore. Bit-identical to the per-query Python method."""
+        uncertainty_boost) - see include/icd_search.h icd_hier_rescore. Bit-identical to the per-query Python method.
+        entities: one NER entity dict per query (batch_calculate_similarities(q, entities[i], hits)): the rescoring then
+        runs on the 22-wide tables of query_params_entities (icd_hier_rescore_entities)."""
         import torch
         from .._native import hier_rescore
         if q_params is None:
-            q_params = [self.query_params(q) for q in queries]
+            if entities is not None:
+                q_params = [self.query_params_entities(q, e or {}) for q, e in zip(queries, entities)]
+            else:
+                q_params = [self.query_params(q) for q in queries]
         qp = torch.tensor(q_params, dtype=torch.float64)
         return hier_rescore(adj, ids, row_tags, qp, self.device_weights(), id_base=id_base)
 

@@ -5,8 +5,8 @@ Follows the reference's services/multi_diagnosis_service.py: match_multiple_diag
 _match_single_diagnosis_enhanced steps 2-4 (:152-175); match confidence is the reference's own
 original formula _calculate_match_confidence (:276-304). NOT reproduced (out of scope, SURVEY.md
 section 2): the semantic-boundary splitter (delimiter split only) and the 12-factor confidence service beyond row
-N3's pieces. The NER service (row N4) is optional: without one, query_entities is {}; the all-device batch path
-(match_diagnoses_batch) never uses entities. Difference by design (row N2): all diagnoses of a
+N3's pieces. The NER service (row N4) is optional: without one, query_entities is {}; with one, the all-device batch path
+(match_diagnoses_batch(..., entities=)) rescores with the diagnoses' entities. Difference by design (row N2): all diagnoses of a
 request are embedded in ONE encoder batch and searched in ONE search_batch call.
 """
 from __future__ import annotations
@@ -80,7 +80,9 @@ class MultiDiagnosisService:
         confs = [d.get("diagnosis_confidence", 0.5) for d in enhanced]
         # one encoder batch + one search batch for the whole request
         matches = None
-        if self.ner_service is None and getattr(self.milvus_service, "supports_device_rescoring", lambda: False)():
+        ner_job = vectors = None
+        device = getattr(self.milvus_service, "supports_device_rescoring", lambda: False)()
+        if self.ner_service is None and device:
             # no entities to match (the reference's rescoring then depends on the query string and the hits' codes only):
             # the whole request stays on the device - encode -> search(2 top_k) -> rescoring -> top_k winners come back.
             # Same DiagnosisMatch objects as the host path below (tests/test_gpu_parity.py, all 1 000 golden strings).
@@ -88,6 +90,17 @@ class MultiDiagnosisService:
                 matches = self.match_diagnoses_batch(diagnoses, top_k=top_k)
             except Exception as exc:
                 logger.error("device-side request path failed (%s): host path", exc)
+                matches = None
+        elif device:
+            # with entities: on live hits they feed three factors that depend on the query and the hit's chapter letter only, so
+            # the rescoring stays on the device as well (query_params_entities, icd_hier_rescore_entities). The classifier runs in
+            # its worker thread while this thread embeds and searches; its entities are joined before the rescoring launch.
+            ner_job = self._ner_pool().submit(self._entities_of, diagnoses)
+            try:
+                vectors = self._embed_diagnoses(diagnoses)
+                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, vectors=vectors, entities=ner_job)
+            except Exception as exc:
+                logger.error("device-side request path with entities failed (%s): host path", exc)
                 matches = None
         if matches is not None:
             return {"original_text": text, "extracted_diagnoses": diagnoses, "matches": matches,
@@ -98,8 +111,10 @@ class MultiDiagnosisService:
         # The entities of the request's diagnoses do not depend on their embeddings: the token classifier runs in a worker thread on
         # its own stream WHILE this thread embeds and searches (both forwards are latency-bound - a few work-groups each, csrc/
         # encoder_small.hpp - and overlap almost entirely: a one-diagnosis request with NER 1.14 -> 0.8 ms). Same results either way.
-        ner_job = self._ner_pool().submit(self._entities_of, diagnoses) if self.ner_service else None
-        vectors = self._embed_diagnoses(diagnoses)
+        if ner_job is None and self.ner_service:
+            ner_job = self._ner_pool().submit(self._entities_of, diagnoses)
+        if vectors is None:
+            vectors = self._embed_diagnoses(diagnoses)
         try:
             hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True)
         except Exception as exc:
@@ -170,22 +185,35 @@ class MultiDiagnosisService:
         return entities
 
     def match_diagnoses_batch(self, diagnoses: List[str], top_k: int = 5, vectors=None,
-                              confidence_statistics: bool = False) -> List[DiagnosisMatch]:
+                              confidence_statistics: bool = False, entities=None) -> List[DiagnosisMatch]:
         """Additive (row N2): embed -> search(2 top_k) -> level reweight -> hierarchical rescoring for MANY diagnosis
         strings with everything between the tokenizer and the final top_k on the GPU: one encoder batch, one search_batch,
         one rescoring launch; only the top_k winners per string come back and become Candidate objects. Same results as
         _match_from_hits(d, milvus.search(encode_query(d), 2 top_k), top_k) per string (tests/test_gpu_parity.py).
         confidence_statistics=True (row N3) also fills DiagnosisMatch.confidence_factors with the three numbers of the
         reference's confidence service that are in scope - semantic_coherence (the live shape: cosine with the embedding
-        of the empty string), model_uncertainty, prediction_variance - computed for the whole batch in two launches."""
+        of the empty string), model_uncertainty, prediction_variance - computed for the whole batch in two launches.
+        entities: the NER entities of every diagnosis (a list of entity dicts, or a Future of one - joined once the search is
+        enqueued): each string is then rescored as _match_from_hits(d, hits, top_k, entities[i]) rescores it, on the device
+        (HierarchicalSimilarityService.query_params_entities, icd_hier_rescore_entities)."""
         from .hierarchical_similarity_service import trusted_factors_row
         if not diagnoses:
             return []
+        import torch
         if vectors is None:
             vectors = self.embedding_service.encode_query_batch(diagnoses, to_device=True)
+        elif not torch.is_tensor(vectors):   # (host vectors, e.g. _embed_diagnoses': the search then keeps its results on the device)
+            vectors = torch.from_numpy(np.ascontiguousarray(vectors, dtype=np.float32)).to(self.milvus_service.row_tags().device)
         hs = self.hierarchical_similarity
-        qps = [hs.query_params(d) for d in diagnoses]   # ([1] is the context relevance the factors report)
+        if entities is None:
+            qps = [hs.query_params(d) for d in diagnoses]   # ([1] is the context relevance the factors report)
         adj, raw, ids, _lv = self.milvus_service.search_batch(vectors, top_k * 2)
+        if entities is not None:
+            if hasattr(entities, "result"):   # (the NER worker's Future: the classifier ran beside the embedding and the search)
+                entities = entities.result()
+            if len(entities) != len(diagnoses):
+                raise ValueError(f"{len(entities)} entity dicts for {len(diagnoses)} diagnoses")
+            qps = [hs.query_params_entities(d, e or {}) for d, e in zip(diagnoses, entities)]   # ([12] entity match, [13..21] alignment)
         order, enh, score, vs, hb, boost = hs.rescore_live_hits_batch(diagnoses, adj, ids, self.milvus_service.row_tags(),
                                                                        q_params=qps)
         # winners only: gather on the device, one copy to the host, plain Python lists for the object loop
@@ -216,10 +244,12 @@ class MultiDiagnosisService:
         out = []
         # (tens of thousands of acyclic objects are born here: the collector's generation-0 passes over them are pure cost)
         with _gc_paused():
-            self._build_matches(out, diagnoses, kk, h_ord, h_enh, h_adj, h_raw, h_boost, h_ids, h_vs, h_hb, recs, sc, qps, conf, trusted_factors_row)
+            self._build_matches(out, diagnoses, kk, h_ord, h_enh, h_adj, h_raw, h_boost, h_ids, h_vs, h_hb, recs, sc, qps, conf, trusted_factors_row,
+                                with_entities=entities is not None)
         return out
 
-    def _build_matches(self, out, diagnoses, kk, h_ord, h_enh, h_adj, h_raw, h_boost, h_ids, h_vs, h_hb, recs, sc, qps, conf, trusted_factors_row):
+    def _build_matches(self, out, diagnoses, kk, h_ord, h_enh, h_adj, h_raw, h_boost, h_ids, h_vs, h_hb, recs, sc, qps, conf, trusted_factors_row,
+                       with_entities=False):
         from ..api.icd_models import bulk_candidates, trusted_match, trusted_matches_ready
         from .hierarchical_similarity_service import SimilarityFactors
         # the corpus' code / title columns (plain lists by row) where the store offers them, and the one-loop constructor once
@@ -228,6 +258,7 @@ class MultiDiagnosisService:
         codes = titles = None
         if cols is not None and recs is getattr(self.milvus_service.client, "records", None):
             codes, titles = cols()
+        chapters = HierarchicalSimilarityService.CHAPTER_ORDER
         for q, diagnosis in enumerate(diagnoses):
             try:
                 # how many winners exist (order < 0 from there on); live hits carry level / parent_code under "metadata": the
@@ -246,12 +277,22 @@ class MultiDiagnosisService:
                     originals = [adj_q[j] if boost_q[j] > 0 else raw_q[j] for j in range(n)]
                 else:
                     originals = raw_q
+                em = ca = None
+                if with_entities:
+                    # the entity match score is one per query; a winner's category alignment is its chapter's entry of the table
+                    # (0.0 for a letter outside it), the value the kernel added - looked up by the winner's code, as row_tag does
+                    qp = qps[q]
+                    em, ca_of = qp[12], dict(zip(chapters, qp[13:22]))
+                    ca = [ca_of.get(((codes[i] if codes is not None else recs[i].get("code")) or "")[:1], 0.0) for i in h_ids[q][:n]]
                 if codes is not None and trusted_matches_ready():
                     ids_q = h_ids[q] if n == kk else h_ids[q][:n]
-                    cands = bulk_candidates(codes, titles, SimilarityFactors, ids_q, enh_q, originals, h_vs[q], h_hb[q], sc, qps[q][1])
+                    if ca is None:
+                        cands = bulk_candidates(codes, titles, SimilarityFactors, ids_q, enh_q, originals, h_vs[q], h_hb[q], sc, qps[q][1])
+                    else:
+                        cands = bulk_candidates(codes, titles, SimilarityFactors, ids_q, enh_q, originals, h_vs[q], h_hb[q], sc, qps[q][1], em, ca)
                 else:
                     cands = trusted_candidates(recs, h_ids[q][:n], enh_q[:n], originals[:n],
-                                               trusted_factors_row(h_vs[q][:n], h_hb[q][:n], sc, qps[q][1]))
+                                               trusted_factors_row(h_vs[q][:n], h_hb[q][:n], sc, qps[q][1], *(() if ca is None else (em, ca))))
                 out.append(trusted_match(diagnosis, cands, self._match_confidence_of_scores(enh_q if n == kk else enh_q[:n]), conf[q] if conf is not None else None))
             except Exception as exc:
                 logger.error("match failed for %s: %s", diagnosis, exc)
