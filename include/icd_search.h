@@ -280,6 +280,23 @@ int icd_pack_winners(int32_t device, const int32_t *order, const int64_t *ids, c
 int icd_cosine_rows(int32_t device, const float *x, const float *y, int64_t y_stride, int64_t nq, int32_t dim,
                     double *out, void *stream);
 
+/* The ICD terminology scan of the confidence service. Replaces the loop of
+ * MultiDimensionalConfidenceService._get_term_specificity_from_icd (services/multidimensional_confidence_service.py:686-692)
+ * that runs when a term is not a name of the cache: for every term t,
+ *   out_first[t] = the smallest i with (term in key_i or key_i in term) and len(term) >= 2 and len(key_i) >= 2, else -1,
+ * Python str containment on Unicode code points.
+ *   key_cp, key_off   device int32: the cache's names in dict order (first occurrence in the CSV), as code points back to back,
+ *                     and n_keys + 1 offsets into key_cp (the caller keeps them consistent)
+ *   term_cp, term_off device int32: the terms the same way (n_terms + 1 offsets)
+ *   out_first         device int32 [n_terms]
+ * ICD_ERR_INVALID for NULL pointers, negative counts or decreasing offsets; ICD_ERR_UNSUPPORTED for a term longer than
+ * ICD_TERM_MAX_LEN code points (scan that one on the host). n_terms == 0: ICD_OK without a launch. Reads the n_terms + 1
+ * term offsets back to the host (a synchronisation of `stream`), then enqueues ONE launch: a work-group per term.
+ */
+#define ICD_TERM_MAX_LEN 32
+int icd_term_first_match(int32_t device, const int32_t *key_cp, const int32_t *key_off, int32_t n_keys, const int32_t *term_cp,
+                         const int32_t *term_off, int32_t n_terms, int32_t *out_first, void *stream);
+
 /* The self-attention of the packed BERT encoder (row a3-a5 / N1 of SURVEY.md section 8: the text -> vector forward the
  * reference reaches through sentence-transformers; rag_project_icd10_amd/services/embedding_service.py _PackedBert runs
  * every Linear of the encoder over packed tokens and calls this for the attention): softmax(Q K^T / sqrt(64)) V per

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "icd_hier_rescore", "icd_hier_rescore_entities",
     "icd_score_stats",
     "icd_cosine_rows",
+    "icd_term_first_match",
     "icd_index_set_second_pass",
     "icd_group_unique_id", "icd_group_create", "icd_group_prepare", "icd_group_connect", "icd_group_search", "icd_group_destroy",
     "icd_unpack_query_slices", "icd_split_bf16x3", "icd_encoder_create", "icd_encoder_encode", "icd_encoder_encode_many", "icd_encoder_destroy", "icd_pack_winners",
@@ -127,6 +128,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_score_stats.argtypes = [i32, vp, vp, i64, i32, i32, vp, vp]
     lib.icd_pack_winners.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp]
     lib.icd_cosine_rows.argtypes = [i32, vp, vp, i64, i64, i32, vp, vp]
+    lib.icd_term_first_match.argtypes = [i32, vp, vp, i32, vp, vp, i32, vp, vp]
     lib.icd_index_debug_counters.argtypes = [vp, vp, i32]
     lib.icd_index_set_profiling.argtypes = [vp, i32]
     lib.icd_index_last_profile.argtypes = [vp, C.POINTER(_Profile)]
@@ -561,6 +563,41 @@ def cosine_rows(x, y):
     _check(lib, lib.icd_cosine_rows(dev.index, x.data_ptr(), y.data_ptr(), stride, nq, dim, out.data_ptr(),
                                     _current_stream_ptr(dev.index)))
     return out
+
+
+TERM_MAX_LEN = 32   # include/icd_search.h ICD_TERM_MAX_LEN
+
+
+def pack_strings(strings):
+    """strings -> (int32 code points back to back, int32 offsets [n + 1]) as numpy arrays: the layout icd_term_first_match reads"""
+    cp = np.frombuffer("".join(strings).encode("utf-32-le"), dtype=np.int32)
+    off = np.zeros(len(strings) + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in strings], out=off[1:])
+    if off[-1] >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 code points")
+    return cp.copy(), off.astype(np.int32)
+
+
+def term_first_match(key_cp, key_off, terms):
+    """icd_term_first_match: for every term (a Python str of at most TERM_MAX_LEN code points), the index of the first key with
+    `term in key or key in term` (both at least two code points long), else -1 - in ONE launch. key_cp / key_off: int32 tensors on
+    a GPU (pack_strings of the keys). Returns a list of ints; raises IcdError (ICD_ERR_UNSUPPORTED) for a longer term."""
+    import torch
+    lib = load_library()
+    dev = key_cp.device
+    assert key_cp.dtype == torch.int32 and key_off.dtype == torch.int32 and key_off.device == dev
+    terms = list(terms)
+    if not terms:
+        return []
+    cp, off = pack_strings(terms)
+    # (one upload: the offsets and the code points side by side; a lone empty code-point array still needs a valid pointer)
+    buf = torch.from_numpy(np.concatenate([off, cp, np.zeros(1, np.int32)])).to(dev)
+    out = torch.empty((len(terms),), dtype=torch.int32, device=dev)
+    n_off = off.size
+    _check(lib, lib.icd_term_first_match(dev.index, key_cp.data_ptr(), key_off.data_ptr(), key_off.numel() - 1,
+                                         buf[n_off:].data_ptr(), buf[:n_off].data_ptr(), len(terms), out.data_ptr(),
+                                         _current_stream_ptr(dev.index)))
+    return out.tolist()
 
 
 def packed_attention(qkv, starts, nseq: int, heads: int, max_len: int, out):

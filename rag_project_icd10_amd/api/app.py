@@ -2,7 +2,7 @@
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
-cut to top_k; 503 when services are missing, 500 with a `detail` string on any exception), `/embed`
+cut to top_k, every match's confidence metrics / factors / level copied as :325-330 does; 503 when services are missing, 500 with a `detail` string on any exception), `/embed`
 (:505-530), `/stats` (:574-599). The LLM, NER, standardisation and resource routes are out of scope.
 
     uvicorn rag_project_icd10_amd.api.app:app --host 0.0.0.0 --port 8005
@@ -55,8 +55,11 @@ async def lifespan(app: FastAPI):
                 ner = MedicalNERService()
             except Exception as exc:
                 logger.error("no NER service (%s): /query extracts by delimiters", exc)
+        # ICD_QUERY_CONFIDENCE=multidimensional: match confidences from the reference's 12-factor service, with its metrics, factors
+        # and level on every diagnosis match (services/multi_diagnosis_service.py:176-207); "match" (the default): the original formula
+        confidence = os.getenv("ICD_QUERY_CONFIDENCE", "match")
         from ..services.multi_diagnosis_service import MultiDiagnosisService
-        install_services(emb, mil, MultiDiagnosisService(emb, mil, ner_service=ner))
+        install_services(emb, mil, MultiDiagnosisService(emb, mil, ner_service=ner, confidence=confidence))
     try:
         yield
     finally:
@@ -100,8 +103,12 @@ async def query_similar(request: QueryRequest):
         candidates, matches = [], []
         for m in result["matches"]:
             candidates.extend(m.candidates)
-            matches.append(DiagnosisMatch(diagnosis_text=m.diagnosis_text, candidates=m.candidates,
-                                          match_confidence=m.match_confidence))
+            dm = DiagnosisMatch(diagnosis_text=m.diagnosis_text, candidates=m.candidates, match_confidence=m.match_confidence)
+            # main.py:325-330 of the reference: the confidence details ride along (None unless the multidimensional mode set them)
+            for name in ("confidence_metrics", "confidence_factors", "confidence_level"):
+                if getattr(m, name, None) is not None:
+                    setattr(dm, name, getattr(m, name))
+            matches.append(dm)
         candidates.sort(key=lambda c: c.score, reverse=True)
         response = QueryResponse(candidates=candidates[:request.top_k],
                                  is_multi_diagnosis=len(result["extracted_diagnoses"]) > 1,

@@ -37,6 +37,7 @@
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
+#include "term_lookup.hpp"
 
 using namespace icd;
 
@@ -1598,6 +1599,32 @@ int icd_cosine_rows(int32_t device, const float *x, const float *y, int64_t y_st
     CosArgs a{};
     a.x = x; a.y = y; a.y_stride = y_stride; a.nq = (int)nq; a.dim = dim; a.out = out;
     hipLaunchKernelGGL(cosine_rows_kernel, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    HIP_TRY(hipGetLastError());
+    return ICD_OK;
+}
+
+int icd_term_first_match(int32_t device, const int32_t *key_cp, const int32_t *key_off, int32_t n_keys, const int32_t *term_cp,
+                         const int32_t *term_off, int32_t n_terms, int32_t *out_first, void *stream_) {
+    if (!key_cp || !key_off || !term_cp || !term_off || !out_first) return fail(ICD_ERR_INVALID, "pointer is NULL");
+    if (n_keys < 0 || n_terms < 0) return fail(ICD_ERR_INVALID, "n_keys=%d n_terms=%d", n_keys, n_terms);
+    if (n_terms == 0) return ICD_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(device));
+    // the terms' lengths decide whether the kernel can take them: read the offsets (n_terms + 1 ints) on the stream
+    std::vector<int32_t> off((size_t)n_terms + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), term_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (off[0] < 0) return fail(ICD_ERR_INVALID, "term_off[0]=%d", off[0]);
+    for (int32_t t = 0; t < n_terms; ++t) {
+        const int32_t len = off[t + 1] - off[t];
+        if (len < 0) return fail(ICD_ERR_INVALID, "term %d: term_off decreases", t);
+        if (len > ICD_TERM_MAX_LEN) return fail(ICD_ERR_UNSUPPORTED, "term %d has %d code points (at most %d)", t, len, ICD_TERM_MAX_LEN);
+    }
+    static_assert(ICD_TERM_MAX_LEN == TERM_MAX_LEN, "ICD_TERM_MAX_LEN and term_lookup.hpp disagree");
+    TermArgs a{};
+    a.key_cp = key_cp; a.key_off = key_off; a.n_keys = n_keys; a.term_cp = term_cp; a.term_off = term_off; a.n_terms = n_terms;
+    a.out_first = out_first;
+    hipLaunchKernelGGL(term_first_match_kernel, dim3((unsigned)n_terms), dim3(TERM_BLOCK), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return ICD_OK;
 }

@@ -2,10 +2,10 @@
 hot path, reduced to the parts that are in scope.
 
 Follows the reference's services/multi_diagnosis_service.py: match_multiple_diagnoses (:51-125) and
-_match_single_diagnosis_enhanced steps 2-4 (:152-175); match confidence is the reference's own
-original formula _calculate_match_confidence (:276-304). NOT reproduced (out of scope, SURVEY.md
-section 2): the semantic-boundary splitter (delimiter split only) and the 12-factor confidence service beyond row
-N3's pieces. The NER service (row N4) is optional: without one, query_entities is {}; with one, the all-device batch path
+_match_single_diagnosis_enhanced steps 2-4 (:152-175). Match confidence: by default (confidence="match") the reference's
+original formula _calculate_match_confidence (:276-304); with confidence="multidimensional" its step 5 (:176-207), the 12-factor
+MultiDimensionalConfidenceService, whose overall confidence becomes match_confidence and whose metrics, factors and level ride
+on the match. NOT reproduced (out of scope): the semantic-boundary splitter (delimiter split only). The NER service (row N4) is optional: without one, query_entities is {}; with one, the all-device batch path
 (match_diagnoses_batch(..., entities=)) rescores with the diagnoses' entities. Difference by design (row N2): all diagnoses of a
 request are embedded in ONE encoder batch and searched in ONE search_batch call.
 """
@@ -53,11 +53,19 @@ class _gc_paused:
                 gc.enable()
         return False
 
+CONFIDENCE_MODES = ("match", "multidimensional")
+
+
 class MultiDiagnosisService:
-    def __init__(self, embedding_service, milvus_service, ner_service=None):
+    def __init__(self, embedding_service, milvus_service, ner_service=None, confidence: str = "match"):
         """ner_service: a MedicalNERService (row N4) or None. The reference always builds one (:28); here it is opt-in
         because its weights are not available offline - with one given, the per-request path extracts the entities of
-        all diagnoses of a request in ONE classifier batch and hands them to the rescoring like the reference (:147-158)."""
+        all diagnoses of a request in ONE classifier batch and hands them to the rescoring like the reference (:147-158).
+        confidence: "match" (the default: _calculate_match_confidence) or "multidimensional" (the reference's enhanced match,
+        :176-207; a diagnosis whose confidence step fails, or gives a value outside [0, 1], keeps the "match" answer)."""
+        if confidence not in CONFIDENCE_MODES:
+            raise ValueError(f"confidence={confidence!r}: one of {CONFIDENCE_MODES}")
+        self.confidence = confidence
         self.embedding_service = embedding_service
         self.milvus_service = milvus_service
         self.ner_service = ner_service
@@ -65,9 +73,9 @@ class MultiDiagnosisService:
                                                                      ner_service=ner_service)
         # the reference's default text mode is "enhanced" (entities + semantic boundaries, :44-47): here whenever there is an NER service
         self.text_processor = DiagnosisTextProcessor(embedding_service=embedding_service, ner_service=ner_service)
-        # row N3: only the embedding cosine and the score statistics of the reference's confidence service
+        # like the reference (:37-41): the confidence service shares the embedding and NER services
         self.confidence_service = MultiDimensionalConfidenceService(
-            embedding_service=embedding_service, hierarchical_similarity_service=self.hierarchical_similarity)
+            embedding_service=embedding_service, ner_service=ner_service, hierarchical_similarity_service=self.hierarchical_similarity)
 
     def match_multiple_diagnoses(self, text: str, top_k: int = 5) -> Dict[str, Any]:
         enhanced = self.text_processor.extract_diagnoses_enhanced(text)
@@ -185,7 +193,7 @@ class MultiDiagnosisService:
         return entities
 
     def match_diagnoses_batch(self, diagnoses: List[str], top_k: int = 5, vectors=None,
-                              confidence_statistics: bool = False, entities=None) -> List[DiagnosisMatch]:
+                              confidence_statistics: bool = False, entities=None, confidence: str = None) -> List[DiagnosisMatch]:
         """Additive (row N2): embed -> search(2 top_k) -> level reweight -> hierarchical rescoring for MANY diagnosis
         strings with everything between the tokenizer and the final top_k on the GPU: one encoder batch, one search_batch,
         one rescoring launch; only the top_k winners per string come back and become Candidate objects. Same results as
@@ -195,8 +203,14 @@ class MultiDiagnosisService:
         of the empty string), model_uncertainty, prediction_variance - computed for the whole batch in two launches.
         entities: the NER entities of every diagnosis (a list of entity dicts, or a Future of one - joined once the search is
         enqueued): each string is then rescored as _match_from_hits(d, hits, top_k, entities[i]) rescores it, on the device
-        (HierarchicalSimilarityService.query_params_entities, icd_hier_rescore_entities)."""
+        (HierarchicalSimilarityService.query_params_entities, icd_hier_rescore_entities).
+        confidence: "match" / "multidimensional" (None: the service's mode). "multidimensional" scores every match with
+        MultiDimensionalConfidenceService.comprehensive_confidence_batch - the cosine, the score statistics and the terminology
+        scan as one launch each - equal to _match_from_hits' per-call scores except the cosine (sklearn's, to ~1e-14)."""
         from .hierarchical_similarity_service import trusted_factors_row
+        confidence = self.confidence if confidence is None else confidence
+        if confidence not in CONFIDENCE_MODES:
+            raise ValueError(f"confidence={confidence!r}: one of {CONFIDENCE_MODES}")
         if not diagnoses:
             return []
         import torch
@@ -242,14 +256,61 @@ class MultiDiagnosisService:
             conf = [{"semantic_coherence": coh[q], "model_uncertainty": stats[q][4], "prediction_variance": stats[q][5]}
                     for q in range(len(diagnoses))]
         out = []
+        failed = set()
         # (tens of thousands of acyclic objects are born here: the collector's generation-0 passes over them are pure cost)
         with _gc_paused():
             self._build_matches(out, diagnoses, kk, h_ord, h_enh, h_adj, h_raw, h_boost, h_ids, h_vs, h_hb, recs, sc, qps, conf, trusted_factors_row,
-                                with_entities=entities is not None)
+                                with_entities=entities is not None, failed=failed)
+        if confidence == "multidimensional":
+            qv = vectors if torch.is_tensor(vectors) else torch.as_tensor(np.asarray(vectors, dtype=np.float32))
+            stats = self.confidence_service.score_statistics_batch(enh, order, top_k=kk).tolist() if adj.is_cuda else None
+            self._multidimensional_batch(out, diagnoses, qv.to(adj.device), entities, stats, failed)
         return out
 
+    @staticmethod
+    def _confidence_inputs(candidates):
+        """the reference's inputs of the confidence step (:176-196): records of the top_k candidates with score = enhanced_score,
+        and the top-ranked hit's three factors (None without hits)"""
+        records = [{"code": c.code, "title": c.title, "score": c.enhanced_score if hasattr(c, "enhanced_score") else c.score,
+                    "level": getattr(c, "level", 1)} for c in candidates]
+        if not candidates:
+            return records, None
+        f = candidates[0].similarity_factors
+        return records, {"vector_similarity": f.vector_similarity, "hierarchy_boost": f.hierarchy_boost,
+                         "entity_match_score": f.entity_match_score}
+
+    def _with_confidence(self, match: DiagnosisMatch, metrics, factors) -> DiagnosisMatch:
+        """the match with the multidimensional confidence (:198-207); the match as it is when the value fails match_confidence's
+        0 <= c <= 1"""
+        try:
+            mc = float(metrics.overall_confidence)
+            if not 0.0 <= mc <= 1.0:
+                raise ValueError(f"overall confidence {mc}")
+            return DiagnosisMatch(diagnosis_text=match.diagnosis_text, candidates=match.candidates, match_confidence=mc,
+                                  confidence_metrics=metrics, confidence_factors=factors,
+                                  confidence_level=self.confidence_service.get_confidence_level(mc))
+        except Exception as exc:
+            logger.error("multidimensional confidence failed for %s (%s): the match confidence stays", match.diagnosis_text, exc)
+            return match
+
+    def _multidimensional_batch(self, out, diagnoses, query_vectors, entities, stats, failed):
+        idx = [q for q in range(len(diagnoses)) if q not in failed]
+        if not idx:
+            return
+        try:
+            inputs = [self._confidence_inputs(out[q].candidates) for q in idx]
+            scored = self.confidence_service.comprehensive_confidence_batch(
+                [diagnoses[q] for q in idx], [r for r, _ in inputs], [f for _, f in inputs], query_vectors=query_vectors[idx],
+                entities=None if entities is None else [entities[q] for q in idx],
+                stats=None if stats is None else [stats[q] for q in idx])
+        except Exception as exc:
+            logger.error("batch multidimensional confidence failed (%s): match confidences stay", exc)
+            return
+        for q, (metrics, factors) in zip(idx, scored):
+            out[q] = self._with_confidence(out[q], metrics, factors)
+
     def _build_matches(self, out, diagnoses, kk, h_ord, h_enh, h_adj, h_raw, h_boost, h_ids, h_vs, h_hb, recs, sc, qps, conf, trusted_factors_row,
-                       with_entities=False):
+                       with_entities=False, failed=None):
         from ..api.icd_models import bulk_candidates, trusted_match, trusted_matches_ready
         from .hierarchical_similarity_service import SimilarityFactors
         # the corpus' code / title columns (plain lists by row) where the store offers them, and the one-loop constructor once
@@ -297,6 +358,8 @@ class MultiDiagnosisService:
             except Exception as exc:
                 logger.error("match failed for %s: %s", diagnosis, exc)
                 out.append(DiagnosisMatch(diagnosis_text=diagnosis, candidates=[], match_confidence=0.0))
+                if failed is not None:
+                    failed.add(q)
 
     def _match_from_hits(self, diagnosis: str, hits: List[Dict[str, Any]], top_k: int,
                          query_entities: Dict[str, Any] = None) -> DiagnosisMatch:
@@ -311,11 +374,22 @@ class MultiDiagnosisService:
                 cand.original_score = float(rec.get("original_score", 0.0))
                 cand.similarity_factors = factors
                 candidates.append(cand)
-            return DiagnosisMatch(diagnosis_text=diagnosis, candidates=candidates,
-                                  match_confidence=self._calculate_match_confidence(candidates))
+            match = DiagnosisMatch(diagnosis_text=diagnosis, candidates=candidates,
+                                   match_confidence=self._calculate_match_confidence(candidates))
         except Exception as exc:  # e.g. a negative score fails Candidate's ge=0 validator
             logger.error("match failed for %s: %s", diagnosis, exc)
             return DiagnosisMatch(diagnosis_text=diagnosis, candidates=[], match_confidence=0.0)
+        if self.confidence != "multidimensional":
+            return match
+        try:
+            records, sf = self._confidence_inputs(candidates)
+            # (the request's entities are extract_medical_entities(diagnosis, filter_drugs=True): the call the confidence service makes)
+            pre = {"query_entities": query_entities} if self.ner_service is not None and query_entities is not None else None
+            metrics, factors = self.confidence_service.calculate_comprehensive_confidence(diagnosis, records, sf, pre=pre)
+        except Exception as exc:
+            logger.error("multidimensional confidence failed for %s (%s): the match confidence stays", diagnosis, exc)
+            return match
+        return self._with_confidence(match, metrics, factors)
 
     def _calculate_match_confidence(self, candidates: List[Candidate]) -> float:
         if not candidates:
