@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define ICD_ABI_VERSION 6   /* 6: icd_encoder_encode_many; the process-wide icd_debug_set_* switches became per-index options (icd_index_create flags, icd_index_set_option); ICD_ENCODER_MAX_TOKENS 512, ICD_ENCODER_MAX_SEQS 64 (round 6). 5: icd_unpack_query_slices, icd_debug_set_stream_one, icd_debug_set_pacing, icd_debug_set_exact_narrow, icd_debug_set_host_one, icd_split_bf16x3, icd_encoder_create / _encode / _destroy, icd_pack_winners (round 5). 4: icd_debug_set_family_order, icd_debug_set_center, icd_stats.centered / mean_share appended, icd_group_prepare / icd_group_connect (round 4). 3: icd_stats.sparse_fallback_armed appended, icd_debug_set_create_probe, icd_packed_attention (round 3). 2: + icd_hier_rescore, icd_score_stats, icd_cosine_rows, icd_debug_set_permute (round 2), the group entry points (round 3) */
+#define ICD_ABI_VERSION 6   /* 6: icd_encoder_encode_many; icd_index_create_view (an addition); the process-wide icd_debug_set_* switches became per-index options (icd_index_create flags, icd_index_set_option); ICD_ENCODER_MAX_TOKENS 512, ICD_ENCODER_MAX_SEQS 64 (round 6). 5: icd_unpack_query_slices, icd_debug_set_stream_one, icd_debug_set_pacing, icd_debug_set_exact_narrow, icd_debug_set_host_one, icd_split_bf16x3, icd_encoder_create / _encode / _destroy, icd_pack_winners (round 5). 4: icd_debug_set_family_order, icd_debug_set_center, icd_stats.centered / mean_share appended, icd_group_prepare / icd_group_connect (round 4). 3: icd_stats.sparse_fallback_armed appended, icd_debug_set_create_probe, icd_packed_attention (round 3). 2: + icd_hier_rescore, icd_score_stats, icd_cosine_rows, icd_debug_set_permute (round 2), the group entry points (round 3) */
 #define ICD_MAX_K 128
 
 typedef struct icd_index icd_index;
@@ -146,6 +146,21 @@ int icd_index_create(const float *corpus, int64_t n, int32_t dim, const int32_t 
                      int32_t flags, icd_index **out);
 
 int icd_index_destroy(icd_index *idx);
+
+/*
+ * A view: an ordinary index over rows rows[0 .. n_rows) of `parent` (a Milvus `filter` expression's selection). The row ids are
+ * the parent's row indices, strictly increasing, inside [0, parent n); anything else is ICD_ERR_INVALID, and so is n_rows = 0.
+ * `rows` is a device pointer when rows_on_device is set. The view is built on the parent's device from the parent's fp32 rows
+ * and levels (a gather kernel: nothing is uploaded), then exactly like icd_index_create with ICD_CREATE_CORPUS_ON_DEVICE: its
+ * own fp16 image, centring decision and probe, sized by max_nq / max_k; `flags` takes the same A/B bits. Every search entry
+ * point, icd_index_stats and icd_index_set_option work on it unchanged; its hits carry the PARENT's global ids (id_base + row),
+ * mapped where the outputs are written, so the (score desc, id asc) order and the stable re-sort are those of the parent's
+ * ranking restricted to the rows. With fewer than k rows the lists are padded (score -inf, id -1, level 0). The view keeps no
+ * pointer into the parent: either may be destroyed first. icd_index_lookup_levels and icd_group_create / _prepare on a view
+ * return ICD_ERR_UNSUPPORTED.
+ */
+int icd_index_create_view(icd_index *parent, const int64_t *rows, int64_t n_rows, int32_t rows_on_device,
+                          int32_t max_nq, int32_t max_k, int32_t flags, icd_index **out);
 
 /* Raw top-k by inner product. out_scores float[nq][k], out_ids int64[nq][k]. */
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k,

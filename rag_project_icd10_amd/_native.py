@@ -23,7 +23,7 @@ MAX_K = 128
 ABI_VERSION = 6   # include/icd_search.h ICD_ABI_VERSION: a stale libicdsearch.so is refused with a clear message
 
 EXPORTED_SYMBOLS = (
-    "icd_abi_version", "icd_last_error", "icd_device_count", "icd_index_create", "icd_index_destroy",
+    "icd_abi_version", "icd_last_error", "icd_device_count", "icd_index_create", "icd_index_create_view", "icd_index_destroy",
     "icd_index_search", "icd_index_search_reweighted", "icd_merge_topk", "icd_index_lookup_levels",
     "icd_index_stats", "icd_index_set_chunks", "icd_index_debug_counters", "icd_index_set_profiling",
     "icd_index_last_profile", "icd_index_profile_summary", "icd_index_set_option", "icd_packed_attention",
@@ -101,6 +101,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_last_error.restype = C.c_char_p
     lib.icd_device_count.restype = C.c_int
     lib.icd_index_create.argtypes = [vp, i64, i32, vp, i64, i32, i32, i32, i32, C.POINTER(vp)]
+    lib.icd_index_create_view.argtypes = [vp, vp, i64, i32, i32, i32, i32, C.POINTER(vp)]
     lib.icd_index_destroy.argtypes = [vp]
     lib.icd_index_search.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]
     lib.icd_index_search_reweighted.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, vp]
@@ -212,10 +213,42 @@ class IcdIndex:
             lptr = lv.ctypes.data if lv is not None else None
         self.n, self.dim, self.device, self.max_nq, self.max_k = int(n), int(dim), int(device), int(max_nq), int(max_k)
         self.id_base = int(id_base)
-        flags = ((CREATE_CORPUS_ON_DEVICE if on_dev else 0) | (0 if permute else CREATE_ROW_ORDER) | (0 if probe else CREATE_NO_PROBE)
-                 | (0 if center else CREATE_NO_CENTER))
+        self.rows = None   # a view's rows of its parent (view())
+        self._ab_flags = (0 if permute else CREATE_ROW_ORDER) | (0 if probe else CREATE_NO_PROBE) | (0 if center else CREATE_NO_CENTER)
+        flags = (CREATE_CORPUS_ON_DEVICE if on_dev else 0) | self._ab_flags
         _check(self._lib, self._lib.icd_index_create(cptr, n, dim, lptr, id_base, device, max_nq, max_k, flags,
                                                       C.byref(self._h)))
+
+    def view(self, rows, *, max_nq: Optional[int] = None, max_k: Optional[int] = None) -> "IcdIndex":
+        """An index over rows `rows` of this one (icd_index_create_view): built on the device from this index's rows and levels,
+        then like any index (its own fp16 image, centring and probe); its hits carry THIS index's global ids. rows: strictly
+        increasing row indices in [0, n), a numpy array or a torch CUDA tensor (int64). max_nq / max_k default to this index's.
+        The view is independent: closing this index first leaves it valid."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        if _is_torch_tensor(rows) and rows.is_cuda:
+            import torch
+            r = rows.to(torch.int64).contiguous().reshape(-1)
+            if r.device.index != self.device:
+                raise ValueError(f"rows on cuda:{r.device.index}, index on device {self.device}")
+            torch.cuda.synchronize(self.device)
+            ptr, on_dev, m = r.data_ptr(), 1, int(r.numel())
+        else:
+            if _is_torch_tensor(rows):
+                rows = rows.detach().cpu().numpy()
+            r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            ptr, on_dev, m = r.ctypes.data, 0, int(r.size)
+        v = IcdIndex.__new__(IcdIndex)
+        v._lib = self._lib
+        v._h = C.c_void_p()
+        v.n, v.dim, v.device = m, self.dim, self.device
+        v.max_nq = int(max_nq if max_nq is not None else self.max_nq)
+        v.max_k = int(max_k if max_k is not None else self.max_k)
+        v.id_base, v._ab_flags = self.id_base, self._ab_flags
+        _check(self._lib, self._lib.icd_index_create_view(self._h, ptr if m else None, m, on_dev, v.max_nq, v.max_k, self._ab_flags,
+                                                           C.byref(v._h)))
+        v.rows = r.cpu().numpy() if on_dev else r.copy()
+        return v
 
     # -- lifecycle -----------------------------------------------------------------------------------
     def close(self):

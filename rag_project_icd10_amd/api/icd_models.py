@@ -214,6 +214,7 @@ class DiagnosisMatch(BaseModel):
 class QueryRequest(BaseModel):
     text: str = Field(..., description="输入的诊断文本", min_length=1)
     top_k: int = Field(default=5, description="返回候选数量", ge=1, le=50)
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields, e.g. 'level >= 2 and code like \"E11%\"'")
 
 
 class QueryResponse(BaseModel):

@@ -47,6 +47,7 @@ class CorpusStore:
         self._matrix: Optional[np.ndarray] = None
         self._meta_bytes = 0   # committed length of meta.jsonl
         self._code_title = None   # code_title_columns(): dropped by every change of `records`
+        self.generation = 0       # bumped by every mutation of the rows (create, drop, load, append): keys caches of derived data
         self.closed = False
 
     # ---- paths ------------------------------------------------------------------------------------
@@ -97,6 +98,7 @@ class CorpusStore:
         self._meta_bytes = 0
         self.records = []
         self._code_title = None
+        self.generation += 1
         self._vectors = []
         self._matrix = np.zeros((0, self.dim), dtype=np.float32)
         for name in ("corpus.f32", "levels.i32", "meta.jsonl"):
@@ -110,6 +112,7 @@ class CorpusStore:
         self._meta_bytes = 0
         self.records = []
         self._code_title = None
+        self.generation += 1
         self._vectors = []
         self._matrix = None
 
@@ -171,6 +174,7 @@ class CorpusStore:
         self._vectors = []
         self.records = []
         self._code_title = None
+        self.generation += 1
         with open(self._file("meta.jsonl"), encoding="utf-8") as f:
             for i, line in enumerate(f):
                 if i >= self.count:
@@ -210,6 +214,7 @@ class CorpusStore:
             self._code_title = None
             self._vectors.append(vectors)
             self.count += len(rows)
+            self.generation += 1
             self._write_manifest()
 
     def matrix(self) -> np.ndarray:

@@ -78,6 +78,8 @@ struct FinArgs {
     // level table
     const int *levels;  // [n] or null
     long long id_base;
+    const long long *row_map;   // nullable (a view, icd_index_create_view): [n] the parent's global id of every local row, strictly
+                                // increasing, so the (score desc, id asc) order and the stable re-sort are the same under either id
     // outputs, any may be null
     float *out_scores;      // raw order [query][k]
     long long *out_ids;
@@ -127,7 +129,7 @@ __device__ __forceinline__ void emit_outputs(const FinArgs &a, int qidx, const u
         }
         if (j < k) {
             if (a.out_scores) a.out_scores[o + j] = sc[e];
-            if (a.out_ids) a.out_ids[o + j] = row[e] >= 0 ? a.id_base + row[e] : -1ll;
+            if (a.out_ids) a.out_ids[o + j] = row[e] >= 0 ? (a.row_map ? a.row_map[row[e]] : a.id_base + row[e]) : -1ll;
         }
     }
     if (!a.out_adj && !a.out_adj_ids && !a.out_adj_raw && !a.out_adj_levels) return;
@@ -148,7 +150,7 @@ __device__ __forceinline__ void emit_outputs(const FinArgs &a, int qidx, const u
             const size_t w = o + pos[e];
             if (a.out_adj) a.out_adj[w] = adj[e];
             if (a.out_adj_raw) a.out_adj_raw[w] = sc[e];
-            if (a.out_adj_ids) a.out_adj_ids[w] = a.id_base + row[e];
+            if (a.out_adj_ids) a.out_adj_ids[w] = a.row_map ? a.row_map[row[e]] : a.id_base + row[e];
             if (a.out_adj_levels) a.out_adj_levels[w] = lvl[e];
         } else if (j < k) {
             const size_t w = o + j;

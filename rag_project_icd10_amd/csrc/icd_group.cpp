@@ -28,6 +28,7 @@
 #include "../../include/icd_search.h"
 
 extern "C" __attribute__((visibility("hidden"))) int icd_internal_fail(int code, const char *fmt, ...);
+extern "C" __attribute__((visibility("hidden"))) int icd_internal_is_view(const icd_index *idx);
 // (icd_search.hip) one launch: the gathered padded slices of a query-sharded search -> the contiguous [nq][k] outputs
 extern "C" __attribute__((visibility("hidden"))) int icd_internal_unpack_query_slices(const void *r_adj, const void *r_ids, const void *r_raw,
         const void *r_lv, int world, long long nq, int k, long long width, void *out_adj, void *out_raw, void *out_ids, void *out_lv, void *stream);
@@ -164,6 +165,7 @@ int icd_group_prepare(icd_index *local, int32_t with_comm, int32_t rank, int32_t
     icd_stats st;
     int rc = icd_index_stats(local, &st);
     if (rc) return rc;
+    if (icd_internal_is_view(local)) return icd_internal_fail(ICD_ERR_UNSUPPORTED, "a view (icd_index_create_view) cannot join a group");
     if (max_nq <= 0 || max_k <= 0 || max_k > st.max_k) return icd_internal_fail(ICD_ERR_INVALID, "max_nq=%d max_k=%d (index max_k %d)", max_nq, max_k, st.max_k);
     if (mode == ICD_GROUP_ROW_SHARD && (max_nq > st.max_nq || (int64_t)world * max_k > 1024))
         return icd_internal_fail(ICD_ERR_INVALID, "row-sharded: max_nq=%d exceeds the index's %d, or world * max_k = %lld > 1024 (merge kernel)", max_nq,

@@ -162,6 +162,7 @@ struct icd_index {
                                     // re-search started its lists at -inf, 0.06-0.07 since it takes finalize's threshold (round 6). With that the two list
                                     // widths meet at k = 50 ... 64 and 16 wins below (profiles/r06_k100_lists.log)
     int64_t n = 0, id_base = 0;
+    long long *row_map = nullptr;   // a view (icd_index_create_view): [n] the parent's global id of every row (finalize.hpp FinArgs::row_map)
     int n_pad = 0;
     int dim = 0;
     int max_nq = 0, max_nq_pad = 0, max_k = 0;
@@ -264,6 +265,15 @@ namespace {
 
 bool valid(icd_index *idx) { return idx && idx->magic == 0x1CD10A3Du; }
 
+}  // namespace
+
+// (icd_group.cpp: a view cannot be a row shard)
+extern "C" __attribute__((visibility("hidden"))) int icd_internal_is_view(const icd_index *idx) {
+    return idx && idx->row_map ? 1 : 0;
+}
+
+namespace {
+
 void free_all(icd_index *x) {
     if (!x) return;
     hipFree(x->corpus); hipFree(x->c16); hipFree(x->levels); hipFree(x->qdev); hipFree(x->q16);
@@ -275,6 +285,7 @@ void free_all(icd_index *x) {
     hipFree(x->o_adj_ids); hipFree(x->o_adj_lv);
     hipFree(x->dbg);
     hipFree(x->pace);
+    hipFree(x->row_map);
     if (x->h_nflag) hipHostFree(x->h_nflag);
     if (x->h_pin) hipHostFree(x->h_pin);
     if (x->ev_nflag) hipEventDestroy(x->ev_nflag);
@@ -569,6 +580,21 @@ __global__ void gather_rows_kernel(const float *src, float *dst, long long strid
     for (int i = threadIdx.x; i < dim / 4; i += blockDim.x) d4[i] = s4[i];
 }
 
+// A view's rows out of its parent (icd_index_create_view): ONE wave per selected row copies it from the parent's fp32 corpus with
+// dwordx4 loads and stores (768 floats = three per lane), lane 0 its level. `map` holds the parent's global ids (validated on the
+// host: strictly increasing, inside the parent), id_base is the parent's.
+__global__ __launch_bounds__(256) void gather_view_rows_kernel(const float *src, const int *src_levels, const long long *map,
+                                                               long long id_base, long long rows, int dim, float *dst, int *dst_levels) {
+    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= rows) return;
+    const long long r = map[i] - id_base;
+    const float4 *s4 = reinterpret_cast<const float4 *>(src + (size_t)r * dim);
+    float4 *d4 = reinterpret_cast<float4 *>(dst + (size_t)i * dim);
+    for (int c = lane; c < dim / 4; c += 64) d4[c] = s4[c];
+    if (dst_levels && lane == 0) dst_levels[i] = src_levels[r];
+}
+
 // Enqueue a search whose queries and outputs are device pointers.
 int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s) {
     const int row_tiles = (int)((x->n + 127) / 128);
@@ -592,7 +618,7 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
     f.qexp = x->qexp; f.rmax = x->rmax_scaled; f.cexp = x->cexp; f.eps_rel = EPS_REL; f.nflag = x->nflag; f.flagged = x->flagged;
     if (use_fast) f.thr0 = x->thr0;
     if (x->cmean) { f.rmax_unc = x->rmax_unc_scaled; f.eps_f32 = 2.0f * (float)x->dim * 5.9604645e-8f; }
-    f.levels = x->levels; f.id_base = x->id_base;
+    f.levels = x->levels; f.id_base = x->id_base; f.row_map = x->row_map;
     f.out_scores = o.scores; f.out_ids = o.ids; f.out_adj = o.adj; f.out_adj_raw = o.adj_raw;
     f.out_adj_ids = o.adj_ids; f.out_adj_levels = o.adj_lv;
 
@@ -1162,9 +1188,14 @@ int icd_device_count(void) {
     return n;
 }
 
-int icd_index_create(const float *corpus, int64_t n, int32_t dim, const int32_t *levels, int64_t id_base,
-                     int32_t device, int32_t max_nq, int32_t max_k, int32_t flags,
-                     icd_index **out) {
+}  // extern "C"
+
+// icd_index_create, and the build of a view (icd_index_create_view): with `view_map` the corpus and levels are the PARENT's device
+// buffers and the index takes rows view_map[i] - id_base of them (gather_view_rows_kernel) instead of a copy of the first n; the rest
+// of the build - fp16 image, centring, workspace, probe - is the same. The caller owns view_map (it becomes the view's row map).
+static int create_index(const float *corpus, int64_t n, int32_t dim, const int32_t *levels, int64_t id_base,
+                        int32_t device, int32_t max_nq, int32_t max_k, int32_t flags, const long long *view_map,
+                        icd_index **out) {
     if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (flags & ~(ICD_CREATE_CORPUS_ON_DEVICE | ICD_CREATE_ROW_ORDER | ICD_CREATE_NO_PROBE | ICD_CREATE_NO_CENTER)) return fail(ICD_ERR_INVALID, "flags=0x%x: unknown bits", flags);
@@ -1204,10 +1235,15 @@ int icd_index_create(const float *corpus, int64_t n, int32_t dim, const int32_t 
     // ST_PAD_ROWS zero rows behind the corpus: the streaming kernel's stages run to the next 256-row boundary
     CR_TRY(dmalloc(&x->corpus, nelem + (size_t)ST_PAD_ROWS * dim));
     CR_TRY(hipMemset(x->corpus + nelem, 0, (size_t)ST_PAD_ROWS * dim * sizeof(float)));
-    CR_TRY(hipMemcpy(x->corpus, corpus, nelem * sizeof(float), corpus_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    if (levels) {
-        CR_TRY(dmalloc(&x->levels, (size_t)n));
-        CR_TRY(hipMemcpy(x->levels, levels, (size_t)n * sizeof(int), corpus_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    if (levels) CR_TRY(dmalloc(&x->levels, (size_t)n));
+    if (view_map) {   // (the parent's rows, gathered on the device: nothing crosses PCIe)
+        hipLaunchKernelGGL(gather_view_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, 0, corpus, levels, view_map,
+                           (long long)id_base, (long long)n, dim, x->corpus, x->levels);
+        CR_TRY(hipGetLastError());
+    } else {
+        CR_TRY(hipMemcpy(x->corpus, corpus, nelem * sizeof(float), corpus_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        if (levels)
+            CR_TRY(hipMemcpy(x->levels, levels, (size_t)n * sizeof(int), corpus_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     }
     CR_TRY(dmalloc(&x->scratch_u32, 4));
     CR_TRY(hipMemset(x->scratch_u32, 0, 4 * sizeof(unsigned)));
@@ -1363,6 +1399,44 @@ int icd_index_create(const float *corpus, int64_t n, int32_t dim, const int32_t 
     }
 #undef CR_TRY
     *out = x;
+    return ICD_OK;
+}
+
+extern "C" {
+
+int icd_index_create(const float *corpus, int64_t n, int32_t dim, const int32_t *levels, int64_t id_base,
+                     int32_t device, int32_t max_nq, int32_t max_k, int32_t flags,
+                     icd_index **out) {
+    return create_index(corpus, n, dim, levels, id_base, device, max_nq, max_k, flags, nullptr, out);
+}
+
+int icd_index_create_view(icd_index *parent, const int64_t *rows, int64_t n_rows, int32_t rows_on_device,
+                          int32_t max_nq, int32_t max_k, int32_t flags, icd_index **out) {
+    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!valid(parent)) return fail(ICD_ERR_STATE, "invalid parent handle");
+    if (!rows || n_rows <= 0) return fail(ICD_ERR_INVALID, "rows NULL or n_rows=%lld: a view holds at least one row", (long long)n_rows);
+    if (n_rows > parent->n) return fail(ICD_ERR_INVALID, "n_rows=%lld exceeds the parent's %lld rows", (long long)n_rows, (long long)parent->n);
+    if (flags & ~(ICD_CREATE_CORPUS_ON_DEVICE | ICD_CREATE_ROW_ORDER | ICD_CREATE_NO_PROBE | ICD_CREATE_NO_CENTER)) return fail(ICD_ERR_INVALID, "flags=0x%x: unknown bits", flags);
+    HIP_TRY(hipSetDevice(parent->device));
+    // the ids are checked (and the parent's id_base added) on the host: a few hundred KB at most, the corpus itself stays on the device
+    std::vector<long long> map((size_t)n_rows);
+    if (rows_on_device) HIP_TRY(hipMemcpy(map.data(), rows, (size_t)n_rows * sizeof(long long), hipMemcpyDeviceToHost));
+    else memcpy(map.data(), rows, (size_t)n_rows * sizeof(long long));
+    for (int64_t i = 0; i < n_rows; ++i) {
+        if (map[i] < 0 || map[i] >= parent->n) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld outside the parent's [0, %lld)", (long long)i, map[i], (long long)parent->n);
+        if (i > 0 && map[i] <= map[i - 1]) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld: row ids must be strictly increasing", (long long)i, map[i]);
+        map[i] += parent->id_base;
+    }
+    long long *dmap = nullptr;
+    HIP_TRY(dmalloc(&dmap, (size_t)n_rows));
+    hipError_t e = hipMemcpy(dmap, map.data(), (size_t)n_rows * sizeof(long long), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(dmap); return fail(ICD_ERR_HIP, "hipMemcpy (row map): %s", hipGetErrorString(e)); }
+    const int rc = create_index(parent->corpus, n_rows, parent->dim, parent->levels, parent->id_base, parent->device, max_nq, max_k,
+                                flags | ICD_CREATE_CORPUS_ON_DEVICE, dmap, out);
+    if (rc) { hipFree(dmap); return rc; }
+    (*out)->row_map = dmap;
+    (*out)->bytes_ws += (size_t)n_rows * sizeof(long long);
     return ICD_OK;
 }
 
@@ -1666,6 +1740,7 @@ int icd_split_bf16x3(int32_t device, const float *x, int64_t rows, int32_t cols,
 
 int icd_index_lookup_levels(icd_index *idx, const int64_t *ids, int64_t count, int32_t *out_levels, void *stream) {
     if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "icd_index_lookup_levels: not supported on a view (its hits carry their levels)");
     std::lock_guard<std::mutex> guard(idx->mu);
     if (!ids || !out_levels || count < 0) return fail(ICD_ERR_INVALID, "bad arguments");
     if (count == 0) return ICD_OK;

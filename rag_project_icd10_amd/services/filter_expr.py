@@ -1,0 +1,348 @@
+"""Milvus-style scalar filter expressions over the corpus's columns (`client.search(..., filter='level >= 2 and code like "E11%"')`).
+
+The documented subset of Milvus's boolean expression grammar that the scalar fields of a row need (tools/build_database.py):
+
+    expr      := or_expr
+    or_expr   := and_expr (("or" | "||") and_expr)*
+    and_expr  := not_expr (("and" | "&&") not_expr)*
+    not_expr  := ("not" | "!") not_expr | "(" expr ")" | predicate
+    predicate := FIELD ("==" | "!=" | "<" | "<=" | ">" | ">=") LITERAL
+               | FIELD ["not"] "in" "[" [LITERAL ("," LITERAL)*] "]"
+               | FIELD "like" STRING
+
+* FIELD: code, main_code, secondary_code, parent_code, category_path, preferred_zh (strings), level (int), has_complication
+  (bool). Strings and bools take `==` and `!=` only; `like` takes strings only.
+* LITERAL: a single- or double-quoted string (backslash escapes the next character), an int, true / false in any case.
+  Keywords (and, or, not, in, like) are matched in any case too.
+* like: "P%" prefix, "%S" suffix, "%X%" infix, no `%` = equality; `_` is an ordinary character.
+
+A syntax error, an unknown field or a type mismatch raises ValueError with the position (0-based, in characters) and the reason.
+Nothing is evaluated by `eval`: the expression is parsed into a small tree and the tree is evaluated over whole column arrays.
+
+`compile(expr)` returns the normalised key of an expression (equal for expressions that differ only in spelling: quotes,
+case of keywords, `&&` / `and`, spaces, redundant parentheses). `select(expr, columns)` returns the sorted int64 row ids that
+match; `Columns` caches its selections per normalised expression (a `Columns` belongs to one generation of the store).
+"""
+from __future__ import annotations
+
+import re
+import threading
+from collections import OrderedDict
+from functools import lru_cache
+from typing import Any, Dict, List, Sequence, Tuple, Union
+
+import numpy as np
+
+STRING_FIELDS = ("code", "main_code", "secondary_code", "parent_code", "category_path", "preferred_zh")
+INT_FIELDS = ("level",)
+BOOL_FIELDS = ("has_complication",)
+FIELDS = STRING_FIELDS + INT_FIELDS + BOOL_FIELDS
+_CMP = ("==", "!=", "<", "<=", ">", ">=")
+_KEYWORDS = ("and", "or", "not", "in", "like", "true", "false")
+
+_TOKEN = re.compile(r"""
+    (?P<ws>\s+)
+  | (?P<str>"(?:[^"\\]|\\.)*"|'(?:[^'\\]|\\.)*')
+  | (?P<int>-?\d+)
+  | (?P<op>==|!=|<=|>=|&&|\|\||<|>|!|\(|\)|\[|\]|,)
+  | (?P<name>[A-Za-z_][A-Za-z0-9_]*)
+""", re.X | re.S)
+
+
+def _error(pos: int, reason: str) -> ValueError:
+    return ValueError(f"filter expression, position {pos}: {reason}")
+
+
+def _tokenize(expr: str) -> List[Tuple[str, Any, int]]:
+    out, pos = [], 0
+    while pos < len(expr):
+        m = _TOKEN.match(expr, pos)
+        if not m:
+            if expr[pos] in "\"'":
+                raise _error(pos, "unterminated string")
+            raise _error(pos, f"unexpected character {expr[pos]!r}")
+        kind = m.lastgroup
+        text = m.group(kind)
+        if kind == "str":
+            out.append(("str", re.sub(r"\\(.)", r"\1", text[1:-1], flags=re.S), pos))
+        elif kind == "int":
+            out.append(("int", int(text), pos))
+        elif kind == "op":
+            out.append(("op", text, pos))
+        elif kind == "name":
+            low = text.lower()
+            if low in ("true", "false"):
+                out.append(("bool", low == "true", pos))
+            elif low in _KEYWORDS:
+                out.append(("kw", low, pos))
+            else:
+                out.append(("name", text, pos))
+        pos = m.end()
+    out.append(("end", None, len(expr)))
+    return out
+
+
+class _Parser:
+    def __init__(self, expr: str):
+        self.toks = _tokenize(expr)
+        self.i = 0
+
+    def peek(self):
+        return self.toks[self.i]
+
+    def take(self):
+        t = self.toks[self.i]
+        self.i += 1
+        return t
+
+    def at(self, kind, *values) -> bool:
+        t = self.peek()
+        return t[0] == kind and (not values or t[1] in values)
+
+    def parse(self):
+        if self.at("end"):
+            raise _error(0, "empty expression")
+        node = self.or_expr()
+        if not self.at("end"):
+            t = self.peek()
+            raise _error(t[2], f"unexpected {self._show(t)} after a complete expression")
+        return node
+
+    def or_expr(self):
+        terms = [self.and_expr()]
+        while self.at("kw", "or") or self.at("op", "||"):
+            self.take()
+            terms.append(self.and_expr())
+        return terms[0] if len(terms) == 1 else ("or", tuple(terms))
+
+    def and_expr(self):
+        terms = [self.not_expr()]
+        while self.at("kw", "and") or self.at("op", "&&"):
+            self.take()
+            terms.append(self.not_expr())
+        return terms[0] if len(terms) == 1 else ("and", tuple(terms))
+
+    def not_expr(self):
+        if self.at("kw", "not") or self.at("op", "!"):
+            self.take()
+            return ("not", self.not_expr())
+        if self.at("op", "("):
+            self.take()
+            node = self.or_expr()
+            t = self.take()
+            if t[:2] != ("op", ")"):
+                raise _error(t[2], f"expected ')', found {self._show(t)}")
+            return node
+        return self.predicate()
+
+    @staticmethod
+    def _show(t) -> str:
+        return "the end of the expression" if t[0] == "end" else repr(t[1]) if t[0] == "str" else str(t[1]).lower() if t[0] == "bool" else str(t[1])
+
+    def literal(self, field: str):
+        t = self.take()
+        if t[0] not in ("str", "int", "bool"):
+            raise _error(t[2], f"expected a literal, found {self._show(t)}")
+        want = "str" if field in STRING_FIELDS else "int" if field in INT_FIELDS else "bool"
+        if t[0] != want:
+            name = {"str": "string", "int": "int", "bool": "bool"}
+            raise _error(t[2], f"type mismatch: {field} is {name[want]}, the literal {self._show(t)} is {name[t[0]]}")
+        return t[1]
+
+    def predicate(self):
+        t = self.take()
+        if t[0] != "name":
+            raise _error(t[2], f"expected a field name, found {self._show(t)}")
+        field, fpos = t[1], t[2]
+        if field not in FIELDS:
+            raise _error(fpos, f"unknown field {field!r} (fields: {', '.join(FIELDS)})")
+        op = self.peek()
+        if op[0] == "op" and op[1] in _CMP:
+            self.take()
+            if field not in INT_FIELDS and op[1] not in ("==", "!="):
+                raise _error(op[2], f"type mismatch: {op[1]} is not defined on {field} (only == and != are)")
+            return ("cmp", field, op[1], self.literal(field))
+        negate = False
+        if op[:2] == ("kw", "not"):
+            self.take()
+            negate = True
+            op = self.peek()
+            if op[:2] != ("kw", "in"):
+                raise _error(op[2], f"expected 'in' after '{field} not', found {self._show(op)}")
+        if op[:2] == ("kw", "in"):
+            self.take()
+            t = self.take()
+            if t[:2] != ("op", "["):
+                raise _error(t[2], f"expected '[' after 'in', found {self._show(t)}")
+            values = []
+            if self.at("op", "]"):
+                self.take()
+            else:
+                while True:
+                    values.append(self.literal(field))
+                    t = self.take()
+                    if t[:2] == ("op", "]"):
+                        break
+                    if t[:2] != ("op", ","):
+                        raise _error(t[2], f"expected ',' or ']' in the list, found {self._show(t)}")
+            # (a canonical list: sorted, without repeats - the normalised key does not depend on how the list was written)
+            return ("in", field, negate, tuple(sorted(set(values), key=lambda v: (str(type(v)), v))))
+        if op[:2] == ("kw", "like"):
+            self.take()
+            if field not in STRING_FIELDS:
+                raise _error(op[2], f"type mismatch: like is not defined on {field} (strings only)")
+            t = self.take()
+            if t[0] != "str":
+                raise _error(t[2], f"like takes a quoted pattern, found {self._show(t)}")
+            pat = t[1]
+            if len(pat) >= 2 and pat[0] == "%" and pat[-1] == "%":
+                how, text = "infix", pat[1:-1]
+            elif pat.startswith("%"):
+                how, text = "suffix", pat[1:]
+            elif pat.endswith("%"):
+                how, text = "prefix", pat[:-1]
+            else:
+                how, text = "eq", pat
+            if "%" in text:
+                raise _error(t[2], f"like pattern {pat!r}: only a leading and / or trailing % is supported")
+            return ("cmp", field, "==", text) if how == "eq" else ("like", field, how, text)
+        raise _error(op[2], f"expected a comparison, 'in', 'not in' or 'like' after {field}, found {self._show(op)}")
+
+
+def _quote(v) -> str:
+    if isinstance(v, bool):
+        return "true" if v else "false"
+    if isinstance(v, int):
+        return str(v)
+    return '"' + v.replace("\\", "\\\\").replace('"', '\\"') + '"'
+
+
+def _key(node) -> str:
+    kind = node[0]
+    if kind == "cmp":
+        return f"{node[1]} {node[2]} {_quote(node[3])}"
+    if kind == "in":
+        return f"{node[1]} {'not in' if node[2] else 'in'} [{', '.join(_quote(v) for v in node[3])}]"
+    if kind == "like":
+        pat = {"prefix": "{}%", "suffix": "%{}", "infix": "%{}%"}[node[2]].format(node[3])
+        return f"{node[1]} like {_quote(pat)}"
+    if kind == "not":
+        return f"not ({_key(node[1])})"
+    return f" {kind} ".join(f"({_key(t)})" for t in node[1])
+
+
+@lru_cache(maxsize=512)
+def _parse(expr: str):
+    if not isinstance(expr, str):
+        raise ValueError(f"filter expression must be a string, not {type(expr).__name__}")
+    node = _Parser(expr).parse()
+    return node, _key(node)
+
+
+def parse(expr: str):
+    """the expression's tree (nested tuples); raises ValueError"""
+    return _parse(expr)[0]
+
+
+def compile(expr: str) -> str:   # noqa: A001 (the name the issue gives the entry point)
+    """the normalised key of `expr`; raises ValueError on a syntax error, an unknown field or a type mismatch"""
+    return _parse(expr)[1]
+
+
+class Columns:
+    """The eight filter fields of a store's rows as column arrays, built once per generation of the store, with a bounded cache
+    of selections keyed by the normalised expression. `generation` is the store's mutation counter when the columns were built."""
+
+    CACHE = 64
+
+    def __init__(self, arrays: Dict[str, np.ndarray], generation: int = 0):
+        self.arrays = arrays
+        self.generation = generation
+        self.n = len(next(iter(arrays.values()))) if arrays else 0
+        self._sel: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        self._lock = threading.Lock()
+
+    @classmethod
+    def from_records(cls, records: Sequence[Dict[str, Any]], generation: int = 0) -> "Columns":
+        arrays: Dict[str, np.ndarray] = {}
+        for f in STRING_FIELDS:
+            arrays[f] = np.array(["" if r.get(f) is None else str(r.get(f)) for r in records], dtype=str) if len(records) \
+                else np.zeros(0, dtype="<U1")
+        arrays["level"] = np.fromiter((int(r.get("level", 1)) for r in records), dtype=np.int64, count=len(records))
+        arrays["has_complication"] = np.fromiter((bool(r.get("has_complication", False)) for r in records), dtype=bool, count=len(records))
+        return cls(arrays, generation)
+
+    def __getitem__(self, field: str) -> np.ndarray:
+        return self.arrays[field]
+
+    def select(self, expr: str) -> np.ndarray:
+        node, key = _parse(expr)
+        with self._lock:
+            hit = self._sel.get(key)
+            if hit is not None:
+                self._sel.move_to_end(key)
+                return hit
+        rows = np.flatnonzero(_eval(node, self.arrays, self.n)).astype(np.int64)
+        rows.setflags(write=False)
+        with self._lock:
+            self._sel[key] = rows
+            while len(self._sel) > self.CACHE:
+                self._sel.popitem(last=False)
+        return rows
+
+
+def _eval(node, cols, n: int) -> np.ndarray:
+    kind = node[0]
+    if kind == "and":
+        m = _eval(node[1][0], cols, n)
+        for t in node[1][1:]:
+            m = m & _eval(t, cols, n)
+        return m
+    if kind == "or":
+        m = _eval(node[1][0], cols, n)
+        for t in node[1][1:]:
+            m = m | _eval(t, cols, n)
+        return m
+    if kind == "not":
+        return ~_eval(node[1], cols, n)
+    col = cols[node[1]]
+    if kind == "cmp":
+        op, v = node[2], node[3]
+        if op == "==":
+            return np.asarray(col == v, dtype=bool).reshape(n)
+        if op == "!=":
+            return np.asarray(col != v, dtype=bool).reshape(n)
+        return {"<": np.less, "<=": np.less_equal, ">": np.greater, ">=": np.greater_equal}[op](col, v)
+    if kind == "in":
+        m = np.isin(col, np.array(node[3], dtype=col.dtype)) if node[3] else np.zeros(n, dtype=bool)
+        return ~m if node[2] else m
+    if kind == "like":
+        how, s = node[2], node[3]
+        if how == "prefix":
+            return np.char.startswith(col, s) if n else np.zeros(0, bool)
+        if how == "suffix":
+            return np.char.endswith(col, s) if n else np.zeros(0, bool)
+        return np.char.find(col, s) >= 0 if n else np.zeros(0, bool)
+    raise AssertionError(kind)
+
+
+def select(expr: str, columns: Union[Columns, Dict[str, np.ndarray]]) -> np.ndarray:
+    """sorted int64 row ids whose columns satisfy `expr`. `columns`: a Columns (selections cached per normalised expression) or a
+    dict field -> array of equal length (evaluated every time). Raises ValueError on a bad expression."""
+    if isinstance(columns, Columns):
+        return columns.select(expr)
+    node = parse(expr)
+    n = len(next(iter(columns.values()))) if columns else 0
+    cols = {f: (np.asarray(c) if f not in STRING_FIELDS else np.asarray(c, dtype=str)) for f, c in columns.items()}
+    missing = [f for f in _fields_of(node) if f not in cols]
+    if missing:
+        raise ValueError(f"filter expression needs column(s) {missing} that were not given")
+    return np.flatnonzero(_eval(node, cols, n)).astype(np.int64)
+
+
+def _fields_of(node) -> List[str]:
+    if node[0] in ("and", "or"):
+        return [f for t in node[1] for f in _fields_of(t)]
+    if node[0] == "not":
+        return _fields_of(node[1])
+    return [node[1]]

@@ -13,18 +13,23 @@ Lite file. `MILVUS_MODE=remote` (a gRPC client of a Milvus server, :84-111) is o
 There is no CPU search path: without libicdsearch.so / an MI355X, loading the collection fails and
 `search` returns [] exactly as the reference does on engine errors (:318-320).
 
-Additive: `search_batch` (many queries per call, numpy or device tensors).
+Additive: `search_batch` (many queries per call, numpy or device tensors); a Milvus `filter` expression on `search` and
+`search_batch` (services/filter_expr.py): the selection's rows become a VIEW of the index (_native.IcdIndex.view, built on the
+device), cached per (normalised expression, store generation) with LRU eviction (`ICD_FILTER_VIEWS`, default 8).
 """
 from __future__ import annotations
 
 import datetime
 import logging
 import os
+import threading
+from collections import OrderedDict
 from typing import Any, Dict, List, Optional
 
 import numpy as np
 
 from ..corpus_store import CorpusStore
+from . import filter_expr
 
 logger = logging.getLogger(__name__)
 
@@ -42,6 +47,14 @@ class MilvusService:
         self._index = None          # rag_project_icd10_amd._native.IcdIndex
         self._index_rows = 0
         self._row_tags = None
+        self._index_gen = -1        # the store generation the index was built from
+        # filtered search: (normalised expression, store generation) -> view of the index over the selected rows, least recently
+        # used first. NER and search run on different threads: every access holds the lock. An evicted view is only dropped from
+        # the cache: a search that still holds it keeps it alive, the last reference closes it.
+        self._views: "OrderedDict[tuple, Any]" = OrderedDict()
+        self._views_lock = threading.Lock()
+        self._max_views = max(1, int(os.getenv("ICD_FILTER_VIEWS", "8")))
+        self._columns = None        # filter_expr.Columns of the store generation they were built from (rebuilt when it moves on)
         self._connect()
         self._setup_collection()
 
@@ -106,7 +119,7 @@ class MilvusService:
             self._drop_index()
             self._loaded = True
             return
-        if self._index is not None and self._index_rows == n:
+        if self._index is not None and self._index_rows == n and self._index_gen == self.client.generation:
             self._loaded = True
             return
         from .._native import IcdIndex
@@ -115,13 +128,16 @@ class MilvusService:
         self._index = IcdIndex(self.client.matrix(), self.client.levels(), device=cfg["gpu_device"],
                                max_nq=cfg["max_batch"], max_k=cfg["max_k"])
         self._index_rows = n
+        self._index_gen = self.client.generation
         self._loaded = True
 
     def _drop_index(self):
+        self._clear_views()
         if self._index is not None:
             self._index.close()
         self._index = None
         self._index_rows = 0
+        self._index_gen = -1
         self._row_tags = None
         self._loaded = False
 
@@ -171,6 +187,7 @@ class MilvusService:
             if mat.ndim != 2 or mat.shape[1] != self.dimension:
                 raise ValueError(f"vector dimension {mat.shape} != {self.dimension}")
             self.client.append(rows, mat)
+            self._clear_views()
             self._loaded = self._index is not None and self._index_rows == self.client.count
             return True
         except Exception as exc:
@@ -181,16 +198,77 @@ class MilvusService:
     def _ready_index(self):
         if self.client is None or not self.client.exists():
             return None
-        if self._index is None or self._index_rows != self.client.count:
+        if self._index is None or self._index_rows != self.client.count or self._index_gen != self.client.generation:
             self._load_collection_to_memory()
         return self._index
 
-    def search(self, query_vector: np.ndarray, top_k: int = 10) -> List[Dict[str, Any]]:
+    # ---- filtered search ------------------------------------------------------------------------------------------------
+    def _clear_views(self):
+        with self._views_lock:
+            self._views.clear()
+
+    def _filter_columns(self) -> "filter_expr.Columns":
+        gen = self.client.generation
+        cols = self._columns
+        if cols is None or cols.generation != gen or cols.n != self.client.count:
+            cols = filter_expr.Columns.from_records(self.client.records, gen)
+            self._columns = cols
+        return cols
+
+    def filter_rows(self, expr: str) -> np.ndarray:
+        """sorted int64 row ids (= hit ids) of the rows that satisfy the Milvus filter expression `expr` (services/filter_expr.py);
+        raises ValueError on a bad expression"""
+        filter_expr.compile(expr)
+        if self.client is None or not self.client.exists():
+            return np.zeros(0, np.int64)
+        return self._filter_columns().select(expr)
+
+    def _filtered_index(self, expr: str):
+        """(index, rows) to search for `expr`: the index itself when every row is selected, None when none is, else the
+        selection's view (cached per normalised expression and store generation). Raises ValueError on a bad expression."""
+        key = filter_expr.compile(expr)
+        index = self._ready_index()
+        if index is None:
+            return None, np.zeros(0, np.int64)
+        rows = self.filter_rows(expr)
+        if len(rows) == 0:
+            return None, rows
+        if len(rows) == index.n:
+            return index, rows
+        ck = (key, self.client.generation)
+        with self._views_lock:
+            view = self._views.get(ck)
+            if view is not None and not view.closed:
+                self._views.move_to_end(ck)
+                return view, rows
+            view = index.view(rows)
+            self._views[ck] = view
+            while len(self._views) > self._max_views:
+                self._views.popitem(last=False)
+        return view, rows
+
+    def filter_views(self) -> List[Dict[str, Any]]:
+        """the cached filter views, least recently used first: expression (normalised), rows, HBM bytes"""
+        with self._views_lock:
+            items = list(self._views.items())
+        out = []
+        for (key, gen), view in items:
+            if view.closed:
+                continue
+            st = view.stats()
+            out.append({"expression": key, "rows": int(st["n"]), "generation": gen,
+                        "bytes": int(st["bytes_corpus_f32"] + st["bytes_corpus_f16"] + st["bytes_workspace"])})
+        return out
+
+    def search(self, query_vector: np.ndarray, top_k: int = 10, filter: Optional[str] = None) -> List[Dict[str, Any]]:   # noqa: A002 (Milvus's name)
         try:
             if self.client is None or not self.client.exists():
                 logger.error("集合 %s 不存在", self.collection_name)
                 return []
-            index = self._ready_index()
+            if filter is not None:
+                index, _rows = self._filtered_index(filter)
+            else:
+                index = self._ready_index()
             if index is None:
                 return []
             # (the reference sends data=[query_vector.tolist()], :282: a plain list has no .tolist and lands in the except below,
@@ -228,13 +306,21 @@ class MilvusService:
             })
         return out
 
-    def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False):
+    def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False, filter: Optional[str] = None):   # noqa: A002
         """Additive: many queries in one call. query_vectors: [nq, dim] numpy array or torch CUDA
         tensor. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order
-        `search` returns hits; or, with as_dicts=True, a list of `search`-shaped hit lists."""
+        `search` returns hits; or, with as_dicts=True, a list of `search`-shaped hit lists.
+        filter: a Milvus filter expression - only the rows it selects are ranked (hit ids stay the corpus's row ids); a selection
+        shorter than top_k pads the lists with id -1, score -inf, level 0. Raises ValueError on a bad expression."""
+        if filter is not None:
+            filter_expr.compile(filter)   # (a bad expression raises before anything is loaded)
         index = self._ready_index()
         if index is None:
             raise RuntimeError(f"collection {self.collection_name} is empty or missing")
+        if filter is not None:
+            index, _rows = self._filtered_index(filter)
+            if index is None:   # nothing selected: no device call
+                return self._empty_hits(query_vectors, int(top_k), as_dicts)
         # (large batches on a corpus of tight families of near-identical rows - ICD sibling codes - are handled inside the
         #  library: a second coarse pass over the queries the first could not certify, and from the next large batch on the
         #  wider partition right away; include/icd_search.h icd_stats.last_second_pass / wide_mode)
@@ -244,6 +330,19 @@ class MilvusService:
         if hasattr(adj, "cpu"):
             adj, raw, ids = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy()
         return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
+
+    def _empty_hits(self, query_vectors, k: int, as_dicts: bool):
+        nq = 1 if getattr(query_vectors, "ndim", 2) == 1 else int(query_vectors.shape[0])
+        if as_dicts:
+            return [[] for _ in range(nq)]
+        if hasattr(query_vectors, "is_cuda") and query_vectors.is_cuda:
+            import torch
+            dev = query_vectors.device
+            return (torch.full((nq, k), float("-inf"), dtype=torch.float64, device=dev),
+                    torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev),
+                    torch.full((nq, k), -1, dtype=torch.int64, device=dev), torch.zeros((nq, k), dtype=torch.int32, device=dev))
+        return (np.full((nq, k), -np.inf, np.float64), np.full((nq, k), -np.inf, np.float32), np.full((nq, k), -1, np.int64),
+                np.zeros((nq, k), np.int32))
 
     # ---- admin (same keys as the reference) -------------------------------------------------------------------------
     def get_collection_stats(self) -> Dict[str, Any]:
@@ -314,6 +413,7 @@ class MilvusService:
             if not self.client:
                 return {"success": True, "message": "客户端已经断开"}
             release_result = self.release_collection()
+            self._clear_views()
             self.client.close()
             self.client = None
             return {"success": True, "message": "Milvus连接已断开，资源已清理", "release_result": release_result}

@@ -14,7 +14,7 @@ from __future__ import annotations
 import gc
 import logging
 import threading
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 
@@ -77,7 +77,9 @@ class MultiDiagnosisService:
         self.confidence_service = MultiDimensionalConfidenceService(
             embedding_service=embedding_service, ner_service=ner_service, hierarchical_similarity_service=self.hierarchical_similarity)
 
-    def match_multiple_diagnoses(self, text: str, top_k: int = 5) -> Dict[str, Any]:
+    def match_multiple_diagnoses(self, text: str, top_k: int = 5, filter: Optional[str] = None) -> Dict[str, Any]:   # noqa: A002
+        """filter: a Milvus filter expression (services/filter_expr.py) - every diagnosis is searched among the rows it selects only
+        (the search of 2 top_k, on the device path and the host path alike); None ranks the whole corpus"""
         enhanced = self.text_processor.extract_diagnoses_enhanced(text)
         diagnoses = [d["text"] for d in enhanced]
         mode = self.text_processor.get_processing_mode()
@@ -95,7 +97,7 @@ class MultiDiagnosisService:
             # the whole request stays on the device - encode -> search(2 top_k) -> rescoring -> top_k winners come back.
             # Same DiagnosisMatch objects as the host path below (tests/test_gpu_parity.py, all 1 000 golden strings).
             try:
-                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k)
+                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, filter=filter)
             except Exception as exc:
                 logger.error("device-side request path failed (%s): host path", exc)
                 matches = None
@@ -106,7 +108,7 @@ class MultiDiagnosisService:
             ner_job = self._ner_pool().submit(self._entities_of, diagnoses)
             try:
                 vectors = self._embed_diagnoses(diagnoses)
-                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, vectors=vectors, entities=ner_job)
+                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, vectors=vectors, entities=ner_job, filter=filter)
             except Exception as exc:
                 logger.error("device-side request path with entities failed (%s): host path", exc)
                 matches = None
@@ -124,7 +126,8 @@ class MultiDiagnosisService:
         if vectors is None:
             vectors = self._embed_diagnoses(diagnoses)
         try:
-            hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True)
+            hit_lists = (self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True) if filter is None
+                         else self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, filter=filter))
         except Exception as exc:
             logger.error("batch search failed: %s", exc)
             hit_lists = [[] for _ in diagnoses]
@@ -193,7 +196,8 @@ class MultiDiagnosisService:
         return entities
 
     def match_diagnoses_batch(self, diagnoses: List[str], top_k: int = 5, vectors=None,
-                              confidence_statistics: bool = False, entities=None, confidence: str = None) -> List[DiagnosisMatch]:
+                              confidence_statistics: bool = False, entities=None, confidence: str = None,
+                              filter: Optional[str] = None) -> List[DiagnosisMatch]:   # noqa: A002
         """Additive (row N2): embed -> search(2 top_k) -> level reweight -> hierarchical rescoring for MANY diagnosis
         strings with everything between the tokenizer and the final top_k on the GPU: one encoder batch, one search_batch,
         one rescoring launch; only the top_k winners per string come back and become Candidate objects. Same results as
@@ -206,7 +210,9 @@ class MultiDiagnosisService:
         (HierarchicalSimilarityService.query_params_entities, icd_hier_rescore_entities).
         confidence: "match" / "multidimensional" (None: the service's mode). "multidimensional" scores every match with
         MultiDimensionalConfidenceService.comprehensive_confidence_batch - the cosine, the score statistics and the terminology
-        scan as one launch each - equal to _match_from_hits' per-call scores except the cosine (sklearn's, to ~1e-14)."""
+        scan as one launch each - equal to _match_from_hits' per-call scores except the cosine (sklearn's, to ~1e-14).
+        filter: a Milvus filter expression: the search of 2 top_k ranks the rows it selects only (MilvusService.search_batch);
+        the rescoring, the entities and both confidence modes then run unchanged on those hits (ids stay the corpus's row ids)."""
         from .hierarchical_similarity_service import trusted_factors_row
         confidence = self.confidence if confidence is None else confidence
         if confidence not in CONFIDENCE_MODES:
@@ -221,7 +227,8 @@ class MultiDiagnosisService:
         hs = self.hierarchical_similarity
         if entities is None:
             qps = [hs.query_params(d) for d in diagnoses]   # ([1] is the context relevance the factors report)
-        adj, raw, ids, _lv = self.milvus_service.search_batch(vectors, top_k * 2)
+        adj, raw, ids, _lv = (self.milvus_service.search_batch(vectors, top_k * 2) if filter is None
+                              else self.milvus_service.search_batch(vectors, top_k * 2, filter=filter))
         if entities is not None:
             if hasattr(entities, "result"):   # (the NER worker's Future: the classifier ran beside the embedding and the search)
                 entities = entities.result()
