@@ -402,7 +402,10 @@ int icd_encoder_create(int32_t device, const icd_encoder_desc *desc, icd_encoder
     // enc_linear_kernel: four waves cover the hidden size (192 or 256 columns of K each); embed / pool: 3 or 4 x 256 columns
     if (d.hidden != 768 && d.hidden != 1024) return fail(ICD_ERR_UNSUPPORTED, "hidden=%d (the small-input encoder is instantiated for 768 and 1024)", d.hidden);
     const int kw = d.hidden == 1024 ? 256 : 192;   // columns of K per wave (four waves cover the hidden size)
-    if (d.inter < 4 * kw || d.inter % (4 * kw) != 0 || d.inter > 16 * kw) return fail(ICD_ERR_UNSUPPORTED, "inter=%d (a multiple of %d, at most %d: four K slices of at most four waves)", d.inter, 4 * kw, 16 * kw);
+    // the FFN-down GEMM: K = inter in ENC_SLABS slices of inter / kw / ENC_SLABS waves each, and its epilogue maps the 16 x 16
+    // outputs of a work-group onto 256 threads - four waves exactly, so inter = 16 kw (4 x hidden). With fewer waves (inter 2 or
+    // 3 x hidden) a quarter or half of the outputs would never be written.
+    if (d.inter != 16 * kw) return fail(ICD_ERR_UNSUPPORTED, "inter=%d (the FFN-down GEMM is written for inter = 4 x hidden = %d)", d.inter, 16 * kw);
     if (d.vocab < 1 || d.max_pos < 1 || d.pos_offset < 0 || d.pos_offset >= d.max_pos) return fail(ICD_ERR_INVALID, "vocab=%d max_pos=%d pos_offset=%d", d.vocab, d.max_pos, d.pos_offset);
     if (!(d.ln_eps > 0.0f)) return fail(ICD_ERR_INVALID, "ln_eps=%g", (double)d.ln_eps);
     if (d.arithmetic != ICD_ENCODER_ARITH_FP32 && d.arithmetic != ICD_ENCODER_ARITH_BF16X3) return fail(ICD_ERR_INVALID, "arithmetic=%d (ICD_ENCODER_ARITH_FP32 or _BF16X3)", d.arithmetic);
