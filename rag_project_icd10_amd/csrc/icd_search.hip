@@ -113,11 +113,9 @@ constexpr float EPS_REL = 1.2e-3f;
 constexpr size_t PACE_WORDS = (size_t)1 << 18;   // arrival counters of a paced coarse sweep: classes x epochs (1 MB)
 constexpr size_t COARSE_CACHED_IMAGE_BYTES = (size_t)96 << 20;   // fp16 images up to this size take CF_CACHED_VAR (both corpus copies then fit the 256 MiB Infinity Cache)
 constexpr int FAST_MAX_K = 100;      // the rescoring window holds up to 256 candidates (four per lane): k + the rows inside 2 eps of the k-th
-constexpr int COARSE_MAX_P = 32;     // P * KP <= FIN_MAX_CAND
-constexpr int PASS2_CHUNKS = 20;     // second coarse pass (and wide_mode): about this many candidate lists per query
-constexpr int PASS2_MAX_P = 24;      // ... at most this many (workspace); 24 x 16 candidates < FIN_MAX_CAND
+// (COARSE_MAX_P, PASS2_CHUNKS, PASS2_MAX_P, PASS2_BELOW: the list planner's, flat_partition.hpp)
+static_assert(FLAT_TILE_ROWS == CO_BN, "flat_partition.hpp plans tiles of CO_BN rows");
 constexpr int PASS2_SKIP = 24;       // ... and leaves this many flagged queries (or fewer) to the streaming kernel: 35 us per 8
-constexpr int PASS2_BELOW = 320;     // the second pass runs when the first gave a query fewer candidates than this
 constexpr int SPARSE_DISARM_AFTER = 96; // the streaming kernel's two fallback launches are dropped after this many consecutive searches with NO flagged query (doubles at every incident)
 constexpr int PASS2_DISARM_AFTER = 4; // the second pass's two launches are dropped after this many consecutive searches that needed neither
 constexpr int WIDE_MIN_NQ = 2048;    // "large batch": below it a query has 16+ lists anyway
@@ -437,8 +435,8 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
     const int n = (int)x->n;
     const int per_max = FIN_MAX_CAND / KP;                       // lists one reduce wave can merge
     const int p_cap = FIN_MAX_CAND / KP;                         // lists finalize<false> can merge
-    const int nwg_max = std::max(1, std::min(x->num_cu, 256));
-    int rows_per_wg = ((n + nwg_max - 1) / nwg_max + 255) / 256 * 256;
+    const int rows_per_wg = stream_rows_per_wg(n, x->num_cu);   // (flat_partition.hpp)
+    if ((long long)rows_per_wg * x->dim * 4 > FLAT_DESC_MAX_BYTES) return fail(ICD_ERR_UNSUPPORTED, "stream kernel: %d rows x dim %d per work-group exceed its buffer descriptor", rows_per_wg, x->dim);
     const int nwg = (n + rows_per_wg - 1) / rows_per_wg;
     int plan[8];
     const int levels = plan_reduce_levels(4 * nwg, per_max, p_out, p_cap, plan);
@@ -485,11 +483,10 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
 // rounded up to whole 8-row LDS-DMA pieces (at most 64); the ring takes the stages that fit next to the candidate buffers.
 struct StreamOnePlan { int rps, rows_per_wg, nwg, stages; };
 inline bool plan_stream_one(int n, int dim, int num_cu, int qb, int cap_entries, StreamOnePlan *p) {
-    const int ncu = std::max(1, std::min(num_cu, 256));
-    const int per_cu = (n + ncu - 1) / ncu;
-    const int rps = std::min(64, ((per_cu + 3) / 4 + 7) / 8 * 8);
-    const int steps = (per_cu + 4 * rps - 1) / (4 * rps);
-    p->rps = rps; p->rows_per_wg = 4 * rps * steps; p->nwg = (n + p->rows_per_wg - 1) / p->rows_per_wg;
+    const StreamOneRows g = plan_stream_one_rows(n, num_cu);   // (flat_partition.hpp)
+    const int rps = g.rps;
+    p->rps = g.rps; p->rows_per_wg = g.rows_per_wg; p->nwg = g.nwg;
+    if ((long long)g.rows_per_wg * dim * 4 > FLAT_DESC_MAX_BYTES) return false;   // (the work-group's buffer descriptor)
     const size_t fixed = (size_t)qb * dim * 4 + (size_t)4 * qb * cap_entries * 8;
     if (fixed + (size_t)4 * 2 * rps * 128 > (size_t)LDS_LIMIT) return false;
     p->stages = (int)std::min<size_t>(8, ((size_t)LDS_LIMIT - fixed) / ((size_t)4 * rps * 128));
@@ -885,65 +882,32 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
         CoarseFlatArgs a{};
         a.q16 = x->q16; a.c16 = x->c16; a.nq = nq; a.n = (int)x->n; a.n_pad = ctiles * 128; a.ctiles = ctiles;
         a.total_units = mtc * ctiles;
-        // A query's lists should number at least two of comparable length: the certificate compares against the
-        // largest score any list may have dropped, and with one list that is the query's own 16th best (8 % of
-        // Gaussian queries then fail, profiles/r01_sizes_before_pmin2.log); with two or more it is about rank 32.
-        a.list_tiles = std::max(1, (ctiles + 1) / 2);
-        // Larger k: every list keeps KP candidates and ends on its own KP-th best, so the bound the certificate
-        // compares the k-th best against sits near rank KP P / 2 of the whole corpus: ask for about k / 4 lists of 16.
-        // Above k = 64 (dim 768) the lists keep 24: a query fails the certificate when ONE list holds more than KP of
-        // the ~1.3 k rows around its top-k - with 16 that happens to 3-5 of 10 000 queries at k = 100 and costs an exact
-        // corpus sweep per batch (0.34 ms); with 24 per list and about k / 6 lists it did not happen. The wider lists make
-        // the coarse pass ~20 % slower (lower thresholds, more appends), so they only pay where that sweep is the larger
-        // cost: k = 100 1.69 -> 1.54 ms, k = 32 would go 0.87 -> 0.99 (profiles/r02_tile_planner_and_shapes.log).
-        if (wide_lists) a.list_tiles = std::max(1, std::min(a.list_tiles, ctiles / ((k + 5) / 6)));
-        else if (k > 8) a.list_tiles = std::max(1, std::min(a.list_tiles, ctiles / ((k + 3) / 4)));
         // The bootstrap level (6th best of the first boot_tiles * 128 rows of a list) must stay far below the k-th best
         // of the whole corpus or the list's bound lands inside the window: fewer tiles for larger k (measured at
         // k = 48 with 8 tiles: 1.6 % of the queries uncertified).
         a.boot_tiles = std::max(1, std::min(CO_BOOT_TILES, 96 / std::max(1, k)));
         a.sparse_from = CO_SPARSE_FROM;
-        int U = plan.U;
+        // ---- the list plan of both passes (flat_partition.hpp plan_coarse_lists): lists per query, tiles per list and
+        // per work-group. No list is longer than the kernel's per-list buffer descriptor reaches (flat_max_list_tiles).
+        CoarsePlanIn pin{};
+        pin.mtc = mtc; pin.ctiles = ctiles; pin.U = plan.U; pin.nq = nq; pin.k = k;
+        pin.kp = kp_c; pin.kp2 = CO_KP; pin.max_cand = FIN_MAX_CAND;
+        pin.wide_lists = wide_lists; pin.wide_now = wide_now; pin.chunks_override = x->chunks_override;
+        pin.pass2 = x->pass2_enabled && x->p2_clean < PASS2_DISARM_AFTER && x->part2_s;
+        pin.partc_cap = (long long)x->partc_cap; pin.part2_cap = (long long)x->part2_cap;
+        pin.max_list_tiles = flat_max_list_tiles(x->dim);
 #ifdef ICD_ABLATE
-        if (const char *e = getenv("ICD_FLAT_U")) U = std::max(U, atoi(e));   // A/B: tiles per work-group
-        if (const char *e = getenv("ICD_FLAT_LIST")) a.list_tiles = std::max(1, atoi(e));   // A/B: tiles per list
+        if (const char *e = getenv("ICD_FLAT_U")) pin.U = std::max(pin.U, atoi(e));   // A/B: tiles per work-group
+        if (const char *e = getenv("ICD_FLAT_LIST")) pin.list_override = std::max(1, atoi(e));   // A/B: tiles per list
         if (const char *e = getenv("ICD_FLAT_BOOT")) a.boot_tiles = std::max(0, atoi(e));   // A/B: bootstrap tiles
         if (const char *e = getenv("ICD_FLAT_SPARSE")) a.sparse_from = std::max(0, atoi(e));   // A/B: first tile of a list with the group pre-filter
 #endif
-        if (x->chunks_override > 0) {   // test hook: about `chunks` lists per query, every work-group's run one list
-            U = std::max(1, (ctiles + x->chunks_override - 1) / x->chunks_override);
-            a.list_tiles = ctiles;
-        } else if (wide_now) {
-            // Wide mode: about PASS2_CHUNKS lists per query, cut out of the SAME long sweeps as the narrow plan (a work-group
-            // keeps its queries in registers and its ring running over ~100 tiles and closes a list every 16). Until round 4
-            // every list was its own work-group (1 576 of them, six rounds on 256 CUs, each loading its queries and refilling
-            // the ring): 0.67 against 0.60 ms on the family corpus, same lists (profiles/r04_wide_long_sweeps.log).
-            a.list_tiles = std::max(1, (ctiles + PASS2_CHUNKS - 1) / PASS2_CHUNKS);
-#ifdef ICD_ABLATE
-            if (getenv("ICD_WIDE_SHORT_SWEEP")) { U = a.list_tiles; a.list_tiles = ctiles; }   // A/B: round 3's partition
-#endif
-        }
-        auto lists_needed_lt = [&](int u, int list_tiles) {   // the largest number of lists of any query tile (same rule as the kernel)
-            int worst = 0;
-            for (int m = 0; m < mtc; ++m) {
-                const long long m1 = (long long)(m + 1) * ctiles;
-                const int wl = (int)((m1 - 1) / u);   // last work-group touching the query tile
-                worst = std::max(worst, flat_first_ordinal(m, wl + 1, ctiles, u, list_tiles));
-            }
-            return worst;
-        };
-        auto lists_needed = [&](int u) { return lists_needed_lt(u, a.list_tiles); };
-        int P = lists_needed(U);
-        // too many lists for the workspace or for finalize's candidate window: longer lists first (the balance of the
-        // partition is untouched), more tiles per work-group only when a list already spans the corpus
-        while (P > COARSE_MAX_P || P * kp_c > FIN_MAX_CAND || (size_t)nq * P * kp_c > x->partc_cap) {
-            if (a.list_tiles < ctiles) a.list_tiles = std::min(ctiles, a.list_tiles + std::max(1, a.list_tiles / 8));
-            else if (U < ctiles) U = std::min(ctiles, U + std::max(1, U / 4));
-            else break;
-            P = lists_needed(U);
-        }
-        if (P > COARSE_MAX_P || P * kp_c > FIN_MAX_CAND || (size_t)nq * P * kp_c > x->partc_cap)
-            return fail(ICD_ERR_INVALID, "coarse workspace too small for nq=%d (lists per query %d)", nq, P);
+        const CoarsePlan cp = plan_coarse_lists(pin);
+        if (!cp.ok)
+            return fail(ICD_ERR_UNSUPPORTED, "coarse pass: no list plan for n=%lld dim=%d nq=%d k=%d (lists per query %d, at most %d tiles per list)",
+                        (long long)x->n, x->dim, nq, k, cp.P, pin.max_list_tiles);
+        const int U = cp.U, P = cp.P;
+        a.list_tiles = cp.list_tiles;
         a.units_per_wg = U; a.P = P;
         {
             a.pos_period = flat_class_period(U, ctiles);
@@ -973,31 +937,23 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
         // one list (the shape icd_index_set_chunks asks for). Everything the host must know is independent of how many
         // queries will be flagged: U2, the list slots per query (worst case over all query tiles of the full batch), the
         // logical work-group count of a full batch. The kernel sizes the sweep from the flagged count on the device.
-        if (x->pass2_enabled && x->p2_clean < PASS2_DISARM_AFTER && P * kp_c < PASS2_BELOW && x->part2_s) {
-            int U2 = std::max(1, (ctiles + PASS2_CHUNKS - 1) / PASS2_CHUNKS);
-            p2 = lists_needed_lt(U2, ctiles);
-            while ((p2 > PASS2_MAX_P || (size_t)nq * p2 * CO_KP > x->part2_cap) && U2 < ctiles) {
-                U2 = std::min(ctiles, U2 + std::max(1, U2 / 8));
-                p2 = lists_needed_lt(U2, ctiles);
+        if (cp.P2 > 0) {
+            const int U2 = cp.U2;
+            p2 = cp.P2;
+            a2 = a;
+            a2.nq_ptr = nullptr; a2.qlist = nullptr;   // (set at the launch: which flag word / list feeds it)
+            a2.units_per_wg = U2; a2.list_tiles = cp.list_tiles2; a2.P = p2;
+            a2.boot_tiles = a.boot_tiles;
+            a2.pos_period = flat_class_period(U2, ctiles);
+            nwg2 = (int)(((long long)mtc * ctiles + U2 - 1) / U2);
+            {
+                const int members = nwg2 / std::max(1, a2.pos_period);
+                const int split = (members + 11) / 12;
+                if (a2.pos_period > 0 && a2.pos_period < (1 << 20)) a2.pos_period *= std::max(1, split);
             }
-            if (p2 <= PASS2_MAX_P && (size_t)nq * p2 * CO_KP <= x->part2_cap && p2 * CO_KP > P * kp_c) {
-                a2 = a;
-                a2.nq_ptr = nullptr; a2.qlist = nullptr;   // (set at the launch: which flag word / list feeds it)
-                a2.units_per_wg = U2; a2.list_tiles = ctiles; a2.P = p2;
-                a2.boot_tiles = a.boot_tiles;
-                a2.pos_period = flat_class_period(U2, ctiles);
-                nwg2 = (int)(((long long)mtc * ctiles + U2 - 1) / U2);
-                {
-                    const int members = nwg2 / std::max(1, a2.pos_period);
-                    const int split = (members + 11) / 12;
-                    if (a2.pos_period > 0 && a2.pos_period < (1 << 20)) a2.pos_period *= std::max(1, split);
-                }
-                a2.nwg_virtual = nwg2;
-                a2.part_scores = x->part2_s; a2.part_rows = x->part2_r; a2.bounds = x->part2_b;
-                a2.shared_thr = x->shared_thr + x->max_nq_pad;
-            } else {
-                p2 = 0;
-            }
+            a2.nwg_virtual = nwg2;
+            a2.part_scores = x->part2_s; a2.part_rows = x->part2_r; a2.bounds = x->part2_b;
+            a2.shared_thr = x->shared_thr + x->max_nq_pad;
         }
         int rc;
         // (dim 1024: the query fragments alone are 256 registers: no pinning, no deeper fragment prefetch and the 32x32x16
@@ -1318,16 +1274,12 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
         CR_TRY(wsalloc(&x->q16, (size_t)x->max_nq_pad * dim));
         // candidate lists of the coarse pass: about k / 4 lists of 16 up to k = 64, about k / 6 lists of 24 above (+ the
         // lists that work-group boundaries add)
-        const int kcap = std::min(max_k, FAST_MAX_K);
-        const int lists_for_max_k = std::min(COARSE_MAX_P, std::max(6, (std::min(kcap, 64) + 3) / 4 + 4));
-        const int wide_for_max_k = kcap > 64 ? std::min(FIN_MAX_CAND / CO_KP_WIDE, (kcap + 5) / 6 + 4) : 0;
-        // (+ the wide partition of large batches on family-shaped corpora, wide_mode: PASS2_MAX_P lists of CO_KP)
-        x->partc_cap = std::max<size_t>((size_t)x->max_nq_pad * std::max(std::max(lists_for_max_k, PASS2_MAX_P) * CO_KP, wide_for_max_k * CO_KP_WIDE),
-                                        (size_t)1 << 20);
+        // (+ the wide partition of large batches on family-shaped corpora, wide_mode: PASS2_MAX_P lists of CO_KP; flat_partition.hpp)
+        x->partc_cap = (size_t)coarse_partc_entries(x->max_nq_pad, std::min(max_k, FAST_MAX_K), CO_KP, CO_KP_WIDE, FIN_MAX_CAND);
         CR_TRY(wsalloc(&x->partc_s, x->partc_cap));
         CR_TRY(wsalloc(&x->partc_r, x->partc_cap));
         CR_TRY(wsalloc(&x->partc_b, x->partc_cap / CO_KP));
-        x->part2_cap = (size_t)x->max_nq_pad * PASS2_MAX_P * CO_KP;
+        x->part2_cap = (size_t)coarse_part2_entries(x->max_nq_pad, CO_KP);
         CR_TRY(wsalloc(&x->part2_s, x->part2_cap));
         CR_TRY(wsalloc(&x->part2_r, x->part2_cap));
         CR_TRY(wsalloc(&x->part2_b, x->part2_cap / CO_KP));
