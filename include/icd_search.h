@@ -162,6 +162,39 @@ int icd_index_destroy(icd_index *idx);
 int icd_index_create_view(icd_index *parent, const int64_t *rows, int64_t n_rows, int32_t rows_on_device,
                           int32_t max_nq, int32_t max_k, int32_t flags, icd_index **out);
 
+/*
+ * Grouping search: Milvus's `group_by_field` / `group_size` (MilvusClient.search(..., group_by_field=, group_size=,
+ * strict_group_size=False); the reference passes neither, services/milvus_service.py:280-285). For every query the k best GROUPS -
+ * a group ranks by its best row - and of each its min(group_size, members) best rows, EXACT: every row is scored with the
+ * canonical chain and reduced per group, so a group is never short because a candidate list was.
+ *
+ * icd_grouping_create: group_of int32[n] (n = the index's rows; host, or device with on_device = 1), any non-negative ids. The
+ * rows are ordered by (group, row) on the host and uploaded with the workspace of the searches (sized for batches of up to
+ * max_nq queries; nothing is allocated later). One grouping per field; any number of them per index, each with its own
+ * workspace. On a view (icd_index_create_view) group_of has one id per row OF THE VIEW. A grouping keeps no pointer into its
+ * index: either may be destroyed first; a search checks that the two belong together. n >= 2^31 rows: ICD_ERR_UNSUPPORTED.
+ * The row-sharded path (icd_group_*) has no grouping search.
+ *
+ * icd_index_search_grouped: outputs [nq][k * group_size], k >= 1, group_size >= 1, k * group_size <= ICD_MAX_K (else
+ * ICD_ERR_INVALID, before any device call).
+ *   reweighted = 0  group-rank-major: the best group's rows best first, then the second group's, ... back to back (a group
+ *                   with fewer than group_size rows takes fewer slots); out_raw the canonical scores, out_ids, out_levels,
+ *                   out_groups (the caller's id of the hit's group). out_adj is not written.
+ *   reweighted = 1  that list through icd_index_search_reweighted's step: out_adj = (double)raw * w[level] and ONE stable
+ *                   descending re-sort of the query's hits; raw, ids, levels and groups travel with the hit.
+ * Unused slots at the end of a query's list: score -inf, id -1, level 0, group -1. out_levels / out_groups may be NULL.
+ * Queries and outputs are host or device pointers as in icd_index_search; device-in / device-out calls only enqueue on
+ * `stream` (graph-capturable). Searches of one grouping share its workspace: one stream at a time, as for an index.
+ */
+typedef struct icd_grouping icd_grouping;
+int icd_grouping_create(icd_index *idx, const int32_t *group_of, int64_t n, int32_t on_device, int32_t max_nq, icd_grouping **out);
+int icd_grouping_destroy(icd_grouping *grouping);
+/* distinct groups, rows of the largest one, device bytes held (any pointer may be NULL) */
+int icd_grouping_stats(icd_grouping *grouping, int64_t *out_groups, int64_t *out_largest, int64_t *out_bytes);
+int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float *queries, int64_t nq, int32_t k, int32_t group_size,
+                             int32_t queries_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                             int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream);
+
 /* Raw top-k by inner product. out_scores float[nq][k], out_ids int64[nq][k]. */
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k,
                      int32_t queries_on_device, int32_t mode,

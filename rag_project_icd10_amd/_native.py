@@ -34,7 +34,9 @@ EXPORTED_SYMBOLS = (
     "icd_index_set_second_pass",
     "icd_group_unique_id", "icd_group_create", "icd_group_prepare", "icd_group_connect", "icd_group_search", "icd_group_destroy",
     "icd_unpack_query_slices", "icd_split_bf16x3", "icd_encoder_create", "icd_encoder_encode", "icd_encoder_encode_many", "icd_encoder_destroy", "icd_pack_winners",
+    "icd_grouping_create", "icd_grouping_destroy", "icd_grouping_stats", "icd_index_search_grouped",
 )
+MAX_K = 128   # include/icd_search.h ICD_MAX_K: the slots of one query's hit list (a grouped search: k * group_size)
 # include/icd_search.h: icd_index_create flags and icd_index_set_option ids (A/B and test options of ONE index)
 CREATE_CORPUS_ON_DEVICE, CREATE_ROW_ORDER, CREATE_NO_PROBE, CREATE_NO_CENTER = 1, 2, 4, 8
 OPTIONS = {"family_order": 1, "stream_one": 2, "host_one": 3, "pacing_shift": 4, "pacing_lead": 5, "exact_narrow": 6, "wide_from": 7}
@@ -105,6 +107,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_index_destroy.argtypes = [vp]
     lib.icd_index_search.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]
     lib.icd_index_search_reweighted.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.icd_grouping_create.argtypes = [vp, vp, i64, i32, i32, C.POINTER(vp)]
+    lib.icd_grouping_destroy.argtypes = [vp]
+    lib.icd_grouping_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_search_grouped.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -366,6 +372,56 @@ class IcdIndex:
             return tuple(torch.cat([o[i] for o in outs]) for i in range(4))
         return tuple(np.concatenate([o[i] for o in outs]) for i in range(4))
 
+    # -- grouping search (Milvus group_by_field / group_size) ------------------------------------------
+    def grouping(self, group_of, *, max_nq: Optional[int] = None) -> "IcdGrouping":
+        """A grouping of this index's rows (icd_grouping_create): group_of holds one non-negative int32 id per row (of a view:
+        per row of the view), a numpy array or a torch CUDA tensor. Created once per field; several may coexist. It holds the
+        workspace of its searches (batches of up to max_nq queries, default this index's max_nq)."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdGrouping(self, group_of, int(max_nq if max_nq is not None else self.max_nq))
+
+    def search_grouped(self, queries, k: int, group_size: int, grouping: "IcdGrouping", reweighted: bool = True):
+        """The k best groups of every query and the group_size best rows of each, exact (icd_index_search_grouped). Outputs are
+        [nq, k * group_size]. reweighted=True: (adj f64, raw f32, ids i64, levels i32, groups i32) in search_reweighted's order
+        (level weight, one stable re-sort of the query's hits); False: (raw, ids, levels, groups) group by group, best group
+        first. Padding: -inf, id -1, level 0, group -1. Device tensors in -> device tensors out on torch's current stream."""
+        q, on_dev = self._prep_queries(queries)
+        if self.closed or grouping is None or grouping.closed:
+            raise IcdError(-5, "index or grouping is closed")
+        if q.shape[-1] != self.dim:
+            raise ValueError(f"query dim {q.shape[-1]} != index dim {self.dim}")
+        k, group_size = int(k), int(group_size)
+        if k < 1 or group_size < 1 or k * group_size > MAX_K:
+            raise ValueError(f"k={k}, group_size={group_size}: need k >= 1, group_size >= 1 and k * group_size <= {MAX_K}")
+        nq, w = int(q.shape[0]), k * group_size
+        outs = []
+        for s0 in range(0, max(nq, 1), grouping.max_nq):
+            qs = q[s0:s0 + grouping.max_nq]
+            m = int(qs.shape[0])
+            if on_dev:
+                import torch
+                mk = lambda dt: torch.empty((m, w), dtype=dt, device=q.device)
+                adj, raw, ids, lv, grp = mk(torch.float64), mk(torch.float32), mk(torch.int64), mk(torch.int32), mk(torch.int32)
+                ptr = lambda t: t.data_ptr()
+                stream = _current_stream_ptr(self.device)
+            else:
+                mk = lambda dt: np.empty((m, w), dtype=dt)
+                adj, raw, ids, lv, grp = mk(np.float64), mk(np.float32), mk(np.int64), mk(np.int32), mk(np.int32)
+                ptr = lambda t: t.ctypes.data
+                stream = None
+            if m:
+                _check(self._lib, self._lib.icd_index_search_grouped(
+                    self._h, grouping._h, ptr(qs), m, k, group_size, 1 if on_dev else 0, 1 if reweighted else 0,
+                    ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(grp), 1 if on_dev else 0, stream))
+            outs.append((adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp))
+        if len(outs) == 1:
+            return outs[0]
+        if on_dev:
+            import torch
+            return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
+        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""
         import torch
@@ -402,6 +458,57 @@ class IcdIndex:
         p = _Profile()
         _check(self._lib, self._lib.icd_index_last_profile(self._h, C.byref(p)))
         return {f: float(getattr(p, f)) for f, _ in _Profile._fields_}
+
+
+class IcdGrouping:
+    """Rows of one IcdIndex ordered by group, with the workspace of the grouped searches (icd_grouping_*). Independent of the
+    index's lifetime: either may be closed first (a search with a closed partner raises)."""
+
+    def __init__(self, index: "IcdIndex", group_of, max_nq: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        keep = None
+        if _is_torch_tensor(group_of) and group_of.is_cuda:
+            import torch
+            keep = group_of.to(torch.int32).contiguous().reshape(-1)
+            if keep.device.index != index.device:
+                raise ValueError(f"group_of on cuda:{keep.device.index}, index on device {index.device}")
+            torch.cuda.synchronize(index.device)
+            ptr, on_dev, n = keep.data_ptr(), 1, int(keep.numel())
+        else:
+            if _is_torch_tensor(group_of):
+                group_of = group_of.detach().cpu().numpy()
+            g64 = np.asarray(group_of).reshape(-1)
+            if g64.size and (g64.min() < 0 or g64.max() > 0x7FFFFFFF):
+                raise ValueError("group ids must be integers in 0 .. 2^31 - 1")
+            keep = np.ascontiguousarray(g64, dtype=np.int32)
+            ptr, on_dev, n = keep.ctypes.data, 0, int(keep.size)
+        if n != index.n:
+            raise ValueError(f"group_of holds {n} ids, the index {index.n} rows")
+        self.n, self.max_nq, self.device = n, int(max_nq), index.device
+        _check(self._lib, self._lib.icd_grouping_create(index._h, ptr, n, on_dev, self.max_nq, C.byref(self._h)))
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "grouping is closed")
+        g, m, b = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_grouping_stats(self._h, C.byref(g), C.byref(m), C.byref(b)))
+        return {"groups": g.value, "largest_group": m.value, "bytes": b.value}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.icd_grouping_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def closed(self) -> bool:
+        return not self._h.value
 
 
 def group_unique_id() -> bytes:

@@ -87,6 +87,11 @@ struct FinArgs {
     float *out_adj_raw;
     long long *out_adj_ids;
     int *out_adj_levels;
+    // grouping search only (group_topk.hpp), all null otherwise: a tag per row that travels with the hit as its level does
+    const int *groups;      // [n] the caller's group id of every row
+    int *out_levels;        // raw order [query][k]
+    int *out_groups;        // raw order; -1 in padding
+    int *out_adj_groups;    // re-sorted order
 };
 
 __device__ __forceinline__ double level_weight(int level) {
@@ -130,9 +135,11 @@ __device__ __forceinline__ void emit_outputs(const FinArgs &a, int qidx, const u
         if (j < k) {
             if (a.out_scores) a.out_scores[o + j] = sc[e];
             if (a.out_ids) a.out_ids[o + j] = row[e] >= 0 ? (a.row_map ? a.row_map[row[e]] : a.id_base + row[e]) : -1ll;
+            if (a.out_levels) a.out_levels[o + j] = lvl[e];
+            if (a.out_groups) a.out_groups[o + j] = row[e] >= 0 ? a.groups[row[e]] : -1;
         }
     }
-    if (!a.out_adj && !a.out_adj_ids && !a.out_adj_raw && !a.out_adj_levels) return;
+    if (!a.out_adj && !a.out_adj_ids && !a.out_adj_raw && !a.out_adj_levels && !a.out_adj_groups) return;
     // stable descending rank of adj among the nres hits
     int pos[2] = {0, 0};
     for (int i = 0; i < nres; ++i) {
@@ -152,12 +159,14 @@ __device__ __forceinline__ void emit_outputs(const FinArgs &a, int qidx, const u
             if (a.out_adj_raw) a.out_adj_raw[w] = sc[e];
             if (a.out_adj_ids) a.out_adj_ids[w] = a.row_map ? a.row_map[row[e]] : a.id_base + row[e];
             if (a.out_adj_levels) a.out_adj_levels[w] = lvl[e];
+            if (a.out_adj_groups) a.out_adj_groups[w] = a.groups[row[e]];
         } else if (j < k) {
             const size_t w = o + j;
             if (a.out_adj) a.out_adj[w] = -INFINITY;
             if (a.out_adj_raw) a.out_adj_raw[w] = -INFINITY;
             if (a.out_adj_ids) a.out_adj_ids[w] = -1ll;
             if (a.out_adj_levels) a.out_adj_levels[w] = 0;
+            if (a.out_adj_groups) a.out_adj_groups[w] = -1;
         }
     }
 }

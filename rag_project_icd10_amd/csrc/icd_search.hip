@@ -34,6 +34,7 @@
 #include "attention_kernel.hpp"
 #include "exact_kernel.hpp"
 #include "finalize.hpp"
+#include "group_topk.hpp"
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
@@ -1860,6 +1861,194 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
     out->ms_exact = span(3, 4);
     out->ms_exact_finalize = span(4, 5);
     out->ms_total = span(0, NUM_EV);
+    return ICD_OK;
+}
+
+// ---- grouping search (group_topk.hpp) ----------------------------------------------------------------
+// A grouping belongs to the index it was created for (n rows, the same device) but keeps no pointer into it: the handle is
+// compared, never followed, outside a search that is given both. Its workspace - the score block S, the per-group keys, the
+// staging of host callers - is allocated here, never inside a search.
+struct icd_grouping {
+    uint32_t magic = 0x1CD96B0Fu;
+    const icd_index *owner = nullptr;
+    int device = 0;
+    int n = 0, G = 0, largest = 0, max_nq = 0, qb = 0, dim = 0;
+    long long ldS = 0;
+    int *group_of = nullptr, *dense_of = nullptr, *order = nullptr, *gpos = nullptr, *seg = nullptr;
+    float *S = nullptr;
+    u64 *best = nullptr;
+    float *qdev = nullptr;
+    double *o_adj = nullptr; float *o_raw = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr, *o_grp = nullptr;
+    size_t bytes = 0;
+    std::mutex mu;
+};
+
+namespace {
+constexpr int GROUP_QUERY_BLOCK = 512;   // queries scored per pass: S = 512 x 40 576 x 4 B = 83 MB stays in the 256-MiB Infinity Cache next to the 124-MB corpus
+bool valid_grouping(icd_grouping *g) { return g && g->magic == 0x1CD96B0Fu; }
+void free_grouping(icd_grouping *g) {
+    if (!g) return;
+    hipFree(g->group_of); hipFree(g->dense_of); hipFree(g->order); hipFree(g->gpos); hipFree(g->seg); hipFree(g->S); hipFree(g->best);
+    hipFree(g->qdev); hipFree(g->o_adj); hipFree(g->o_raw); hipFree(g->o_ids); hipFree(g->o_lv); hipFree(g->o_grp);
+    g->magic = 0;
+    delete g;
+}
+}  // namespace
+
+int icd_grouping_create(icd_index *idx, const int32_t *group_of, int64_t n, int32_t on_device, int32_t max_nq, icd_grouping **out) {
+    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!group_of) return fail(ICD_ERR_INVALID, "group_of is NULL");
+    if (n != idx->n) return fail(ICD_ERR_INVALID, "group_of holds %lld ids, the index %lld rows", (long long)n, (long long)idx->n);
+    if (n >= 0x7FFFFFFFll) return fail(ICD_ERR_UNSUPPORTED, "n=%lld: a grouping addresses rows with 31 bits", (long long)n);
+    if (max_nq <= 0) return fail(ICD_ERR_INVALID, "max_nq=%d", max_nq);
+    HIP_TRY(hipSetDevice(idx->device));
+    std::vector<int> ids((size_t)n);
+    if (on_device) HIP_TRY(hipMemcpy(ids.data(), group_of, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    else memcpy(ids.data(), group_of, (size_t)n * sizeof(int));
+    for (int64_t i = 0; i < n; ++i)
+        if (ids[i] < 0) return fail(ICD_ERR_INVALID, "group_of[%lld]=%d: group ids are non-negative (-1 marks padding in the outputs)", (long long)i, ids[i]);
+    // rows in (group, row) order; dense group numbers in the order of the caller's ids
+    std::vector<int> order((size_t)n), gpos((size_t)n), dense((size_t)n), seg;
+    for (int64_t i = 0; i < n; ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ids[a] < ids[b]; });
+    int largest = 0;
+    for (int64_t p = 0; p < n; ++p) {
+        if (p == 0 || ids[order[p]] != ids[order[p - 1]]) {
+            if (!seg.empty()) largest = std::max(largest, (int)p - seg.back());
+            seg.push_back((int)p);
+        }
+        gpos[p] = (int)seg.size() - 1;
+        dense[order[p]] = gpos[p];
+    }
+    largest = std::max(largest, (int)n - seg.back());
+    const int G = (int)seg.size();
+    seg.push_back((int)n);
+
+    icd_grouping *g = new (std::nothrow) icd_grouping();
+    if (!g) return fail(ICD_ERR_NOMEM, "host allocation failed");
+    g->owner = idx; g->device = idx->device; g->n = (int)n; g->G = G; g->largest = largest; g->max_nq = max_nq; g->dim = idx->dim;
+    g->qb = std::min(GROUP_QUERY_BLOCK, (max_nq + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE);
+    g->ldS = ((long long)n + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE;
+    const size_t no = (size_t)max_nq * ICD_MAX_K;
+#define GR_TRY(expr)                                                                                                       \
+    do {                                                                                                                   \
+        hipError_t e_ = (expr);                                                                                            \
+        if (e_ != hipSuccess) {                                                                                            \
+            free_grouping(g);                                                                                              \
+            return fail(e_ == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+        }                                                                                                                  \
+    } while (0)
+    GR_TRY(dmalloc(&g->group_of, (size_t)n)); GR_TRY(dmalloc(&g->dense_of, (size_t)n)); GR_TRY(dmalloc(&g->order, (size_t)n));
+    GR_TRY(dmalloc(&g->gpos, (size_t)n)); GR_TRY(dmalloc(&g->seg, (size_t)G + 1));
+    GR_TRY(dmalloc(&g->S, (size_t)g->qb * g->ldS)); GR_TRY(dmalloc(&g->best, (size_t)g->qb * G));
+    GR_TRY(dmalloc(&g->qdev, (size_t)max_nq * idx->dim));
+    GR_TRY(dmalloc(&g->o_adj, no)); GR_TRY(dmalloc(&g->o_raw, no)); GR_TRY(dmalloc(&g->o_ids, no)); GR_TRY(dmalloc(&g->o_lv, no)); GR_TRY(dmalloc(&g->o_grp, no));
+    GR_TRY(hipMemcpy(g->group_of, ids.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->dense_of, dense.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->order, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->gpos, gpos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->seg, seg.data(), ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice));
+#undef GR_TRY
+    g->bytes = (size_t)n * 20 + ((size_t)G + 1) * 4 + (size_t)g->qb * g->ldS * 4 + (size_t)g->qb * G * 8 + (size_t)max_nq * idx->dim * 4 + no * 28;
+    *out = g;
+    return ICD_OK;
+}
+
+int icd_grouping_destroy(icd_grouping *grouping) {
+    if (!valid_grouping(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    hipSetDevice(grouping->device);
+    hipDeviceSynchronize();
+    free_grouping(grouping);
+    return ICD_OK;
+}
+
+int icd_grouping_stats(icd_grouping *grouping, int64_t *out_groups, int64_t *out_largest, int64_t *out_bytes) {
+    if (!valid_grouping(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    if (out_groups) *out_groups = grouping->G;
+    if (out_largest) *out_largest = grouping->largest;
+    if (out_bytes) *out_bytes = (int64_t)grouping->bytes;
+    return ICD_OK;
+}
+
+int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float *queries, int64_t nq, int32_t k, int32_t group_size,
+                             int32_t queries_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                             int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream) {
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_grouping(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    icd_grouping *g = grouping;
+    if (g->owner != idx || g->n != idx->n || g->device != idx->device || g->dim != idx->dim)
+        return fail(ICD_ERR_INVALID, "the grouping was created for another index");
+    if (k < 1 || group_size < 1 || (int64_t)k * group_size > ICD_MAX_K)
+        return fail(ICD_ERR_INVALID, "k=%d group_size=%d: need k >= 1, group_size >= 1 and k * group_size <= %d", k, group_size, ICD_MAX_K);
+    if (nq < 0 || nq > g->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the grouping's max_nq=%d", (long long)nq, g->max_nq);
+    if (!out_ids || !out_raw || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (nq == 0) return ICD_OK;
+    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
+    std::lock_guard<std::mutex> guard(g->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const bool capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+        if (capturing && (!queries_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
+    }
+    const float *dq = queries;
+    if (!queries_on_device) {
+        HIP_TRY(hipMemcpyAsync(g->qdev, queries, (size_t)nq * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        dq = g->qdev;
+    }
+    double *d_adj = out_adj; float *d_raw = out_raw; long long *d_ids = reinterpret_cast<long long *>(out_ids); int *d_lv = out_levels, *d_grp = out_groups;
+    if (!out_on_device) {
+        d_adj = out_adj ? g->o_adj : nullptr; d_raw = g->o_raw; d_ids = g->o_ids;
+        d_lv = out_levels ? g->o_lv : nullptr; d_grp = out_groups ? g->o_grp : nullptr;
+    }
+    const int ks = k * group_size;
+    const int ntiles = (int)(g->ldS / GROUP_TILE);
+    const bool small_kp = k <= 16 && group_size <= 16;
+    for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {
+        const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
+        GroupScoreArgs sa{};
+        sa.corpus = idx->corpus; sa.queries = dq + (size_t)q0 * idx->dim; sa.order = g->order;
+        sa.nq = nb; sa.n = g->n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
+        sa.S = g->S; sa.ldS = g->ldS;
+        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)(ntiles * sa.mtiles)), dim3(256), 0, s, sa);
+        HIP_TRY(hipGetLastError());
+
+        HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
+        GroupBestArgs ba{};
+        ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
+        ba.nq = nb; ba.n = g->n; ba.G = g->G; ba.best = g->best;
+        ba.R = nb >= 64 ? 1024 : 128;
+        ba.nranges = (g->n + ba.R - 1) / ba.R;
+        constexpr int QW = 4;
+        const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
+        hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
+        HIP_TRY(hipGetLastError());
+
+        GroupFinishArgs fa{};
+        fa.best = g->best; fa.S = g->S; fa.ldS = g->ldS; fa.order = g->order; fa.seg = g->seg; fa.dense_of = g->dense_of;
+        fa.nq = nb; fa.G = g->G; fa.k = k; fa.s = group_size; fa.q_base = (int)q0;
+        fa.fin.k = ks; fa.fin.levels = idx->levels; fa.fin.id_base = idx->id_base; fa.fin.row_map = idx->row_map; fa.fin.groups = g->group_of;
+        if (reweighted) {
+            fa.fin.out_adj = d_adj; fa.fin.out_adj_raw = d_raw; fa.fin.out_adj_ids = d_ids; fa.fin.out_adj_levels = d_lv; fa.fin.out_adj_groups = d_grp;
+        } else {
+            fa.fin.out_scores = d_raw; fa.fin.out_ids = d_ids; fa.fin.out_levels = d_lv; fa.fin.out_groups = d_grp;
+        }
+        if (small_kp) hipLaunchKernelGGL((group_finish_kernel<16, 2>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
+        else hipLaunchKernelGGL((group_finish_kernel<128, 4>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!out_on_device) {
+        const size_t no = (size_t)nq * ks;
+        if (out_adj) HIP_TRY(hipMemcpyAsync(out_adj, d_adj, no * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_raw, d_raw, no * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_ids, d_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
+        if (out_levels) HIP_TRY(hipMemcpyAsync(out_levels, d_lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (out_groups) HIP_TRY(hipMemcpyAsync(out_groups, d_grp, no * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    if (!out_on_device || !queries_on_device) HIP_TRY(hipStreamSynchronize(s));
     return ICD_OK;
 }
 

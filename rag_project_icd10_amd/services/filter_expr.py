@@ -37,6 +37,10 @@ STRING_FIELDS = ("code", "main_code", "secondary_code", "parent_code", "category
 INT_FIELDS = ("level",)
 BOOL_FIELDS = ("has_complication",)
 FIELDS = STRING_FIELDS + INT_FIELDS + BOOL_FIELDS
+# grouping search (Milvus group_by_field): the eight fields, and `category` - an extension: the first element of category_path
+# (the three-character category a code belongs to), the code itself where the path is empty
+GROUP_FIELDS = FIELDS + ("category",)
+MAX_GROUPED_HITS = 128   # include/icd_search.h ICD_MAX_K: top_k * group_size of one query
 _CMP = ("==", "!=", "<", "<=", ">", ">=")
 _KEYWORDS = ("and", "or", "not", "in", "like", "true", "false")
 
@@ -249,6 +253,19 @@ def compile(expr: str) -> str:   # noqa: A001 (the name the issue gives the entr
     return _parse(expr)[1]
 
 
+def check_grouping(field, top_k, group_size) -> None:
+    """the arguments of a grouping search (group_by_field, limit, group_size); ValueError names the offending limit"""
+    if not isinstance(field, str) or field not in GROUP_FIELDS:
+        raise ValueError(f"group_by_field={field!r}: not one of {', '.join(GROUP_FIELDS)}")
+    if isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or group_size < 1:
+        raise ValueError(f"group_size={group_size!r}: must be an integer >= 1")
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+        raise ValueError(f"top_k={top_k!r}: must be an integer >= 1")
+    if int(top_k) * int(group_size) > MAX_GROUPED_HITS:
+        raise ValueError(f"top_k * group_size = {int(top_k) * int(group_size)} exceeds {MAX_GROUPED_HITS} hits per query "
+                         f"(top_k={top_k} groups of group_size={group_size})")
+
+
 class Columns:
     """The eight filter fields of a store's rows as column arrays, built once per generation of the store, with a bounded cache
     of selections keyed by the normalised expression. `generation` is the store's mutation counter when the columns were built."""
@@ -260,6 +277,7 @@ class Columns:
         self.generation = generation
         self.n = len(next(iter(arrays.values()))) if arrays else 0
         self._sel: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        self._groups: Dict[str, Any] = {}
         self._lock = threading.Lock()
 
     @classmethod
@@ -274,6 +292,28 @@ class Columns:
 
     def __getitem__(self, field: str) -> np.ndarray:
         return self.arrays[field]
+
+    def group_ids(self, field: str):
+        """(ids int32 [n], values): the rows' group under `field` as the rank of its value among the sorted distinct values
+        (values[ids[row]] is the row's value). An empty string is a value like any other: the rows without a parent_code form
+        one group. Cached per field."""
+        check_grouping(field, 1, 1)
+        with self._lock:
+            hit = self._groups.get(field)
+        if hit is not None:
+            return hit
+        if field == "category":
+            path, code = self.arrays["category_path"], self.arrays["code"]
+            col = np.array([(p.split(">")[0].strip() or c) for p, c in zip(path.tolist(), code.tolist())], dtype=str) if self.n \
+                else np.zeros(0, dtype="<U1")
+        else:
+            col = self.arrays[field]
+        values, ids = np.unique(col, return_inverse=True)
+        out = (np.ascontiguousarray(ids.reshape(-1), dtype=np.int32), values)
+        out[0].setflags(write=False)
+        with self._lock:
+            self._groups[field] = out
+        return out
 
     def select(self, expr: str) -> np.ndarray:
         node, key = _parse(expr)

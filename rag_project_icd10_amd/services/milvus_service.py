@@ -54,6 +54,9 @@ class MilvusService:
         self._views: "OrderedDict[tuple, Any]" = OrderedDict()
         self._views_lock = threading.Lock()
         self._max_views = max(1, int(os.getenv("ICD_FILTER_VIEWS", "8")))
+        # grouping search: (field, store generation, normalised filter or None) -> (the index or view it belongs to, IcdGrouping)
+        self._groupings: "OrderedDict[tuple, Any]" = OrderedDict()
+        self._max_groupings = max(1, int(os.getenv("ICD_GROUPINGS", "16")))
         self._columns = None        # filter_expr.Columns of the store generation they were built from (rebuilt when it moves on)
         self._connect()
         self._setup_collection()
@@ -206,6 +209,46 @@ class MilvusService:
     def _clear_views(self):
         with self._views_lock:
             self._views.clear()
+            self._groupings.clear()
+
+    # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
+    def _grouping(self, field: str, index, rows, filter_key):
+        """(IcdGrouping, values) of `field` for `index` - the store's index, or the view of the filter whose normalised form is
+        filter_key and whose rows are `rows` (the view then gets the parent's group ids restricted to them). Cached per
+        (field, store generation, filter) and dropped where the views are."""
+        ids, values = self._filter_columns().group_ids(field)
+        ck = (field, self.client.generation, filter_key)
+        with self._views_lock:
+            hit = self._groupings.get(ck)
+            if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
+                self._groupings.move_to_end(ck)
+                return hit[1], values
+            grouping = index.grouping(ids if filter_key is None else ids[rows], max_nq=min(index.max_nq, 2048))
+            self._groupings[ck] = (index, grouping)
+            while len(self._groupings) > self._max_groupings:
+                self._groupings.popitem(last=False)
+        return grouping, values
+
+    def groupings(self) -> List[Dict[str, Any]]:
+        """the cached groupings, least recently used first: field, filter (normalised, None: the whole store), groups, rows of the
+        largest group, HBM bytes"""
+        with self._views_lock:
+            items = list(self._groupings.items())
+        out = []
+        for (field, gen, fkey), (index, grouping) in items:
+            if grouping.closed:
+                continue
+            st = grouping.stats()
+            out.append({"field": field, "filter": fkey, "generation": gen, "groups": int(st["groups"]),
+                        "largest_group": int(st["largest_group"]), "bytes": int(st["bytes"])})
+        return out
+
+    def _search_grouped(self, index, rows, filter, query_vectors, top_k: int, field: str, group_size: int):   # noqa: A002
+        """(adj, raw, ids, levels, group values' ids, values) of a grouped search on the store's index or a filter's view"""
+        whole = filter is None or index is self._index
+        grouping, values = self._grouping(field, index, rows, None if whole else filter_expr.compile(filter))
+        adj, raw, ids, levels, groups = index.search_grouped(query_vectors, int(top_k), int(group_size), grouping)
+        return adj, raw, ids, levels, groups, values
 
     def _filter_columns(self) -> "filter_expr.Columns":
         gen = self.client.generation
@@ -260,13 +303,22 @@ class MilvusService:
                         "bytes": int(st["bytes_corpus_f32"] + st["bytes_corpus_f16"] + st["bytes_workspace"])})
         return out
 
-    def search(self, query_vector: np.ndarray, top_k: int = 10, filter: Optional[str] = None) -> List[Dict[str, Any]]:   # noqa: A002 (Milvus's name)
+    def search(self, query_vector: np.ndarray, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002 (Milvus's name)
+               group_by_field: Optional[str] = None, group_size: int = 1) -> List[Dict[str, Any]]:
+        """group_by_field (one of filter_expr.GROUP_FIELDS) / group_size: Milvus's grouping search - the hits are the top_k best
+        GROUPS' group_size best rows each (exact), re-sorted by adjusted score like any hit list; every hit's metadata then
+        carries the group's value under the field's name. top_k * group_size <= 128. A bad grouping argument raises ValueError."""
+        if group_by_field is not None:
+            filter_expr.check_grouping(group_by_field, top_k, group_size)
+        elif group_size != 1:
+            raise ValueError("group_size needs group_by_field")
         try:
             if self.client is None or not self.client.exists():
                 logger.error("集合 %s 不存在", self.collection_name)
                 return []
+            rows = None
             if filter is not None:
-                index, _rows = self._filtered_index(filter)
+                index, rows = self._filtered_index(filter)
             else:
                 index = self._ready_index()
             if index is None:
@@ -275,16 +327,20 @@ class MilvusService:
             #  an array's values arrive as float32 either way - converting through a Python list cost 35 us of a 130-us call)
             query_vector.tolist  # noqa: B018
             q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
+            if group_by_field is not None:
+                adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, q, top_k, group_by_field, group_size)
+                return self._hits_to_dicts(adj[0], raw[0], ids[0], (group_by_field, groups[0], values))
             adj, raw, ids, levels = index.search_reweighted(q, int(top_k))
             return self._hits_to_dicts(adj[0], raw[0], ids[0])
         except Exception as exc:
             logger.error("搜索失败: %s", exc)
             return []
 
-    def _hits_to_dicts(self, adj, raw, ids) -> List[Dict[str, Any]]:
+    def _hits_to_dicts(self, adj, raw, ids, group=None) -> List[Dict[str, Any]]:
+        """group: None, or (field, the hits' group ids, the field's sorted distinct values) of a grouping search"""
         out = []
         recs = self.client.records
-        for a, r, i in zip(adj, raw, ids):
+        for j, (a, r, i) in enumerate(zip(adj, raw, ids)):
             i = int(i)
             if i < 0:
                 continue
@@ -304,23 +360,43 @@ class MilvusService:
                     "semantic_text": hit.get("semantic_text", ""),
                 },
             })
+            if group is not None:
+                out[-1]["metadata"][group[0]] = group[2][int(group[1][j])].item()
         return out
 
-    def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False, filter: Optional[str] = None):   # noqa: A002
+    def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False, filter: Optional[str] = None,   # noqa: A002
+                     group_by_field: Optional[str] = None, group_size: int = 1):
         """Additive: many queries in one call. query_vectors: [nq, dim] numpy array or torch CUDA
         tensor. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order
         `search` returns hits; or, with as_dicts=True, a list of `search`-shaped hit lists.
         filter: a Milvus filter expression - only the rows it selects are ranked (hit ids stay the corpus's row ids); a selection
-        shorter than top_k pads the lists with id -1, score -inf, level 0. Raises ValueError on a bad expression."""
+        shorter than top_k pads the lists with id -1, score -inf, level 0. Raises ValueError on a bad expression.
+        group_by_field / group_size: as in `search`; the arrays are then [nq, top_k * group_size] and a fifth one follows, the
+        hits' group ids (int32, -1 in padding: ranks of the field's sorted distinct values)."""
+        if group_by_field is not None:
+            filter_expr.check_grouping(group_by_field, top_k, group_size)
+        elif group_size != 1:
+            raise ValueError("group_size needs group_by_field")
         if filter is not None:
             filter_expr.compile(filter)   # (a bad expression raises before anything is loaded)
         index = self._ready_index()
         if index is None:
             raise RuntimeError(f"collection {self.collection_name} is empty or missing")
+        rows = None
         if filter is not None:
-            index, _rows = self._filtered_index(filter)
+            index, rows = self._filtered_index(filter)
             if index is None:   # nothing selected: no device call
-                return self._empty_hits(query_vectors, int(top_k), as_dicts)
+                empty = self._empty_hits(query_vectors, int(top_k) * int(group_size), as_dicts)
+                if group_by_field is None or as_dicts:
+                    return empty
+                return empty + (empty[3] - 1,)
+        if group_by_field is not None:
+            adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, query_vectors, top_k, group_by_field, group_size)
+            if not as_dicts:
+                return adj, raw, ids, levels, groups
+            if hasattr(adj, "cpu"):
+                adj, raw, ids, groups = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy(), groups.cpu().numpy()
+            return [self._hits_to_dicts(adj[q], raw[q], ids[q], (group_by_field, groups[q], values)) for q in range(len(ids))]
         # (large batches on a corpus of tight families of near-identical rows - ICD sibling codes - are handled inside the
         #  library: a second coarse pass over the queries the first could not certify, and from the next large batch on the
         #  wider partition right away; include/icd_search.h icd_stats.last_second_pass / wide_mode)

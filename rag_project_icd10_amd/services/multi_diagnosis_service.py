@@ -56,6 +56,16 @@ class _gc_paused:
 CONFIDENCE_MODES = ("match", "multidimensional")
 
 
+def _search_options(filter, group_by_field, group_size) -> Dict[str, Any]:   # noqa: A002
+    """keyword arguments of MilvusService.search_batch for a request's filter / grouping: only the ones that were given"""
+    opts: Dict[str, Any] = {}
+    if filter is not None:
+        opts["filter"] = filter
+    if group_by_field is not None or group_size != 1:
+        opts["group_by_field"], opts["group_size"] = group_by_field, group_size
+    return opts
+
+
 class MultiDiagnosisService:
     def __init__(self, embedding_service, milvus_service, ner_service=None, confidence: str = "match"):
         """ner_service: a MedicalNERService (row N4) or None. The reference always builds one (:28); here it is opt-in
@@ -77,7 +87,8 @@ class MultiDiagnosisService:
         self.confidence_service = MultiDimensionalConfidenceService(
             embedding_service=embedding_service, ner_service=ner_service, hierarchical_similarity_service=self.hierarchical_similarity)
 
-    def match_multiple_diagnoses(self, text: str, top_k: int = 5, filter: Optional[str] = None) -> Dict[str, Any]:   # noqa: A002
+    def match_multiple_diagnoses(self, text: str, top_k: int = 5, filter: Optional[str] = None,   # noqa: A002
+                                 group_by_field: Optional[str] = None, group_size: int = 1) -> Dict[str, Any]:
         """filter: a Milvus filter expression (services/filter_expr.py) - every diagnosis is searched among the rows it selects only
         (the search of 2 top_k, on the device path and the host path alike); None ranks the whole corpus"""
         enhanced = self.text_processor.extract_diagnoses_enhanced(text)
@@ -89,6 +100,7 @@ class MultiDiagnosisService:
                     "extraction_metadata": {"enhanced_results_count": 0, "avg_extraction_confidence": 0.0}}
         confs = [d.get("diagnosis_confidence", 0.5) for d in enhanced]
         # one encoder batch + one search batch for the whole request
+        grouped = {} if group_by_field is None and group_size == 1 else {"group_by_field": group_by_field, "group_size": group_size}
         matches = None
         ner_job = vectors = None
         device = getattr(self.milvus_service, "supports_device_rescoring", lambda: False)()
@@ -97,7 +109,7 @@ class MultiDiagnosisService:
             # the whole request stays on the device - encode -> search(2 top_k) -> rescoring -> top_k winners come back.
             # Same DiagnosisMatch objects as the host path below (tests/test_gpu_parity.py, all 1 000 golden strings).
             try:
-                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, filter=filter)
+                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, filter=filter, **grouped)
             except Exception as exc:
                 logger.error("device-side request path failed (%s): host path", exc)
                 matches = None
@@ -108,7 +120,7 @@ class MultiDiagnosisService:
             ner_job = self._ner_pool().submit(self._entities_of, diagnoses)
             try:
                 vectors = self._embed_diagnoses(diagnoses)
-                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, vectors=vectors, entities=ner_job, filter=filter)
+                matches = self.match_diagnoses_batch(diagnoses, top_k=top_k, vectors=vectors, entities=ner_job, filter=filter, **grouped)
             except Exception as exc:
                 logger.error("device-side request path with entities failed (%s): host path", exc)
                 matches = None
@@ -126,8 +138,7 @@ class MultiDiagnosisService:
         if vectors is None:
             vectors = self._embed_diagnoses(diagnoses)
         try:
-            hit_lists = (self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True) if filter is None
-                         else self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, filter=filter))
+            hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, **_search_options(filter, group_by_field, group_size))
         except Exception as exc:
             logger.error("batch search failed: %s", exc)
             hit_lists = [[] for _ in diagnoses]
@@ -197,7 +208,8 @@ class MultiDiagnosisService:
 
     def match_diagnoses_batch(self, diagnoses: List[str], top_k: int = 5, vectors=None,
                               confidence_statistics: bool = False, entities=None, confidence: str = None,
-                              filter: Optional[str] = None) -> List[DiagnosisMatch]:   # noqa: A002
+                              filter: Optional[str] = None, group_by_field: Optional[str] = None,   # noqa: A002
+                              group_size: int = 1) -> List[DiagnosisMatch]:
         """Additive (row N2): embed -> search(2 top_k) -> level reweight -> hierarchical rescoring for MANY diagnosis
         strings with everything between the tokenizer and the final top_k on the GPU: one encoder batch, one search_batch,
         one rescoring launch; only the top_k winners per string come back and become Candidate objects. Same results as
@@ -212,7 +224,9 @@ class MultiDiagnosisService:
         MultiDimensionalConfidenceService.comprehensive_confidence_batch - the cosine, the score statistics and the terminology
         scan as one launch each - equal to _match_from_hits' per-call scores except the cosine (sklearn's, to ~1e-14).
         filter: a Milvus filter expression: the search of 2 top_k ranks the rows it selects only (MilvusService.search_batch);
-        the rescoring, the entities and both confidence modes then run unchanged on those hits (ids stay the corpus's row ids)."""
+        the rescoring, the entities and both confidence modes then run unchanged on those hits (ids stay the corpus's row ids).
+        group_by_field / group_size: Milvus's grouping search (MilvusService.search_batch): the search of 2 top_k then returns the
+        group_size best rows of the 2 top_k best GROUPS, and the rescoring runs on those hits (2 top_k group_size <= 128)."""
         from .hierarchical_similarity_service import trusted_factors_row
         confidence = self.confidence if confidence is None else confidence
         if confidence not in CONFIDENCE_MODES:
@@ -227,8 +241,7 @@ class MultiDiagnosisService:
         hs = self.hierarchical_similarity
         if entities is None:
             qps = [hs.query_params(d) for d in diagnoses]   # ([1] is the context relevance the factors report)
-        adj, raw, ids, _lv = (self.milvus_service.search_batch(vectors, top_k * 2) if filter is None
-                              else self.milvus_service.search_batch(vectors, top_k * 2, filter=filter))
+        adj, raw, ids = self.milvus_service.search_batch(vectors, top_k * 2, **_search_options(filter, group_by_field, group_size))[:3]
         if entities is not None:
             if hasattr(entities, "result"):   # (the NER worker's Future: the classifier ran beside the embedding and the search)
                 entities = entities.result()
