@@ -312,7 +312,7 @@ __device__ __forceinline__ void compact_all_parallel(char *smem, Sel2 &st, uint3
 //   8192 no select at all   16384 no LDS-DMA inside the tile loop   65536 (with 32768) no lane swaps
 // Variants that were measured and dropped (per-wave DMA slots, branch-free select, 3/6-stage rings, select deferred into
 // the next tile's MFMA gaps, the first two selects built for the 16x16x32 shape before the lane swap let it keep this
-// one - bit 32768 IS that shape and is part of the product) live in experiments/r02_flat_variants/ with their logs.
+// one - bit 32768 IS that shape and is part of the product) are recorded in HISTORY.md, their logs under profiles/.
 constexpr int CF_PRODUCT_VAR = 1 + 2 + 8 + 128 + 16 + 2048 + 32768;   // measured: profiles/r02_ab_flat_variants.log, profiles/r02_coarse_variants_rg_w8_all.log (+ 16 + 2048: -2 %; + 32768: -2 % at 37 000 rows, -4 % on 1.25 M-row shards)
 // The first pass over a corpus whose fp16 image stays in the Infinity Cache (the 37k - 40k-row ICD corpus: 57 - 62 MB): the
 // LDS-DMA pieces spread over a whole stage interval and the three-instruction bootstrap. Interleaved A/Bs on four boxes

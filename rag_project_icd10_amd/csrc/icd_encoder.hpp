@@ -213,17 +213,15 @@ inline int enc_big_enqueue_t(icd_encoder *e, int T, int nb, int pooling, int nor
 #ifdef ICD_ABLATE
     if (const char *v = getenv("ICD_ENCBIG_LDS")) lds_pin = (size_t)atoi(v);   // A/B: 0 = as many work-groups per CU as the registers allow
 #endif
-    auto k_qkv = enc_linear_big_kernel<ITER, TM, TNQ, 0, true, false, 1, PF, BF>;
-    auto k_ao = enc_linear_big_kernel<ITER, TM, TNO, 2, false, true, 1, PF, BF>;
-    auto k_up = enc_linear_big_kernel<ITER, TM, TNU, 1, true, true, 1, PF, BF>;
-    auto k_down = enc_linear_big_kernel<ITER, TM, TNO, 2, false, true, ENC_SLABS, PF, BF>;
-    auto k_down_last = enc_linear_big_kernel<ITER, TM, TNO, 2, false, false, ENC_SLABS, PF, BF>;   // the last layer's: row-major, for the pooling kernel
-    {
-        static int c0[MAX_DEVICES] = {}, c1[MAX_DEVICES] = {}, c2[MAX_DEVICES] = {}, c3[MAX_DEVICES] = {}, c4[MAX_DEVICES] = {};   // (per instantiation and device; calls on a handle are serialised)
-        HIP_TRY(ensure_dynamic_lds(k_qkv, e->device, lds_pin, c0)); HIP_TRY(ensure_dynamic_lds(k_ao, e->device, lds_pin, c1));
-        HIP_TRY(ensure_dynamic_lds(k_up, e->device, lds_pin, c2)); HIP_TRY(ensure_dynamic_lds(k_down, e->device, lds_pin, c3));
-        HIP_TRY(ensure_dynamic_lds(k_down_last, e->device, lds_pin, c4));
-    }
+    constexpr auto k_qkv = enc_linear_big_kernel<ITER, TM, TNQ, 0, true, false, 1, PF, BF>;
+    constexpr auto k_ao = enc_linear_big_kernel<ITER, TM, TNO, 2, false, true, 1, PF, BF>;
+    constexpr auto k_up = enc_linear_big_kernel<ITER, TM, TNU, 1, true, true, 1, PF, BF>;
+    constexpr auto k_down = enc_linear_big_kernel<ITER, TM, TNO, 2, false, true, ENC_SLABS, PF, BF>;
+    constexpr auto k_down_last = enc_linear_big_kernel<ITER, TM, TNO, 2, false, false, ENC_SLABS, PF, BF>;   // the last layer's: row-major, for the pooling kernel
+    // (per instantiation and device; calls on a handle are serialised. The launches below report through ONE hipGetLastError)
+    HIP_TRY(ensure_dynamic_lds<k_qkv>(e->device, lds_pin)); HIP_TRY(ensure_dynamic_lds<k_ao>(e->device, lds_pin));
+    HIP_TRY(ensure_dynamic_lds<k_up>(e->device, lds_pin)); HIP_TRY(ensure_dynamic_lds<k_down>(e->device, lds_pin));
+    HIP_TRY(ensure_dynamic_lds<k_down_last>(e->device, lds_pin));
     {
         EncEmbedArgs a{};
         a.meta = g.d_meta; a.word = d.word_emb; a.pos = d.pos_emb; a.type0 = d.type_emb0; a.H = H; a.KW = KW; a.y = g.y[0];

@@ -16,21 +16,6 @@
 
 #include "../../include/icd_search.h"
 #include "coarse_flat_kernel.hpp"
-// The dropped coarse-kernel forms of rounds 1-4 (row groups, eight waves, 16-query groups, K-split wave pairs) live on the git
-// branch archive/experiments-r01-r04 (directory experiments/); an A/B build that wants them checks that directory out and
-// adds EXTRA=-DICD_WITH_EXPERIMENTS. The tree itself carries only the shipped kernels and the variants of the shipped stage.
-#if defined(ICD_ABLATE) && !defined(ICD_FV_LIST) && defined(ICD_WITH_EXPERIMENTS)
-#define ICD_ABLATE_EXPERIMENTS 1
-#endif
-#if defined(ICD_ABLATE) && defined(ICD_WITH_EXPERIMENTS)
-#define ICD_ABLATE_KSPLIT 1
-#include "../../experiments/r04_ksplit_kernel/coarse_ksplit_kernel.hpp"   // (wave pairs split K, 64 queries per wave)
-#endif
-#ifdef ICD_ABLATE_EXPERIMENTS
-#include "../../experiments/r02_rg_kernel/coarse_rg_kernel.hpp"   // (A/B builds only: the row-group experiment)
-#include "../../experiments/r02_w8_kernel/coarse_w8_kernel.hpp"   // (A/B builds only: eight waves, two per SIMD)
-#include "../../experiments/r02_g16_kernel/coarse_g16_kernel.hpp" // (A/B builds only: the flat geometry on 16x16x32)
-#endif
 #include "attention_kernel.hpp"
 #include "exact_kernel.hpp"
 #include "finalize.hpp"
@@ -39,13 +24,16 @@
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
 #include "term_lookup.hpp"
+#include "search_policy.hpp"   // (host only: the adaptive rules of the AUTO path, PASS2_SKIP ... WIDE_REPROBE)
 
 using namespace icd;
 
 namespace {
-
 thread_local std::string g_err = "";
-int fail(int code, const char *fmt, ...) {
+}  // namespace
+
+// The ONE error hook: the text icd_last_error returns, thread-local. icd_group.cpp reports through it too (hence the linkage).
+extern "C" __attribute__((visibility("hidden"))) int icd_internal_fail(int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -55,9 +43,10 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+namespace {
+constexpr auto &fail = icd_internal_fail;
 }  // namespace
 
-// (icd_group.cpp reports its errors through the same thread-local text)
 // Query-sharded gather (icd_group.cpp): the all-gathered send buffers hold, per rank r, one PADDED slice of `width` queries
 // in four arrays (adj f64 | ids i64 | raw f32 | levels i32, each [world][width * k]); rank r's valid part is the first
 // (hi_r - lo_r) queries. ONE launch scatters every rank's valid hits to the contiguous [nq][k] outputs (it replaces four
@@ -90,16 +79,6 @@ extern "C" __attribute__((visibility("hidden"))) int icd_internal_unpack_query_s
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int icd_internal_fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 namespace {
 
 #define HIP_TRY(expr)                                                                              \
@@ -114,26 +93,32 @@ constexpr float EPS_REL = 1.2e-3f;
 constexpr size_t PACE_WORDS = (size_t)1 << 18;   // arrival counters of a paced coarse sweep: classes x epochs (1 MB)
 constexpr size_t COARSE_CACHED_IMAGE_BYTES = (size_t)96 << 20;   // fp16 images up to this size take CF_CACHED_VAR (both corpus copies then fit the 256 MiB Infinity Cache)
 constexpr int FAST_MAX_K = 100;      // the rescoring window holds up to 256 candidates (four per lane): k + the rows inside 2 eps of the k-th
-// (COARSE_MAX_P, PASS2_CHUNKS, PASS2_MAX_P, PASS2_BELOW: the list planner's, flat_partition.hpp)
+// (COARSE_MAX_P, PASS2_CHUNKS, PASS2_MAX_P, PASS2_BELOW: the list planner's, flat_partition.hpp; PASS2_SKIP, SPARSE_DISARM_AFTER,
+//  PASS2_DISARM_AFTER, WIDE_MIN_NQ, WIDE_REPROBE: the adaptive rules', search_policy.hpp)
 static_assert(FLAT_TILE_ROWS == CO_BN, "flat_partition.hpp plans tiles of CO_BN rows");
-constexpr int PASS2_SKIP = 24;       // ... and leaves this many flagged queries (or fewer) to the streaming kernel: 35 us per 8
-constexpr int SPARSE_DISARM_AFTER = 96; // the streaming kernel's two fallback launches are dropped after this many consecutive searches with NO flagged query (doubles at every incident)
-constexpr int PASS2_DISARM_AFTER = 4; // the second pass's two launches are dropped after this many consecutive searches that needed neither
-constexpr int WIDE_MIN_NQ = 2048;    // "large batch": below it a query has 16+ lists anyway
-constexpr int WIDE_REPROBE = 64;
 constexpr int NUM_EV = 6;
 constexpr int EV_RING = 128;         // profiled searches kept for icd_index_profile_summary
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, device): every launcher keeps, per device, the
+// hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, device): every kernel keeps, per device, the
 // largest size it has configured and raises it when a launch needs more (two indexes of different dim share kernels).
 constexpr int MAX_DEVICES = 64;
-template <typename K>
-hipError_t ensure_dynamic_lds(K kern, int device, size_t bytes, int *configured /* [MAX_DEVICES] */) {
+template <auto KERN>
+hipError_t ensure_dynamic_lds(int device, size_t bytes) {
+    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
     if (device < 0 || device >= MAX_DEVICES) return hipErrorInvalidDevice;
     if ((size_t)configured[device] >= bytes) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) configured[device] = (int)bytes;
     return e;
+}
+// ONE launch of a kernel with dynamic LDS: its limit raised to `lds_limit` when this device has not seen as much (some launchers
+// ask for more than the launch's own `lds`), the launch, the launch's error.
+template <auto KERN, typename... Args>
+hipError_t launch_lds(int device, size_t lds_limit, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args) {
+    const hipError_t e = ensure_dynamic_lds<KERN>(device, lds_limit);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(KERN, grid, block, lds, s, args...);
+    return hipGetLastError();
 }
 
 template <typename T>
@@ -216,29 +201,7 @@ struct icd_index {
     size_t bytes_ws = 0;
     // knobs / counters
     int chunks_override = 0;
-    // adaptive list count of LARGE batches (>= WIDE_MIN_NQ queries): when the second coarse pass had to rescue most of the
-    // previous large batch (a corpus of tight families), the first pass is planned with its list count right away
-    bool wide_mode = false;        // plan the first pass with PASS2_CHUNKS lists per query
-    int wide_runs = 0;             // large searches since wide_mode was entered (every WIDE_REPROBE-th runs narrow again)
-    bool last_narrow_large = false; // the last search was a large batch with the narrow plan and the second pass behind it
-    int64_t last_narrow_nq = 0;     // ... and its size: the flagged counters read at the NEXT search are fractions of THIS batch
-    // The second pass costs a search that flags nothing two launches that read a counter and leave (~9 us per 10 000-query
-    // step). They are armed while nothing is known about the corpus (the first searches of an index) and whenever a recent
-    // search flagged more queries than the streaming kernel takes cheaply; after PASS2_DISARM_AFTER consecutive searches
-    // that flagged fewer they are left out (a batch that then flags many takes the exact re-search once and re-arms them).
-    int p2_clean = 0;              // consecutive evaluated searches with <= PASS2_SKIP queries flagged by the first finalize
-    bool p2_eval_pending = false;  // the last search's counters have not been looked at yet
-    // The exact re-search behind every search is four launches: streaming kernel + list reduction (few flagged queries:
-    // one corpus sweep per 8) and fp32-MFMA kernel + finalize (many). With nothing flagged each reads a counter and leaves.
-    // After `sparse_need` consecutive searches whose re-search had nothing to do (counted on the device, so searches the
-    // host never looked at count too) the streaming pair is left out and the MFMA kernel takes any count >= 1. Measured at
-    // 10 000 x 37 000 (profiles/r03_sparse_fallback_policy.log): the pair costs a clean search ~3.4 us (0.5 %); without it
-    // a search with 1-8 flagged queries takes 1.25 instead of 0.72 ms, once - the run restarts and the requirement
-    // doubles. The break-even of the two is ~150 clean searches (ski rental); 96 stays below it (at most 2.6 x the
-    // cost of the best fixed choice in hindsight, 2 x at the break-even).
-    int sparse_need = SPARSE_DISARM_AFTER;
-    int sparse_run_seen = 0;       // the device's run length when the host last saw a completed search
-    bool sparse_disarmed = false;  // the last fast-path search went without the streaming pair
+    SearchPolicy pol;              // what the AUTO path remembers between searches: wide mode of large batches, the second pass and the streaming pair armed or not (search_policy.hpp)
     std::mutex mu;   // host-side state of the handle (plans, adaptive counters, profiling ring): calls on one handle are serialised; the DEVICE workspace still belongs to one stream at a time (header)
     int probe_flagged = -1, probe_left = -1;   // the corpus-shape probe of icd_index_create: queries its first finalize flagged / its second pass left (-1: not run)
     bool pass2_enabled = true;     // test hook (icd_index_set_second_pass)
@@ -295,10 +258,26 @@ void free_all(icd_index *x) {
     delete x;
 }
 
+// ---- launchers ---------------------------------------------------------------------------------------------------------------
+
 // candidates per exact list: the smallest of 16 / 32 / 64 / 128 that holds k. (32 is round 4's: the serving path searches
 // top_k * 2 = 20, and finalize merges at most 512 candidates per query - 8 lists of 64 gave a few hundred flagged queries 80
 // two-wave work-groups, 16 lists of 32 give them 160.)
 int exact_kp_for(int k) { return k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : 128)); }
+
+// the chunk count in [c_lo, c_hi] whose last round of `slots` work-groups is fullest (mtiles x c work-groups in all); the
+// first count whose last round is at least `enough` full is taken at once
+int fullest_round(int mtiles, int slots, int c_lo, int c_hi, double enough) {
+    double best = 0;
+    int bestc = c_lo;
+    for (int c = c_lo; c <= c_hi; ++c) {
+        const long items = (long)mtiles * c;
+        const double util = (double)items / (double)(((items + slots - 1) / slots) * slots);
+        if (util > best + 1e-9) { best = util; bestc = c; }
+        if (util >= enough) { bestc = c; break; }
+    }
+    return bestc;
+}
 
 // chunk count heuristic: enough work-groups to fill the chip, few enough lists to merge. `slots` = the work-groups the
 // chip holds at once: ONE per CU for every instantiation of exact_topk (its LDS - two 33-KB operand stages + the candidate
@@ -307,21 +286,8 @@ int exact_kp_for(int k) { return k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : 
 // ONE round.
 int pick_chunks(int mtiles, int row_tiles, int pmax, int slots) {
     int p = 1;
-    if (mtiles * 2 <= slots) {
-        p = std::max(1, slots / mtiles);
-    } else {
-        // the smallest p whose last round of work-groups is at least 90 % full (else the fullest)
-        double best = 0;
-        int bestp = 1;
-        const double want = 0.9;
-        for (int c = 1; c <= std::min(pmax, 8); ++c) {
-            const long items = (long)mtiles * c;
-            const double util = (double)items / (double)(((items + slots - 1) / slots) * slots);
-            if (util > best + 1e-9) { best = util; bestp = c; }
-            if (util >= want) { bestp = c; break; }
-        }
-        p = bestp;
-    }
+    if (mtiles * 2 <= slots) p = std::max(1, slots / mtiles);
+    else p = fullest_round(mtiles, slots, 1, std::min(pmax, 8), 0.9);   // the smallest p whose last round of work-groups is at least 90 % full (else the fullest)
     p = std::min(p, pmax);
     p = std::min(p, std::max(1, row_tiles));
     return std::max(1, p);
@@ -329,93 +295,19 @@ int pick_chunks(int mtiles, int row_tiles, int pmax, int slots) {
 
 template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32>
 int launch_exact(icd_index *x, const ExactArgs &a, int mtiles, hipStream_t s) {
-    auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP>;
+    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP>;
     const size_t lds = exact_lds_bytes<KP, E, NW, CAPV, BK>();
-    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)((int)lds), configured));
-    hipLaunchKernelGGL(kern, dim3(mtiles * a.P), dim3(NW * 64), lds, s, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(mtiles * a.P), dim3(NW * 64), lds, s, a));
     return ICD_OK;
 }
 
 template <int D, int VAR = CF_PRODUCT_VAR, int KP = CO_KP, bool PERSIST = false>
 int launch_coarse_flat(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_flat_kernel<D, VAR, KP, PERSIST>;
+    constexpr auto kern = coarse_flat_kernel<D, VAR, KP, PERSIST>;
     constexpr int lds = cf_lds_bytes(VAR);
-    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lds<kern>(x->device, (size_t)(lds), dim3(nwg), dim3(256), lds, s, a));
     return ICD_OK;
 }
-
-#ifdef ICD_ABLATE_KSPLIT
-template <int D, int KP = CO_KP, int TV = 0>
-int launch_coarse_ksplit(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_ksplit_kernel<D, KP, TV>;
-    constexpr int lds = ks_lds_bytes();
-    static int configured[MAX_DEVICES] = {};
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-#endif
-#ifdef ICD_ABLATE_EXPERIMENTS
-template <int D, int KP = CO_KP, int VAR = 0>
-int launch_coarse_rg(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_rg_kernel<D, KP, VAR>;
-    constexpr int lds = rg_lds_bytes();
-    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-template <int D, int KP = CO_KP, int VAR = 0>
-int launch_coarse_g16(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_g16_kernel<D, KP, VAR>;
-    constexpr int lds = w8_lds_bytes();
-    static int configured[MAX_DEVICES] = {};
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-template <int D, int KP = CO_KP, int VAR = 0>
-int launch_coarse_g16r(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_g16r_kernel<D, KP, VAR>;
-    constexpr int lds = g16_lds_bytes();
-    static int configured[MAX_DEVICES] = {};
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-template <int D, int KP = CO_KP, int VAR = 0>
-int launch_coarse_w8rg(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_w8rg_kernel<D, KP, VAR>;
-    constexpr int lds = w8_lds_bytes();
-    static int configured[MAX_DEVICES] = {};
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-template <int D, int KP = CO_KP, int VAR = 0>
-int launch_coarse_w8(icd_index *x, const CoarseFlatArgs &a, int nwg, hipStream_t s) {
-    auto kern = coarse_w8_kernel<D, KP, VAR>;
-    constexpr int lds = w8_lds_bytes();
-    static int configured[MAX_DEVICES] = {};
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)(lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-#endif
 
 // streaming exact kernel + list reduction for a sparse query set (device-side gated when nq_ptr is given).
 // p_out = 0: choose the smallest number of output lists (direct tiny-batch path); returns it in *p_used.
@@ -457,13 +349,10 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
         const size_t cap = (l % 2 == 0) ? x->partx_cap + (size_t)128 * FIN_MAX_CAND_X : x->lists_cap;
         if ((size_t)a.nq * plan[l] * KP > cap) return fail(ICD_ERR_INVALID, "stream workspace too small for reduction level %d", l);
     }
-    auto kern = stream_topk_kernel<KP, E, QB>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB>;
     const size_t lds = stream_lds_bytes<KP, E, QB>(x->dim, stages);
     if (lds > (size_t)LDS_LIMIT) return fail(ICD_ERR_INVALID, "stream kernel: dim=%d does not fit LDS with %d queries per pass", x->dim, QB);
-    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)((int)lds), configured));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(nwg), dim3(256), lds, s, a));
     int nlists = 4 * nwg;
     for (int l = 0; l < levels; ++l) {   // lists -> partx -> lists -> ... -> partx
         ReduceArgs r{};
@@ -512,38 +401,31 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
         a.done_value = ++x->done_seq;
         x->done_armed = true;
     }
-    auto kern = stream_topk_kernel<KP, E, QB, true>;
     // (at least 84 KB: ONE work-group per CU whatever the corpus size - the fence-free sc1 hand-off of the kernel's tail is the
     //  form measured for one work-group per CU, MI355X_MICROARCH.md visibility table)
     const size_t lds = std::max<size_t>(stream_one_lds_bytes<KP, E, QB>(x->dim, pl.stages, pl.rps), (size_t)84 * 1024);
-    static int configured[MAX_DEVICES] = {};
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, true>;
     if constexpr (QB == 1) {
         if (host_q) {   // the vector in the kernel arguments: no copy command in front of the launch
-            auto kern_in = stream_one_inline_kernel<KP, E>;
-            static int configured_in[MAX_DEVICES] = {};
-            HIP_TRY(ensure_dynamic_lds(kern_in, x->device, (size_t)LDS_LIMIT, configured_in));
+            constexpr auto kern_in = stream_one_inline_kernel<KP, E>;
             StreamInlineQuery iq;
             memcpy(iq.v, host_q, (size_t)x->dim * sizeof(float));
             a.queries = nullptr;
-            hipLaunchKernelGGL(kern_in, dim3(pl.nwg), dim3(256), lds, s, a, iq);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_lds<kern_in>(x->device, (size_t)LDS_LIMIT, dim3(pl.nwg), dim3(256), lds, s, a, iq));
             return ICD_OK;
         }
     }
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)LDS_LIMIT, configured));
-    hipLaunchKernelGGL(kern, dim3(pl.nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lds<kern>(x->device, (size_t)LDS_LIMIT, dim3(pl.nwg), dim3(256), lds, s, a));
     return ICD_OK;
 }
 
 template <bool RESCORE, bool DEEP, int EWM>
 int launch_finalize_t(icd_index *x, const FinArgs &a, hipStream_t s) {
-    auto kern = finalize_kernel<RESCORE, DEEP, EWM>;
+    constexpr auto kern = finalize_kernel<RESCORE, DEEP, EWM>;
     const size_t lds = 4 * fin_wave_lds_bytes(RESCORE, x->dim, a.lds_cand > 0 ? a.lds_cand : a.P * a.KP, EWM);
-    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
-    HIP_TRY(ensure_dynamic_lds(kern, x->device, (size_t)((int)(4 * fin_wave_lds_bytes(RESCORE, x->dim, (!RESCORE && EWM >= 4) ? FIN_MAX_CAND_X : FIN_MAX_CAND, EWM))), configured));
-    hipLaunchKernelGGL(kern, dim3((a.nq + 3) / 4), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
+    // (the limit: the largest window this instantiation is ever launched with)
+    const size_t lds_limit = (size_t)((int)(4 * fin_wave_lds_bytes(RESCORE, x->dim, (!RESCORE && EWM >= 4) ? FIN_MAX_CAND_X : FIN_MAX_CAND, EWM)));
+    HIP_TRY(launch_lds<kern>(x->device, lds_limit, dim3((a.nq + 3) / 4), dim3(256), lds, s, a));
     return ICD_OK;
 }
 
@@ -593,9 +475,596 @@ __global__ __launch_bounds__(256) void gather_view_rows_kernel(const float *src,
     if (dst_levels && lane == 0) dst_levels[i] = src_levels[r];
 }
 
+// ---- A/B switches of the shipped kernels -------------------------------------------------------------------------------------
+// `make ABLATE=1` builds a library whose searches read these from the environment (scripts/gpu_ab_*.sh, scripts/probe/); the
+// product build knows the defaults only. Performance switches: the results are the same whatever they are set to.
+struct SearchOverrides {
+    int exact_cfg = 0;            // ICD_EXACT_CFG: 1 / 2 = earlier forms of exact_topk at k <= 16, 3 = the one-work-group-per-CU form at k <= 32
+    int flat_u = 0;               // ICD_FLAT_U: at least this many tiles per work-group of the coarse sweep
+    int flat_list = 0;            // ICD_FLAT_LIST: tiles per list (0: the planner's)
+    int flat_boot = -1;           // ICD_FLAT_BOOT: bootstrap tiles (-1: the rule's)
+    int flat_sparse = -1;         // ICD_FLAT_SPARSE: first tile of a list with the group pre-filter (-1: CO_SPARSE_FROM)
+    int xcd_mode = -1;            // ICD_XCD_MODE: 0 identity, 1 XCD swizzle only, 2 classes unsplit
+    bool dim1024_full = false;    // ICD_1024_FULL: dim 1024 with the 768 form of the coarse kernel
+    bool fin_skip_walk = false;   // ICD_FIN_SKIP_WALK
+    bool has_flat_var = false;    // ICD_FLAT_VAR: stage / select variants of the flat kernel (dim 768), those of ICD_FV_LIST when the build names them
+    int flat_var = 0;
+};
+#ifdef ICD_ABLATE
+SearchOverrides search_overrides() {
+    SearchOverrides o;
+    if (const char *e = getenv("ICD_EXACT_CFG")) o.exact_cfg = atoi(e);
+    if (const char *e = getenv("ICD_FLAT_U")) o.flat_u = atoi(e);
+    if (const char *e = getenv("ICD_FLAT_LIST")) o.flat_list = std::max(1, atoi(e));
+    if (const char *e = getenv("ICD_FLAT_BOOT")) o.flat_boot = std::max(0, atoi(e));
+    if (const char *e = getenv("ICD_FLAT_SPARSE")) o.flat_sparse = std::max(0, atoi(e));
+    if (const char *e = getenv("ICD_XCD_MODE")) o.xcd_mode = atoi(e);
+    o.dim1024_full = getenv("ICD_1024_FULL") != nullptr;
+    o.fin_skip_walk = getenv("ICD_FIN_SKIP_WALK") != nullptr;
+    if (const char *e = getenv("ICD_FLAT_VAR")) { o.has_flat_var = true; o.flat_var = atoi(e); }
+    return o;
+}
+// the variant of exact_topk the overrides ask for at this list width, if any: true = taken, *rc its result
+bool launch_exact_variant(icd_index *x, const SearchOverrides &ov, int kpx, const ExactArgs &a, int mtx, hipStream_t s, int *rc) {
+    if (kpx == 16 && ov.exact_cfg == 1) *rc = launch_exact<16, 1, 4>(x, a, mtx, s);
+    else if (kpx == 16 && ov.exact_cfg == 2) *rc = launch_exact<16, 1, 4, 64, 16, 1>(x, a, mtx, s);
+    else if (kpx == 32 && ov.exact_cfg == 3) *rc = launch_exact<32, 2, 4, 112>(x, a, mtx, s);
+    else return false;
+    return true;
+}
+// ... and of the first coarse pass
+bool launch_coarse_variant(icd_index *x, const SearchOverrides &ov, const CoarseFlatArgs &a, int nwg, hipStream_t s, int *rc) {
+    if (x->dim == 1024) {
+        if (!ov.dim1024_full) return false;
+        *rc = launch_coarse_flat<1024, CF_PRODUCT_VAR>(x, a, nwg, s);   // A/B: the 768 form
+        return true;
+    }
+    if (!ov.has_flat_var) return false;
+    const int v = ov.flat_var;
+    if (false) {}
+#define ICD_FV_CASE(V) else if (v == V) *rc = launch_coarse_flat<768, V>(x, a, nwg, s);
+#ifdef ICD_FV_LIST
+    ICD_FV_LIST
+#else
+    ICD_FV_CASE(0) ICD_FV_CASE(139) ICD_FV_CASE(143) ICD_FV_CASE(155) ICD_FV_CASE(171) ICD_FV_CASE(187) ICD_FV_CASE(2187) ICD_FV_CASE(2203)
+    ICD_FV_CASE(2235) ICD_FV_CASE(1163) ICD_FV_CASE(4235) ICD_FV_CASE(4251)
+    ICD_FV_CASE(34971) ICD_FV_CASE(35995) ICD_FV_CASE(39067) ICD_FV_CASE(100507) ICD_FV_CASE(104603) ICD_FV_CASE(32923) ICD_FV_CASE(32955) ICD_FV_CASE(34843) ICD_FV_CASE(166043) ICD_FV_CASE(297115) ICD_FV_CASE(559259) ICD_FV_CASE(1083547)
+#endif
+#undef ICD_FV_CASE
+    else *rc = fail(ICD_ERR_INVALID, "ICD_FLAT_VAR=%d is not built", v);
+    return true;
+}
+#else
+inline SearchOverrides search_overrides() { return SearchOverrides{}; }
+inline bool launch_exact_variant(icd_index *, const SearchOverrides &, int, const ExactArgs &, int, hipStream_t, int *) { return false; }
+inline bool launch_coarse_variant(icd_index *, const SearchOverrides &, const CoarseFlatArgs &, int, hipStream_t, int *) { return false; }
+#endif
+
+// ---- the search paths --------------------------------------------------------------------------------------------------------
+// What the four paths of a search share, computed once by search_device.
+struct SearchCtx {
+    icd_index *x;
+    const float *dq;
+    int nq, k;
+    hipStream_t s;
+    SearchOverrides ov;
+    bool use_fast;       // AUTO on an index with an fp16 image
+    int row_tiles;
+    FinArgs f;           // what every finalize launch of this search starts from
+    // exact-kernel configuration (full run, or fallback over the flagged list)
+    int kpx, nwx;
+    int wg_per_cu_x;     // work-groups of exact_topk a CU holds (its LDS)
+    int bmq, mtx;
+    int cand_x, pmax_x;  // lists per query finalize<false> merges: 2048 candidates at k <= 64 (its top-k prefilter keeps that cheap), 512 above
+    int p_dense_max;     // chunk limit of the device-sized partition of a flagged list
+    // sparse: streaming kernel (+ list reduction) instead of / next to the MFMA exact kernel
+    // queries per pass: host-known for direct calls (1, 2, 4 or 8), 8 for the device-gated fallback
+    int p_sparse;        // lists per slot that finalize<false> merges (32 / 8 / 4)
+    int sparse_max;      // how many flagged queries still go to the streaming kernel
+    bool stream_ok;      // small batches (the reference's one-query-per-call shape): stream the corpus once, exact, no coarse pass
+};
+
+SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s) {
+    SearchCtx c{};
+    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast;
+    c.ov = search_overrides();
+    c.row_tiles = (int)((x->n + 127) / 128);
+    FinArgs &f = c.f;
+    f.k = k; f.queries = dq; f.corpus = x->corpus; f.dim = x->dim; f.qnorm = x->qnorm; f.qbad = x->qbad;
+    f.qexp = x->qexp; f.rmax = x->rmax_scaled; f.cexp = x->cexp; f.eps_rel = EPS_REL; f.nflag = x->nflag; f.flagged = x->flagged;
+    if (use_fast) f.thr0 = x->thr0;
+    if (x->cmean) { f.rmax_unc = x->rmax_unc_scaled; f.eps_f32 = 2.0f * (float)x->dim * 5.9604645e-8f; }
+    f.levels = x->levels; f.id_base = x->id_base; f.row_map = x->row_map;
+    f.out_scores = o.scores; f.out_ids = o.ids; f.out_adj = o.adj; f.out_adj_raw = o.adj_raw;
+    f.out_adj_ids = o.adj_ids; f.out_adj_levels = o.adj_lv;
+
+    c.kpx = exact_kp_for(k);
+    c.nwx = c.kpx <= 64 ? 4 : 2;
+    c.wg_per_cu_x = c.kpx <= 32 ? 2 : 1;
+    if (c.kpx == 32 && c.ov.exact_cfg == 3) c.wg_per_cu_x = 1;
+    c.bmq = c.nwx * 32;
+    c.mtx = (nq + c.bmq - 1) / c.bmq;
+    c.cand_x = c.kpx <= 64 ? FIN_MAX_CAND_X : FIN_MAX_CAND;
+    c.pmax_x = std::min(64, c.cand_x / c.kpx);
+    c.p_dense_max = c.cand_x / c.kpx;
+    c.p_sparse = FIN_MAX_CAND / c.kpx;
+    // How many flagged queries still go to the streaming kernel: it re-reads the corpus once per 8 queries (~37 us at
+    // 37k rows); the fp32-MFMA kernel, its short list cut into up to 2048 / KP chunks, needs ~0.22 ms for any count up to a
+    // few hundred: they meet near 45 (ST_FALLBACK_MAX_ACTIVE, stream_kernel.hpp); the list workspace caps it by k.
+    // (the first reduction level leaves at most 512 lists per slot in the second workspace)
+    c.sparse_max = (int)std::min<size_t>(std::min<size_t>(ST_FALLBACK_MAX_ACTIVE, x->lists_cap / ((size_t)1024 * c.kpx)),
+                                         c.kpx == 16 ? (size_t)ST_FALLBACK_MAX_ACTIVE : x->partx_cap / ((size_t)512 * c.kpx));
+    c.stream_ok = x->dim % (32 * ST_PF) == 0 && stream_fits(c.kpx, 1, x->dim);
+    return c;
+}
+
+int run_stream(const SearchCtx &c, const int *qlist, const int *nq_ptr, int nqs, int p_out, int *p_used, const float *thr0 = nullptr) {
+    icd_index *x = c.x;
+    int qb = nq_ptr ? 8 : (nqs <= 1 ? 1 : (nqs <= 2 ? 2 : (nqs <= 4 ? 4 : 8)));
+    const int max_act = nq_ptr ? c.sparse_max : std::max(c.sparse_max, nqs);   // (a direct call - up to ST_MAX_ACTIVE queries - is not gated)
+    while (qb > 1 && !stream_fits(c.kpx, qb, x->dim)) qb >>= 1;
+#define ICD_ST(KPV, EV) \
+    (qb == 1 ? launch_stream<KPV, EV, 1>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0) : \
+     qb == 2 ? launch_stream<KPV, EV, 2>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0) : \
+     qb == 4 ? launch_stream<KPV, EV, 4>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0) : \
+               launch_stream<KPV, EV, 8>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0))
+    if (c.kpx == 16) return ICD_ST(16, 2);
+    if (c.kpx == 32) return ICD_ST(32, 2);
+    if (c.kpx == 64) return ICD_ST(64, 3);
+    return ICD_ST(128, 4);
+#undef ICD_ST
+}
+
+// A chunk count the exact kernel's list workspace holds for EVERY query of the batch (all of them may be flagged: all-zero
+// queries, duplicate rows): lowered until it fits, an error if one chunk does not, then rounded to whole row tiles per chunk.
+int fit_chunks(const SearchCtx &c, int *p) {
+    const icd_index *x = c.x;
+    int px = *p;
+    while (px > 1 && (size_t)c.nq * px * c.kpx > x->partx_cap) --px;
+    if ((size_t)c.nq * px * c.kpx > x->partx_cap) return fail(ICD_ERR_INVALID, "workspace too small for nq=%d k=%d", c.nq, c.k);
+    const int tiles_per = (c.row_tiles + px - 1) / px;
+    *p = (c.row_tiles + tiles_per - 1) / tiles_per;
+    return ICD_OK;
+}
+
+// The exact search of every path: over all queries (qlist / nq_ptr null) or over a flagged list whose length only the device
+// knows. `stream`: the streaming kernel + list reduction takes up to sparse_max queries; `mfma`: exact_topk takes the rest;
+// finalize<false> merges either's lists and is the last launch of the search (it copies the counters to the host).
+int run_exact(const SearchCtx &c, const int *qlist, const int *nq_ptr, int px, bool mfma, bool stream, bool stream_launch = true,
+              bool track_run = false, const float *thr0 = nullptr) {
+    icd_index *x = c.x;
+    const int nq = c.nq, kpx = c.kpx;
+    hipStream_t s = c.s;
+    const int sparse_here = stream_launch ? c.sparse_max : 0;   // (streaming pair left out: the MFMA kernel takes every count >= 1)
+    if (!nq_ptr) x->last_chunks = px;   // (the fallback keeps the coarse pass's chunk count)
+    int rc = ICD_OK;
+    if (stream && stream_launch) {
+        int used = px;
+        rc = run_stream(c, qlist, nq_ptr, nq, mfma ? px : 0, &used, thr0);   // alone: fewest output lists
+        if (rc) return rc;
+        px = used;
+        if (!nq_ptr) x->last_chunks = px;
+    }
+    int px_dense = 0;
+    if (mfma) {
+        // The MFMA kernel may have to take EVERY query (all of them flagged): its list count is sized against
+        // the workspace like a full exact run; only the streaming kernel (<= ST_MAX_ACTIVE slots) uses px.
+        int pm = px;
+        if (stream) {
+            pm = pick_chunks(c.mtx, c.row_tiles, c.pmax_x, x->num_cu * c.wg_per_cu_x);
+            rc = fit_chunks(c, &pm);
+            if (rc) return rc;
+            px_dense = pm;
+        }
+        ExactArgs a{};
+        a.corpus = x->corpus; a.queries = c.dq; a.qlist = qlist; a.nq_ptr = nq_ptr; a.nq = nq;
+        a.min_active = stream ? sparse_here : 0;
+        a.adaptive_one_per_cu = c.wg_per_cu_x > 1 ? x->num_cu : 0;
+        a.adaptive_max_p = stream ? c.p_dense_max : 0;   // fallback: the chunk count follows the actual flagged count
+        a.n = (int)x->n; a.dim = x->dim; a.P = pm;
+        a.rows_per_chunk = ((c.row_tiles + pm - 1) / pm) * 128;
+        a.part_scores = x->partx_s; a.part_rows = x->partx_r; a.thr0 = thr0;
+        // (LDS: k <= 16 two work-groups per CU - 17 KB of stage + 60-entry buffers; k <= 64 one of four waves - 34 KB +
+        //  112-entry buffers; larger k two waves. Eight waves on 64-entry buffers at k <= 32 - two per SIMD - were built and
+        //  are slower, 9.2 against 7.2 ms per 10 000 queries: a 64-entry buffer with 32 kept is compacted after every append)
+        if (launch_exact_variant(x, c.ov, kpx, a, c.mtx, s, &rc)) {}
+        else if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2>(x, a, c.mtx, s);
+        else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16>(x, a, c.mtx, s);
+        else if (kpx == 64) rc = launch_exact<64, 2, 4, 112>(x, a, c.mtx, s);
+        else rc = launch_exact<128, 3, 2>(x, a, c.mtx, s);
+        if (rc) return rc;
+    }
+    rec(x, 4, s);
+    FinArgs g = c.f;
+    g.part_scores = x->partx_s; g.part_rows = x->partx_r; g.P = px; g.KP = kpx;
+    g.P_dense = px_dense; g.sparse_max = sparse_here; g.track_run = track_run ? 1 : 0; g.lds_cand = std::max(px, (stream && mfma) ? c.p_dense_max : px_dense) * kpx;
+    g.dense_grid = c.mtx * std::max(1, px_dense); g.dense_bmq = c.bmq; g.dense_max_p = (stream && mfma) ? c.p_dense_max : 0; g.dense_one_per_cu = c.wg_per_cu_x > 1 ? x->num_cu : 0; g.n_rows = (int)x->n;
+    g.nq = nq; g.nq_ptr = nq_ptr; g.qlist = qlist;
+    g.counters = x->nflag; g.host_counters = x->h_nflag_dev;   // (the last launch of every search: no separate copy)
+    rc = launch_finalize<false>(x, g, s);
+    rec(x, 5, s);
+    return rc;
+}
+
+// a host caller's ONE query whose copy search_common left out (host_q): every path but the single-launch kernel wants it
+// in device memory after all - the copy it would have got, enqueued before anything that reads dq
+int stage_host_query(const SearchCtx &c) {
+    icd_index *x = c.x;
+    if (!x->host_q) return ICD_OK;
+    const size_t qbytes = (size_t)x->dim * sizeof(float);
+    memcpy(x->h_pin, x->host_q, qbytes);
+    HIP_TRY(hipMemcpyAsync(x->qdev, x->h_pin, qbytes, hipMemcpyHostToDevice, c.s));
+    x->host_q = nullptr;
+    return ICD_OK;
+}
+
+// (the fallback counter starts every search at zero: the exact-only paths clear it themselves, the fast path in its
+//  query-prep launch - one launch less per step)
+
+// ---- path 1: a handful of queries, streamed (exact, no coarse pass) ---------------------------------------------------------
+int search_tiny(const SearchCtx &c) {
+    icd_index *x = c.x;
+    const int nq = c.nq;
+    hipStream_t s = c.s;
+    x->last_mode = ICD_MODE_EXACT;
+    x->last_chunks = c.p_sparse;
+    StreamOnePlan pl;
+    // (up to FOUR queries: at eight the sweep is bound by the lanes' fmaf chains, not by memory - 40 of a wave's 64 lanes hold
+    //  rows in this form - and the general path is 12 us faster: profiles/r05_single_query.log)
+    const int qb1 = nq <= 1 ? 1 : (nq <= 2 ? 2 : 4);
+    const bool one = nq <= 4 && c.kpx == 16 && x->opt_stream_one && plan_stream_one((int)x->n, x->dim, x->num_cu, qb1, 64 * 2, &pl) &&
+                     (size_t)nq * pl.nwg * c.kpx * 2 <= x->lists_cap;
+    if (one) {   // up to four queries (the reference's call shape is ONE; a /query request batches its D diagnoses): ONE launch,
+                 // no memset, no reduction, no finalize
+        rec(x, 3, s);
+        const float *hq = qb1 == 1 ? x->host_q : nullptr;   // (a host caller's ONE query: search_common left the copy out)
+        if (!hq) { const int rcq = stage_host_query(c); if (rcq) return rcq; }
+        const bool poll = x->host_one_call && (x->opt_host_one & 2) != 0;
+        const int rc1 = qb1 == 1 ? launch_stream_one<16, 2, 1>(x, c.dq, 1, c.f, s, hq, poll) : qb1 == 2 ? launch_stream_one<16, 2, 2>(x, c.dq, 2, c.f, s)
+                      : launch_stream_one<16, 2, 4>(x, c.dq, (int)nq, c.f, s);
+        rec(x, 4, s);
+        rec(x, 5, s);
+        return rc1;
+    }
+    { const int rcq = stage_host_query(c); if (rcq) return rcq; }
+    HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), s));
+    rec(x, 3, s);
+    return run_exact(c, nullptr, nullptr, c.p_sparse, false, true);
+}
+
+// ---- path 2: EXACT at k > 32, NARROW certified lists ------------------------------------------------------------------------
+// Lists of KP >= k need 64- or 128-entry candidate buffers: one work-group of four waves per CU at k <= 64, of two above
+// (0.39 / 0.15 of the fp32 MFMA peak at k = 50 / 100, against 0.59 at k = 20). Instead: the k <= 32 configuration (lists
+// of 32, two work-groups per CU) over ROW-STRIDED chunks - chunk c holds rows c, c + P, ... so that neighbouring rows
+// (an ICD family in code order) spread evenly - with P large enough that a list holds ~k / P << 32 members of the top-k,
+// and finalize CHECKS it: a full list whose worst kept key beats the k-th best of the merge may have dropped a member
+// of the top-k; such a query is re-searched with KP >= k lists (the flagged-list machinery of the AUTO fallback).
+// Results are the exact top-k either way. *taken = false: the lists do not fit the workspace, the plain path takes the search.
+int search_exact_narrow(const SearchCtx &c, bool *taken) {
+    icd_index *x = c.x;
+    const int nq = c.nq, k = c.k;
+    hipStream_t s = c.s;
+    *taken = false;
+    HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), s));
+    const int slots = x->num_cu * 2;
+    const int mtx_n = (nq + 127) / 128;                   // query tiles of THIS configuration (four waves x 32 queries; c.mtx counts the KP >= k configuration's tiles, 64 queries at k > 64: ADVICE r5)
+    const int p_need = std::max(2, (k + 7) / 8);          // ~8 members of the top-k per list when they spread evenly
+    // the count at or above p_need whose last round of work-groups is fullest (a short batch: enough chunks to fill the chip)
+    const int pn = fullest_round(mtx_n, slots, p_need, std::min(FIN_MAX_CAND_X / 32, std::max(p_need + 8, slots / std::max(1, mtx_n))), 2.0);
+    if (!((size_t)nq * pn * 32 <= x->partx_cap && pn * 32 <= FIN_MAX_CAND_X)) return ICD_OK;
+    *taken = true;
+    x->last_chunks = pn;
+    x->fallback_word = 0;
+    rec(x, 3, s);
+    ExactArgs a{};
+    a.corpus = x->corpus; a.queries = c.dq; a.nq = nq; a.n = (int)x->n; a.dim = x->dim; a.P = pn; a.strided = 1;
+    a.rows_per_chunk = 128;   // (unused by the strided form)
+    a.part_scores = x->partx_s; a.part_rows = x->partx_r;
+    int rc = launch_exact<32, 1, 4, 62, 16, 2, 16>(x, a, mtx_n, s);
+    if (rc) return rc;
+    rec(x, 4, s);
+    FinArgs g = c.f;
+    g.part_scores = x->partx_s; g.part_rows = x->partx_r; g.P = pn; g.KP = 32; g.nq = nq; g.lds_cand = pn * 32;
+    g.narrow_check = 1; g.nflag = x->nflag; g.flagged = x->flagged;
+    rc = launch_finalize<false>(x, g, s);
+    if (rc) return rc;
+    rec(x, 5, s);
+    // the queries the check could not clear (none on data whose rows spread): KP >= k lists over the flagged list
+    return run_exact(c, x->flagged, x->nflag, std::min(c.p_sparse, c.row_tiles), true, c.stream_ok, true, false, nullptr);
+}
+
+// ---- path 3: plain EXACT ------------------------------------------------------------------------------------------------------
+int search_exact(const SearchCtx &c) {
+    icd_index *x = c.x;
+    HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), c.s));
+    int px = pick_chunks(c.mtx, c.row_tiles, c.pmax_x, x->num_cu * c.wg_per_cu_x);
+    const int rc = fit_chunks(c, &px);
+    if (rc) return rc;
+    x->last_chunks = px;
+    rec(x, 3, c.s);
+    return run_exact(c, nullptr, nullptr, px, true, false);
+}
+
+// ---- path 4: AUTO = prep -> coarse -> finalize(certify + rescore) -> retry -> second pass -> exact fallback -----------------
+// The plan of the two coarse passes of one AUTO search.
+struct AutoPlan {
+    bool wide_lists;     // 24 candidates per list instead of 16 (large k)
+    bool wide_now;       // wide mode: the first pass planned with the second pass's list count
+    bool sparse_off;     // the exact re-search goes without the streaming pair
+    int kp_c;            // candidates per list of the first pass
+    int ctiles, U, nwg;  // corpus tiles swept, tiles per work-group and work-groups of the first pass
+    int pc;              // its lists per query
+    CoarseFlatArgs a;
+    int p2, nwg2;        // the second pass: lists per query (0: none) and logical work-groups of a full batch
+    CoarseFlatArgs a2;   // (nq_ptr / qlist set at the launch: which flag word / list feeds it)
+};
+
+// query prep: fp16 queries, norms and scales; clears the coarse thresholds and the fallback counters
+int auto_prep(const SearchCtx &c, int nq_pad) {
+    icd_index *x = c.x;
+    ConvertArgs cv{};
+    cv.src = c.dq; cv.dst = x->q16; cv.rows = c.nq; cv.rows_pad = nq_pad; cv.dim = x->dim; cv.mode = 0;
+    cv.norm = x->qnorm; cv.scale_exp = x->qexp; cv.bad = x->qbad; cv.zero_u32 = x->shared_thr; cv.zero_i32 = x->nflag;
+    cv.zero_u32b = x->shared_thr + x->max_nq_pad;
+    hipLaunchKernelGGL(convert_rows_kernel, dim3((nq_pad + 3) / 4), dim3(256), 0, c.s, cv);
+    HIP_TRY(hipGetLastError());
+    rec(x, 1, c.s);
+    return ICD_OK;
+}
+
+// A class of work-groups that stream the same tiles should have about a dozen members per XCD-local group: many more and
+// they all hit the same L2 channel at the same time (measured slower), so large classes are split into sub-classes
+// (l mod T s also start on the same tile). xcd_mode: the A/B switch (0 identity, 1 XCD swizzle only, 2 classes unsplit).
+int split_class_period(int U, int ctiles, int nwg, int xcd_mode = -1) {
+    int period = flat_class_period(U, ctiles);
+    const int members = nwg / std::max(1, period);
+    int split = (members + 11) / 12;
+    if (xcd_mode == 0) period = 0;
+    else if (xcd_mode == 1) period = 1 << 30;
+    else if (xcd_mode == 2) split = 1;
+    if (period > 0 && period < (1 << 20)) period *= std::max(1, split);
+    return period;
+}
+
+// Takes in the previous search's counters (when they have arrived), decides this search's shape and plans both passes:
+// the flat partition of the (query tile x corpus tile) grid over the CUs (coarse_flat_kernel.hpp).
+int auto_plan(const SearchCtx &c, int nq_pad, AutoPlan &pl) {
+    icd_index *x = c.x;
+    const int nq = c.nq, k = c.k;
+    const int mtc = nq_pad / 128;
+    // corpus tiles to sweep and tiles per work-group (flat_partition.hpp: a few zero tiles behind the corpus buy a tile
+    // count that shares a factor with U, i.e. work-groups that stream the same tiles together)
+    const int ctiles_min = (int)((x->n + 127) / 128);
+    const FlatPlan plan = plan_flat_tiles(mtc, ctiles_min, x->n_pad / 128 - ctiles_min, x->num_cu);
+    const int ctiles = plan.ctiles;
+    pl.ctiles = ctiles;
+    pl.wide_lists = k > x->opt_wide_from && x->dim == 768;
+    // ---- adaptive list count of large batches (search_policy.hpp) ------------------------------------------------------
+    // The counters of the previous search sit in pinned host memory once its copy event has completed (hipEventQuery: no
+    // wait).
+    // (while the stream is being captured into a HIP graph nothing may be queried: the plan is the one the host state gives now,
+    //  and it is frozen into the graph - a performance decision only, the replayed search returns the exact top-k either way)
+    const bool counters_in = !x->capturing && hipEventQuery(x->ev_nflag) == hipSuccess;   // (every search enqueued so far has completed)
+    if (counters_in) policy_take_counters(x->pol, search_counters(x->h_nflag));
+    const SearchDecision dec = policy_decide(x->pol, x->adapt_enabled, nq, k, x->chunks_override);
+    pl.sparse_off = dec.sparse_off;
+    pl.wide_now = dec.wide_now;
+    pl.kp_c = pl.wide_lists ? CO_KP_WIDE : CO_KP;
+
+    CoarseFlatArgs &a = pl.a;
+    a = CoarseFlatArgs{};
+    a.q16 = x->q16; a.c16 = x->c16; a.nq = nq; a.n = (int)x->n; a.n_pad = ctiles * 128; a.ctiles = ctiles;
+    a.total_units = mtc * ctiles;
+    // The bootstrap level (6th best of the first boot_tiles * 128 rows of a list) must stay far below the k-th best
+    // of the whole corpus or the list's bound lands inside the window: fewer tiles for larger k (measured at
+    // k = 48 with 8 tiles: 1.6 % of the queries uncertified).
+    a.boot_tiles = c.ov.flat_boot >= 0 ? c.ov.flat_boot : std::max(1, std::min(CO_BOOT_TILES, 96 / std::max(1, k)));
+    a.sparse_from = c.ov.flat_sparse >= 0 ? c.ov.flat_sparse : CO_SPARSE_FROM;
+    // ---- the list plan of both passes (flat_partition.hpp plan_coarse_lists): lists per query, tiles per list and
+    // per work-group. No list is longer than the kernel's per-list buffer descriptor reaches (flat_max_list_tiles).
+    CoarsePlanIn pin{};
+    pin.mtc = mtc; pin.ctiles = ctiles; pin.U = std::max(plan.U, c.ov.flat_u); pin.nq = nq; pin.k = k;
+    pin.kp = pl.kp_c; pin.kp2 = CO_KP; pin.max_cand = FIN_MAX_CAND;
+    pin.wide_lists = pl.wide_lists; pin.wide_now = pl.wide_now; pin.chunks_override = x->chunks_override;
+    pin.pass2 = x->pass2_enabled && x->pol.pass2_armed() && x->part2_s;
+    pin.partc_cap = (long long)x->partc_cap; pin.part2_cap = (long long)x->part2_cap;
+    pin.max_list_tiles = flat_max_list_tiles(x->dim);
+    if (c.ov.flat_list > 0) pin.list_override = c.ov.flat_list;
+    const CoarsePlan cp = plan_coarse_lists(pin);
+    if (!cp.ok)
+        return fail(ICD_ERR_UNSUPPORTED, "coarse pass: no list plan for n=%lld dim=%d nq=%d k=%d (lists per query %d, at most %d tiles per list)",
+                    (long long)x->n, x->dim, nq, k, cp.P, pin.max_list_tiles);
+    const int U = cp.U;
+    pl.U = U; pl.pc = cp.P;
+    x->last_chunks = cp.P;
+    pl.nwg = (a.total_units + U - 1) / U;
+    a.list_tiles = cp.list_tiles;
+    a.units_per_wg = U; a.P = cp.P;
+    a.pos_period = split_class_period(U, ctiles, pl.nwg, c.ov.xcd_mode);
+    a.part_scores = x->partc_s; a.part_rows = x->partc_r; a.bounds = x->partc_b; a.shared_thr = x->shared_thr;
+    a.dbg = x->dbg;
+    a.nwg_virtual = pl.nwg;
+    // ---- the second pass's plan: the same sweep cut into about PASS2_CHUNKS lists per query, every work-group's run
+    // one list (the shape icd_index_set_chunks asks for). Everything the host must know is independent of how many
+    // queries will be flagged: U2, the list slots per query (worst case over all query tiles of the full batch), the
+    // logical work-group count of a full batch. The kernel sizes the sweep from the flagged count on the device.
+    pl.p2 = 0; pl.nwg2 = 0;
+    pl.a2 = CoarseFlatArgs{};
+    if (cp.P2 > 0) {
+        const int U2 = cp.U2;
+        CoarseFlatArgs &a2 = pl.a2;
+        pl.p2 = cp.P2;
+        a2 = a;
+        a2.nq_ptr = nullptr; a2.qlist = nullptr;
+        a2.units_per_wg = U2; a2.list_tiles = cp.list_tiles2; a2.P = pl.p2;
+        a2.boot_tiles = a.boot_tiles;
+        pl.nwg2 = (int)(((long long)mtc * ctiles + U2 - 1) / U2);
+        a2.pos_period = split_class_period(U2, ctiles, pl.nwg2);
+        a2.nwg_virtual = pl.nwg2;
+        a2.part_scores = x->part2_s; a2.part_rows = x->part2_r; a2.bounds = x->part2_b;
+        a2.shared_thr = x->shared_thr + x->max_nq_pad;
+    }
+    return ICD_OK;
+}
+
+// the first coarse pass: which form of the flat kernel sweeps the fp16 image
+int auto_coarse(const SearchCtx &c, AutoPlan &pl) {
+    icd_index *x = c.x;
+    hipStream_t s = c.s;
+    CoarseFlatArgs &a = pl.a;
+    const int nwg = pl.nwg;
+    int rc;
+    // (dim 1024: the query fragments alone are 256 registers: no pinning, no deeper fragment prefetch and the 32x32x16
+    //  shape there; the quad select and the synchronised compaction apply)
+    if (launch_coarse_variant(x, c.ov, a, nwg, s, &rc)) return rc;   // (A/B builds only)
+    if (x->dim == 1024) return launch_coarse_flat<1024, (CF_PRODUCT_VAR & (3 | 16 | 2048))>(x, a, nwg, s);
+    if (pl.wide_lists) return launch_coarse_flat<768, CF_PRODUCT_VAR, CO_KP_WIDE>(x, a, nwg, s);
+    if ((size_t)x->n_pad * x->dim * 2 <= COARSE_CACHED_IMAGE_BYTES) return launch_coarse_flat<768, CF_CACHED_VAR>(x, a, nwg, s);   // (the image stays in the Infinity Cache)
+    // an image streamed from HBM (a row shard): the classes of work-groups that sweep the same tiles are paced so that a
+    // tile is fetched once per XCD instead of once per work-group (coarse_flat_kernel.hpp, VAR 67108864)
+    const int t0 = flat_class_period(pl.U, pl.ctiles);
+    const int members0 = t0 > 0 ? nwg / t0 : 0;
+    const int epochs = x->opt_pace_shift >= 0 ? (pl.U >> x->opt_pace_shift) + 1 : 0;
+    if (x->opt_pace_shift >= 0 && members0 >= 4 && (size_t)t0 * epochs <= PACE_WORDS) {
+        a.pace = x->pace; a.pace_period = t0; a.pace_epochs = epochs; a.pace_shift = x->opt_pace_shift; a.pace_lead = std::max(1, x->opt_pace_lead);
+        HIP_TRY(hipMemsetAsync(x->pace, 0, (size_t)t0 * epochs * sizeof(unsigned int), s));
+    }
+    return launch_coarse_flat<768, CF_PACED_VAR>(x, a, nwg, s);
+}
+
+// The first finalize: certifies and rescores every query from the first pass's lists; `g` is left as the base of the
+// launches behind it (all queries, in query order). *wide_fin: it ran with the widest window already.
+int auto_first_finalize(const SearchCtx &c, const AutoPlan &pl, FinArgs &g, bool *wide_fin) {
+    icd_index *x = c.x;
+    const int nq = c.nq, k = c.k;
+    hipStream_t s = c.s;
+    g = c.f;
+    g.part_scores = x->partc_s; g.part_rows = x->partc_r; g.bounds = x->partc_b; g.P = pl.pc; g.KP = pl.kp_c; g.nq = nq;
+    g.perm_mul = x->perm_mul; g.perm_mod = x->perm_mod;
+    g.perm_inv = (x->perm_mod > 0 && (double)x->perm_mod * (double)x->perm_mod < 9007199254740992.0) ? 1.0 / (double)x->perm_mod : 0.0;
+    // Wide mode (a corpus of tight families, decided from earlier counters): the window sized for k would certify
+    // next to nothing and its rescoring be thrown away (0.13 of 1.5 ms per 10 000 queries): the widest window takes
+    // every query at once, and the retry below has nothing to add.
+    *wide_fin = pl.wide_now && k <= 32 && pl.pc * g.KP >= 128;
+    if (*wide_fin) g.wide_window = 1;
+    if (c.ov.fin_skip_walk) g.skip_walk = 1;
+    if (*wide_fin && x->opt_family_order && nq >= 1024) {
+        // every query's window is its family (the corpus is in code order): visit the queries family by family, XCD by XCD
+        OrderArgs o{};
+        o.part_scores = g.part_scores; o.part_rows = g.part_rows; o.P = g.P; o.KP = g.KP; o.nq = nq;
+        o.perm_mul = g.perm_mul; o.perm_mod = g.perm_mod; o.perm_inv = g.perm_inv;
+        o.shift = 6;
+        while (((long long)x->n >> o.shift) >= ORDER_BUCKETS) ++o.shift;
+        o.key = x->order_key; o.hist = x->order_hist; o.order = x->order;
+        // (the scatter kernel leaves the histogram zero again; a search that failed between the two launches would not:
+        //  cleared here, 4 KB, so that a stale count can never push a position past the order buffer)
+        HIP_TRY(hipMemsetAsync(x->order_hist, 0, 2 * ORDER_BUCKETS * sizeof(unsigned int), s));
+        hipLaunchKernelGGL(order_keys_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, o);
+        hipLaunchKernelGGL(order_scatter_kernel, dim3((nq + 1023) / 1024), dim3(1024), 0, s, o);
+        HIP_TRY(hipGetLastError());
+        g.qlist = x->order; g.lists_by_query = 1; g.nq = 4 * ((nq + 3) / 4);
+    }
+    const int rc = *wide_fin ? launch_finalize_t<true, false, 4>(x, g, s) : launch_finalize<true>(x, g, s);
+    g.qlist = nullptr; g.lists_by_query = 0; g.nq = nq;
+    return rc;
+}
+
+// Second chance before the exact re-search. A query fails the first pass when more candidates lie within 2 eps of
+// its k-th best than the window sized for k holds (32 or 64 for k <= 32): a family of near-identical rows, the
+// shape ICD sibling codes have. Its lists may hold 128-512 candidates: the same kernel with the widest window
+// (256) certifies it from them in microseconds where the exact sweep costs 2.5-5 us per query
+// (profiles/r02_family_corpus_probe.log: 1 000 queries 2.7 / 5.2 ms -> see there). Only launched when the lists can
+// fill a wider window (mid-size batches; 10 000 queries have 5 lists of 16); gated on the flagged count on the device.
+int auto_wide_retry(const SearchCtx &c, const FinArgs &g) {
+    icd_index *x = c.x;
+    FinArgs g2 = g;
+    g2.qlist = x->flagged; g2.nq_ptr = x->nflag; g2.lists_by_query = 1; g2.wide_window = 1;
+    g2.nflag = x->nflag + 1; g2.flagged = x->flagged + x->max_nq_pad;
+    const int rc = launch_finalize_t<true, false, 4>(x, g2, c.s);
+    if (rc) return rc;
+    x->fallback_word = 1;
+    return ICD_OK;
+}
+
+// Second coarse pass, over the queries that are still flagged only. A large batch gives a query 5-8 lists of 16
+// candidates: a family of near-identical rows larger than that (ICD sibling codes repeat their ancestors' names:
+// 124-row families of mutual cosine 0.99 sit inside 2 eps of each other) cannot be certified from them, whatever
+// the window. The same kernel sweeps the corpus again for the flagged queries with about PASS2_CHUNKS lists each
+// (the partition sized on the device from the flagged count, one block per CU looping over the logical
+// work-groups), finalize certifies from those lists with the widest window, and only what still fails goes to the
+// exact re-search. A batch with nothing flagged pays two launches that read one counter and leave.
+int auto_second_pass(const SearchCtx &c, AutoPlan &pl, const FinArgs &g) {
+    icd_index *x = c.x;
+    hipStream_t s = c.s;
+    CoarseFlatArgs &a2 = pl.a2;
+    const int w_in = x->fallback_word;
+    a2.nq_ptr = x->nflag + w_in;
+    a2.qlist = x->flagged + (size_t)w_in * x->max_nq_pad;
+    a2.skip_below = PASS2_SKIP;
+    const int grid2 = std::max(8, std::min(pl.nwg2, x->num_cu) & ~7);
+    int rc;
+    if (x->dim == 1024) rc = launch_coarse_flat<1024, (CF_PRODUCT_VAR & (3 | 16 | 2048)), CO_KP, true>(x, a2, grid2, s);
+    else rc = launch_coarse_flat<768, CF_PRODUCT_VAR, CO_KP, true>(x, a2, grid2, s);
+    if (rc) return rc;
+    FinArgs g3 = g;
+    g3.part_scores = x->part2_s; g3.part_rows = x->part2_r; g3.bounds = x->part2_b; g3.P = pl.p2; g3.KP = CO_KP;
+    g3.qlist = a2.qlist; g3.nq_ptr = a2.nq_ptr; g3.lists_by_query = 0; g3.wide_window = 1; g3.skip_below = PASS2_SKIP;
+    g3.nflag = x->nflag + 2; g3.flagged = x->flagged + (size_t)2 * x->max_nq_pad;
+    rc = launch_finalize_t<true, false, 4>(x, g3, s);
+    if (rc) return rc;
+    x->fallback_word = 2;
+    x->last_p2 = pl.p2; x->last_p2_word = w_in;
+    return ICD_OK;
+}
+
+// fallback over the flagged list, both device-side gated on its length: the streaming kernel for
+// a sparse list (<= ST_MAX_ACTIVE queries), the fp32-MFMA kernel for a dense one. Both leave
+// [slot][p_sparse][KP] lists for the same finalize launch.
+int auto_fallback(const SearchCtx &c, bool sparse_off) {
+    icd_index *x = c.x;
+    const int *fl_list = x->flagged + (size_t)x->fallback_word * x->max_nq_pad;
+    const int *fl_count = x->nflag + x->fallback_word;
+    int px = std::min(c.p_sparse, c.row_tiles);
+    if (px < c.p_sparse) {   // tiny corpus: MFMA kernel only. EVERY query may be flagged (all-zero queries, duplicate rows):
+        // the list count is sized against the workspace like a full exact run
+        const int rc = fit_chunks(c, &px);
+        if (rc) return rc;
+        return run_exact(c, fl_list, fl_count, px, true, false, true, true, c.f.thr0);
+    }
+    return run_exact(c, fl_list, fl_count, c.p_sparse, true, c.stream_ok, !sparse_off, true, c.f.thr0);
+}
+
+int search_auto(const SearchCtx &c) {
+    icd_index *x = c.x;
+    const int nq_pad = ((c.nq + 127) / 128) * 128;
+    int rc = auto_prep(c, nq_pad);
+    if (rc) return rc;
+    AutoPlan pl;
+    rc = auto_plan(c, nq_pad, pl);
+    if (rc) return rc;
+    rc = auto_coarse(c, pl);
+    if (rc) return rc;
+    rec(x, 2, c.s);
+    FinArgs g;
+    bool wide_fin = false;
+    rc = auto_first_finalize(c, pl, g, &wide_fin);
+    if (rc) return rc;
+    x->fallback_word = 0;
+    if (!wide_fin && c.k <= 32 && pl.pc * g.KP >= 128) {
+        rc = auto_wide_retry(c, g);
+        if (rc) return rc;
+    }
+    if (pl.p2 > 0) {
+        rc = auto_second_pass(c, pl, g);
+        if (rc) return rc;
+    }
+    policy_note_search(x->pol, x->adapt_enabled, x->pass2_enabled, c.nq, pl.p2, pl.wide_now, x->chunks_override, pl.pc * pl.kp_c);
+    rec(x, 3, c.s);
+    return auto_fallback(c, pl.sparse_off);
+}
+
 // Enqueue a search whose queries and outputs are device pointers.
 int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s) {
-    const int row_tiles = (int)((x->n + 127) / 128);
     const bool use_fast = (mode == ICD_MODE_AUTO) && x->fast && k <= FAST_MAX_K && (x->dim == 768 || x->dim == 1024);
     x->prof_now = !x->capturing && x->profiling && (x->prof_tick++ % x->prof_every == 0);
     if (x->prof_now) {
@@ -610,524 +1079,16 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
     x->last_p2 = 0;
     x->last_mode = use_fast ? ICD_MODE_AUTO : ICD_MODE_EXACT;
     rec(x, 0, s);
-
-    FinArgs f{};
-    f.k = k; f.queries = dq; f.corpus = x->corpus; f.dim = x->dim; f.qnorm = x->qnorm; f.qbad = x->qbad;
-    f.qexp = x->qexp; f.rmax = x->rmax_scaled; f.cexp = x->cexp; f.eps_rel = EPS_REL; f.nflag = x->nflag; f.flagged = x->flagged;
-    if (use_fast) f.thr0 = x->thr0;
-    if (x->cmean) { f.rmax_unc = x->rmax_unc_scaled; f.eps_f32 = 2.0f * (float)x->dim * 5.9604645e-8f; }
-    f.levels = x->levels; f.id_base = x->id_base; f.row_map = x->row_map;
-    f.out_scores = o.scores; f.out_ids = o.ids; f.out_adj = o.adj; f.out_adj_raw = o.adj_raw;
-    f.out_adj_ids = o.adj_ids; f.out_adj_levels = o.adj_lv;
-
-    // exact-kernel configuration (full run, or fallback over the flagged list)
-    const int kpx = exact_kp_for(k);
-    const int nwx = kpx <= 64 ? 4 : 2;
-    int wg_per_cu_x = kpx <= 32 ? 2 : 1;   // work-groups of exact_topk a CU holds (its LDS)
-#ifdef ICD_ABLATE
-    if (kpx == 32 && getenv("ICD_EXACT_CFG") && atoi(getenv("ICD_EXACT_CFG")) == 3) wg_per_cu_x = 1;
-#endif
-    const int ex = kpx == 16 ? 1 : (kpx <= 64 ? 2 : 3);
-    const int bmq = nwx * 32;
-    const int mtx = (nq + bmq - 1) / bmq;
-    // lists per query finalize<false> merges: 2048 candidates at k <= 64 (its top-k prefilter keeps that cheap), 512 above
-    const int cand_x = kpx <= 64 ? FIN_MAX_CAND_X : FIN_MAX_CAND;
-    const int pmax_x = std::min(64, cand_x / kpx);
-    const int p_dense_max = cand_x / kpx;   // chunk limit of the device-sized partition of a flagged list
-    // sparse: streaming kernel (+ list reduction) instead of / next to the MFMA exact kernel
-    // queries per pass: host-known for direct calls (1, 2, 4 or 8), 8 for the device-gated fallback
-    const int p_sparse = FIN_MAX_CAND / kpx;   // lists per slot that finalize<false> merges (32 / 8 / 4)
-    // How many flagged queries still go to the streaming kernel: it re-reads the corpus once per 8 queries (~37 us at
-    // 37k rows); the fp32-MFMA kernel, its short list cut into up to 2048 / KP chunks, needs ~0.22 ms for any count up to a
-    // few hundred: they meet near 45 (ST_FALLBACK_MAX_ACTIVE, stream_kernel.hpp); the list workspace caps it by k.
-    // (the first reduction level leaves at most 512 lists per slot in the second workspace)
-    const int sparse_max = (int)std::min<size_t>(std::min<size_t>(ST_FALLBACK_MAX_ACTIVE, x->lists_cap / ((size_t)1024 * kpx)),
-                                                 kpx == 16 ? (size_t)ST_FALLBACK_MAX_ACTIVE : x->partx_cap / ((size_t)512 * kpx));
-    auto run_stream = [&](const int *qlist, const int *nq_ptr, int nqs, int p_out, int *p_used, const float *thr0 = nullptr) -> int {
-        int qb = nq_ptr ? 8 : (nqs <= 1 ? 1 : (nqs <= 2 ? 2 : (nqs <= 4 ? 4 : 8)));
-        const int max_act = nq_ptr ? sparse_max : std::max(sparse_max, nqs);   // (a direct call - up to ST_MAX_ACTIVE queries - is not gated)
-        while (qb > 1 && !stream_fits(kpx, qb, x->dim)) qb >>= 1;
-#define ICD_ST(KPV, EV) \
-        (qb == 1 ? launch_stream<KPV, EV, 1>(x, dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, s, thr0) : \
-         qb == 2 ? launch_stream<KPV, EV, 2>(x, dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, s, thr0) : \
-         qb == 4 ? launch_stream<KPV, EV, 4>(x, dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, s, thr0) : \
-                   launch_stream<KPV, EV, 8>(x, dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, s, thr0))
-        if (kpx == 16) return ICD_ST(16, 2);
-        if (kpx == 32) return ICD_ST(32, 2);
-        if (kpx == 64) return ICD_ST(64, 3);
-        return ICD_ST(128, 4);
-#undef ICD_ST
-    };
-    auto fit_p = [&](int p, size_t cap, int kp) {
-        while (p > 1 && (size_t)nq * p * kp > cap) --p;
-        return p;
-    };
-    auto run_exact = [&](const int *qlist, const int *nq_ptr, int px, bool mfma, bool stream, bool stream_launch = true, bool track_run = false, const float *thr0 = nullptr) -> int {
-        const int sparse_here = stream_launch ? sparse_max : 0;   // (streaming pair left out: the MFMA kernel takes every count >= 1)
-        if (!nq_ptr) x->last_chunks = px;   // (the fallback keeps the coarse pass's chunk count)
-        int rc = ICD_OK;
-        if (stream && stream_launch) {
-            int used = px;
-            rc = run_stream(qlist, nq_ptr, nq, mfma ? px : 0, &used, thr0);   // alone: fewest output lists
-            if (rc) return rc;
-            px = used;
-            if (!nq_ptr) x->last_chunks = px;
-        }
-        int px_dense = 0;
-        if (mfma) {
-            // The MFMA kernel may have to take EVERY query (all of them flagged): its list count is sized against
-            // the workspace like a full exact run; only the streaming kernel (<= ST_MAX_ACTIVE slots) uses px.
-            int pm = px;
-            if (stream) {
-                pm = pick_chunks(mtx, row_tiles, pmax_x, x->num_cu * wg_per_cu_x);
-                pm = fit_p(pm, x->partx_cap, kpx);
-                if ((size_t)nq * pm * kpx > x->partx_cap) return fail(ICD_ERR_INVALID, "workspace too small for nq=%d k=%d", nq, k);
-                const int tiles_per = (row_tiles + pm - 1) / pm;
-                pm = (row_tiles + tiles_per - 1) / tiles_per;
-                px_dense = pm;
-            }
-            ExactArgs a{};
-            a.corpus = x->corpus; a.queries = dq; a.qlist = qlist; a.nq_ptr = nq_ptr; a.nq = nq;
-            a.min_active = stream ? sparse_here : 0;
-            a.adaptive_one_per_cu = wg_per_cu_x > 1 ? x->num_cu : 0;
-            a.adaptive_max_p = stream ? p_dense_max : 0;   // fallback: the chunk count follows the actual flagged count
-            a.n = (int)x->n; a.dim = x->dim; a.P = pm;
-            a.rows_per_chunk = ((row_tiles + pm - 1) / pm) * 128;
-            a.part_scores = x->partx_s; a.part_rows = x->partx_r; a.thr0 = thr0;
-            // (LDS: k <= 16 two work-groups per CU - 17 KB of stage + 60-entry buffers; k <= 64 one of four waves - 34 KB +
-            //  112-entry buffers; larger k two waves. Eight waves on 64-entry buffers at k <= 32 - two per SIMD - were built and
-            //  are slower, 9.2 against 7.2 ms per 10 000 queries: a 64-entry buffer with 32 kept is compacted after every append)
-#ifdef ICD_ABLATE
-            if (kpx == 16 && getenv("ICD_EXACT_CFG") && atoi(getenv("ICD_EXACT_CFG")) == 1) rc = launch_exact<16, 1, 4>(x, a, mtx, s);
-            else if (kpx == 16 && getenv("ICD_EXACT_CFG") && atoi(getenv("ICD_EXACT_CFG")) == 2) rc = launch_exact<16, 1, 4, 64, 16, 1>(x, a, mtx, s);
-            else
-#endif
-            if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2>(x, a, mtx, s);
-#ifdef ICD_ABLATE
-            else if (kpx == 32 && getenv("ICD_EXACT_CFG") && atoi(getenv("ICD_EXACT_CFG")) == 3) rc = launch_exact<32, 2, 4, 112>(x, a, mtx, s);
-#endif
-            else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16>(x, a, mtx, s);
-            else if (kpx == 64) rc = launch_exact<64, 2, 4, 112>(x, a, mtx, s);
-            else rc = launch_exact<128, 3, 2>(x, a, mtx, s);
-            if (rc) return rc;
-        }
-        rec(x, 4, s);
-        FinArgs g = f;
-        g.part_scores = x->partx_s; g.part_rows = x->partx_r; g.P = px; g.KP = kpx;
-        g.P_dense = px_dense; g.sparse_max = sparse_here; g.track_run = track_run ? 1 : 0; g.lds_cand = std::max(px, (stream && mfma) ? p_dense_max : px_dense) * kpx;
-        g.dense_grid = mtx * std::max(1, px_dense); g.dense_bmq = bmq; g.dense_max_p = (stream && mfma) ? p_dense_max : 0; g.dense_one_per_cu = wg_per_cu_x > 1 ? x->num_cu : 0; g.n_rows = (int)x->n;
-        g.nq = nq; g.nq_ptr = nq_ptr; g.qlist = qlist;
-        g.counters = x->nflag; g.host_counters = x->h_nflag_dev;   // (the last launch of every search: no separate copy)
-        rc = launch_finalize<false>(x, g, s);
-        rec(x, 5, s);
-        (void)ex;
-        return rc;
-    };
-
-    // a host caller's ONE query whose copy search_common left out (host_q): every path but the single-launch kernel wants it
-    // in device memory after all - the copy it would have got, enqueued before anything that reads dq
-    auto stage_host_query = [&]() -> int {
-        if (!x->host_q) return ICD_OK;
-        const size_t qbytes = (size_t)x->dim * sizeof(float);
-        memcpy(x->h_pin, x->host_q, qbytes);
-        HIP_TRY(hipMemcpyAsync(x->qdev, x->h_pin, qbytes, hipMemcpyHostToDevice, s));
-        x->host_q = nullptr;
-        return ICD_OK;
-    };
-    // small batches (the reference's one-query-per-call shape): stream the corpus once, exact, no coarse pass
-    const bool stream_ok = x->dim % (32 * ST_PF) == 0 && stream_fits(kpx, 1, x->dim);
+    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s);
     // (k > 16 needs the 64-entry lists of the streaming kernel, ~0.9 ms per 16 queries: the coarse pass is faster there)
-    const bool tiny = stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE);
-    // (the fallback counter starts every search at zero: the exact-only paths clear it here, the fast path in its
-    //  query-prep launch - one launch less per step)
-    if (tiny) {
-        x->last_mode = ICD_MODE_EXACT;
-        x->last_chunks = p_sparse;
-        StreamOnePlan pl;
-        // (up to FOUR queries: at eight the sweep is bound by the lanes' fmaf chains, not by memory - 40 of a wave's 64 lanes hold
-        //  rows in this form - and the general path is 12 us faster: profiles/r05_single_query.log)
-        const int qb1 = nq <= 1 ? 1 : (nq <= 2 ? 2 : 4);
-        bool one = nq <= 4 && kpx == 16 && x->opt_stream_one && plan_stream_one((int)x->n, x->dim, x->num_cu, qb1, 64 * 2, &pl) &&
-                   (size_t)nq * pl.nwg * kpx * 2 <= x->lists_cap;
-        if (one) {   // up to four queries (the reference's call shape is ONE; a /query request batches its D diagnoses): ONE launch,
-                     // no memset, no reduction, no finalize
-            rec(x, 3, s);
-            const float *hq = qb1 == 1 ? x->host_q : nullptr;   // (a host caller's ONE query: search_common left the copy out)
-            if (!hq) { const int rcq = stage_host_query(); if (rcq) return rcq; }
-            const bool poll = x->host_one_call && (x->opt_host_one & 2) != 0;
-            const int rc1 = qb1 == 1 ? launch_stream_one<16, 2, 1>(x, dq, 1, f, s, hq, poll) : qb1 == 2 ? launch_stream_one<16, 2, 2>(x, dq, 2, f, s)
-                          : launch_stream_one<16, 2, 4>(x, dq, (int)nq, f, s);
-            rec(x, 4, s);
-            rec(x, 5, s);
-            return rc1;
-        }
-        { const int rcq = stage_host_query(); if (rcq) return rcq; }
-        HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), s));
-        rec(x, 3, s);
-        return run_exact(nullptr, nullptr, p_sparse, false, true);
+    if (c.stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE)) return search_tiny(c);
+    { const int rcq = stage_host_query(c); if (rcq) return rcq; }
+    if (!use_fast && c.kpx > 32 && x->opt_exact_narrow && nq > ST_MAX_ACTIVE && c.row_tiles >= 64) {
+        bool taken = false;
+        const int rc = search_exact_narrow(c, &taken);
+        if (rc || taken) return rc;
     }
-    { const int rcq = stage_host_query(); if (rcq) return rcq; }
-    if (!use_fast && kpx > 32 && x->opt_exact_narrow && nq > ST_MAX_ACTIVE && row_tiles >= 64) {
-        // ---- k > 32: NARROW certified lists -----------------------------------------------------------------------------------
-        // Lists of KP >= k need 64- or 128-entry candidate buffers: one work-group of four waves per CU at k <= 64, of two above
-        // (0.39 / 0.15 of the fp32 MFMA peak at k = 50 / 100, against 0.59 at k = 20). Instead: the k <= 32 configuration (lists
-        // of 32, two work-groups per CU) over ROW-STRIDED chunks - chunk c holds rows c, c + P, ... so that neighbouring rows
-        // (an ICD family in code order) spread evenly - with P large enough that a list holds ~k / P << 32 members of the top-k,
-        // and finalize CHECKS it: a full list whose worst kept key beats the k-th best of the merge may have dropped a member
-        // of the top-k; such a query is re-searched with KP >= k lists (the flagged-list machinery of the AUTO fallback).
-        // Results are the exact top-k either way.
-        HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), s));
-        const int slots = x->num_cu * 2;
-        const int mtx_n = (nq + 127) / 128;                   // query tiles of THIS configuration (four waves x 32 queries; `mtx` above counts the KP >= k configuration's tiles, 64 queries at k > 64: ADVICE r5)
-        const int p_need = std::max(2, (k + 7) / 8);          // ~8 members of the top-k per list when they spread evenly
-        int pn = p_need;
-        {   // the count at or above p_need whose last round of work-groups is fullest
-            double best = 0;
-            for (int c = p_need; c <= std::min(FIN_MAX_CAND_X / 32, std::max(p_need + 8, slots / std::max(1, mtx_n))); ++c) {   // (a short batch: enough chunks to fill the chip)
-                const long items = (long)mtx_n * c;
-                const double util = (double)items / (double)(((items + slots - 1) / slots) * slots);
-                if (util > best + 1e-9) { best = util; pn = c; }
-            }
-        }
-        if ((size_t)nq * pn * 32 <= x->partx_cap && pn * 32 <= FIN_MAX_CAND_X) {
-            x->last_chunks = pn;
-            x->fallback_word = 0;
-            rec(x, 3, s);
-            ExactArgs a{};
-            a.corpus = x->corpus; a.queries = dq; a.nq = nq; a.n = (int)x->n; a.dim = x->dim; a.P = pn; a.strided = 1;
-            a.rows_per_chunk = 128;   // (unused by the strided form)
-            a.part_scores = x->partx_s; a.part_rows = x->partx_r;
-            int rc = launch_exact<32, 1, 4, 62, 16, 2, 16>(x, a, mtx_n, s);
-            if (rc) return rc;
-            rec(x, 4, s);
-            FinArgs g = f;
-            g.part_scores = x->partx_s; g.part_rows = x->partx_r; g.P = pn; g.KP = 32; g.nq = nq; g.lds_cand = pn * 32;
-            g.narrow_check = 1; g.nflag = x->nflag; g.flagged = x->flagged;
-            rc = launch_finalize<false>(x, g, s);
-            if (rc) return rc;
-            rec(x, 5, s);
-            // the queries the check could not clear (none on data whose rows spread): KP >= k lists over the flagged list
-            int px = std::min(p_sparse, row_tiles);
-            return run_exact(x->flagged, x->nflag, px, true, stream_ok, true, false, nullptr);
-        }
-    }
-    if (!use_fast) {
-        HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), s));
-        int px = pick_chunks(mtx, row_tiles, pmax_x, x->num_cu * wg_per_cu_x);
-        px = fit_p(px, x->partx_cap, kpx);
-        if ((size_t)nq * px * kpx > x->partx_cap) return fail(ICD_ERR_INVALID, "workspace too small for nq=%d k=%d", nq, k);
-        {
-            const int tiles_per = (row_tiles + px - 1) / px;
-            px = (row_tiles + tiles_per - 1) / tiles_per;
-        }
-        x->last_chunks = px;
-        rec(x, 3, s);
-        return run_exact(nullptr, nullptr, px, true, false);
-    }
-
-    // ---- AUTO: prep -> coarse -> finalize(certify + rescore) -> exact fallback ------------------
-    const int nq_pad = ((nq + 127) / 128) * 128;
-    ConvertArgs cv{};
-    cv.src = dq; cv.dst = x->q16; cv.rows = nq; cv.rows_pad = nq_pad; cv.dim = x->dim; cv.mode = 0;
-    cv.norm = x->qnorm; cv.scale_exp = x->qexp; cv.bad = x->qbad; cv.zero_u32 = x->shared_thr; cv.zero_i32 = x->nflag;
-    cv.zero_u32b = x->shared_thr + x->max_nq_pad;
-    hipLaunchKernelGGL(convert_rows_kernel, dim3((nq_pad + 3) / 4), dim3(256), 0, s, cv);
-    HIP_TRY(hipGetLastError());
-    rec(x, 1, s);
-
-    const int mtc = nq_pad / 128;
-    // corpus tiles to sweep and tiles per work-group (flat_partition.hpp: a few zero tiles behind the corpus buy a tile
-    // count that shares a factor with U, i.e. work-groups that stream the same tiles together)
-    const int ctiles_min = (int)((x->n + 127) / 128);
-    const FlatPlan plan = plan_flat_tiles(mtc, ctiles_min, x->n_pad / 128 - ctiles_min, x->num_cu);
-    const int ctiles = plan.ctiles;
-    int pc = 0;
-    const bool wide_lists = k > x->opt_wide_from && x->dim == 768;
-    // ---- adaptive list count of large batches -------------------------------------------------------------------------
-    // The counters of the previous search sit in pinned host memory once its copy event has completed (hipEventQuery: no
-    // wait). If that search was a large batch on the narrow plan and its second coarse pass had to take in a quarter of
-    // the queries and certified most of them, the corpus is one of tight families (ICD sibling codes): large batches then
-    // start with the second pass's list count (1.5 instead of 2.2 ms per 10 000 queries there; 7 % slower on Gaussian data,
-    // which is why it is not the default). Every WIDE_REPROBE-th large search runs narrow again and decides anew.
-    const bool large = nq >= WIDE_MIN_NQ;
-    // (while the stream is being captured into a HIP graph nothing may be queried: the plan is the one the host state gives now,
-    //  and it is frozen into the graph - a performance decision only, the replayed search returns the exact top-k either way)
-    const bool counters_in = !x->capturing && hipEventQuery(x->ev_nflag) == hipSuccess;   // (every search enqueued so far has completed)
-    if (counters_in) {
-        const int run = x->h_nflag[4];
-        if (x->sparse_disarmed && run < x->sparse_need) x->sparse_need = std::min(x->sparse_need * 2, 1 << 16);   // an incident
-        x->sparse_run_seen = run;
-    }
-    const bool sparse_off = x->adapt_enabled && x->sparse_run_seen >= x->sparse_need;
-    x->sparse_disarmed = sparse_off;
-    if (x->p2_eval_pending && counters_in) {
-        x->p2_clean = x->h_nflag[0] > PASS2_SKIP ? 0 : std::min(x->p2_clean + 1, 1 << 20);
-        x->p2_eval_pending = false;
-    }
-    if (x->last_narrow_large && counters_in) {
-        const int f0 = x->h_nflag[0], f2 = x->h_nflag[2];
-        const long long n_prev = x->last_narrow_nq;   // (x->last_nq already holds the CURRENT batch's size: ADVICE r3)
-        if (n_prev > 0) {
-            if (!x->wide_mode && (long long)f0 * 4 > n_prev && (long long)f2 * 2 < f0) { x->wide_mode = true; x->wide_runs = 0; }
-            else if (x->wide_mode && (long long)f0 * 20 <= n_prev) x->wide_mode = false;   // (a narrow re-probe that certified 95 %)
-        }
-        x->last_narrow_large = false;
-    }
-    bool wide_now = false;
-    if (large && x->wide_mode && x->chunks_override == 0 && k <= 32) wide_now = (++x->wide_runs % WIDE_REPROBE) != 0;
-    const int kp_c = wide_lists ? CO_KP_WIDE : CO_KP;
-    CoarseFlatArgs a2{};      // the second pass's arguments (filled next to the first pass's)
-    int nwg2 = 0, p2 = 0;
-    {
-        // ---- product: flat partition of the (query tile x corpus tile) grid over the CUs (coarse_flat_kernel.hpp) ----
-        CoarseFlatArgs a{};
-        a.q16 = x->q16; a.c16 = x->c16; a.nq = nq; a.n = (int)x->n; a.n_pad = ctiles * 128; a.ctiles = ctiles;
-        a.total_units = mtc * ctiles;
-        // The bootstrap level (6th best of the first boot_tiles * 128 rows of a list) must stay far below the k-th best
-        // of the whole corpus or the list's bound lands inside the window: fewer tiles for larger k (measured at
-        // k = 48 with 8 tiles: 1.6 % of the queries uncertified).
-        a.boot_tiles = std::max(1, std::min(CO_BOOT_TILES, 96 / std::max(1, k)));
-        a.sparse_from = CO_SPARSE_FROM;
-        // ---- the list plan of both passes (flat_partition.hpp plan_coarse_lists): lists per query, tiles per list and
-        // per work-group. No list is longer than the kernel's per-list buffer descriptor reaches (flat_max_list_tiles).
-        CoarsePlanIn pin{};
-        pin.mtc = mtc; pin.ctiles = ctiles; pin.U = plan.U; pin.nq = nq; pin.k = k;
-        pin.kp = kp_c; pin.kp2 = CO_KP; pin.max_cand = FIN_MAX_CAND;
-        pin.wide_lists = wide_lists; pin.wide_now = wide_now; pin.chunks_override = x->chunks_override;
-        pin.pass2 = x->pass2_enabled && x->p2_clean < PASS2_DISARM_AFTER && x->part2_s;
-        pin.partc_cap = (long long)x->partc_cap; pin.part2_cap = (long long)x->part2_cap;
-        pin.max_list_tiles = flat_max_list_tiles(x->dim);
-#ifdef ICD_ABLATE
-        if (const char *e = getenv("ICD_FLAT_U")) pin.U = std::max(pin.U, atoi(e));   // A/B: tiles per work-group
-        if (const char *e = getenv("ICD_FLAT_LIST")) pin.list_override = std::max(1, atoi(e));   // A/B: tiles per list
-        if (const char *e = getenv("ICD_FLAT_BOOT")) a.boot_tiles = std::max(0, atoi(e));   // A/B: bootstrap tiles
-        if (const char *e = getenv("ICD_FLAT_SPARSE")) a.sparse_from = std::max(0, atoi(e));   // A/B: first tile of a list with the group pre-filter
-#endif
-        const CoarsePlan cp = plan_coarse_lists(pin);
-        if (!cp.ok)
-            return fail(ICD_ERR_UNSUPPORTED, "coarse pass: no list plan for n=%lld dim=%d nq=%d k=%d (lists per query %d, at most %d tiles per list)",
-                        (long long)x->n, x->dim, nq, k, cp.P, pin.max_list_tiles);
-        const int U = cp.U, P = cp.P;
-        a.list_tiles = cp.list_tiles;
-        a.units_per_wg = U; a.P = P;
-        {
-            a.pos_period = flat_class_period(U, ctiles);
-            // A class of work-groups that stream the same tiles should have about a dozen members per XCD-local
-            // group: many more and they all hit the same L2 channel at the same time (measured slower), so large
-            // classes are split into sub-classes (l mod T s also start on the same tile).
-            const int nwg_ = (a.total_units + U - 1) / U;
-            const int members = nwg_ / std::max(1, a.pos_period);
-            int split = (members + 11) / 12;
-#ifdef ICD_ABLATE
-            if (const char *e = getenv("ICD_XCD_MODE")) {   // A/B switch: 0 identity, 1 XCD swizzle only, 2 classes unsplit
-                const int m = atoi(e);
-                if (m == 0) a.pos_period = 0;
-                else if (m == 1) a.pos_period = 1 << 30;
-                else if (m == 2) split = 1;
-            }
-#endif
-            if (a.pos_period > 0 && a.pos_period < (1 << 20)) a.pos_period *= std::max(1, split);
-        }
-        a.part_scores = x->partc_s; a.part_rows = x->partc_r; a.bounds = x->partc_b; a.shared_thr = x->shared_thr;
-        a.dbg = x->dbg;
-        pc = P;
-        x->last_chunks = P;
-        const int nwg = (a.total_units + U - 1) / U;
-        a.nwg_virtual = nwg;
-        // ---- the second pass's plan: the same sweep cut into about PASS2_CHUNKS lists per query, every work-group's run
-        // one list (the shape icd_index_set_chunks asks for). Everything the host must know is independent of how many
-        // queries will be flagged: U2, the list slots per query (worst case over all query tiles of the full batch), the
-        // logical work-group count of a full batch. The kernel sizes the sweep from the flagged count on the device.
-        if (cp.P2 > 0) {
-            const int U2 = cp.U2;
-            p2 = cp.P2;
-            a2 = a;
-            a2.nq_ptr = nullptr; a2.qlist = nullptr;   // (set at the launch: which flag word / list feeds it)
-            a2.units_per_wg = U2; a2.list_tiles = cp.list_tiles2; a2.P = p2;
-            a2.boot_tiles = a.boot_tiles;
-            a2.pos_period = flat_class_period(U2, ctiles);
-            nwg2 = (int)(((long long)mtc * ctiles + U2 - 1) / U2);
-            {
-                const int members = nwg2 / std::max(1, a2.pos_period);
-                const int split = (members + 11) / 12;
-                if (a2.pos_period > 0 && a2.pos_period < (1 << 20)) a2.pos_period *= std::max(1, split);
-            }
-            a2.nwg_virtual = nwg2;
-            a2.part_scores = x->part2_s; a2.part_rows = x->part2_r; a2.bounds = x->part2_b;
-            a2.shared_thr = x->shared_thr + x->max_nq_pad;
-        }
-        int rc;
-        // (dim 1024: the query fragments alone are 256 registers: no pinning, no deeper fragment prefetch and the 32x32x16
-        //  shape there; the quad select and the synchronised compaction apply)
-#ifdef ICD_ABLATE
-        if (x->dim == 1024 && getenv("ICD_1024_FULL")) rc = launch_coarse_flat<1024, CF_PRODUCT_VAR>(x, a, nwg, s);   // A/B: the 768 form
-        else
-#endif
-        if (x->dim == 1024) rc = launch_coarse_flat<1024, (CF_PRODUCT_VAR & (3 | 16 | 2048))>(x, a, nwg, s);
-#ifdef ICD_ABLATE_EXPERIMENTS
-        else if (const char *wv = getenv("ICD_W8_VAR")) {   // A/B builds: the eight-wave kernel
-            const int v = atoi(wv);
-            if (v == 0 && !wide_lists) rc = launch_coarse_w8<768>(x, a, nwg, s);
-            else if (v == 1) rc = launch_coarse_w8<768, CO_KP, 1>(x, a, nwg, s);
-            else if (v == 20 && !wide_lists) rc = launch_coarse_g16<768>(x, a, nwg, s);
-            else if (v == 21) rc = launch_coarse_g16<768, CO_KP, 1>(x, a, nwg, s);
-            else if (v == 30 && !wide_lists) rc = launch_coarse_g16r<768>(x, a, nwg, s);
-            else if (v == 10 && !wide_lists) rc = launch_coarse_w8rg<768>(x, a, nwg, s);
-            else if (v == 11) rc = launch_coarse_w8rg<768, CO_KP, 1>(x, a, nwg, s);
-            else if (v == 12) rc = launch_coarse_w8rg<768, CO_KP, 2>(x, a, nwg, s);
-            else if (v == 14) rc = launch_coarse_w8rg<768, CO_KP, 4>(x, a, nwg, s);
-            else return fail(ICD_ERR_INVALID, "ICD_W8_VAR=%d is not built", v);
-        }
-        else if (const char *rv = getenv("ICD_RG_VAR")) {   // A/B builds: the row-group kernel and its timing variants
-            const int v = atoi(rv);
-            if (wide_lists) rc = launch_coarse_rg<768, CO_KP_WIDE>(x, a, nwg, s);
-            else if (v == 0) rc = launch_coarse_rg<768>(x, a, nwg, s);
-            else if (v == 1) rc = launch_coarse_rg<768, CO_KP, 1>(x, a, nwg, s);
-            else if (v == 4) rc = launch_coarse_rg<768, CO_KP, 4>(x, a, nwg, s);
-            else if (v == 8) rc = launch_coarse_rg<768, CO_KP, 8>(x, a, nwg, s);
-            else if (v == 16) rc = launch_coarse_rg<768, CO_KP, 16>(x, a, nwg, s);
-            else if (v == 36) rc = launch_coarse_rg<768, CO_KP, 36>(x, a, nwg, s);
-            else if (v == 64) rc = launch_coarse_rg<768, CO_KP, 64>(x, a, nwg, s);
-            else if (v == 68) rc = launch_coarse_rg<768, CO_KP, 68>(x, a, nwg, s);
-            else if (v == 100) rc = launch_coarse_rg<768, CO_KP, 100>(x, a, nwg, s);
-            else return fail(ICD_ERR_INVALID, "ICD_RG_VAR=%d is not built", v);
-        }
-#endif
-#ifdef ICD_ABLATE_KSPLIT
-        else if (getenv("ICD_KS_VAR") && !wide_lists) {   // A/B builds: the K-split pair kernel (experiments/r04_ksplit_kernel)
-            const int v = atoi(getenv("ICD_KS_VAR"));
-            if (v == 0) rc = launch_coarse_ksplit<768, CO_KP, 0>(x, a, nwg, s);
-            else if (v == 1) rc = launch_coarse_ksplit<768, CO_KP, 1>(x, a, nwg, s);
-            else if (v == 2) rc = launch_coarse_ksplit<768, CO_KP, 2>(x, a, nwg, s);
-            else if (v == 5) rc = launch_coarse_ksplit<768, CO_KP, 5>(x, a, nwg, s);
-            else return fail(ICD_ERR_INVALID, "ICD_KS_VAR=%d is not built", v);
-        }
-#endif
-#ifdef ICD_ABLATE
-        else if (const char *fv = getenv("ICD_FLAT_VAR")) {   // A/B builds: stage / select variants of the flat kernel
-            const int v = atoi(fv);
-            if (false) {}
-#define ICD_FV_CASE(V) else if (v == V) rc = launch_coarse_flat<768, V>(x, a, nwg, s);
-#ifdef ICD_FV_LIST
-            ICD_FV_LIST
-#else
-            ICD_FV_CASE(0) ICD_FV_CASE(139) ICD_FV_CASE(143) ICD_FV_CASE(155) ICD_FV_CASE(171) ICD_FV_CASE(187) ICD_FV_CASE(2187) ICD_FV_CASE(2203)
-            ICD_FV_CASE(2235) ICD_FV_CASE(1163) ICD_FV_CASE(4235) ICD_FV_CASE(4251)
-            ICD_FV_CASE(34971) ICD_FV_CASE(35995) ICD_FV_CASE(39067) ICD_FV_CASE(100507) ICD_FV_CASE(104603) ICD_FV_CASE(32923) ICD_FV_CASE(32955) ICD_FV_CASE(34843) ICD_FV_CASE(166043) ICD_FV_CASE(297115) ICD_FV_CASE(559259) ICD_FV_CASE(1083547)
-#endif
-#undef ICD_FV_CASE
-            else return fail(ICD_ERR_INVALID, "ICD_FLAT_VAR=%d is not built", v);
-        }
-#endif
-        else if (wide_lists) rc = launch_coarse_flat<768, CF_PRODUCT_VAR, CO_KP_WIDE>(x, a, nwg, s);
-        else if ((size_t)x->n_pad * x->dim * 2 <= COARSE_CACHED_IMAGE_BYTES) rc = launch_coarse_flat<768, CF_CACHED_VAR>(x, a, nwg, s);   // (the image stays in the Infinity Cache)
-        else {
-            // an image streamed from HBM (a row shard): the classes of work-groups that sweep the same tiles are paced so that a
-            // tile is fetched once per XCD instead of once per work-group (coarse_flat_kernel.hpp, VAR 67108864)
-            const int t0 = flat_class_period(U, ctiles);
-            const int members0 = t0 > 0 ? nwg / t0 : 0;
-            const int epochs = x->opt_pace_shift >= 0 ? (U >> x->opt_pace_shift) + 1 : 0;
-            if (x->opt_pace_shift >= 0 && members0 >= 4 && (size_t)t0 * epochs <= PACE_WORDS) {
-                a.pace = x->pace; a.pace_period = t0; a.pace_epochs = epochs; a.pace_shift = x->opt_pace_shift; a.pace_lead = std::max(1, x->opt_pace_lead);
-                HIP_TRY(hipMemsetAsync(x->pace, 0, (size_t)t0 * epochs * sizeof(unsigned int), s));
-            }
-            rc = launch_coarse_flat<768, CF_PACED_VAR>(x, a, nwg, s);
-        }
-        if (rc) return rc;
-    }
-    rec(x, 2, s);
-    {
-        FinArgs g = f;
-        g.part_scores = x->partc_s; g.part_rows = x->partc_r; g.bounds = x->partc_b; g.P = pc; g.KP = wide_lists ? CO_KP_WIDE : CO_KP; g.nq = nq;
-        g.perm_mul = x->perm_mul; g.perm_mod = x->perm_mod;
-        g.perm_inv = (x->perm_mod > 0 && (double)x->perm_mod * (double)x->perm_mod < 9007199254740992.0) ? 1.0 / (double)x->perm_mod : 0.0;
-        // Wide mode (a corpus of tight families, decided from earlier counters): the window sized for k would certify
-        // next to nothing and its rescoring be thrown away (0.13 of 1.5 ms per 10 000 queries): the widest window takes
-        // every query at once, and the retry below has nothing to add.
-        const bool wide_fin = wide_now && k <= 32 && pc * g.KP >= 128;
-        if (wide_fin) g.wide_window = 1;
-#ifdef ICD_ABLATE
-        if (getenv("ICD_FIN_SKIP_WALK")) g.skip_walk = 1;
-#endif
-        if (wide_fin && x->opt_family_order && nq >= 1024) {
-            // every query's window is its family (the corpus is in code order): visit the queries family by family, XCD by XCD
-            OrderArgs o{};
-            o.part_scores = g.part_scores; o.part_rows = g.part_rows; o.P = g.P; o.KP = g.KP; o.nq = nq;
-            o.perm_mul = g.perm_mul; o.perm_mod = g.perm_mod; o.perm_inv = g.perm_inv;
-            o.shift = 6;
-            while (((long long)x->n >> o.shift) >= ORDER_BUCKETS) ++o.shift;
-            o.key = x->order_key; o.hist = x->order_hist; o.order = x->order;
-            // (the scatter kernel leaves the histogram zero again; a search that failed between the two launches would not:
-            //  cleared here, 4 KB, so that a stale count can never push a position past the order buffer)
-            HIP_TRY(hipMemsetAsync(x->order_hist, 0, 2 * ORDER_BUCKETS * sizeof(unsigned int), s));
-            hipLaunchKernelGGL(order_keys_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, o);
-            hipLaunchKernelGGL(order_scatter_kernel, dim3((nq + 1023) / 1024), dim3(1024), 0, s, o);
-            HIP_TRY(hipGetLastError());
-            g.qlist = x->order; g.lists_by_query = 1; g.nq = 4 * ((nq + 3) / 4);
-        }
-        int rc = wide_fin ? launch_finalize_t<true, false, 4>(x, g, s) : launch_finalize<true>(x, g, s);
-        if (rc) return rc;
-        g.qlist = nullptr; g.lists_by_query = 0; g.nq = nq;
-        // Second chance before the exact re-search. A query fails the first pass when more candidates lie within 2 eps of
-        // its k-th best than the window sized for k holds (32 or 64 for k <= 32): a family of near-identical rows, the
-        // shape ICD sibling codes have. Its lists may hold 128-512 candidates: the same kernel with the widest window
-        // (256) certifies it from them in microseconds where the exact sweep costs 2.5-5 us per query
-        // (profiles/r02_family_corpus_probe.log: 1 000 queries 2.7 / 5.2 ms -> see there). Only launched when the lists can
-        // fill a wider window (mid-size batches; 10 000 queries have 5 lists of 16); gated on the flagged count on the device.
-        x->fallback_word = 0;
-        if (!wide_fin && k <= 32 && pc * g.KP >= 128) {
-            FinArgs g2 = g;
-            g2.qlist = x->flagged; g2.nq_ptr = x->nflag; g2.lists_by_query = 1; g2.wide_window = 1;
-            g2.nflag = x->nflag + 1; g2.flagged = x->flagged + x->max_nq_pad;
-            rc = launch_finalize_t<true, false, 4>(x, g2, s);
-            if (rc) return rc;
-            x->fallback_word = 1;
-        }
-        // Second coarse pass, over the queries that are still flagged only. A large batch gives a query 5-8 lists of 16
-        // candidates: a family of near-identical rows larger than that (ICD sibling codes repeat their ancestors' names:
-        // 124-row families of mutual cosine 0.99 sit inside 2 eps of each other) cannot be certified from them, whatever
-        // the window. The same kernel sweeps the corpus again for the flagged queries with about PASS2_CHUNKS lists each
-        // (the partition sized on the device from the flagged count, one block per CU looping over the logical
-        // work-groups), finalize certifies from those lists with the widest window, and only what still fails goes to the
-        // exact re-search. A batch with nothing flagged pays two launches that read one counter and leave.
-        if (p2 > 0) {
-            const int w_in = x->fallback_word;
-            a2.nq_ptr = x->nflag + w_in;
-            a2.qlist = x->flagged + (size_t)w_in * x->max_nq_pad;
-            a2.skip_below = PASS2_SKIP;
-            const int grid2 = std::max(8, std::min(nwg2, x->num_cu) & ~7);
-            if (x->dim == 1024) rc = launch_coarse_flat<1024, (CF_PRODUCT_VAR & (3 | 16 | 2048)), CO_KP, true>(x, a2, grid2, s);
-            else rc = launch_coarse_flat<768, CF_PRODUCT_VAR, CO_KP, true>(x, a2, grid2, s);
-            if (rc) return rc;
-            FinArgs g3 = g;
-            g3.part_scores = x->part2_s; g3.part_rows = x->part2_r; g3.bounds = x->part2_b; g3.P = p2; g3.KP = CO_KP;
-            g3.qlist = a2.qlist; g3.nq_ptr = a2.nq_ptr; g3.lists_by_query = 0; g3.wide_window = 1; g3.skip_below = PASS2_SKIP;
-            g3.nflag = x->nflag + 2; g3.flagged = x->flagged + (size_t)2 * x->max_nq_pad;
-            rc = launch_finalize_t<true, false, 4>(x, g3, s);
-            if (rc) return rc;
-            x->fallback_word = 2;
-            x->last_p2 = p2; x->last_p2_word = w_in;
-        }
-        x->last_narrow_large = x->adapt_enabled && large && p2 > 0 && !wide_now && x->chunks_override == 0;
-        if (x->last_narrow_large) x->last_narrow_nq = nq;
-        x->p2_eval_pending = x->pass2_enabled && pc * kp_c < PASS2_BELOW;   // (a search the second pass applies to, armed or not)
-    }
-    rec(x, 3, s);
-    const int *fl_list = x->flagged + (size_t)x->fallback_word * x->max_nq_pad;
-    const int *fl_count = x->nflag + x->fallback_word;
-    // fallback over the flagged list, both device-side gated on its length: the streaming kernel for
-    // a sparse list (<= ST_MAX_ACTIVE queries), the fp32-MFMA kernel for a dense one. Both leave
-    // [slot][p_sparse][KP] lists for the same finalize launch.
-    int px = std::min(p_sparse, row_tiles);
-    if (px < p_sparse) {   // tiny corpus: MFMA kernel only. EVERY query may be flagged (all-zero queries, duplicate rows):
-        // the list count is sized against the workspace like a full exact run
-        px = fit_p(px, x->partx_cap, kpx);
-        if ((size_t)nq * px * kpx > x->partx_cap) return fail(ICD_ERR_INVALID, "workspace too small for nq=%d k=%d", nq, k);
-        const int tiles_per = (row_tiles + px - 1) / px;
-        px = (row_tiles + tiles_per - 1) / tiles_per;
-        return run_exact(fl_list, fl_count, px, true, false, true, true, f.thr0);
-    }
-    return run_exact(fl_list, fl_count, p_sparse, true, stream_ok, !sparse_off, true, f.thr0);
+    return use_fast ? search_auto(c) : search_exact(c);
 }
 
 }  // namespace
@@ -1341,11 +1302,9 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
         const int prc = search_device(x, x->qdev, pq, pk, ICD_MODE_AUTO, o, 0);
         if (prc) { free_all(x); return prc; }
         CR_TRY(hipDeviceSynchronize());
-        const int f0 = x->h_nflag[0], f2 = x->h_nflag[2];
-        x->probe_flagged = f0; x->probe_left = f2;
-        x->wide_mode = x->last_narrow_large && (long long)f0 * 4 > pq && (long long)f2 * 2 < f0;
-        x->wide_runs = 0; x->last_narrow_large = false; x->p2_clean = 0; x->p2_eval_pending = false;
-        x->sparse_run_seen = 0; x->sparse_disarmed = false;
+        x->probe_flagged = x->h_nflag[0]; x->probe_left = x->h_nflag[2];
+        policy_take_counters(x->pol, search_counters(x->h_nflag));   // (the rule of every later search decides)
+        x->pol.reset();
         x->last_nq = 0; x->last_p2 = 0; x->fallback_word = 0; x->last_chunks = 0; x->last_mode = ICD_MODE_AUTO;
         CR_TRY(hipMemset(x->nflag, 0, 8 * sizeof(int)));
         memset(x->h_nflag, 0, 8 * sizeof(int));
@@ -1538,10 +1497,7 @@ int icd_merge_topk(int32_t device, const float *scores, const int64_t *ids, cons
     a.G = G; a.nq = (int)nq; a.k = k;
     a.out_adj = out_adj; a.out_raw = out_raw; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels;
     const size_t lds = 4 * (1024 * 16 + 128 * 24);
-    static int configured[MAX_DEVICES] = {};   // (guarded by the caller's one-stream-per-handle contract; worst case a repeated call)
-    HIP_TRY(ensure_dynamic_lds(merge_topk_kernel, device, (size_t)((int)lds), configured));
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(((int)nq + 3) / 4), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lds<merge_topk_kernel>(device, lds, dim3(((int)nq + 3) / 4), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a));
     return ICD_OK;
 }
 
@@ -1728,9 +1684,9 @@ int icd_index_stats(icd_index *idx, icd_stats *out) {
     out->last_fallback = nf;
     out->last_second_pass = (idx->last_p2 > 0 && idx->h_nflag && idx->last_nq > 0) ? idx->h_nflag[idx->last_p2_word] : 0;
     out->last_second_pass_lists = idx->last_p2;
-    out->wide_mode = idx->wide_mode ? 1 : 0;
-    out->second_pass_armed = (idx->pass2_enabled && idx->p2_clean < PASS2_DISARM_AFTER) ? 1 : 0;
-    out->sparse_fallback_armed = idx->sparse_disarmed ? 0 : 1;
+    out->wide_mode = idx->pol.wide_mode ? 1 : 0;
+    out->second_pass_armed = (idx->pass2_enabled && idx->pol.pass2_armed()) ? 1 : 0;
+    out->sparse_fallback_armed = idx->pol.sparse_disarmed ? 0 : 1;
     out->centered = idx->cmean ? 1 : 0; out->mean_share = idx->mean_share;
     out->last_chunks = idx->last_chunks; out->last_mode = idx->last_mode;
     return ICD_OK;
@@ -1771,9 +1727,7 @@ int icd_index_set_second_pass(icd_index *idx, int32_t enabled) {
     std::lock_guard<std::mutex> guard(idx->mu);
     idx->pass2_enabled = enabled != 0;
     idx->adapt_enabled = enabled == 1;
-    if (!idx->pass2_enabled || !idx->adapt_enabled) { idx->wide_mode = false; idx->last_narrow_large = false; }
-    idx->p2_clean = 0; idx->p2_eval_pending = false;   // (re-armed)
-    idx->sparse_need = SPARSE_DISARM_AFTER; idx->sparse_run_seen = 0; idx->sparse_disarmed = false;
+    idx->pol.rearm(idx->pass2_enabled && idx->adapt_enabled);
     if (idx->nflag) { HIP_TRY(hipSetDevice(idx->device)); HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipMemset(idx->nflag + 4, 0, sizeof(int))); idx->h_nflag[4] = 0; }
     return ICD_OK;
 }
