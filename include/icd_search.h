@@ -212,6 +212,33 @@ int icd_index_search_reweighted(icd_index *idx, const float *queries, int64_t nq
                                 int32_t out_on_device, void *stream);
 
 /*
+ * Range search, offset and iterator pages (Milvus's search_params {"radius", "range_filter"}, `offset`, search_iterator; the
+ * reference passes none of them, services/milvus_service.py:280-285): for every query the min(k, rows in the band) best rows
+ * STRICTLY INSIDE A BAND of the (score desc, id asc) ranking, exact, best first. A row is in the band iff
+ *     radius[q] < score                      (radius NULL: no floor)
+ *     score <= range_filter[q]               (range_filter NULL: no ceiling; Milvus's rule for IP: radius < distance <= range_filter)
+ *     (score, id) ranks strictly behind the cursor (after_scores[q], after_ids[q]): score < after score, or equal score bits and
+ *     id > after id (both NULL: no cursor). The cursor is a hit an earlier search of this index returned - its RAW score and its id
+ *     (global, as searches return them; on a view the parent's, and an id outside the view still cuts the view's ranking in place).
+ * Plain float comparisons on the canonical score; rows whose score is NaN are never hits. Bounds are per query, [nq] each, host
+ * pointers or (bounds_on_device = 1) device pointers. k in 1 .. ICD_MAX_K and within the index's max_k.
+ *   reweighted = 0  out_raw, out_ids, out_levels in raw order; out_adj is not written.
+ *   reweighted = 1  that list through icd_index_search_reweighted's step (adj = (double)raw * w[level], one stable descending
+ *                   re-sort of the query's hits): out_adj, out_raw, out_ids, out_levels. The band is on the RAW score.
+ * Slots behind the band's last row: score -inf, id -1, level 0. out_levels may be NULL. With no bound at all the outputs equal
+ * icd_index_search / icd_index_search_reweighted in ICD_MODE_EXACT bit for bit.
+ * ICD_ERR_INVALID before any device call: k out of range, exactly one of after_scores / after_ids, host bounds holding NaN or
+ * radius >= range_filter. Device-resident bounds are not validated (that would synchronise): an empty band yields padding.
+ * Queries and outputs as in icd_index_search; with device queries, outputs AND bounds the call only enqueues on `stream`
+ * (graph-capturable: the bounds' staging is the index's own, allocated at create); host bounds synchronise like host buffers.
+ * Up to four queries at k <= 16 are ONE launch (an iterator's page), up to 64 the streaming kernel, more the fp32-MFMA kernel.
+ */
+int icd_index_search_range(icd_index *idx, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
+                           const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
+                           int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                           int32_t *out_levels, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "icd_group_unique_id", "icd_group_create", "icd_group_prepare", "icd_group_connect", "icd_group_search", "icd_group_destroy",
     "icd_unpack_query_slices", "icd_split_bf16x3", "icd_encoder_create", "icd_encoder_encode", "icd_encoder_encode_many", "icd_encoder_destroy", "icd_pack_winners",
     "icd_grouping_create", "icd_grouping_destroy", "icd_grouping_stats", "icd_index_search_grouped",
+    "icd_index_search_range",
 )
 MAX_K = 128   # include/icd_search.h ICD_MAX_K: the slots of one query's hit list (a grouped search: k * group_size)
 # include/icd_search.h: icd_index_create flags and icd_index_set_option ids (A/B and test options of ONE index)
@@ -111,6 +112,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_grouping_destroy.argtypes = [vp]
     lib.icd_grouping_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_grouped.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_index_search_range.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -419,6 +421,74 @@ class IcdIndex:
             return outs[0]
         if on_dev:
             import torch
+            return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
+        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+
+    # -- range search, offset, iterator pages (Milvus radius / range_filter, offset, search_iterator) ----
+    def search_range(self, queries, k: int = 10, *, radius=None, range_filter=None, after=None, reweighted: bool = True):
+        """The min(k, rows in the band) best rows strictly inside a band of every query's ranking, exact (icd_index_search_range):
+        radius < score <= range_filter, and - after=(scores, ids), a hit an earlier search returned: its raw score and its id -
+        ranked strictly behind that hit. Bounds are scalars (broadcast) or one value per query (arrays / CUDA tensors); the band
+        is on the raw inner product. reweighted=True: (adj f64, raw f32, ids i64, levels i32) in search_reweighted's order;
+        False: (raw, ids, levels) in raw order. Padding behind the band's last row: -inf, id -1, level 0. Device tensors in ->
+        device tensors out on torch's current stream (the bounds are moved to the device if they are not there)."""
+        q, on_dev = self._prep_queries(queries)
+        self._validate(q, k)
+        nq = int(q.shape[0])
+        a_sc, a_id = (None, None) if after is None else after
+        if (a_sc is None) != (a_id is None):
+            raise ValueError("after = (scores, ids): both or neither")
+        if on_dev:
+            import torch
+
+            def bound(v, dt):
+                if v is None:
+                    return None
+                t = torch.as_tensor(v).to(device=q.device, dtype=dt).reshape(-1)
+                if t.numel() == 1 and nq != 1:
+                    t = t.expand(nq)
+                if t.numel() != nq:
+                    raise ValueError(f"a bound holds {t.numel()} values for {nq} queries")
+                return t.contiguous()
+            f32, i64t = torch.float32, torch.int64
+        else:
+            def bound(v, dt):
+                if v is None:
+                    return None
+                if _is_torch_tensor(v):
+                    v = v.detach().cpu().numpy()
+                t = np.asarray(v, dtype=dt).reshape(-1)
+                if t.size == 1 and nq != 1:
+                    t = np.broadcast_to(t, (nq,))
+                if t.size != nq:
+                    raise ValueError(f"a bound holds {t.size} values for {nq} queries")
+                return np.ascontiguousarray(t)
+            f32, i64t = np.float32, np.int64
+        lo, hi, asc, aid = bound(radius, f32), bound(range_filter, f32), bound(a_sc, f32), bound(a_id, i64t)
+        outs = []
+        for s0 in range(0, max(nq, 1), self.max_nq):
+            qs = q[s0:s0 + self.max_nq]
+            m = int(qs.shape[0])
+            if on_dev:
+                mk = lambda dt: torch.empty((m, k), dtype=dt, device=q.device)
+                adj, raw, ids, lv = mk(torch.float64), mk(torch.float32), mk(torch.int64), mk(torch.int32)
+                ptr = lambda t: t.data_ptr()
+                stream = _current_stream_ptr(self.device)
+            else:
+                mk = lambda dt: np.empty((m, k), dtype=dt)
+                adj, raw, ids, lv = mk(np.float64), mk(np.float32), mk(np.int64), mk(np.int32)
+                ptr = lambda t: t.ctypes.data
+                stream = None
+            part = [None if b is None else b[s0:s0 + self.max_nq] for b in (lo, hi, asc, aid)]   # (kept alive over the call)
+            if m:
+                _check(self._lib, self._lib.icd_index_search_range(
+                    self._h, ptr(qs), m, k, 1 if on_dev else 0, *[None if b is None else ptr(b) for b in part],
+                    1 if on_dev else 0, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv),
+                    1 if on_dev else 0, stream))
+            outs.append((adj, raw, ids, lv) if reweighted else (raw, ids, lv))
+        if len(outs) == 1:
+            return outs[0]
+        if on_dev:
             return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
         return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
 

@@ -4,7 +4,7 @@ Mirrors the reference's main.py for these routes: lifespan-owned service globals
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
 cut to top_k, every match's confidence metrics / factors / level copied as :325-330 does; 503 when services are missing, 500 with a `detail` string on any exception), `/embed`
 (:505-530), `/stats` (:574-599). `/query` takes a Milvus `filter` expression (services/filter_expr.py; a bad one is a 400), `/stats`
-lists the cached filter views and groupings; `/query` also takes Milvus's `group_by_field` / `group_size`. The LLM, NER, standardisation and resource routes are out of scope.
+lists the cached filter views and groupings; `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). The LLM, NER, standardisation and resource routes are out of scope.
 
     uvicorn rag_project_icd10_amd.api.app:app --host 0.0.0.0 --port 8005
 """
@@ -114,10 +114,23 @@ async def query_similar(request: QueryRequest):
             filter_expr.check_grouping(request.group_by_field, request.top_k * 2, request.group_size)
         except ValueError as exc:
             raise HTTPException(status_code=400, detail=str(exc))
+    ranged = request.radius is not None or request.range_filter is not None
+    if ranged:
+        # (a bad band, or one next to grouping, is a 400 as well)
+        from ..services import range_search
+        try:
+            radius, range_filter = range_search.check_bounds(request.radius, request.range_filter)
+            if grouped:
+                raise ValueError("radius / range_filter cannot be combined with group_by_field")
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
     try:
         if not embedding_service or not milvus_service or not multi_diagnosis_service:
             raise HTTPException(status_code=503, detail="服务未就绪")
-        if grouped:
+        if ranged:
+            result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter,
+                                                                      radius=radius, range_filter=range_filter)
+        elif grouped:
             result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter,
                                                                       group_by_field=request.group_by_field, group_size=request.group_size)
         elif request.filter is None:

@@ -217,6 +217,8 @@ class QueryRequest(BaseModel):
     filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields, e.g. 'level >= 2 and code like \"E11%\"'")
     group_by_field: Optional[str] = Field(default=None, description="Milvus grouping search: a scalar field, or 'category'; the search then ranks groups (2 * top_k * group_size <= 128)")
     group_size: int = Field(default=1, description="rows returned per group (with group_by_field)", ge=1, le=128)
+    radius: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is ABOVE this are ranked")
+    range_filter: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is at or below this are ranked (radius < range_filter)")
 
 
 class QueryResponse(BaseModel):

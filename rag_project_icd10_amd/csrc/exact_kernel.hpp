@@ -40,6 +40,7 @@ struct ExactArgs {
                            // (finalize.hpp, narrow_check). Lists carry global row ids either way.
     float *part_scores;    // [slot][P][KP]
     int *part_rows;        // [slot][P][KP]
+    const BandQ *band;     // BAND = true only: [query] the band every hit of the query lies in (topk_select.hpp)
 };
 
 // chunk count of the adaptive layout (device: exact_topk_kernel; the same call in finalize.hpp)
@@ -70,7 +71,13 @@ __host__ __device__ inline int exact_adaptive_chunks(int nq_active, int bmq, int
 // two waves fitted a CU: `--mode exact` at k = 20 ran at 0.27 of the fp32 MFMA peak against 0.59 at k = 10.)
 // GROUP: rows of a 32-row block tested between two overflow checks (32, or 16: two half blocks, for buffers with little room
 // above KP)
-template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32>
+// BAND: range search. Lane (c, h) holds 64 scores of ONE query per tile, so the query's band is four
+// registers per lane, loaded once: scores outside it are overwritten with -inf right behind the tile's MFMAs - before the
+// first-tile bootstrap, whose "KP rows of this tile reach t0" must count rows of the band only - and never pass the filter
+// (-inf passes no threshold). The floor seeds the list threshold (strict: thr_row = 0), which is a true lower bound of every
+// hit and spares a chunk's first tiles their compactions. Lists are plain KP >= k lists: no thr0, no narrow certificate -
+// both reason about the top of the WHOLE ranking. BAND = false compiles to what it compiled to before the parameter existed.
+template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false>
 __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
     constexpr int BMQ = NW * 32, BN = 128, LDT = BK + 1, NT = NW * 64;
     constexpr int CAP = CAPV, LIMIT = CAP - GROUP;
@@ -134,6 +141,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
 
     // this lane's half of its query's stage (slots past the end read the last query; their lists are never written)
     const float *qsrc;
+    float band_hi = INFINITY;
+    u64 band_below = ~0ull;
     {
         const int sq = min(my_slot, nq - 1);
         const int gq = a.qlist ? a.qlist[sq] : sq;
@@ -141,6 +150,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
         if (a.thr0 && my_valid) {
             const float t0 = a.thr0[gq];
             if (t0 > -INFINITY) { st.thr = t0; st.thr_row = 0xFFFFFFFFu; }   // (rows that tie with it pass)
+        }
+        if constexpr (BAND) {
+            const BandQ b = a.band[gq];
+            band_hi = b.hi; band_below = b.below;
+            if (my_valid && b.lo > st.thr) st.thr = b.lo;   // (thr_row stays 0: a row AT the floor is out)
         }
     }
     float bq[QH];   // the stage's k-step pairs of the query operand: bq[s] = (k = 2 s | 2 s + 1)
@@ -230,6 +244,16 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
 
         // fused select
         const bool partial = tile_row0 + BN > row_end;
+        if constexpr (BAND) {
+            // (keys carry the LOCAL row of the strided form; the band path runs contiguous chunks: local = global)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const uint32_t row = (uint32_t)(tile_row0 + t * 32 + 4 * h + (r & 3) + 8 * (r >> 2));
+                    acc[t][r] = band_under(acc[t][r], row, band_hi, band_below) ? acc[t][r] : -INFINITY;
+                }
+        }
         if (KP <= 32 && tile_row0 == row_begin && !partial) {
             // Threshold bootstrap of a chunk's first tile. Starting at -inf every row of the first tiles is appended and
             // each 16-register group ends in a compaction of all 32 queries (~1 ms per chunk: more than a 9-tile

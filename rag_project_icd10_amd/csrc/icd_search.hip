@@ -219,6 +219,12 @@ struct icd_index {
     int64_t last_nq = 0;
     int last_chunks = 0, last_mode = 0;
     int last_p2 = 0, last_p2_word = 0;   // lists per query of the last search's second pass (0: none) and the counter that fed it
+    // range search (icd_index_search_range): the packed bands of a call's queries. Device bounds are packed by band_pack_kernel;
+    // host bounds on the host (a view's row map is kept there too) into the pinned block, copied only where a path wants them
+    // in device memory - the single-launch kernel takes up to four in its arguments. Allocated at create, like everything else.
+    BandQ *band_dev = nullptr, *h_band = nullptr;   // [max_nq] each
+    std::vector<long long> h_row_map;   // a view: the host's copy of row_map (the cursor's id -> first local row behind it)
+    int band_pending = 0;               // host-packed bands of the current call not yet copied to band_dev
     unsigned long long *dbg = nullptr;  // diagnostic cycle counters [8192][4][4]
     unsigned int *pace = nullptr;       // [PACE_WORDS] arrival counters of the paced coarse sweep (coarse_flat_kernel.hpp, 67108864)
 };
@@ -248,6 +254,8 @@ void free_all(icd_index *x) {
     hipFree(x->dbg);
     hipFree(x->pace);
     hipFree(x->row_map);
+    hipFree(x->band_dev);
+    if (x->h_band) hipHostFree(x->h_band);
     if (x->h_nflag) hipHostFree(x->h_nflag);
     if (x->h_pin) hipHostFree(x->h_pin);
     if (x->ev_nflag) hipEventDestroy(x->ev_nflag);
@@ -293,9 +301,9 @@ int pick_chunks(int mtiles, int row_tiles, int pmax, int slots) {
     return std::max(1, p);
 }
 
-template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32>
+template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false>
 int launch_exact(icd_index *x, const ExactArgs &a, int mtiles, hipStream_t s) {
-    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP>;
+    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP, BAND>;
     const size_t lds = exact_lds_bytes<KP, E, NW, CAPV, BK>();
     HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(mtiles * a.P), dim3(NW * 64), lds, s, a));
     return ICD_OK;
@@ -322,9 +330,9 @@ inline bool stream_fits(int kp, int qb, int dim) {
     return (size_t)qb * dim * 4 + (size_t)4 * 2 * ST_STAGE_BYTES + (size_t)4 * qb * 64 * e * 8 <= (size_t)LDS_LIMIT;
 }
 
-template <int KP, int E, int QB>
+template <int KP, int E, int QB, bool BAND = false>
 int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq_ptr, int nq, int max_active,
-                  int p_out, int *p_used, hipStream_t s, const float *thr0 = nullptr) {
+                  int p_out, int *p_used, hipStream_t s, const float *thr0 = nullptr, const BandQ *band = nullptr) {
     const int n = (int)x->n;
     const int per_max = FIN_MAX_CAND / KP;                       // lists one reduce wave can merge
     const int p_cap = FIN_MAX_CAND / KP;                         // lists finalize<false> can merge
@@ -339,7 +347,7 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
     StreamArgs a{};
     a.corpus = x->corpus; a.queries = dq; a.qlist = qlist; a.nq_ptr = nq_ptr; a.nq = std::min(nq, max_active);
     a.max_active = max_active; a.n = n; a.dim = x->dim; a.rows_per_wg = rows_per_wg; a.nwg = nwg;
-    a.list_scores = x->lists_s; a.list_rows = x->lists_r; a.thr0 = thr0;
+    a.list_scores = x->lists_s; a.list_rows = x->lists_r; a.thr0 = thr0; a.band.q = band;
     // wave-private LDS ring: as many 8-KB stages per wave as fit next to the queries and candidate buffers
     int stages = 4;
     while (stages > 2 && stream_lds_bytes<KP, E, QB>(x->dim, stages) > (size_t)LDS_LIMIT) --stages;
@@ -349,7 +357,7 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
         const size_t cap = (l % 2 == 0) ? x->partx_cap + (size_t)128 * FIN_MAX_CAND_X : x->lists_cap;
         if ((size_t)a.nq * plan[l] * KP > cap) return fail(ICD_ERR_INVALID, "stream workspace too small for reduction level %d", l);
     }
-    constexpr auto kern = stream_topk_kernel<KP, E, QB>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, false, BAND>;
     const size_t lds = stream_lds_bytes<KP, E, QB>(x->dim, stages);
     if (lds > (size_t)LDS_LIMIT) return fail(ICD_ERR_INVALID, "stream kernel: dim=%d does not fit LDS with %d queries per pass", x->dim, QB);
     HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(nwg), dim3(256), lds, s, a));
@@ -383,8 +391,9 @@ inline bool plan_stream_one(int n, int dim, int num_cu, int qb, int cap_entries,
     return p->nwg >= 1 && p->nwg <= 256 && p->stages >= 2;
 }
 
-template <int KP, int E, int QB>
-int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, hipStream_t s, const float *host_q = nullptr, bool poll_done = false) {
+template <int KP, int E, int QB, bool BAND = false>
+int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, hipStream_t s, const float *host_q = nullptr, bool poll_done = false,
+                      const BandArgs *band = nullptr) {
     StreamOnePlan pl;
     if (!plan_stream_one((int)x->n, x->dim, x->num_cu, QB, 64 * E, &pl)) return fail(ICD_ERR_INVALID, "single-launch stream kernel: no plan for n=%lld dim=%d", (long long)x->n, x->dim);
     if ((size_t)nq * pl.nwg * KP * 2 > x->lists_cap) return fail(ICD_ERR_INVALID, "stream workspace too small");
@@ -396,6 +405,7 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
     a.ticket = reinterpret_cast<u64 *>(x->nflag + 6);                   // nflag[6..7]: 8-byte aligned, zeroed at create, only ever counts up
     a.fin = f;
     a.fin.counters = x->nflag; a.fin.host_counters = x->h_nflag_dev;
+    if (band) a.band = *band;
     if (poll_done) {
         a.done = reinterpret_cast<u64 *>(x->h_pin_dev + PIN_Q_BYTES + PIN_OUT_BYTES);
         a.done_value = ++x->done_seq;
@@ -404,10 +414,10 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
     // (at least 84 KB: ONE work-group per CU whatever the corpus size - the fence-free sc1 hand-off of the kernel's tail is the
     //  form measured for one work-group per CU, MI355X_MICROARCH.md visibility table)
     const size_t lds = std::max<size_t>(stream_one_lds_bytes<KP, E, QB>(x->dim, pl.stages, pl.rps), (size_t)84 * 1024);
-    constexpr auto kern = stream_topk_kernel<KP, E, QB, true>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, true, BAND>;
     if constexpr (QB == 1) {
         if (host_q) {   // the vector in the kernel arguments: no copy command in front of the launch
-            constexpr auto kern_in = stream_one_inline_kernel<KP, E>;
+            constexpr auto kern_in = stream_one_inline_kernel<KP, E, BAND>;
             StreamInlineQuery iq;
             memcpy(iq.v, host_q, (size_t)x->dim * sizeof(float));
             a.queries = nullptr;
@@ -449,6 +459,7 @@ void rec(icd_index *x, int i, hipStream_t s) {
 struct Outs {
     float *scores; long long *ids;
     double *adj; float *adj_raw; long long *adj_ids; int *adj_lv;
+    int *lv;   // raw order (the range search's raw form; never together with adj_lv: the two share the staging of host callers)
 };
 
 // rows 0, stride, 2 stride, ... of the fp32 corpus as a query batch (the corpus-shape probe of icd_index_create)
@@ -562,11 +573,12 @@ struct SearchCtx {
     int p_sparse;        // lists per slot that finalize<false> merges (32 / 8 / 4)
     int sparse_max;      // how many flagged queries still go to the streaming kernel
     bool stream_ok;      // small batches (the reference's one-query-per-call shape): stream the corpus once, exact, no coarse pass
+    const BandArgs *band;   // range search: the queries' bands (nullptr: none, and no band kernel runs)
 };
 
-SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s) {
+SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s, const BandArgs *band) {
     SearchCtx c{};
-    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast;
+    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast; c.band = band;
     c.ov = search_overrides();
     c.row_tiles = (int)((x->n + 127) / 128);
     FinArgs &f = c.f;
@@ -576,7 +588,7 @@ SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use
     if (x->cmean) { f.rmax_unc = x->rmax_unc_scaled; f.eps_f32 = 2.0f * (float)x->dim * 5.9604645e-8f; }
     f.levels = x->levels; f.id_base = x->id_base; f.row_map = x->row_map;
     f.out_scores = o.scores; f.out_ids = o.ids; f.out_adj = o.adj; f.out_adj_raw = o.adj_raw;
-    f.out_adj_ids = o.adj_ids; f.out_adj_levels = o.adj_lv;
+    f.out_adj_ids = o.adj_ids; f.out_adj_levels = o.adj_lv; f.out_levels = o.lv;
 
     c.kpx = exact_kp_for(k);
     c.nwx = c.kpx <= 64 ? 4 : 2;
@@ -603,15 +615,21 @@ int run_stream(const SearchCtx &c, const int *qlist, const int *nq_ptr, int nqs,
     int qb = nq_ptr ? 8 : (nqs <= 1 ? 1 : (nqs <= 2 ? 2 : (nqs <= 4 ? 4 : 8)));
     const int max_act = nq_ptr ? c.sparse_max : std::max(c.sparse_max, nqs);   // (a direct call - up to ST_MAX_ACTIVE queries - is not gated)
     while (qb > 1 && !stream_fits(c.kpx, qb, x->dim)) qb >>= 1;
-#define ICD_ST(KPV, EV) \
-    (qb == 1 ? launch_stream<KPV, EV, 1>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0) : \
-     qb == 2 ? launch_stream<KPV, EV, 2>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0) : \
-     qb == 4 ? launch_stream<KPV, EV, 4>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0) : \
-               launch_stream<KPV, EV, 8>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0))
-    if (c.kpx == 16) return ICD_ST(16, 2);
-    if (c.kpx == 32) return ICD_ST(32, 2);
-    if (c.kpx == 64) return ICD_ST(64, 3);
-    return ICD_ST(128, 4);
+#define ICD_ST(KPV, EV, BANDV, BQ) \
+    (qb == 1 ? launch_stream<KPV, EV, 1, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ) : \
+     qb == 2 ? launch_stream<KPV, EV, 2, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ) : \
+     qb == 4 ? launch_stream<KPV, EV, 4, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ) : \
+               launch_stream<KPV, EV, 8, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ))
+    if (c.band) {   // (range search: the same sweep, band instantiations)
+        if (c.kpx == 16) return ICD_ST(16, 2, true, c.band->q);
+        if (c.kpx == 32) return ICD_ST(32, 2, true, c.band->q);
+        if (c.kpx == 64) return ICD_ST(64, 3, true, c.band->q);
+        return ICD_ST(128, 4, true, c.band->q);
+    }
+    if (c.kpx == 16) return ICD_ST(16, 2, false, nullptr);
+    if (c.kpx == 32) return ICD_ST(32, 2, false, nullptr);
+    if (c.kpx == 64) return ICD_ST(64, 3, false, nullptr);
+    return ICD_ST(128, 4, false, nullptr);
 #undef ICD_ST
 }
 
@@ -667,7 +685,14 @@ int run_exact(const SearchCtx &c, const int *qlist, const int *nq_ptr, int px, b
         // (LDS: k <= 16 two work-groups per CU - 17 KB of stage + 60-entry buffers; k <= 64 one of four waves - 34 KB +
         //  112-entry buffers; larger k two waves. Eight waves on 64-entry buffers at k <= 32 - two per SIMD - were built and
         //  are slower, 9.2 against 7.2 ms per 10 000 queries: a 64-entry buffer with 32 kept is compacted after every append)
-        if (launch_exact_variant(x, c.ov, kpx, a, c.mtx, s, &rc)) {}
+        if (c.band) {   // (range search: the same four configurations, band instantiations)
+            a.band = c.band->q;
+            if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2, 32, true>(x, a, c.mtx, s);
+            else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16, true>(x, a, c.mtx, s);
+            else if (kpx == 64) rc = launch_exact<64, 2, 4, 112, 32, 1, 32, true>(x, a, c.mtx, s);
+            else rc = launch_exact<128, 3, 2, 192, 32, 1, 32, true>(x, a, c.mtx, s);
+        }
+        else if (launch_exact_variant(x, c.ov, kpx, a, c.mtx, s, &rc)) {}
         else if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2>(x, a, c.mtx, s);
         else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16>(x, a, c.mtx, s);
         else if (kpx == 64) rc = launch_exact<64, 2, 4, 112>(x, a, c.mtx, s);
@@ -698,6 +723,16 @@ int stage_host_query(const SearchCtx &c) {
     return ICD_OK;
 }
 
+// host-packed bands of a range search (icd_index_search_range left them in the pinned block): every path but the single-launch
+// kernel - which takes them in its arguments - reads them from device memory
+int stage_host_bands(const SearchCtx &c) {
+    icd_index *x = c.x;
+    if (!c.band || x->band_pending <= 0) return ICD_OK;
+    HIP_TRY(hipMemcpyAsync(x->band_dev, x->h_band, (size_t)x->band_pending * sizeof(BandQ), hipMemcpyHostToDevice, c.s));
+    x->band_pending = 0;
+    return ICD_OK;
+}
+
 // (the fallback counter starts every search at zero: the exact-only paths clear it themselves, the fast path in its
 //  query-prep launch - one launch less per step)
 
@@ -720,6 +755,16 @@ int search_tiny(const SearchCtx &c) {
         const float *hq = qb1 == 1 ? x->host_q : nullptr;   // (a host caller's ONE query: search_common left the copy out)
         if (!hq) { const int rcq = stage_host_query(c); if (rcq) return rcq; }
         const bool poll = x->host_one_call && (x->opt_host_one & 2) != 0;
+        if (c.band) {   // a page of a range search: still ONE launch (host-packed bands travel in the arguments)
+            BandArgs b = *c.band;
+            if (x->band_pending > 0) { b.q = nullptr; x->band_pending = 0; }
+            const int rcb = qb1 == 1 ? launch_stream_one<16, 2, 1, true>(x, c.dq, 1, c.f, s, hq, poll, &b)
+                          : qb1 == 2 ? launch_stream_one<16, 2, 2, true>(x, c.dq, 2, c.f, s, nullptr, false, &b)
+                                     : launch_stream_one<16, 2, 4, true>(x, c.dq, (int)nq, c.f, s, nullptr, false, &b);
+            rec(x, 4, s);
+            rec(x, 5, s);
+            return rcb;
+        }
         const int rc1 = qb1 == 1 ? launch_stream_one<16, 2, 1>(x, c.dq, 1, c.f, s, hq, poll) : qb1 == 2 ? launch_stream_one<16, 2, 2>(x, c.dq, 2, c.f, s)
                       : launch_stream_one<16, 2, 4>(x, c.dq, (int)nq, c.f, s);
         rec(x, 4, s);
@@ -727,6 +772,7 @@ int search_tiny(const SearchCtx &c) {
         return rc1;
     }
     { const int rcq = stage_host_query(c); if (rcq) return rcq; }
+    { const int rcb = stage_host_bands(c); if (rcb) return rcb; }
     HIP_TRY(hipMemsetAsync(x->nflag, 0, sizeof(int), s));
     rec(x, 3, s);
     return run_exact(c, nullptr, nullptr, c.p_sparse, false, true);
@@ -1064,8 +1110,10 @@ int search_auto(const SearchCtx &c) {
 }
 
 // Enqueue a search whose queries and outputs are device pointers.
-int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s) {
-    const bool use_fast = (mode == ICD_MODE_AUTO) && x->fast && k <= FAST_MAX_K && (x->dim == 768 || x->dim == 1024);
+// band: a range search (icd_index_search_range; mode EXACT) - the streaming forms up to ST_MAX_ACTIVE queries, plain lists of
+// KP >= k on the MFMA kernel above; nullptr for every other caller, and no band kernel runs.
+int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s, const BandArgs *band = nullptr) {
+    const bool use_fast = !band && (mode == ICD_MODE_AUTO) && x->fast && k <= FAST_MAX_K && (x->dim == 768 || x->dim == 1024);
     x->prof_now = !x->capturing && x->profiling && (x->prof_tick++ % x->prof_every == 0);
     if (x->prof_now) {
         const int slot = (int)(x->prof_count % EV_RING);
@@ -1079,11 +1127,12 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
     x->last_p2 = 0;
     x->last_mode = use_fast ? ICD_MODE_AUTO : ICD_MODE_EXACT;
     rec(x, 0, s);
-    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s);
+    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s, band);
     // (k > 16 needs the 64-entry lists of the streaming kernel, ~0.9 ms per 16 queries: the coarse pass is faster there)
     if (c.stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE)) return search_tiny(c);
     { const int rcq = stage_host_query(c); if (rcq) return rcq; }
-    if (!use_fast && c.kpx > 32 && x->opt_exact_narrow && nq > ST_MAX_ACTIVE && c.row_tiles >= 64) {
+    { const int rcb = stage_host_bands(c); if (rcb) return rcb; }
+    if (!band && !use_fast && c.kpx > 32 && x->opt_exact_narrow && nq > ST_MAX_ACTIVE && c.row_tiles >= 64) {
         bool taken = false;
         const int rc = search_exact_narrow(c, &taken);
         if (rc || taken) return rc;
@@ -1270,6 +1319,8 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
     CR_TRY(hipHostMalloc(reinterpret_cast<void **>(&x->h_pin), PIN_Q_BYTES + PIN_OUT_BYTES + PIN_DONE_BYTES, hipHostMallocMapped));
     CR_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&x->h_pin_dev), x->h_pin, 0));
     memset(x->h_pin + PIN_Q_BYTES + PIN_OUT_BYTES, 0, PIN_DONE_BYTES);   // (the completion word: sequence numbers start at 1)
+    CR_TRY(wsalloc(&x->band_dev, (size_t)max_nq));
+    CR_TRY(hipHostMalloc(reinterpret_cast<void **>(&x->h_band), (size_t)max_nq * sizeof(BandQ), hipHostMallocDefault));
     CR_TRY(wsalloc(&x->pace, PACE_WORDS));
     CR_TRY(wsalloc(&x->dbg, (size_t)8192 * 16));
     CR_TRY(hipMemset(x->dbg, 0, (size_t)8192 * 16 * 8));
@@ -1314,6 +1365,15 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
     return ICD_OK;
 }
 
+// The bounds of a range search as the caller gave them (icd_index_search_range): packed into BandQ inside search_common, under
+// the handle's mutex.
+struct RangeBounds {
+    const float *radius, *range_filter, *after_scores;
+    const long long *after_ids;
+    bool on_device;
+};
+static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s, BandArgs *out);
+
 extern "C" {
 
 int icd_index_create(const float *corpus, int64_t n, int32_t dim, const int32_t *levels, int64_t id_base,
@@ -1348,6 +1408,7 @@ int icd_index_create_view(icd_index *parent, const int64_t *rows, int64_t n_rows
                                 flags | ICD_CREATE_CORPUS_ON_DEVICE, dmap, out);
     if (rc) { hipFree(dmap); return rc; }
     (*out)->row_map = dmap;
+    (*out)->h_row_map = std::move(map);
     (*out)->bytes_ws += (size_t)n_rows * sizeof(long long);
     return ICD_OK;
 }
@@ -1370,10 +1431,11 @@ static void copy_pinned_out(icd_index *x, const Outs &user, size_t no_small) {
     if (user.scores) memcpy(user.scores, h, no_small * 4);        h += no_small * 4;
     if (user.adj_raw) memcpy(user.adj_raw, h, no_small * 4);      h += no_small * 4;
     if (user.adj_lv) memcpy(user.adj_lv, h, no_small * 4);
+    else if (user.lv) memcpy(user.lv, h, no_small * 4);
 }
 
 static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t k, int32_t q_on_device,
-                         int32_t mode, Outs user, int32_t out_on_device, void *stream) {
+                         int32_t mode, Outs user, int32_t out_on_device, void *stream, const RangeBounds *range = nullptr) {
     if (!valid(x)) return fail(ICD_ERR_STATE, "invalid handle");
     std::lock_guard<std::mutex> guard(x->mu);
     if (nq < 0 || nq > x->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds max_nq=%d", (long long)nq, x->max_nq);
@@ -1387,7 +1449,12 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         x->capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
         if (x->capturing && (!q_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
+        if (x->capturing && range && !range->on_device) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
     }
+    BandArgs band{};
+    x->band_pending = 0;
+    if (range) { const int rcb = pack_bands(x, *range, (int)nq, s, &band); if (rcb) return rcb; }
+    const bool host_bands = range && !range->on_device;
     const float *dq = queries;
     if (!q_on_device) {
         const size_t qbytes = (size_t)nq * x->dim * sizeof(float);
@@ -1412,6 +1479,7 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
         dev.scores = user.scores ? reinterpret_cast<float *>(d) : nullptr;                     d += no_small * 4;
         dev.adj_raw = user.adj_raw ? reinterpret_cast<float *>(d) : nullptr;                   d += no_small * 4;
         dev.adj_lv = user.adj_lv ? reinterpret_cast<int *>(d) : nullptr;
+        dev.lv = (user.lv && !user.adj_lv) ? reinterpret_cast<int *>(d) : nullptr;
     } else if (!out_on_device) {
         dev.scores = user.scores ? x->o_scores : nullptr;
         dev.ids = user.ids ? x->o_ids : nullptr;
@@ -1419,10 +1487,12 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
         dev.adj_raw = user.adj_raw ? x->o_adj_raw : nullptr;
         dev.adj_ids = user.adj_ids ? x->o_adj_ids : nullptr;
         dev.adj_lv = user.adj_lv ? x->o_adj_lv : nullptr;
+        dev.lv = (user.lv && !user.adj_lv) ? x->o_adj_lv : nullptr;
     }
     x->done_armed = false;
     x->host_one_call = !q_on_device && nq == 1 && pinned_out && !x->capturing;
-    int rc = search_device(x, dq, (int)nq, k, mode, dev, s);
+    int rc = search_device(x, dq, (int)nq, k, mode, dev, s, range ? &band : nullptr);
+    x->band_pending = 0;
     x->host_q = nullptr;
     x->host_one_call = false;
     if (rc) return rc;
@@ -1458,9 +1528,107 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
         if (user.adj_raw) HIP_TRY(hipMemcpyAsync(user.adj_raw, dev.adj_raw, no * sizeof(float), hipMemcpyDeviceToHost, s));
         if (user.adj_ids) HIP_TRY(hipMemcpyAsync(user.adj_ids, dev.adj_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
         if (user.adj_lv) HIP_TRY(hipMemcpyAsync(user.adj_lv, dev.adj_lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
+        else if (user.lv) HIP_TRY(hipMemcpyAsync(user.lv, dev.lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
     }
-    if (!out_on_device || !q_on_device) HIP_TRY(hipStreamSynchronize(s));
+    if (!out_on_device || !q_on_device || host_bands) HIP_TRY(hipStreamSynchronize(s));   // (host bounds went through the pinned block)
     return ICD_OK;
+}
+
+}  // extern "C"
+
+// ---- range search: the callers' bounds -> BandQ (topk_select.hpp) --------------------------------------
+// The cursor names a hit by its GLOBAL id; the kernels compare keys of LOCAL rows. cut = the first local row whose id is larger
+// than the cursor's: id - id_base + 1 clamped to [0, n], or on a view the upper bound in its strictly increasing row map - once
+// per query, here, not per score.
+__global__ void band_pack_kernel(const float *radius, const float *range_filter, const float *after_scores, const long long *after_ids,
+                                 int nq, const long long *row_map, long long n, long long id_base, BandQ *out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    BandQ b;
+    b.lo = radius ? radius[q] : -INFINITY;
+    b.hi = range_filter ? range_filter[q] : INFINITY;
+    b.below = ~0ull;
+    if (b.lo != b.lo || b.hi != b.hi) { b.lo = INFINITY; b.hi = -INFINITY; }   // (NaN bounds, unseen by the host: an empty band)
+    if (after_scores) {
+        const float as = after_scores[q];
+        const long long id = after_ids[q];
+        long long cut;
+        if (row_map) {
+            long long lo = 0, hi = n;   // first local row with row_map[row] > id
+            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (row_map[mid] > id) hi = mid; else lo = mid + 1; }
+            cut = lo;
+        } else {
+            cut = id < id_base ? 0 : (id - id_base >= n ? n : id - id_base + 1);
+        }
+        b.below = as != as ? 0ull : band_below(order_f32(as), (uint32_t)cut);
+    }
+    out[q] = b;
+}
+
+static uint32_t host_order_f32(float v) {
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+// Host bounds were validated by icd_index_search_range (no NaN, radius < range_filter); device bounds cannot be without a
+// synchronisation: an empty or inverted band simply yields padding.
+static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s, BandArgs *out) {
+    out->q = x->band_dev;
+    if (rb.on_device) {
+        hipLaunchKernelGGL(band_pack_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, rb.radius, rb.range_filter, rb.after_scores,
+                           rb.after_ids, nq, x->row_map, (long long)x->n, (long long)x->id_base, x->band_dev);
+        HIP_TRY(hipGetLastError());
+        return ICD_OK;
+    }
+    for (int q = 0; q < nq; ++q) {
+        BandQ b;
+        b.lo = rb.radius ? rb.radius[q] : -INFINITY;
+        b.hi = rb.range_filter ? rb.range_filter[q] : INFINITY;
+        b.below = ~0ull;
+        if (rb.after_scores) {
+            const long long id = rb.after_ids[q];
+            long long cut;
+            if (x->row_map) cut = std::upper_bound(x->h_row_map.begin(), x->h_row_map.end(), id) - x->h_row_map.begin();
+            else cut = id < x->id_base ? 0 : (id - x->id_base >= x->n ? x->n : id - x->id_base + 1);
+            b.below = band_below(host_order_f32(rb.after_scores[q]), (uint32_t)cut);
+        }
+        x->h_band[q] = b;
+        if (q < 4) out->inl[q] = b;
+    }
+    x->band_pending = nq;
+    return ICD_OK;
+}
+
+extern "C" {
+
+int icd_index_search_range(icd_index *idx, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
+                           const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
+                           int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                           int32_t *out_levels, int32_t out_on_device, void *stream) {
+    // (the checks that need neither the handle nor the device come first)
+    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a range search returns 1 .. %d hits per query", k, ICD_MAX_K);
+    if ((after_scores == nullptr) != (after_ids == nullptr)) return fail(ICD_ERR_INVALID, "after_scores and after_ids: both or neither (a cursor is a hit's score AND id)");
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (!bounds_on_device) {
+        for (int64_t q = 0; q < nq; ++q) {
+            if (radius && std::isnan(radius[q])) return fail(ICD_ERR_INVALID, "radius[%lld] is NaN", (long long)q);
+            if (range_filter && std::isnan(range_filter[q])) return fail(ICD_ERR_INVALID, "range_filter[%lld] is NaN", (long long)q);
+            if (after_scores && std::isnan(after_scores[q])) return fail(ICD_ERR_INVALID, "after_scores[%lld] is NaN", (long long)q);
+            if (radius && range_filter && !(radius[q] < range_filter[q]))
+                return fail(ICD_ERR_INVALID, "query %lld: radius=%g must be below range_filter=%g (hits have radius < score <= range_filter)", (long long)q, (double)radius[q], (double)range_filter[q]);
+        }
+    }
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    Outs o{};
+    if (reweighted) {
+        o.adj = out_adj; o.adj_raw = out_raw; o.adj_ids = reinterpret_cast<long long *>(out_ids); o.adj_lv = out_levels;
+    } else {
+        o.scores = out_raw; o.ids = reinterpret_cast<long long *>(out_ids); o.lv = out_levels;
+    }
+    RangeBounds rb{radius, range_filter, after_scores, reinterpret_cast<const long long *>(after_ids), bounds_on_device != 0};
+    return search_common(idx, queries, nq, k, queries_on_device, ICD_MODE_EXACT, o, out_on_device, stream, &rb);
 }
 
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,

@@ -69,6 +69,8 @@ struct StreamArgs {
     // index's mapped host block - behind its outputs (system-scope release); nullptr = nobody polls
     u64 *done;
     u64 done_value;
+    // BAND = true only (range search): the band every hit of a query lies in
+    BandArgs band;
 };
 
 // ONE query handed over IN the kernel arguments (a host caller's call: no H2D copy command in front of the launch). The
@@ -144,7 +146,10 @@ __device__ __forceinline__ void wait_vmcnt_uniform(int n) {
 #undef ICD_VM
 }
 
-template <int KP, int E, int QB, bool ONE>
+// BAND: only rows inside the query's band (topk_select.hpp, BandQ) are hits. The band of a pass's queries is wave-uniform
+// (scalar registers); the floor seeds the list threshold - strict, thr_row = 0 - and the ceiling and the cursor are two more
+// compares where a row is tested. Everything behind the select (lists, merges, emit_outputs' padding) is unchanged.
+template <int KP, int E, int QB, bool ONE, bool BAND = false>
 __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const float *qsrc) {
     constexpr int CAP = 64 * E;
     static_assert(!ONE || (QB <= 4 && KP <= 16), "the single-launch form serves up to four queries at k <= 16");
@@ -200,6 +205,17 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
                 const int slot = q0 + min(qi, nqp - 1);
                 const float t0 = a.thr0[a.qlist ? a.qlist[slot] : slot];
                 if (t0 > -INFINITY) { thr[qi] = t0; thr_row[qi] = 0xFFFFFFFFu; }   // (rows that tie with it pass)
+            }
+        }
+        float band_hi[QB];
+        u64 band_below[QB];
+        if constexpr (BAND) {
+#pragma unroll
+            for (int qi = 0; qi < QB; ++qi) {
+                const int slot = q0 + min(qi, nqp - 1);
+                const BandQ b = a.band.q ? a.band.q[a.qlist ? a.qlist[slot] : slot] : a.band.inl[slot & 3];
+                band_hi[qi] = b.hi; band_below[qi] = b.below;
+                if (b.lo > thr[qi]) thr[qi] = b.lo;   // (thr_row stays 0: a row AT the floor is out)
             }
         }
 
@@ -266,7 +282,8 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
 #pragma unroll
             for (int qi = 0; qi < QB; ++qi) {
                 const float v = acc[qi];
-                const bool pass = rvalid && (v > thr[qi] || (v == thr[qi] && row < thr_row[qi])) && v != -INFINITY;
+                bool pass = rvalid && (v > thr[qi] || (v == thr[qi] && row < thr_row[qi])) && v != -INFINITY;
+                if constexpr (BAND) pass = pass & band_under(v, row, band_hi[qi], band_below[qi]);
                 const u64 m = __ballot(pass);
                 if (m) {
                     u64 *qb = bufs + (size_t)qi * CAP;
@@ -494,14 +511,14 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
     }
 }
 
-template <int KP, int E, int QB, bool ONE = false>
+template <int KP, int E, int QB, bool ONE = false, bool BAND = false>
 __global__ __launch_bounds__(256) void stream_topk_kernel(StreamArgs a) {
-    stream_topk_body<KP, E, QB, ONE>(a, a.queries);
+    stream_topk_body<KP, E, QB, ONE, BAND>(a, a.queries);
 }
 // the single-launch form of ONE query whose vector arrives in the kernel arguments (StreamInlineQuery)
-template <int KP, int E>
+template <int KP, int E, bool BAND = false>
 __global__ __launch_bounds__(256) void stream_one_inline_kernel(StreamArgs a, StreamInlineQuery q) {
-    stream_topk_body<KP, E, 1, true>(a, q.v);
+    stream_topk_body<KP, E, 1, true, BAND>(a, q.v);
 }
 
 // One wave per (slot, output list g): merge lists g, g + P_out, g + 2 P_out, ... of the slot's nlists

@@ -33,6 +33,31 @@ __device__ __forceinline__ float key_score(u64 k) { return unorder_f32((uint32_t
 __device__ __forceinline__ uint32_t key_row(u64 k) { return ~(uint32_t)k; }
 // key 0 is below every real key (a real key has row <= 0x7FFFFFFE so its low word is >= 0x80000001)
 
+// ---- band of one query (range search, offset, iterator pages: DESIGN.md section 11) ------------------------------------------
+// A row is a hit iff  lo < score  and  score <= hi  and  make_key(score, row) < below  (plain float compares on the
+// canonical score; `below` cuts the (score desc, row asc) ranking strictly behind a cursor). No bound: -inf, +inf, ~0.
+// `below` is built from the cursor (score, cut) with cut = the first LOCAL row whose id is larger than the cursor's id:
+// rows of the cursor's score pass from `cut` on, so  below = (order(score) << 32 | ~cut) + 1  (cut = 0: the carry lets
+// every row of that score through).
+struct BandQ {
+    float lo, hi;
+    u64 below;
+};
+__host__ __device__ inline u64 band_below(uint32_t ordered_score, uint32_t cut) {
+    return (((u64)ordered_score << 32) | (u64)(~cut)) + 1ull;
+}
+// (bitwise on purpose: the short-circuit form became per-score branches in exact_topk, 64 of them per tile and lane)
+__device__ __forceinline__ bool band_under(float v, uint32_t row, float hi, u64 below) {
+    const uint32_t o = order_f32(v), bo = (uint32_t)(below >> 32), br = (uint32_t)below;
+    return (v <= hi) & ((o < bo) | ((o == bo) & (~row < br)));
+}
+// Kernel argument: the bands of a launch's queries, [query index] in device memory - or, q == nullptr, those of the up to
+// four queries of a single-launch call in the arguments themselves (a host caller's page: no copy, no launch in front).
+struct BandArgs {
+    const BandQ *q;
+    BandQ inl[4];
+};
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 template <typename T>

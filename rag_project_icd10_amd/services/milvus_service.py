@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..corpus_store import CorpusStore
-from . import filter_expr
+from . import filter_expr, range_search
 
 logger = logging.getLogger(__name__)
 
@@ -303,15 +303,32 @@ class MilvusService:
                         "bytes": int(st["bytes_corpus_f32"] + st["bytes_corpus_f16"] + st["bytes_workspace"])})
         return out
 
+    @staticmethod
+    def _check_band(top_k, group_by_field, radius, range_filter, offset, search_params):
+        """(radius, range_filter, offset, banded) of a search's range arguments; ValueError on a bad one or on a combination with
+        grouping (Milvus refuses that too)"""
+        radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
+        offset = range_search.check_offset(offset, top_k)
+        banded = radius is not None or range_filter is not None or offset > 0
+        if banded and group_by_field is not None:
+            raise ValueError("radius / range_filter / offset cannot be combined with group_by_field")
+        return radius, range_filter, offset, banded
+
     def search(self, query_vector: np.ndarray, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002 (Milvus's name)
-               group_by_field: Optional[str] = None, group_size: int = 1) -> List[Dict[str, Any]]:
+               group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
+               range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
         """group_by_field (one of filter_expr.GROUP_FIELDS) / group_size: Milvus's grouping search - the hits are the top_k best
         GROUPS' group_size best rows each (exact), re-sorted by adjusted score like any hit list; every hit's metadata then
-        carries the group's value under the field's name. top_k * group_size <= 128. A bad grouping argument raises ValueError."""
+        carries the group's value under the field's name. top_k * group_size <= 128. A bad grouping argument raises ValueError.
+        radius / range_filter (also search_params={"params": {"radius": .., "range_filter": ..}}): Milvus's range search - only
+        rows with radius < inner product <= range_filter are ranked (the band is on the RAW score, `original_score`). offset: the
+        hits of ranks offset .. offset + top_k of that ranking (offset + top_k <= 16384), then re-sorted by adjusted score. Exact
+        (services/range_search.py). A bad range argument, or one next to group_by_field, raises ValueError."""
         if group_by_field is not None:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
+        radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         try:
             if self.client is None or not self.client.exists():
                 logger.error("集合 %s 不存在", self.collection_name)
@@ -330,7 +347,10 @@ class MilvusService:
             if group_by_field is not None:
                 adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, q, top_k, group_by_field, group_size)
                 return self._hits_to_dicts(adj[0], raw[0], ids[0], (group_by_field, groups[0], values))
-            adj, raw, ids, levels = index.search_reweighted(q, int(top_k))
+            if banded:
+                adj, raw, ids, levels = range_search.search_band(index, q, int(top_k), radius, range_filter, offset)
+            else:
+                adj, raw, ids, levels = index.search_reweighted(q, int(top_k))
             return self._hits_to_dicts(adj[0], raw[0], ids[0])
         except Exception as exc:
             logger.error("搜索失败: %s", exc)
@@ -364,19 +384,43 @@ class MilvusService:
                 out[-1]["metadata"][group[0]] = group[2][int(group[1][j])].item()
         return out
 
+    def search_iterator(self, query_vector, batch_size: int = 10, limit: int = -1, filter: Optional[str] = None,   # noqa: A002
+                        radius: Optional[float] = None, range_filter: Optional[float] = None,
+                        search_params: Optional[Dict[str, Any]] = None) -> "range_search.SearchIterator":
+        """pymilvus's search_iterator: an object whose next() returns the following batch_size hits of the query's ranking (inside
+        the band, on the filter's selection) as a `search`-shaped list, [] when exhausted or after `limit` hits, and close().
+        Pages are disjoint and exact at any depth; batch_size <= 128. The iterator keeps the index (or view) and the store
+        generation it started on: next() raises RuntimeError after the store changed. Bad arguments raise ValueError."""
+        radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
+        if filter is not None:
+            filter_expr.compile(filter)
+        if self.client is None or not self.client.exists():
+            index = None
+        elif filter is not None:
+            index, _ = self._filtered_index(filter)
+        else:
+            index = self._ready_index()
+        client = self.client
+        return range_search.SearchIterator(index, query_vector, batch_size, limit, radius, range_filter, self._hits_to_dicts,
+                                           lambda: (id(self.client), None if client is None else (client.generation, client.count)))
+
     def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False, filter: Optional[str] = None,   # noqa: A002
-                     group_by_field: Optional[str] = None, group_size: int = 1):
+                     group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
+                     range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None):
         """Additive: many queries in one call. query_vectors: [nq, dim] numpy array or torch CUDA
         tensor. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order
         `search` returns hits; or, with as_dicts=True, a list of `search`-shaped hit lists.
         filter: a Milvus filter expression - only the rows it selects are ranked (hit ids stay the corpus's row ids); a selection
         shorter than top_k pads the lists with id -1, score -inf, level 0. Raises ValueError on a bad expression.
         group_by_field / group_size: as in `search`; the arrays are then [nq, top_k * group_size] and a fifth one follows, the
-        hits' group ids (int32, -1 in padding: ranks of the field's sorted distinct values)."""
+        hits' group ids (int32, -1 in padding: ranks of the field's sorted distinct values).
+        radius / range_filter / offset / search_params: as in `search`, the same band for every query of the batch; lists shorter
+        than top_k are padded like a short filter selection's."""
         if group_by_field is not None:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
+        radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         if filter is not None:
             filter_expr.compile(filter)   # (a bad expression raises before anything is loaded)
         index = self._ready_index()
@@ -400,7 +444,10 @@ class MilvusService:
         # (large batches on a corpus of tight families of near-identical rows - ICD sibling codes - are handled inside the
         #  library: a second coarse pass over the queries the first could not certify, and from the next large batch on the
         #  wider partition right away; include/icd_search.h icd_stats.last_second_pass / wide_mode)
-        adj, raw, ids, levels = index.search_reweighted(query_vectors, int(top_k))
+        if banded:
+            adj, raw, ids, levels = range_search.search_band(index, query_vectors, int(top_k), radius, range_filter, offset)
+        else:
+            adj, raw, ids, levels = index.search_reweighted(query_vectors, int(top_k))
         if not as_dicts:
             return adj, raw, ids, levels
         if hasattr(adj, "cpu"):

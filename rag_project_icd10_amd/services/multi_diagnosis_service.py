@@ -56,9 +56,13 @@ class _gc_paused:
 CONFIDENCE_MODES = ("match", "multidimensional")
 
 
-def _search_options(filter, group_by_field, group_size) -> Dict[str, Any]:   # noqa: A002
-    """keyword arguments of MilvusService.search_batch for a request's filter / grouping: only the ones that were given"""
+def _search_options(filter, group_by_field, group_size, radius=None, range_filter=None) -> Dict[str, Any]:   # noqa: A002
+    """keyword arguments of MilvusService.search_batch for a request's filter / grouping / range: only the ones that were given"""
     opts: Dict[str, Any] = {}
+    if radius is not None:
+        opts["radius"] = radius
+    if range_filter is not None:
+        opts["range_filter"] = range_filter
     if filter is not None:
         opts["filter"] = filter
     if group_by_field is not None or group_size != 1:
@@ -88,9 +92,12 @@ class MultiDiagnosisService:
             embedding_service=embedding_service, ner_service=ner_service, hierarchical_similarity_service=self.hierarchical_similarity)
 
     def match_multiple_diagnoses(self, text: str, top_k: int = 5, filter: Optional[str] = None,   # noqa: A002
-                                 group_by_field: Optional[str] = None, group_size: int = 1) -> Dict[str, Any]:
+                                 group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
+                                 range_filter: Optional[float] = None) -> Dict[str, Any]:
         """filter: a Milvus filter expression (services/filter_expr.py) - every diagnosis is searched among the rows it selects only
-        (the search of 2 top_k, on the device path and the host path alike); None ranks the whole corpus"""
+        (the search of 2 top_k, on the device path and the host path alike); None ranks the whole corpus.
+        radius / range_filter: Milvus's range search - only rows with radius < inner product <= range_filter are ranked
+        (MilvusService.search_batch); a diagnosis with fewer than 2 top_k such rows is rescored on the shorter list."""
         enhanced = self.text_processor.extract_diagnoses_enhanced(text)
         diagnoses = [d["text"] for d in enhanced]
         mode = self.text_processor.get_processing_mode()
@@ -101,6 +108,10 @@ class MultiDiagnosisService:
         confs = [d.get("diagnosis_confidence", 0.5) for d in enhanced]
         # one encoder batch + one search batch for the whole request
         grouped = {} if group_by_field is None and group_size == 1 else {"group_by_field": group_by_field, "group_size": group_size}
+        if radius is not None:
+            grouped["radius"] = radius
+        if range_filter is not None:
+            grouped["range_filter"] = range_filter
         matches = None
         ner_job = vectors = None
         device = getattr(self.milvus_service, "supports_device_rescoring", lambda: False)()
@@ -138,7 +149,7 @@ class MultiDiagnosisService:
         if vectors is None:
             vectors = self._embed_diagnoses(diagnoses)
         try:
-            hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, **_search_options(filter, group_by_field, group_size))
+            hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, **_search_options(filter, group_by_field, group_size, radius, range_filter))
         except Exception as exc:
             logger.error("batch search failed: %s", exc)
             hit_lists = [[] for _ in diagnoses]
@@ -209,7 +220,8 @@ class MultiDiagnosisService:
     def match_diagnoses_batch(self, diagnoses: List[str], top_k: int = 5, vectors=None,
                               confidence_statistics: bool = False, entities=None, confidence: str = None,
                               filter: Optional[str] = None, group_by_field: Optional[str] = None,   # noqa: A002
-                              group_size: int = 1) -> List[DiagnosisMatch]:
+                              group_size: int = 1, radius: Optional[float] = None,
+                              range_filter: Optional[float] = None) -> List[DiagnosisMatch]:
         """Additive (row N2): embed -> search(2 top_k) -> level reweight -> hierarchical rescoring for MANY diagnosis
         strings with everything between the tokenizer and the final top_k on the GPU: one encoder batch, one search_batch,
         one rescoring launch; only the top_k winners per string come back and become Candidate objects. Same results as
@@ -226,7 +238,9 @@ class MultiDiagnosisService:
         filter: a Milvus filter expression: the search of 2 top_k ranks the rows it selects only (MilvusService.search_batch);
         the rescoring, the entities and both confidence modes then run unchanged on those hits (ids stay the corpus's row ids).
         group_by_field / group_size: Milvus's grouping search (MilvusService.search_batch): the search of 2 top_k then returns the
-        group_size best rows of the 2 top_k best GROUPS, and the rescoring runs on those hits (2 top_k group_size <= 128)."""
+        group_size best rows of the 2 top_k best GROUPS, and the rescoring runs on those hits (2 top_k group_size <= 128).
+        radius / range_filter: Milvus's range search (MilvusService.search_batch): lists shorter than 2 top_k arrive padded, as a
+        short filter selection's do."""
         from .hierarchical_similarity_service import trusted_factors_row
         confidence = self.confidence if confidence is None else confidence
         if confidence not in CONFIDENCE_MODES:
@@ -241,7 +255,7 @@ class MultiDiagnosisService:
         hs = self.hierarchical_similarity
         if entities is None:
             qps = [hs.query_params(d) for d in diagnoses]   # ([1] is the context relevance the factors report)
-        adj, raw, ids = self.milvus_service.search_batch(vectors, top_k * 2, **_search_options(filter, group_by_field, group_size))[:3]
+        adj, raw, ids = self.milvus_service.search_batch(vectors, top_k * 2, **_search_options(filter, group_by_field, group_size, radius, range_filter))[:3]
         if entities is not None:
             if hasattr(entities, "result"):   # (the NER worker's Future: the classifier ran beside the embedding and the search)
                 entities = entities.result()
