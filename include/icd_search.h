@@ -239,6 +239,50 @@ int icd_index_search_range(icd_index *idx, const float *queries, int64_t nq, int
                            int32_t *out_levels, int32_t out_on_device, void *stream);
 
 /*
+ * Masked search: a Milvus `filter` applied as a bitset over the index's rows, tested inside the scan - a DIFFERENT filter per
+ * query of one batch, and no second index per filter (a view, icd_index_create_view, stays the faster form
+ * of ONE filter over a large batch).
+ *
+ * icd_rowmask_create: the rows of `idx` that may be hits, rows[0 .. n_rows): the index's row indices, strictly increasing, inside
+ * [0, n), as for a view (anything else is ICD_ERR_INVALID); host, or device with rows_on_device = 1. n_rows = 0 is allowed: the
+ * empty mask. The mask is a device bitset of n / 8 bytes (row r = bit r & 31 of word r >> 5, zero-padded to whole 128-row tiles);
+ * a host list is packed on the host and uploaded, a device list is packed by a kernel. Any number of masks per index. A mask
+ * keeps no pointer into its index: either may be destroyed first; a search checks that the two belong together (the same
+ * handle, the same creation, the same n). On a view: ICD_ERR_UNSUPPORTED - mask the parent. The row-sharded path (icd_group_*)
+ * has no masked search.
+ *
+ * icd_index_search_masked: icd_index_search_range (same arguments, same outputs, same checks) over, for query q, the ranking
+ * restricted to the rows of masks[q]: the min(k, rows of the mask inside the band) best of them, best first, then padding
+ * (score -inf, id -1, level 0). `masks` is a HOST array of nq handles; a NULL entry leaves that query unfiltered, and with
+ * masks NULL or every entry NULL the call IS icd_index_search_range. With the same mask M on every query the outputs equal those
+ * of icd_index_create_view(rows of M) searched in ICD_MODE_EXACT, bit for bit; ids are the index's own global ids. An empty mask
+ * yields padding. A mask of another index is ICD_ERR_INVALID, a destroyed one ICD_ERR_STATE, a view as `idx`
+ * ICD_ERR_UNSUPPORTED. Always exact (the fp16 coarse path has no masked certificate): up to four queries at k <= 16 are ONE
+ * launch, up to 64 the streaming kernel, more the fp32-MFMA kernel. The table of bitset pointers goes through staging allocated
+ * with the index - nothing is allocated in a search. With device queries, outputs and bounds the call only enqueues on `stream`,
+ * like icd_index_search_range (the pinned table is guarded by an event: the NEXT masked call of the index waits until this
+ * call's copy of it has run); but the table is filled on the host at call time, so a masked call is NOT graph-capturable
+ * (ICD_ERR_INVALID while `stream` is capturing). The event guards the pinned block only: the device copy of the table is ONE
+ * buffer per index, like the workspace and the bounds' staging, so the index serves one stream at a time - a masked call
+ * enqueued on a second stream while an earlier call's kernels still run on another may overwrite the table under them; order
+ * the streams yourself, as for every other search of one index. A mask must outlive the searches that were enqueued with it:
+ * icd_rowmask_destroy synchronises the device first.
+ */
+typedef struct icd_rowmask icd_rowmask;
+int icd_rowmask_create(icd_index *idx, const int64_t *rows, int64_t n_rows, int32_t rows_on_device, icd_rowmask **out);
+int icd_rowmask_destroy(icd_rowmask *m);
+/* rows selected, device bytes held (either pointer may be NULL) */
+int icd_rowmask_stats(icd_rowmask *m, int64_t *out_rows, int64_t *out_bytes);
+/* The host packer of icd_rowmask_create, on its own (no device, no handle): rows[0 .. n_rows) of an index of n rows ->
+ * out_words[0 .. out_count), out_count >= 4 * ceil(n / 128); every word is written (zero where no row is). ICD_ERR_INVALID for a
+ * list that is not strictly increasing inside [0, n), or a buffer too short. */
+int icd_rowmask_pack(const int64_t *rows, int64_t n_rows, int64_t n, uint32_t *out_words, int64_t out_count);
+int icd_index_search_masked(icd_index *idx, icd_rowmask *const *masks, const float *queries, int64_t nq, int32_t k,
+                            int32_t queries_on_device, const float *radius, const float *range_filter, const float *after_scores,
+                            const int64_t *after_ids, int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw,
+                            int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

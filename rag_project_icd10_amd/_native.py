@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "icd_unpack_query_slices", "icd_split_bf16x3", "icd_encoder_create", "icd_encoder_encode", "icd_encoder_encode_many", "icd_encoder_destroy", "icd_pack_winners",
     "icd_grouping_create", "icd_grouping_destroy", "icd_grouping_stats", "icd_index_search_grouped",
     "icd_index_search_range",
+    "icd_rowmask_create", "icd_rowmask_destroy", "icd_rowmask_stats", "icd_rowmask_pack", "icd_index_search_masked",
 )
 MAX_K = 128   # include/icd_search.h ICD_MAX_K: the slots of one query's hit list (a grouped search: k * group_size)
 # include/icd_search.h: icd_index_create flags and icd_index_set_option ids (A/B and test options of ONE index)
@@ -113,6 +114,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_grouping_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_grouped.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_index_search_range.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.icd_rowmask_create.argtypes = [vp, vp, i64, i32, C.POINTER(vp)]
+    lib.icd_rowmask_destroy.argtypes = [vp]
+    lib.icd_rowmask_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_rowmask_pack.argtypes = [vp, i64, i64, vp, i64]
+    lib.icd_index_search_masked.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -432,9 +438,51 @@ class IcdIndex:
         is on the raw inner product. reweighted=True: (adj f64, raw f32, ids i64, levels i32) in search_reweighted's order;
         False: (raw, ids, levels) in raw order. Padding behind the band's last row: -inf, id -1, level 0. Device tensors in ->
         device tensors out on torch's current stream (the bounds are moved to the device if they are not there)."""
+        return self._search_band(queries, k, radius, range_filter, after, reweighted, None)
+
+    # -- masked search (a Milvus filter as a per-query bitset over the rows) ----------------------------
+    def rowmask(self, rows) -> "IcdRowMask":
+        """A row mask of this index (icd_rowmask_create): rows = strictly increasing row indices in [0, n), a numpy array or a
+        torch CUDA tensor (int64); an empty list is the empty mask. A bitset of n / 8 bytes on the device; any number per index."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdRowMask(self, rows)
+
+    def search_masked(self, queries, k: int, masks, *, radius=None, range_filter=None, after=None, reweighted: bool = True):
+        """search_range over, for every query, the ranking restricted to the rows of its mask (icd_index_search_masked): masks is
+        ONE IcdRowMask for every query, or a sequence of length nq of IcdRowMask or None (None: that query is unfiltered). Same
+        bounds, outputs and padding as search_range; ids are this index's own. With one mask on every query the outputs equal
+        view(rows).search in MODE_EXACT bit for bit. Device tensors in -> device tensors out on torch's
+        current stream, enqueued only; the call is not graph-capturable (the mask table is staged on the host at call time)."""
+        return self._search_band(queries, k, radius, range_filter, after, reweighted, masks)
+
+    def _search_band(self, queries, k, radius, range_filter, after, reweighted, masks):
         q, on_dev = self._prep_queries(queries)
         self._validate(q, k)
         nq = int(q.shape[0])
+        mask_h = None
+        if masks is not None:
+            # [query] -> handle as a uint64 array, built without a Python loop over the queries (10 000 of them cost milliseconds
+            # in front of the launch): the distinct mask objects are found by identity and checked once each
+            if isinstance(masks, IcdRowMask):
+                uniq, inverse = [masks], np.zeros(nq, np.int64)
+            else:
+                masks = list(masks)
+                if len(masks) != nq:
+                    raise ValueError(f"masks holds {len(masks)} entries for {nq} queries")
+                ident = np.fromiter(map(id, masks), np.int64, nq)
+                _, first, inverse = np.unique(ident, return_index=True, return_inverse=True)
+                uniq = [masks[i] for i in first]
+            vals = np.zeros(max(len(uniq), 1), np.uint64)
+            for j, m_ in enumerate(uniq):
+                if m_ is None:
+                    continue
+                if not isinstance(m_, IcdRowMask):
+                    raise TypeError("masks: IcdRowMask or None per query")
+                if m_.closed:
+                    raise IcdError(-5, "a row mask is closed")
+                vals[j] = m_._h.value
+            mask_h = np.ascontiguousarray(vals[inverse.reshape(-1)]) if nq else np.zeros(1, np.uint64)   # (kept alive over the calls below)
         a_sc, a_id = (None, None) if after is None else after
         if (a_sc is None) != (a_id is None):
             raise ValueError("after = (scores, ids): both or neither")
@@ -480,9 +528,15 @@ class IcdIndex:
                 ptr = lambda t: t.ctypes.data
                 stream = None
             part = [None if b is None else b[s0:s0 + self.max_nq] for b in (lo, hi, asc, aid)]   # (kept alive over the call)
-            if m:
+            if m and mask_h is None:
                 _check(self._lib, self._lib.icd_index_search_range(
                     self._h, ptr(qs), m, k, 1 if on_dev else 0, *[None if b is None else ptr(b) for b in part],
+                    1 if on_dev else 0, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv),
+                    1 if on_dev else 0, stream))
+            elif m:
+                _check(self._lib, self._lib.icd_index_search_masked(
+                    self._h, mask_h.ctypes.data + 8 * s0, ptr(qs), m, k, 1 if on_dev else 0,
+                    *[None if b is None else ptr(b) for b in part],
                     1 if on_dev else 0, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv),
                     1 if on_dev else 0, stream))
             outs.append((adj, raw, ids, lv) if reweighted else (raw, ids, lv))
@@ -568,6 +622,72 @@ class IcdGrouping:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.icd_grouping_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def closed(self) -> bool:
+        return not self._h.value
+
+
+def rowmask_words(n: int) -> int:
+    """32-bit words of a row mask's bitset over n rows: whole 128-row tiles (include/icd_search.h, icd_rowmask_create)"""
+    return (int(n) + 127) // 128 * 4
+
+
+def pack_rowmask(rows, n: int) -> np.ndarray:
+    """The bitset a host row list becomes (icd_rowmask_pack, the packer icd_rowmask_create runs on a host list; no device
+    needed): uint32[rowmask_words(n)], row r = bit r & 31 of word r >> 5, zero-padded. rows: strictly increasing, in [0, n)."""
+    lib = load_library()
+    r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+    out = np.empty(rowmask_words(n), dtype=np.uint32)
+    rc = lib.icd_rowmask_pack(r.ctypes.data if r.size else None, int(r.size), int(n), out.ctypes.data, int(out.size))
+    if rc == -1:
+        raise ValueError(lib.icd_last_error().decode("utf-8", "replace"))
+    _check(lib, rc)
+    return out
+
+
+class IcdRowMask:
+    """A set of rows of one IcdIndex as a device bitset (icd_rowmask_*): what search_masked tests inside the scan. Independent
+    of the index's lifetime: either may be closed first (a search with a closed partner raises)."""
+
+    def __init__(self, index: "IcdIndex", rows):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        if _is_torch_tensor(rows) and rows.is_cuda:
+            import torch
+            keep = rows.to(torch.int64).contiguous().reshape(-1)
+            if keep.device.index != index.device:
+                raise ValueError(f"rows on cuda:{keep.device.index}, index on device {index.device}")
+            torch.cuda.synchronize(index.device)
+            ptr, on_dev, m = keep.data_ptr(), 1, int(keep.numel())
+        else:
+            if _is_torch_tensor(rows):
+                rows = rows.detach().cpu().numpy()
+            keep = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+            ptr, on_dev, m = keep.ctypes.data, 0, int(keep.size)
+        self.n, self.rows, self.device = index.n, m, index.device
+        rc = self._lib.icd_rowmask_create(index._h, ptr if m else None, m, on_dev, C.byref(self._h))
+        if rc == -1:
+            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+        _check(self._lib, rc)
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "row mask is closed")
+        r, b = C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_rowmask_stats(self._h, C.byref(r), C.byref(b)))
+        return {"rows": r.value, "bytes": b.value}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.icd_rowmask_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -4,7 +4,7 @@ Mirrors the reference's main.py for these routes: lifespan-owned service globals
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
 cut to top_k, every match's confidence metrics / factors / level copied as :325-330 does; 503 when services are missing, 500 with a `detail` string on any exception), `/embed`
 (:505-530), `/stats` (:574-599). `/query` takes a Milvus `filter` expression (services/filter_expr.py; a bad one is a 400), `/stats`
-lists the cached filter views and groupings; `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). The LLM, NER, standardisation and resource routes are out of scope.
+lists the cached filter views, filter masks and groupings; `/query` takes `filter_mode` ("view" / "mask"; anything else is a 400); `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). The LLM, NER, standardisation and resource routes are out of scope.
 
     uvicorn rag_project_icd10_amd.api.app:app --host 0.0.0.0 --port 8005
 """
@@ -104,6 +104,11 @@ async def query_similar(request: QueryRequest):
             filter_expr.compile(request.filter)
         except ValueError as exc:
             raise HTTPException(status_code=400, detail=str(exc))
+    if request.filter_mode not in ("view", "mask"):
+        raise HTTPException(status_code=400, detail=f"filter_mode={request.filter_mode!r}: one of ('view', 'mask')")
+    if request.filter_mode == "mask" and request.filter is not None and request.group_by_field is not None:
+        raise HTTPException(status_code=400, detail="filter_mode='mask' cannot be combined with group_by_field")
+    mode = {} if request.filter_mode == "view" else {"filter_mode": request.filter_mode}
     grouped = request.group_by_field is not None or request.group_size != 1
     if grouped:
         # (a bad grouping is a 400 like a bad filter; /query searches top_k * 2, with grouping that is top_k * 2 GROUPS)
@@ -129,14 +134,14 @@ async def query_similar(request: QueryRequest):
             raise HTTPException(status_code=503, detail="服务未就绪")
         if ranged:
             result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter,
-                                                                      radius=radius, range_filter=range_filter)
+                                                                      radius=radius, range_filter=range_filter, **mode)
         elif grouped:
             result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter,
-                                                                      group_by_field=request.group_by_field, group_size=request.group_size)
+                                                                      group_by_field=request.group_by_field, group_size=request.group_size, **mode)
         elif request.filter is None:
             result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k)
         else:
-            result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter)
+            result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter, **mode)
         candidates, matches = [], []
         for m in result["matches"]:
             candidates.extend(m.candidates)
@@ -180,6 +185,8 @@ async def get_stats():
             stats["milvus"] = milvus_service.get_collection_stats()
             if hasattr(milvus_service, "filter_views"):   # the cached filter views: expression, rows, HBM bytes
                 stats["filter_views"] = milvus_service.filter_views()
+            if hasattr(milvus_service, "filter_masks"):   # the cached filter masks (filter_mode "mask", per-query filters): expression, rows, HBM bytes
+                stats["filter_masks"] = milvus_service.filter_masks()
             if hasattr(milvus_service, "groupings"):      # the cached groupings: field, groups, largest group, HBM bytes
                 stats["groupings"] = milvus_service.groupings()
         if embedding_service:

@@ -215,6 +215,7 @@ class QueryRequest(BaseModel):
     text: str = Field(..., description="输入的诊断文本", min_length=1)
     top_k: int = Field(default=5, description="返回候选数量", ge=1, le=50)
     filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields, e.g. 'level >= 2 and code like \"E11%\"'")
+    filter_mode: str = Field(default="view", description="how the filter is applied: 'view' (a cached view of the selected rows) or 'mask' (a row mask tested inside the scan: no second index)")
     group_by_field: Optional[str] = Field(default=None, description="Milvus grouping search: a scalar field, or 'category'; the search then ranks groups (2 * top_k * group_size <= 128)")
     group_size: int = Field(default=1, description="rows returned per group (with group_by_field)", ge=1, le=128)
     radius: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is ABOVE this are ranked")

@@ -41,6 +41,7 @@ struct ExactArgs {
     float *part_scores;    // [slot][P][KP]
     int *part_rows;        // [slot][P][KP]
     const BandQ *band;     // BAND = true only: [query] the band every hit of the query lies in (topk_select.hpp)
+    RowMasks mask;         // MASK = true only: [query] the bitset of the rows that may be hits (topk_select.hpp)
 };
 
 // chunk count of the adaptive layout (device: exact_topk_kernel; the same call in finalize.hpp)
@@ -77,13 +78,19 @@ __host__ __device__ inline int exact_adaptive_chunks(int nq_active, int bmq, int
 // (-inf passes no threshold). The floor seeds the list threshold (strict: thr_row = 0), which is a true lower bound of every
 // hit and spares a chunk's first tiles their compactions. Lists are plain KP >= k lists: no thr0, no narrow certificate -
 // both reason about the top of the WHOLE ranking. BAND = false compiles to what it compiled to before the parameter existed.
-template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false>
+// MASK (with BAND): the query's row mask is one more term of that overwrite. The lane keeps its query's
+// bitset pointer, loaded once where the band is; per tile it loads the tile's four words (one aligned 16-byte load, issued
+// behind the MFMA loop: nothing is held across it) and uses the 16 bits 4 h + (r & 3) + 8 (r >> 2) of word t. Masked-out
+// rows are -inf in front of the bootstrap like rows outside the band, so its count is a count of masked-in rows.
+// MASK = false compiles to what it compiled to before the parameter existed.
+template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false, bool MASK = false>
 __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
     constexpr int BMQ = NW * 32, BN = 128, LDT = BK + 1, NT = NW * 64;
     constexpr int CAP = CAPV, LIMIT = CAP - GROUP;
     static_assert(GROUP == 32 || GROUP == 16, "a whole 32-row block or half of one per overflow check");
     static_assert(CAP <= 64 * E && LIMIT >= KP && CAP % 2 == 0, "candidate buffer: KP kept + GROUP appended per check, E keys per lane");
     static_assert(BK == 16 || BK == 32, "stage depth");
+    static_assert(BAND || !MASK, "a row mask rides on the band's overwrite");
     constexpr int C4 = BK / 4;             // float4 per corpus row and stage
     constexpr int CL = (BN * C4) / NT;     // corpus float4 loads per thread per stage
     constexpr int QH = BK / 2;             // floats of a query a lane holds per stage = k-step pairs per stage
@@ -143,6 +150,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
     const float *qsrc;
     float band_hi = INFINITY;
     u64 band_below = ~0ull;
+    const uint32_t *mask_words = nullptr;
     {
         const int sq = min(my_slot, nq - 1);
         const int gq = a.qlist ? a.qlist[sq] : sq;
@@ -156,6 +164,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
             band_hi = b.hi; band_below = b.below;
             if (my_valid && b.lo > st.thr) st.thr = b.lo;   // (thr_row stays 0: a row AT the floor is out)
         }
+        if constexpr (MASK) mask_words = a.mask[gq];
     }
     float bq[QH];   // the stage's k-step pairs of the query operand: bq[s] = (k = 2 s | 2 s + 1)
     auto q_pairs = [&](const float4 (&qreg)[Q4]) {
@@ -246,12 +255,19 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
         const bool partial = tile_row0 + BN > row_end;
         if constexpr (BAND) {
             // (keys carry the LOCAL row of the strided form; the band path runs contiguous chunks: local = global)
+            uint32_t mw[4] = {~0u, ~0u, ~0u, ~0u};   // word t of the tile's mask, shifted so that bit (r & 3) + 8 (r >> 2) is register r's row
+            if constexpr (MASK) {
+                const uint4 m4 = *reinterpret_cast<const uint4 *>(mask_words + (tile_row0 >> 5));   // (tile_row0 is a multiple of 128)
+                mw[0] = m4.x >> (4 * h); mw[1] = m4.y >> (4 * h); mw[2] = m4.z >> (4 * h); mw[3] = m4.w >> (4 * h);
+            }
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const uint32_t row = (uint32_t)(tile_row0 + t * 32 + 4 * h + (r & 3) + 8 * (r >> 2));
-                    acc[t][r] = band_under(acc[t][r], row, band_hi, band_below) ? acc[t][r] : -INFINITY;
+                    bool in = band_under(acc[t][r], row, band_hi, band_below);
+                    if constexpr (MASK) in = in & (((mw[t] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0u);
+                    acc[t][r] = in ? acc[t][r] : -INFINITY;
                 }
         }
         if (KP <= 32 && tile_row0 == row_begin && !partial) {

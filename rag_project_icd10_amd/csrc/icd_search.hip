@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -225,6 +226,13 @@ struct icd_index {
     BandQ *band_dev = nullptr, *h_band = nullptr;   // [max_nq] each
     std::vector<long long> h_row_map;   // a view: the host's copy of row_map (the cursor's id -> first local row behind it)
     int band_pending = 0;               // host-packed bands of the current call not yet copied to band_dev
+    // masked search (icd_index_search_masked): [query] -> bitset, filled on the host into the pinned table and copied to the
+    // device one per call; mask_ones = the all-ones bitset (rows [0, n)) an unmasked query of a masked batch reads
+    const uint32_t **mask_dev = nullptr, **h_mask = nullptr;   // [max_nq] each
+    uint32_t *mask_ones = nullptr;
+    hipEvent_t ev_mask = nullptr;       // recorded behind the table's copy: the next masked call waits for it before it refills the
+    bool mask_copy_pending = false;     // pinned table - whatever became of the call in between (an error return included)
+    unsigned long long uid = 0;         // identity of this index among all ever created in the process (a row mask remembers it)
     unsigned long long *dbg = nullptr;  // diagnostic cycle counters [8192][4][4]
     unsigned int *pace = nullptr;       // [PACE_WORDS] arrival counters of the paced coarse sweep (coarse_flat_kernel.hpp, 67108864)
 };
@@ -256,6 +264,9 @@ void free_all(icd_index *x) {
     hipFree(x->row_map);
     hipFree(x->band_dev);
     if (x->h_band) hipHostFree(x->h_band);
+    hipFree(x->mask_dev); hipFree(x->mask_ones);
+    if (x->h_mask) hipHostFree(x->h_mask);
+    if (x->ev_mask) hipEventDestroy(x->ev_mask);
     if (x->h_nflag) hipHostFree(x->h_nflag);
     if (x->h_pin) hipHostFree(x->h_pin);
     if (x->ev_nflag) hipEventDestroy(x->ev_nflag);
@@ -301,9 +312,9 @@ int pick_chunks(int mtiles, int row_tiles, int pmax, int slots) {
     return std::max(1, p);
 }
 
-template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false>
+template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false, bool MASK = false>
 int launch_exact(icd_index *x, const ExactArgs &a, int mtiles, hipStream_t s) {
-    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP, BAND>;
+    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP, BAND, MASK>;
     const size_t lds = exact_lds_bytes<KP, E, NW, CAPV, BK>();
     HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(mtiles * a.P), dim3(NW * 64), lds, s, a));
     return ICD_OK;
@@ -330,9 +341,9 @@ inline bool stream_fits(int kp, int qb, int dim) {
     return (size_t)qb * dim * 4 + (size_t)4 * 2 * ST_STAGE_BYTES + (size_t)4 * qb * 64 * e * 8 <= (size_t)LDS_LIMIT;
 }
 
-template <int KP, int E, int QB, bool BAND = false>
+template <int KP, int E, int QB, bool BAND = false, bool MASK = false>
 int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq_ptr, int nq, int max_active,
-                  int p_out, int *p_used, hipStream_t s, const float *thr0 = nullptr, const BandQ *band = nullptr) {
+                  int p_out, int *p_used, hipStream_t s, const float *thr0 = nullptr, const BandQ *band = nullptr, RowMasks mask = nullptr) {
     const int n = (int)x->n;
     const int per_max = FIN_MAX_CAND / KP;                       // lists one reduce wave can merge
     const int p_cap = FIN_MAX_CAND / KP;                         // lists finalize<false> can merge
@@ -347,7 +358,7 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
     StreamArgs a{};
     a.corpus = x->corpus; a.queries = dq; a.qlist = qlist; a.nq_ptr = nq_ptr; a.nq = std::min(nq, max_active);
     a.max_active = max_active; a.n = n; a.dim = x->dim; a.rows_per_wg = rows_per_wg; a.nwg = nwg;
-    a.list_scores = x->lists_s; a.list_rows = x->lists_r; a.thr0 = thr0; a.band.q = band;
+    a.list_scores = x->lists_s; a.list_rows = x->lists_r; a.thr0 = thr0; a.band.q = band; a.mask = mask;
     // wave-private LDS ring: as many 8-KB stages per wave as fit next to the queries and candidate buffers
     int stages = 4;
     while (stages > 2 && stream_lds_bytes<KP, E, QB>(x->dim, stages) > (size_t)LDS_LIMIT) --stages;
@@ -357,7 +368,7 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
         const size_t cap = (l % 2 == 0) ? x->partx_cap + (size_t)128 * FIN_MAX_CAND_X : x->lists_cap;
         if ((size_t)a.nq * plan[l] * KP > cap) return fail(ICD_ERR_INVALID, "stream workspace too small for reduction level %d", l);
     }
-    constexpr auto kern = stream_topk_kernel<KP, E, QB, false, BAND>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, false, BAND, MASK>;
     const size_t lds = stream_lds_bytes<KP, E, QB>(x->dim, stages);
     if (lds > (size_t)LDS_LIMIT) return fail(ICD_ERR_INVALID, "stream kernel: dim=%d does not fit LDS with %d queries per pass", x->dim, QB);
     HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(nwg), dim3(256), lds, s, a));
@@ -391,9 +402,9 @@ inline bool plan_stream_one(int n, int dim, int num_cu, int qb, int cap_entries,
     return p->nwg >= 1 && p->nwg <= 256 && p->stages >= 2;
 }
 
-template <int KP, int E, int QB, bool BAND = false>
+template <int KP, int E, int QB, bool BAND = false, bool MASK = false>
 int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, hipStream_t s, const float *host_q = nullptr, bool poll_done = false,
-                      const BandArgs *band = nullptr) {
+                      const BandArgs *band = nullptr, RowMasks mask = nullptr) {
     StreamOnePlan pl;
     if (!plan_stream_one((int)x->n, x->dim, x->num_cu, QB, 64 * E, &pl)) return fail(ICD_ERR_INVALID, "single-launch stream kernel: no plan for n=%lld dim=%d", (long long)x->n, x->dim);
     if ((size_t)nq * pl.nwg * KP * 2 > x->lists_cap) return fail(ICD_ERR_INVALID, "stream workspace too small");
@@ -406,6 +417,7 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
     a.fin = f;
     a.fin.counters = x->nflag; a.fin.host_counters = x->h_nflag_dev;
     if (band) a.band = *band;
+    a.mask = mask;
     if (poll_done) {
         a.done = reinterpret_cast<u64 *>(x->h_pin_dev + PIN_Q_BYTES + PIN_OUT_BYTES);
         a.done_value = ++x->done_seq;
@@ -414,10 +426,10 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
     // (at least 84 KB: ONE work-group per CU whatever the corpus size - the fence-free sc1 hand-off of the kernel's tail is the
     //  form measured for one work-group per CU, MI355X_MICROARCH.md visibility table)
     const size_t lds = std::max<size_t>(stream_one_lds_bytes<KP, E, QB>(x->dim, pl.stages, pl.rps), (size_t)84 * 1024);
-    constexpr auto kern = stream_topk_kernel<KP, E, QB, true, BAND>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, true, BAND, MASK>;
     if constexpr (QB == 1) {
         if (host_q) {   // the vector in the kernel arguments: no copy command in front of the launch
-            constexpr auto kern_in = stream_one_inline_kernel<KP, E, BAND>;
+            constexpr auto kern_in = stream_one_inline_kernel<KP, E, BAND, MASK>;
             StreamInlineQuery iq;
             memcpy(iq.v, host_q, (size_t)x->dim * sizeof(float));
             a.queries = nullptr;
@@ -574,11 +586,12 @@ struct SearchCtx {
     int sparse_max;      // how many flagged queries still go to the streaming kernel
     bool stream_ok;      // small batches (the reference's one-query-per-call shape): stream the corpus once, exact, no coarse pass
     const BandArgs *band;   // range search: the queries' bands (nullptr: none, and no band kernel runs)
+    RowMasks mask;          // masked search (with band): [query] -> bitset in device memory (nullptr: none, and no mask kernel runs)
 };
 
-SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s, const BandArgs *band) {
+SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s, const BandArgs *band, RowMasks mask) {
     SearchCtx c{};
-    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast; c.band = band;
+    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast; c.band = band; c.mask = mask;
     c.ov = search_overrides();
     c.row_tiles = (int)((x->n + 127) / 128);
     FinArgs &f = c.f;
@@ -615,11 +628,18 @@ int run_stream(const SearchCtx &c, const int *qlist, const int *nq_ptr, int nqs,
     int qb = nq_ptr ? 8 : (nqs <= 1 ? 1 : (nqs <= 2 ? 2 : (nqs <= 4 ? 4 : 8)));
     const int max_act = nq_ptr ? c.sparse_max : std::max(c.sparse_max, nqs);   // (a direct call - up to ST_MAX_ACTIVE queries - is not gated)
     while (qb > 1 && !stream_fits(c.kpx, qb, x->dim)) qb >>= 1;
-#define ICD_ST(KPV, EV, BANDV, BQ) \
-    (qb == 1 ? launch_stream<KPV, EV, 1, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ) : \
-     qb == 2 ? launch_stream<KPV, EV, 2, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ) : \
-     qb == 4 ? launch_stream<KPV, EV, 4, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ) : \
-               launch_stream<KPV, EV, 8, BANDV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ))
+#define ICD_ST_M(KPV, EV, BANDV, BQ, MASKV, MQ) \
+    (qb == 1 ? launch_stream<KPV, EV, 1, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ) : \
+     qb == 2 ? launch_stream<KPV, EV, 2, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ) : \
+     qb == 4 ? launch_stream<KPV, EV, 4, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ) : \
+               launch_stream<KPV, EV, 8, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ))
+#define ICD_ST(KPV, EV, BANDV, BQ) ICD_ST_M(KPV, EV, BANDV, BQ, false, nullptr)
+    if (c.band && c.mask) {   // (masked search: the band instantiations with the row-mask term)
+        if (c.kpx == 16) return ICD_ST_M(16, 2, true, c.band->q, true, c.mask);
+        if (c.kpx == 32) return ICD_ST_M(32, 2, true, c.band->q, true, c.mask);
+        if (c.kpx == 64) return ICD_ST_M(64, 3, true, c.band->q, true, c.mask);
+        return ICD_ST_M(128, 4, true, c.band->q, true, c.mask);
+    }
     if (c.band) {   // (range search: the same sweep, band instantiations)
         if (c.kpx == 16) return ICD_ST(16, 2, true, c.band->q);
         if (c.kpx == 32) return ICD_ST(32, 2, true, c.band->q);
@@ -631,6 +651,7 @@ int run_stream(const SearchCtx &c, const int *qlist, const int *nq_ptr, int nqs,
     if (c.kpx == 64) return ICD_ST(64, 3, false, nullptr);
     return ICD_ST(128, 4, false, nullptr);
 #undef ICD_ST
+#undef ICD_ST_M
 }
 
 // A chunk count the exact kernel's list workspace holds for EVERY query of the batch (all of them may be flagged: all-zero
@@ -685,7 +706,14 @@ int run_exact(const SearchCtx &c, const int *qlist, const int *nq_ptr, int px, b
         // (LDS: k <= 16 two work-groups per CU - 17 KB of stage + 60-entry buffers; k <= 64 one of four waves - 34 KB +
         //  112-entry buffers; larger k two waves. Eight waves on 64-entry buffers at k <= 32 - two per SIMD - were built and
         //  are slower, 9.2 against 7.2 ms per 10 000 queries: a 64-entry buffer with 32 kept is compacted after every append)
-        if (c.band) {   // (range search: the same four configurations, band instantiations)
+        if (c.band && c.mask) {   // (masked search: the band instantiations with the row-mask term)
+            a.band = c.band->q; a.mask = c.mask;
+            if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2, 32, true, true>(x, a, c.mtx, s);
+            else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16, true, true>(x, a, c.mtx, s);
+            else if (kpx == 64) rc = launch_exact<64, 2, 4, 112, 32, 1, 32, true, true>(x, a, c.mtx, s);
+            else rc = launch_exact<128, 3, 2, 192, 32, 1, 32, true, true>(x, a, c.mtx, s);
+        }
+        else if (c.band) {   // (range search: the same four configurations, band instantiations)
             a.band = c.band->q;
             if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2, 32, true>(x, a, c.mtx, s);
             else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16, true>(x, a, c.mtx, s);
@@ -758,6 +786,14 @@ int search_tiny(const SearchCtx &c) {
         if (c.band) {   // a page of a range search: still ONE launch (host-packed bands travel in the arguments)
             BandArgs b = *c.band;
             if (x->band_pending > 0) { b.q = nullptr; x->band_pending = 0; }
+            if (c.mask) {   // (the pointer table is in device memory already: search_common copied it)
+                const int rcm = qb1 == 1 ? launch_stream_one<16, 2, 1, true, true>(x, c.dq, 1, c.f, s, hq, poll, &b, c.mask)
+                              : qb1 == 2 ? launch_stream_one<16, 2, 2, true, true>(x, c.dq, 2, c.f, s, nullptr, false, &b, c.mask)
+                                         : launch_stream_one<16, 2, 4, true, true>(x, c.dq, (int)nq, c.f, s, nullptr, false, &b, c.mask);
+                rec(x, 4, s);
+                rec(x, 5, s);
+                return rcm;
+            }
             const int rcb = qb1 == 1 ? launch_stream_one<16, 2, 1, true>(x, c.dq, 1, c.f, s, hq, poll, &b)
                           : qb1 == 2 ? launch_stream_one<16, 2, 2, true>(x, c.dq, 2, c.f, s, nullptr, false, &b)
                                      : launch_stream_one<16, 2, 4, true>(x, c.dq, (int)nq, c.f, s, nullptr, false, &b);
@@ -1112,7 +1148,8 @@ int search_auto(const SearchCtx &c) {
 // Enqueue a search whose queries and outputs are device pointers.
 // band: a range search (icd_index_search_range; mode EXACT) - the streaming forms up to ST_MAX_ACTIVE queries, plain lists of
 // KP >= k on the MFMA kernel above; nullptr for every other caller, and no band kernel runs.
-int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s, const BandArgs *band = nullptr) {
+// mask (with band): a masked search (icd_index_search_masked) - the same dispatch, the instantiations with the row-mask term.
+int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s, const BandArgs *band = nullptr, RowMasks mask = nullptr) {
     const bool use_fast = !band && (mode == ICD_MODE_AUTO) && x->fast && k <= FAST_MAX_K && (x->dim == 768 || x->dim == 1024);
     x->prof_now = !x->capturing && x->profiling && (x->prof_tick++ % x->prof_every == 0);
     if (x->prof_now) {
@@ -1127,7 +1164,7 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
     x->last_p2 = 0;
     x->last_mode = use_fast ? ICD_MODE_AUTO : ICD_MODE_EXACT;
     rec(x, 0, s);
-    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s, band);
+    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s, band, mask);
     // (k > 16 needs the 64-entry lists of the streaming kernel, ~0.9 ms per 16 queries: the coarse pass is faster there)
     if (c.stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE)) return search_tiny(c);
     { const int rcq = stage_host_query(c); if (rcq) return rcq; }
@@ -1182,6 +1219,7 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
     icd_index *x = new (std::nothrow) icd_index();
     if (!x) return fail(ICD_ERR_NOMEM, "host allocation failed");
     x->device = device; x->n = n; x->id_base = id_base; x->dim = dim;
+    { static std::atomic<unsigned long long> next_uid{0}; x->uid = ++next_uid; }
     x->opt_permute = !(flags & ICD_CREATE_ROW_ORDER); x->opt_probe = !(flags & ICD_CREATE_NO_PROBE); x->opt_center = !(flags & ICD_CREATE_NO_CENTER);
     x->n_pad = (int)(((n + 127) / 128 + FLAT_SPARE_TILES) * 128);   // (zero tiles behind the fp16 image: plan_flat_tiles)
     x->max_nq = max_nq; x->max_nq_pad = ((max_nq + 127) / 128) * 128; x->max_k = max_k;
@@ -1321,6 +1359,16 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
     memset(x->h_pin + PIN_Q_BYTES + PIN_OUT_BYTES, 0, PIN_DONE_BYTES);   // (the completion word: sequence numbers start at 1)
     CR_TRY(wsalloc(&x->band_dev, (size_t)max_nq));
     CR_TRY(hipHostMalloc(reinterpret_cast<void **>(&x->h_band), (size_t)max_nq * sizeof(BandQ), hipHostMallocDefault));
+    if (!view_map) {   // (row masks are the parent's alternative to a view: a view has none)
+        CR_TRY(wsalloc(&x->mask_dev, (size_t)max_nq));
+        CR_TRY(hipHostMalloc(reinterpret_cast<void **>(&x->h_mask), (size_t)max_nq * sizeof(uint32_t *), hipHostMallocDefault));
+        CR_TRY(hipEventCreateWithFlags(&x->ev_mask, hipEventDisableTiming));
+        const size_t mw = (size_t)rowmask_tile_words(n) + ROWMASK_TAIL_WORDS;
+        std::vector<uint32_t> ones(mw, 0u);
+        for (int64_t r = 0; r < n; r += 32) ones[(size_t)(r >> 5)] = n - r >= 32 ? ~0u : ((1u << (n - r)) - 1u);
+        CR_TRY(wsalloc(&x->mask_ones, mw));
+        CR_TRY(hipMemcpy(x->mask_ones, ones.data(), mw * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
     CR_TRY(wsalloc(&x->pace, PACE_WORDS));
     CR_TRY(wsalloc(&x->dbg, (size_t)8192 * 16));
     CR_TRY(hipMemset(x->dbg, 0, (size_t)8192 * 16 * 8));
@@ -1373,6 +1421,20 @@ struct RangeBounds {
     bool on_device;
 };
 static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s, BandArgs *out);
+
+// ---- row masks (icd_rowmask_create) ---------------------------------------------------------------------
+// A mask belongs to the index it was created for but keeps no pointer into it: handle and identity are compared, never followed.
+struct icd_rowmask {
+    uint32_t magic = 0x1CD3A5C1u;
+    const icd_index *owner = nullptr;
+    unsigned long long owner_uid = 0;
+    int device = 0;
+    int64_t n = 0, rows = 0;
+    uint32_t *bits = nullptr;   // [rowmask_tile_words(n) + ROWMASK_TAIL_WORDS]
+    size_t bytes = 0;
+};
+static bool valid_rowmask(const icd_rowmask *m) { return m && m->magic == 0x1CD3A5C1u; }
+static int stage_masks(icd_index *x, icd_rowmask *const *masks, int nq, hipStream_t s);
 
 extern "C" {
 
@@ -1435,7 +1497,8 @@ static void copy_pinned_out(icd_index *x, const Outs &user, size_t no_small) {
 }
 
 static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t k, int32_t q_on_device,
-                         int32_t mode, Outs user, int32_t out_on_device, void *stream, const RangeBounds *range = nullptr) {
+                         int32_t mode, Outs user, int32_t out_on_device, void *stream, const RangeBounds *range = nullptr,
+                         icd_rowmask *const *masks = nullptr) {
     if (!valid(x)) return fail(ICD_ERR_STATE, "invalid handle");
     std::lock_guard<std::mutex> guard(x->mu);
     if (nq < 0 || nq > x->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds max_nq=%d", (long long)nq, x->max_nq);
@@ -1450,7 +1513,9 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
         x->capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
         if (x->capturing && (!q_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
         if (x->capturing && range && !range->on_device) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
+        if (x->capturing && masks) return fail(ICD_ERR_INVALID, "a masked search stages its mask table on the host at call time: it cannot be captured into a graph");
     }
+    if (masks) { const int rcm = stage_masks(x, masks, (int)nq, s); if (rcm) return rcm; }
     BandArgs band{};
     x->band_pending = 0;
     if (range) { const int rcb = pack_bands(x, *range, (int)nq, s, &band); if (rcb) return rcb; }
@@ -1491,7 +1556,7 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
     }
     x->done_armed = false;
     x->host_one_call = !q_on_device && nq == 1 && pinned_out && !x->capturing;
-    int rc = search_device(x, dq, (int)nq, k, mode, dev, s, range ? &band : nullptr);
+    int rc = search_device(x, dq, (int)nq, k, mode, dev, s, range ? &band : nullptr, masks ? x->mask_dev : nullptr);
     x->band_pending = 0;
     x->host_q = nullptr;
     x->host_one_call = false;
@@ -1530,7 +1595,7 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
         if (user.adj_lv) HIP_TRY(hipMemcpyAsync(user.adj_lv, dev.adj_lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
         else if (user.lv) HIP_TRY(hipMemcpyAsync(user.lv, dev.lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
     }
-    if (!out_on_device || !q_on_device || host_bands) HIP_TRY(hipStreamSynchronize(s));   // (host bounds went through the pinned block)
+    if (!out_on_device || !q_on_device || host_bands) HIP_TRY(hipStreamSynchronize(s));   // (host bounds went through the pinned block; the mask table's block is guarded by its own event, stage_masks)
     return ICD_OK;
 }
 
@@ -1563,6 +1628,25 @@ __global__ void band_pack_kernel(const float *radius, const float *range_filter,
         b.below = as != as ? 0ull : band_below(order_f32(as), (uint32_t)cut);
     }
     out[q] = b;
+}
+
+// the [query] -> bitset table of a masked search: filled in the pinned block under the handle's mutex, one copy per call. An
+// event recorded right behind the copy guards the block: the next masked call waits for it before it refills the block, so
+// neither a device-in / device-out call (which only enqueues) nor an error return further down leaves a copy reading a block
+// that is being rewritten.
+static int stage_masks(icd_index *x, icd_rowmask *const *masks, int nq, hipStream_t s) {
+    if (!x->mask_dev) return fail(ICD_ERR_UNSUPPORTED, "a masked search on a view is not supported: mask the parent");
+    if (x->mask_copy_pending) { HIP_TRY(hipEventSynchronize(x->ev_mask)); x->mask_copy_pending = false; }
+    for (int q = 0; q < nq; ++q) x->h_mask[q] = masks[q] ? masks[q]->bits : x->mask_ones;
+    const hipError_t ec = hipMemcpyAsync(x->mask_dev, x->h_mask, (size_t)nq * sizeof(uint32_t *), hipMemcpyHostToDevice, s);
+    const hipError_t ee = hipEventRecord(x->ev_mask, s);   // (also behind a copy that failed to enqueue: whatever did get queued is covered)
+    x->mask_copy_pending = ee == hipSuccess;
+    if (ec != hipSuccess || ee != hipSuccess) {
+        hipStreamSynchronize(s);
+        x->mask_copy_pending = false;
+        return fail(ICD_ERR_HIP, "mask table: %s", hipGetErrorString(ec != hipSuccess ? ec : ee));
+    }
+    return ICD_OK;
 }
 
 static uint32_t host_order_f32(float v) {
@@ -1629,6 +1713,138 @@ int icd_index_search_range(icd_index *idx, const float *queries, int64_t nq, int
     }
     RangeBounds rb{radius, range_filter, after_scores, reinterpret_cast<const long long *>(after_ids), bounds_on_device != 0};
     return search_common(idx, queries, nq, k, queries_on_device, ICD_MODE_EXACT, o, out_on_device, stream, &rb);
+}
+
+// ---- row masks --------------------------------------------------------------------------------------------------------------
+// A row list that already sits on the device -> bitset: one memset in front, then one vector atomicOr per row. The list is
+// checked here as well (inside [0, n), strictly increasing): a bad entry sets *err and writes nothing.
+__global__ void rowmask_build_kernel(const long long *rows, long long n_rows, long long n, uint32_t *bits, int *err) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const long long r = rows[i];
+    if (r < 0 || r >= n || (i > 0 && rows[i - 1] >= r)) { atomicOr(err, 1); return; }
+    atomicOr(bits + (r >> 5), 1u << (r & 31));
+}
+
+int icd_rowmask_pack(const int64_t *rows, int64_t n_rows, int64_t n, uint32_t *out_words, int64_t out_count) {
+    if (n <= 0 || n_rows < 0 || (n_rows > 0 && !rows) || !out_words) return fail(ICD_ERR_INVALID, "rows / out_words NULL, n=%lld or n_rows=%lld", (long long)n, (long long)n_rows);
+    if (out_count < rowmask_tile_words(n)) return fail(ICD_ERR_INVALID, "out_count=%lld: %lld rows need %lld words", (long long)out_count, (long long)n, rowmask_tile_words(n));
+    for (int64_t i = 0; i < n_rows; ++i) {   // (checked before anything is written)
+        if (rows[i] < 0 || rows[i] >= n) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld outside the index's [0, %lld)", (long long)i, (long long)rows[i], (long long)n);
+        if (i > 0 && rows[i] <= rows[i - 1]) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld: row ids must be strictly increasing", (long long)i, (long long)rows[i]);
+    }
+    memset(out_words, 0, (size_t)out_count * sizeof(uint32_t));
+    for (int64_t i = 0; i < n_rows; ++i) out_words[rows[i] >> 5] |= 1u << (rows[i] & 31);
+    return ICD_OK;
+}
+
+int icd_rowmask_create(icd_index *idx, const int64_t *rows, int64_t n_rows, int32_t rows_on_device, icd_rowmask **out) {
+    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(ICD_ERR_INVALID, "rows NULL or n_rows=%lld", (long long)n_rows);
+    if (n_rows > idx->n) return fail(ICD_ERR_INVALID, "n_rows=%lld exceeds the index's %lld rows", (long long)n_rows, (long long)idx->n);
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "row masks on a view are not supported: mask the parent");
+    HIP_TRY(hipSetDevice(idx->device));
+    const size_t words = (size_t)rowmask_tile_words(idx->n) + ROWMASK_TAIL_WORDS;
+    std::vector<uint32_t> packed;
+    if (!rows_on_device) {   // a host list: checked and packed here, one upload
+        packed.resize(words);
+        const int rcp = icd_rowmask_pack(rows, n_rows, idx->n, packed.data(), (int64_t)words);
+        if (rcp) return rcp;
+    }
+    icd_rowmask *m = new (std::nothrow) icd_rowmask();
+    if (!m) return fail(ICD_ERR_NOMEM, "host allocation failed");
+    m->owner = idx; m->owner_uid = idx->uid; m->device = idx->device; m->n = idx->n; m->rows = n_rows; m->bytes = words * sizeof(uint32_t);
+    int *derr = nullptr;
+    int herr = 0;
+    hipError_t e = dmalloc(&m->bits, words);
+    if (e == hipSuccess && !rows_on_device) e = hipMemcpy(m->bits, packed.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && rows_on_device) {
+        e = hipMemset(m->bits, 0, words * sizeof(uint32_t));
+        if (e == hipSuccess && n_rows > 0) {
+            e = dmalloc(&derr, 1);
+            if (e == hipSuccess) e = hipMemset(derr, 0, sizeof(int));
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(rowmask_build_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, 0,
+                                   reinterpret_cast<const long long *>(rows), (long long)n_rows, (long long)idx->n, m->bits, derr);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpy(&herr, derr, sizeof(int), hipMemcpyDeviceToHost);
+            hipFree(derr);
+        }
+    }
+    if (e != hipSuccess || herr) {
+        hipFree(m->bits);
+        m->magic = 0;
+        delete m;
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "row mask: %s", hipGetErrorString(e));
+        return fail(ICD_ERR_INVALID, "rows: row ids must be strictly increasing and inside the index's [0, %lld)", (long long)idx->n);
+    }
+    *out = m;
+    return ICD_OK;
+}
+
+int icd_rowmask_destroy(icd_rowmask *m) {
+    if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "invalid row mask handle");
+    hipSetDevice(m->device);
+    hipDeviceSynchronize();
+    hipFree(m->bits);
+    m->magic = 0;
+    delete m;
+    return ICD_OK;
+}
+
+int icd_rowmask_stats(icd_rowmask *m, int64_t *out_rows, int64_t *out_bytes) {
+    if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "invalid row mask handle");
+    if (out_rows) *out_rows = m->rows;
+    if (out_bytes) *out_bytes = (int64_t)m->bytes;
+    return ICD_OK;
+}
+
+int icd_index_search_masked(icd_index *idx, icd_rowmask *const *masks, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
+                            const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
+                            int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                            int32_t *out_levels, int32_t out_on_device, void *stream) {
+    if (!masks)   // (no table at all: the range search, which the all-NULL table equals bit for bit)
+        return icd_index_search_range(idx, queries, nq, k, queries_on_device, radius, range_filter, after_scores, after_ids, bounds_on_device,
+                                      reweighted, out_adj, out_raw, out_ids, out_levels, out_on_device, stream);
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a masked search on a view is not supported: mask the parent");
+    if (nq < 0 || nq > idx->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds max_nq=%d", (long long)nq, idx->max_nq);
+    bool any = false;
+    for (int64_t q = 0; q < nq; ++q) {
+        const icd_rowmask *m = masks[q];
+        if (!m) continue;
+        any = true;
+        if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "masks[%lld]: invalid row mask handle", (long long)q);
+        if (m->owner != idx || m->owner_uid != idx->uid || m->n != idx->n || m->device != idx->device)
+            return fail(ICD_ERR_INVALID, "masks[%lld] was created for another index", (long long)q);
+    }
+    if (!any)
+        return icd_index_search_range(idx, queries, nq, k, queries_on_device, radius, range_filter, after_scores, after_ids, bounds_on_device,
+                                      reweighted, out_adj, out_raw, out_ids, out_levels, out_on_device, stream);
+    // (from here on: icd_index_search_range's checks and call, with the mask table)
+    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a masked search returns 1 .. %d hits per query", k, ICD_MAX_K);
+    if ((after_scores == nullptr) != (after_ids == nullptr)) return fail(ICD_ERR_INVALID, "after_scores and after_ids: both or neither (a cursor is a hit's score AND id)");
+    if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (!bounds_on_device) {
+        for (int64_t q = 0; q < nq; ++q) {
+            if (radius && std::isnan(radius[q])) return fail(ICD_ERR_INVALID, "radius[%lld] is NaN", (long long)q);
+            if (range_filter && std::isnan(range_filter[q])) return fail(ICD_ERR_INVALID, "range_filter[%lld] is NaN", (long long)q);
+            if (after_scores && std::isnan(after_scores[q])) return fail(ICD_ERR_INVALID, "after_scores[%lld] is NaN", (long long)q);
+            if (radius && range_filter && !(radius[q] < range_filter[q]))
+                return fail(ICD_ERR_INVALID, "query %lld: radius=%g must be below range_filter=%g (hits have radius < score <= range_filter)", (long long)q, (double)radius[q], (double)range_filter[q]);
+        }
+    }
+    Outs o{};
+    if (reweighted) {
+        o.adj = out_adj; o.adj_raw = out_raw; o.adj_ids = reinterpret_cast<long long *>(out_ids); o.adj_lv = out_levels;
+    } else {
+        o.scores = out_raw; o.ids = reinterpret_cast<long long *>(out_ids); o.lv = out_levels;
+    }
+    RangeBounds rb{radius, range_filter, after_scores, reinterpret_cast<const long long *>(after_ids), bounds_on_device != 0};
+    return search_common(idx, queries, nq, k, queries_on_device, ICD_MODE_EXACT, o, out_on_device, stream, &rb, masks);
 }
 
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,

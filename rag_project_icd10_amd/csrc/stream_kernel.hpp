@@ -71,6 +71,8 @@ struct StreamArgs {
     u64 done_value;
     // BAND = true only (range search): the band every hit of a query lies in
     BandArgs band;
+    // MASK = true only: [query index] the bitset of the rows that may be hits
+    RowMasks mask;
 };
 
 // ONE query handed over IN the kernel arguments (a host caller's call: no H2D copy command in front of the launch). The
@@ -149,10 +151,14 @@ __device__ __forceinline__ void wait_vmcnt_uniform(int n) {
 // BAND: only rows inside the query's band (topk_select.hpp, BandQ) are hits. The band of a pass's queries is wave-uniform
 // (scalar registers); the floor seeds the list threshold - strict, thr_row = 0 - and the ceiling and the cursor are two more
 // compares where a row is tested. Everything behind the select (lists, merges, emit_outputs' padding) is unchanged.
-template <int KP, int E, int QB, bool ONE, bool BAND = false>
+// MASK (with BAND): the bitset pointers of a pass's queries are wave-uniform like the band; the 64 bits of
+// a step's rows are read per query at the head of the step (scalar loads: the vmcnt accounting of the LDS-DMA ring sees none
+// of them) and a row's bit is one more term of `pass`.
+template <int KP, int E, int QB, bool ONE, bool BAND = false, bool MASK = false>
 __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const float *qsrc) {
     constexpr int CAP = 64 * E;
     static_assert(!ONE || (QB <= 4 && KP <= 16), "the single-launch form serves up to four queries at k <= 16");
+    static_assert(BAND || !MASK, "a row mask rides on the band's test");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (the gate looks at the device's count itself: a.nq is already clamped to max_active by the host, and a list longer
     //  than that belongs to the MFMA kernel alone - round 3: the clamped count used to pass the gate and cost 24 sweeps)
@@ -218,6 +224,17 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
                 if (b.lo > thr[qi]) thr[qi] = b.lo;   // (thr_row stays 0: a row AT the floor is out)
             }
         }
+        const uint32_t *mask_words[QB];
+        const int mask_tile_words = (int)rowmask_tile_words(a.n);
+        if constexpr (MASK) {
+#pragma unroll
+            for (int qi = 0; qi < QB; ++qi) {
+                const int slot = q0 + min(qi, nqp - 1);
+                const u64 p = (u64)a.mask[a.qlist ? a.qlist[slot] : slot];   // (the same word in every lane: made a scalar pair)
+                mask_words[qi] = reinterpret_cast<const uint32_t *>(((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(p >> 32)) << 32) |
+                                                                    (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)p));
+            }
+        }
 
         // stage cursor of the DMA stream: (step, slice) -> ring slot; runs D - 1 stages ahead of the reader.
         // Past the last stage it re-reads the last step (valid memory, never consumed).
@@ -242,6 +259,11 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
             float acc[QB];
 #pragma unroll
             for (int qi = 0; qi < QB; ++qi) acc[qi] = 0.0f;
+            u64 mask_bits[QB];   // bit `lane` = this lane's row of the step
+            if constexpr (MASK) {
+#pragma unroll
+                for (int qi = 0; qi < QB; ++qi) mask_bits[qi] = rowmask_bits64(mask_words[qi], r0, mask_tile_words);
+            }
             for (int s = 0; s < nsl; ++s) {
                 // stage (t, s) has landed when at most D - 2 younger stages are outstanding
                 if constexpr (ONE) wait_vmcnt_uniform((D - 2) * NP);
@@ -284,6 +306,7 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
                 const float v = acc[qi];
                 bool pass = rvalid && (v > thr[qi] || (v == thr[qi] && row < thr_row[qi])) && v != -INFINITY;
                 if constexpr (BAND) pass = pass & band_under(v, row, band_hi[qi], band_below[qi]);
+                if constexpr (MASK) pass = pass & (((mask_bits[qi] >> lane) & 1ull) != 0ull);
                 const u64 m = __ballot(pass);
                 if (m) {
                     u64 *qb = bufs + (size_t)qi * CAP;
@@ -511,14 +534,14 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
     }
 }
 
-template <int KP, int E, int QB, bool ONE = false, bool BAND = false>
+template <int KP, int E, int QB, bool ONE = false, bool BAND = false, bool MASK = false>
 __global__ __launch_bounds__(256) void stream_topk_kernel(StreamArgs a) {
-    stream_topk_body<KP, E, QB, ONE, BAND>(a, a.queries);
+    stream_topk_body<KP, E, QB, ONE, BAND, MASK>(a, a.queries);
 }
 // the single-launch form of ONE query whose vector arrives in the kernel arguments (StreamInlineQuery)
-template <int KP, int E, bool BAND = false>
+template <int KP, int E, bool BAND = false, bool MASK = false>
 __global__ __launch_bounds__(256) void stream_one_inline_kernel(StreamArgs a, StreamInlineQuery q) {
-    stream_topk_body<KP, E, 1, true, BAND>(a, q.v);
+    stream_topk_body<KP, E, 1, true, BAND, MASK>(a, q.v);
 }
 
 // One wave per (slot, output list g): merge lists g, g + P_out, g + 2 P_out, ... of the slot's nlists

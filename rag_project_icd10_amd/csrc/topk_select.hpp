@@ -58,6 +58,28 @@ struct BandArgs {
     BandQ inl[4];
 };
 
+// ---- row mask of one query (filtered search without a view: DESIGN.md section 12) -------------------------------------------
+// A device bitset over the index's rows: row r is bit r & 31 of word r >> 5. The words cover a whole number of 128-row tiles
+// (rowmask_tile_words: a tile's four words are ONE aligned 16-byte load, and the partial last tile reads zero bits, never past
+// the end) and ROWMASK_TAIL_WORDS zero words follow them: the streaming kernel reads the up to three words a wave's 64 rows
+// touch from any 8-row boundary. A launch gets [query index] -> bitset; an unmasked query of a masked batch points at the
+// index's own all-ones bitset instead of taking a branch.
+constexpr int ROWMASK_TAIL_WORDS = 4;
+__host__ __device__ inline long long rowmask_tile_words(long long n) { return (n + 127) / 128 * 4; }
+typedef const uint32_t *const *RowMasks;
+// the bitset read as CONSTANT memory (nothing writes it while a search runs): a wave-uniform address is then a scalar load
+typedef __attribute__((address_space(4))) const uint32_t rowmask_word;
+
+// The 64 bits of rows r0 .. r0 + 63 (bit i = row r0 + i), r0 wave-uniform and a multiple of 8. r0 at or past the end of the
+// index reads the last tile's words (in bounds; such rows are never valid).
+__device__ __forceinline__ u64 rowmask_bits64(const uint32_t *mask, int r0, int tile_words) {
+    rowmask_word *m = (rowmask_word *)(uintptr_t)mask;
+    const int wi = min(r0 >> 5, tile_words - 1), sh = r0 & 31;
+    const u64 lo = ((u64)m[wi + 1] << 32) | (u64)m[wi];
+    const u64 hi = (u64)m[wi + 2] << 32;
+    return (lo >> sh) | ((hi << (31 - sh)) << 1);   // (two steps: sh = 0 shifts the third word out altogether)
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 template <typename T>

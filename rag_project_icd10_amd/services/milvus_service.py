@@ -15,7 +15,9 @@ There is no CPU search path: without libicdsearch.so / an MI355X, loading the co
 
 Additive: `search_batch` (many queries per call, numpy or device tensors); a Milvus `filter` expression on `search` and
 `search_batch` (services/filter_expr.py): the selection's rows become a VIEW of the index (_native.IcdIndex.view, built on the
-device), cached per (normalised expression, store generation) with LRU eviction (`ICD_FILTER_VIEWS`, default 8).
+device), cached per (normalised expression, store generation) with LRU eviction (`ICD_FILTER_VIEWS`, default 8). With
+`filter_mode="mask"`, or a LIST of expressions (one per query of a `search_batch`), the selection becomes a ROW MASK instead
+(_native.IcdIndex.rowmask: a bitset of n / 8 bytes tested inside the scan, `ICD_FILTER_MASKS`, default 256).
 """
 from __future__ import annotations
 
@@ -54,6 +56,11 @@ class MilvusService:
         self._views: "OrderedDict[tuple, Any]" = OrderedDict()
         self._views_lock = threading.Lock()
         self._max_views = max(1, int(os.getenv("ICD_FILTER_VIEWS", "8")))
+        # masked search: (normalised expression, store generation) -> (the index it belongs to, IcdRowMask), least recently used
+        # first, under the same lock and dropped where the views are. An evicted mask is closed by its last reference (a batch
+        # in flight, an iterator).
+        self._masks: "OrderedDict[tuple, Any]" = OrderedDict()
+        self._max_masks = max(1, int(os.getenv("ICD_FILTER_MASKS", "256")))
         # grouping search: (field, store generation, normalised filter or None) -> (the index or view it belongs to, IcdGrouping)
         self._groupings: "OrderedDict[tuple, Any]" = OrderedDict()
         self._max_groupings = max(1, int(os.getenv("ICD_GROUPINGS", "16")))
@@ -210,6 +217,7 @@ class MilvusService:
         with self._views_lock:
             self._views.clear()
             self._groupings.clear()
+            self._masks.clear()
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
     def _grouping(self, field: str, index, rows, filter_key):
@@ -303,6 +311,77 @@ class MilvusService:
                         "bytes": int(st["bytes_corpus_f32"] + st["bytes_corpus_f16"] + st["bytes_workspace"])})
         return out
 
+    # ---- masked search (a filter as a bitset over the rows, per query) ---------------------------------------------------------
+    FILTER_MODES = ("view", "mask")
+
+    @staticmethod
+    def _check_filter_args(filter, filter_mode, group_by_field, nq=None):   # noqa: A002
+        """the checks of `filter` / `filter_mode` that need no store and no device: ValueError on a bad mode, a bad expression
+        (also inside a list), a list whose length is not nq, a list or mask mode next to group_by_field. Returns True when the
+        search takes the mask path."""
+        if filter_mode not in MilvusService.FILTER_MODES:
+            raise ValueError(f"filter_mode={filter_mode!r}: one of {MilvusService.FILTER_MODES}")
+        per_query = isinstance(filter, (list, tuple))
+        if per_query:
+            if nq is None:
+                raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_batch")
+            if len(filter) != nq:
+                raise ValueError(f"filter holds {len(filter)} expressions for {nq} queries")
+            for e in filter:
+                if e is not None:
+                    filter_expr.compile(e)
+        elif filter is not None:
+            filter_expr.compile(filter)
+        masked = per_query or (filter is not None and filter_mode == "mask")
+        if masked and group_by_field is not None:
+            raise ValueError("a per-query filter list / filter_mode='mask' cannot be combined with group_by_field")
+        return masked
+
+    def _filter_mask(self, index, expr):
+        """the row mask of `expr` on the store's index: None when the expression is None or selects every row, else the
+        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation)"""
+        if expr is None:
+            return None
+        key = filter_expr.compile(expr)
+        ck = (key, self.client.generation)
+        with self._views_lock:
+            hit = self._masks.get(ck)
+            if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
+                self._masks.move_to_end(ck)
+                return hit[1]
+        rows = self.filter_rows(expr)
+        if len(rows) == index.n:
+            return None
+        with self._views_lock:
+            mask = index.rowmask(rows)
+            self._masks[ck] = (index, mask)
+            while len(self._masks) > self._max_masks:
+                self._masks.popitem(last=False)
+        return mask
+
+    def _masks_for(self, index, filter, nq: int):   # noqa: A002
+        """one entry per query: None (unfiltered) or the expression's mask; equal expressions share one mask"""
+        exprs = list(filter) if isinstance(filter, (list, tuple)) else [filter] * nq
+        seen: Dict[Any, Any] = {}
+        out = []
+        for e in exprs:
+            if e not in seen:
+                seen[e] = self._filter_mask(index, e)
+            out.append(seen[e])
+        return out
+
+    def filter_masks(self) -> List[Dict[str, Any]]:
+        """the cached filter masks, least recently used first: expression (normalised), rows, HBM bytes"""
+        with self._views_lock:
+            items = list(self._masks.items())
+        out = []
+        for (key, gen), (_index, mask) in items:
+            if mask.closed:
+                continue
+            st = mask.stats()
+            out.append({"expression": key, "rows": int(st["rows"]), "generation": gen, "bytes": int(st["bytes"])})
+        return out
+
     @staticmethod
     def _check_band(top_k, group_by_field, radius, range_filter, offset, search_params):
         """(radius, range_filter, offset, banded) of a search's range arguments; ValueError on a bad one or on a combination with
@@ -316,8 +395,11 @@ class MilvusService:
 
     def search(self, query_vector: np.ndarray, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002 (Milvus's name)
                group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
-               range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
-        """group_by_field (one of filter_expr.GROUP_FIELDS) / group_size: Milvus's grouping search - the hits are the top_k best
+               range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None,
+               filter_mode: str = "view") -> List[Dict[str, Any]]:
+        """filter_mode: "view" (the default: the selection's cached view) or "mask" (the selection as a row mask of the index
+        itself: no second index); the hits are the same. A bad value raises ValueError.
+        group_by_field (one of filter_expr.GROUP_FIELDS) / group_size: Milvus's grouping search - the hits are the top_k best
         GROUPS' group_size best rows each (exact), re-sorted by adjusted score like any hit list; every hit's metadata then
         carries the group's value under the field's name. top_k * group_size <= 128. A bad grouping argument raises ValueError.
         radius / range_filter (also search_params={"params": {"radius": .., "range_filter": ..}}): Milvus's range search - only
@@ -329,11 +411,27 @@ class MilvusService:
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
         radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
+        if filter_mode not in self.FILTER_MODES:
+            raise ValueError(f"filter_mode={filter_mode!r}: one of {self.FILTER_MODES}")
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_batch")
+        masked = filter is not None and filter_mode == "mask"   # (a bad expression is logged below and gives [], as on the view path)
+        if masked and group_by_field is not None:
+            raise ValueError("filter_mode='mask' cannot be combined with group_by_field")
         try:
             if self.client is None or not self.client.exists():
                 logger.error("集合 %s 不存在", self.collection_name)
                 return []
             rows = None
+            if masked:
+                index = self._ready_index()
+                if index is None:
+                    return []
+                query_vector.tolist  # noqa: B018
+                q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
+                pair = (index, self._masks_for(index, filter, 1))
+                adj, raw, ids, levels = range_search.search_band(pair, q, int(top_k), radius, range_filter, offset)
+                return self._hits_to_dicts(adj[0], raw[0], ids[0])
             if filter is not None:
                 index, rows = self._filtered_index(filter)
             else:
@@ -386,16 +484,25 @@ class MilvusService:
 
     def search_iterator(self, query_vector, batch_size: int = 10, limit: int = -1, filter: Optional[str] = None,   # noqa: A002
                         radius: Optional[float] = None, range_filter: Optional[float] = None,
-                        search_params: Optional[Dict[str, Any]] = None) -> "range_search.SearchIterator":
+                        search_params: Optional[Dict[str, Any]] = None, filter_mode: str = "view") -> "range_search.SearchIterator":
         """pymilvus's search_iterator: an object whose next() returns the following batch_size hits of the query's ranking (inside
         the band, on the filter's selection) as a `search`-shaped list, [] when exhausted or after `limit` hits, and close().
         Pages are disjoint and exact at any depth; batch_size <= 128. The iterator keeps the index (or view) and the store
-        generation it started on: next() raises RuntimeError after the store changed. Bad arguments raise ValueError."""
+        generation it started on: next() raises RuntimeError after the store changed. Bad arguments raise ValueError.
+        filter_mode="mask": the pages are those of the filter's row mask on the index itself (the same pages; the iterator keeps
+        its own reference to the mask)."""
         radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
-        if filter is not None:
-            filter_expr.compile(filter)
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("search_iterator takes one filter expression")
+        masked = self._check_filter_args(filter, filter_mode, None)
         if self.client is None or not self.client.exists():
             index = None
+        elif masked:
+            index = self._ready_index()
+            if index is not None:
+                mask = self._filter_mask(index, filter)
+                if mask is not None:
+                    index = None if mask.rows == 0 else (index, mask)
         elif filter is not None:
             index, _ = self._filtered_index(filter)
         else:
@@ -406,12 +513,18 @@ class MilvusService:
 
     def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False, filter: Optional[str] = None,   # noqa: A002
                      group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
-                     range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None):
+                     range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None,
+                     filter_mode: str = "view"):
         """Additive: many queries in one call. query_vectors: [nq, dim] numpy array or torch CUDA
         tensor. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order
         `search` returns hits; or, with as_dicts=True, a list of `search`-shaped hit lists.
         filter: a Milvus filter expression - only the rows it selects are ranked (hit ids stay the corpus's row ids); a selection
         shorter than top_k pads the lists with id -1, score -inf, level 0. Raises ValueError on a bad expression.
+        filter may also be a list or tuple with ONE expression (or None: unfiltered) PER QUERY: every query is then ranked over its
+        own selection in one call - row masks tested inside the scan, whatever filter_mode says. A length
+        other than nq, a bad expression in it, or group_by_field next to it raise ValueError before anything is loaded. A query
+        whose selection is empty comes back as padding ([] with as_dicts). filter_mode="mask" serves a single expression the same
+        way, without a view; the default "view" is the cached view.
         group_by_field / group_size: as in `search`; the arrays are then [nq, top_k * group_size] and a fifth one follows, the
         hits' group ids (int32, -1 in padding: ranks of the field's sorted distinct values).
         radius / range_filter / offset / search_params: as in `search`, the same band for every query of the batch; lists shorter
@@ -421,12 +534,23 @@ class MilvusService:
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
         radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
-        if filter is not None:
-            filter_expr.compile(filter)   # (a bad expression raises before anything is loaded)
+        nq = None
+        if isinstance(filter, (list, tuple)) or filter_mode != "view":   # (only the mask path counts the queries: the default path takes whatever it took)
+            shape = np.shape(query_vectors)
+            nq = 1 if len(shape) == 1 else int(shape[0])
+        masked = self._check_filter_args(filter, filter_mode, group_by_field, nq)   # (a bad expression raises before anything is loaded)
         index = self._ready_index()
         if index is None:
             raise RuntimeError(f"collection {self.collection_name} is empty or missing")
         rows = None
+        if masked:
+            pair = (index, self._masks_for(index, filter, nq))
+            adj, raw, ids, levels = range_search.search_band(pair, query_vectors, int(top_k), radius, range_filter, offset)
+            if not as_dicts:
+                return adj, raw, ids, levels
+            if hasattr(adj, "cpu"):
+                adj, raw, ids = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy()
+            return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
         if filter is not None:
             index, rows = self._filtered_index(filter)
             if index is None:   # nothing selected: no device call

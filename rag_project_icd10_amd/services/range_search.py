@@ -97,11 +97,39 @@ def _cursor_of(raw: np.ndarray, ids: np.ndarray, want: int):
     return sc, cid
 
 
+class MaskedIndex:
+    """An (index, masks) pair with an index's band-search surface: search_range runs IcdIndex.search_masked with the pair's
+    masks - ONE IcdRowMask for every query, or one entry (IcdRowMask or None) per query. Holds a reference
+    to its masks: a mask evicted from a cache lives as long as a pair that pages over it."""
+
+    def __init__(self, index, masks):
+        self.index, self.masks = index, masks
+
+    @property
+    def max_k(self) -> int:
+        return self.index.max_k
+
+    @property
+    def closed(self) -> bool:
+        ms = self.masks if isinstance(self.masks, (list, tuple)) else [self.masks]
+        return self.index.closed or any(m is not None and m.closed for m in ms)
+
+    def search_range(self, queries, k, **kw):
+        return self.index.search_masked(queries, k, self.masks, **kw)
+
+
+def _band_index(index):
+    """an index, a view, or the pair (index, masks) -> the object whose search_range serves it"""
+    return MaskedIndex(*index) if isinstance(index, tuple) else index
+
+
 def search_band(index, queries, k: int, radius=None, range_filter=None, offset: int = 0):
     """(adj, raw, ids, levels), each [nq, k], of ranks offset .. offset + k of every query's band ranking (raw order), then
     reweighted and re-sorted. offset + k <= the index's page: ONE search and a slice; beyond: the skipped ranks are walked with raw
     pages (`after` cursor) and only the last page is reweighted - ceil(offset / page) extra searches. Device tensors in -> device
-    tensors out (offset = 0 never leaves the device)."""
+    tensors out (offset = 0 never leaves the device). index: an IcdIndex (or view), or the pair (index, masks) of a masked search -
+    the ranking is then every query's own mask's."""
+    index = _band_index(index)
     k, offset = int(k), int(offset)
     if offset == 0:
         return index.search_range(queries, k, radius=radius, range_filter=range_filter)
@@ -129,10 +157,12 @@ class SearchIterator:
     """pymilvus's iterator surface: next() -> a `search`-shaped hit list of up to batch_size hits ([] when exhausted), close().
     Page i + 1 is the band search behind the raw-order LAST hit of page i, so pages are disjoint and their raw-order concatenation
     is the band's full ranking; every page is handed out re-sorted by adjusted score like any hit list. The iterator pins the
-    index (or filter view) and the store generation it started on: after a mutation of the store next() raises RuntimeError
-    instead of paging through two different corpora. One launch per next() at batch_size <= 16."""
+    index (or filter view, or the pair (index, mask) of a masked search) and the store generation it started on: after a mutation
+    of the store next() raises RuntimeError instead of paging through two different corpora. One launch per next() at
+    batch_size <= 16."""
 
     def __init__(self, index, query_vector, batch_size: int, limit: int, radius, range_filter, to_hits, generation_of):
+        index = None if index is None else _band_index(index)
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
             raise ValueError("batch_size must be a positive integer")
         page = PAGE if index is None else min(PAGE, int(index.max_k))
