@@ -283,6 +283,58 @@ int icd_index_search_masked(icd_index *idx, icd_rowmask *const *masks, const flo
                             int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream);
 
 /*
+ * Hybrid search: Milvus's hybrid_search over dense requests (MilvusClient.hybrid_search(reqs=[AnnSearchRequest, ...], ranker=
+ * RRFRanker | WeightedRanker, limit=k); the reference sends one search per phrasing, services/milvus_service.py:280-285, and has
+ * no merge of its own). Every query carries R requests, 1 <= R <= ICD_MAX_REQUESTS; request r has a vector, a limit limits[r] in
+ * 1 .. ICD_MAX_K shared by all queries of the call, and optionally per (query, request) a row mask and a band. DESIGN.md
+ * section 13.
+ *   sub-list (q, r)   what icd_index_search_masked returns, raw order, for vector queries[q][r] at k = limits[r] with
+ *                     masks[q * R + r], radius[q * R + r], range_filter[q * R + r]; with masks, radius and range_filter all NULL
+ *                     what icd_index_search returns in `mode`. Rank j counts from 0; padding slots are not hits.
+ *   ICD_RANKER_RRF       fused(id) = sum over r ascending, for every r whose list holds id, of 1.0 / (rrf_c + j_r + 1), in
+ *                        double, from 0.0, left to right, every operation rounded once. 0 < rrf_c < 16384 (Milvus: 60).
+ *   ICD_RANKER_WEIGHTED  fused(id) = sum over r ascending of weights[r] * norm((double)score_r), product and sum rounded
+ *                        separately; weights[r] in [0, 1]; norm: ICD_NORM_NONE s, ICD_NORM_COSINE (1 + s) * 0.5, ICD_NORM_ATAN
+ *                        0.5 + atan(s) / pi (Milvus's rule for metric IP; the device's atan need not round as the host's does).
+ *   answer            the min(k, distinct ids) best ids by (fused desc, id asc), 1 <= k <= ICD_MAX_K; the other slots are padding:
+ *                     fused -inf, id -1, level 0, request bits 0 (adj -inf).
+ *   reweighted = 0    out_fused, out_ids, out_levels, out_reqbits in that order; out_adj is not written.
+ *   reweighted = 1    that list through icd_index_search_reweighted's step on the double score: out_adj = fused * w[level] and ONE
+ *                     stable descending re-sort of the query's hits; fused, ids, levels and request bits travel with the hit.
+ *   out_reqbits       uint32 [nq][k]: bit r set iff request r's list held the id. out_levels / out_reqbits may be NULL.
+ *
+ * icd_fusion_create: the workspace of the hybrid searches of `idx` for up to max_total = nq * R sub-lists per call: their staging
+ * (ICD_MAX_K scores and ids each), the staging of host callers (their vectors, and one block of 256 x ICD_MAX_K output slots that
+ * a host caller's outputs pass through 256 queries at a time); the per-request limits and weights are copied into the launch. Nothing is allocated in a search. A fusion keeps no pointer into its index: the handle is compared,
+ * never followed, and either may be destroyed first. It serves one stream at a time, like the index it belongs to. On an index
+ * of 2^31 rows or more: ICD_ERR_UNSUPPORTED. The row-sharded path (icd_group_*) has no hybrid search.
+ *
+ * icd_index_search_hybrid: queries [nq][R][dim]; masks a HOST array of nq * R handles (NULL entries: unfiltered) or NULL; radius /
+ * range_filter nq * R floats each or NULL (host, or device with bounds_on_device = 1; -inf / +inf leave one sub-list unbounded).
+ * ONE sub-search over the nq * R vectors at k = max limits[r] into the fusion's staging, then one launch of hybrid_fuse_kernel.
+ * ICD_ERR_INVALID before any device call: R, a limit or k out of range, a limit above the index's max_k, nq * R above the
+ * fusion's max_total or the index's max_nq, a weight outside [0, 1] or NaN (ICD_RANKER_WEIGHTED), rrf_c out of range
+ * (ICD_RANKER_RRF), an unknown ranker / norm / mode, host bounds holding NaN or radius >= range_filter, a fusion or a mask
+ * created for another index. A destroyed fusion or mask: ICD_ERR_STATE. On a view bands are allowed and masks are
+ * ICD_ERR_UNSUPPORTED, as for icd_index_search_masked; ties break on the local row, which orders as the global id does.
+ * With device queries, outputs and bounds and no masks the call only enqueues on `stream` (graph-capturable); with masks it is
+ * not graph-capturable, for the reason icd_index_search_masked gives (ICD_ERR_INVALID while capturing).
+ */
+#define ICD_MAX_REQUESTS 8
+typedef struct icd_fusion icd_fusion;
+enum { ICD_RANKER_RRF = 0, ICD_RANKER_WEIGHTED = 1 };
+enum { ICD_NORM_NONE = 0, ICD_NORM_COSINE = 1, ICD_NORM_ATAN = 2 };
+int icd_fusion_create(icd_index *idx, int64_t max_total, icd_fusion **out);
+int icd_fusion_destroy(icd_fusion *fusion);
+/* sub-lists per call, device bytes held (either pointer may be NULL) */
+int icd_fusion_stats(icd_fusion *fusion, int64_t *out_max_total, int64_t *out_bytes);
+int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *queries, int64_t nq, int32_t R, int32_t queries_on_device,
+                            const int32_t *limits, icd_rowmask *const *masks, const float *radius, const float *range_filter,
+                            int32_t bounds_on_device, int32_t mode, int32_t ranker, double rrf_c, const double *weights, int32_t norm,
+                            int32_t k, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
+                            uint32_t *out_reqbits, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -37,7 +37,11 @@ EXPORTED_SYMBOLS = (
     "icd_grouping_create", "icd_grouping_destroy", "icd_grouping_stats", "icd_index_search_grouped",
     "icd_index_search_range",
     "icd_rowmask_create", "icd_rowmask_destroy", "icd_rowmask_stats", "icd_rowmask_pack", "icd_index_search_masked",
+    "icd_fusion_create", "icd_fusion_destroy", "icd_fusion_stats", "icd_index_search_hybrid",
 )
+MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
+RANKER_RRF, RANKER_WEIGHTED = 0, 1
+NORMS = {"none": 0, "cosine": 1, "atan": 2}   # ICD_NORM_*
 MAX_K = 128   # include/icd_search.h ICD_MAX_K: the slots of one query's hit list (a grouped search: k * group_size)
 # include/icd_search.h: icd_index_create flags and icd_index_set_option ids (A/B and test options of ONE index)
 CREATE_CORPUS_ON_DEVICE, CREATE_ROW_ORDER, CREATE_NO_PROBE, CREATE_NO_CENTER = 1, 2, 4, 8
@@ -119,6 +123,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_rowmask_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.icd_rowmask_pack.argtypes = [vp, i64, i64, vp, i64]
     lib.icd_index_search_masked.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.icd_fusion_create.argtypes = [vp, i64, C.POINTER(vp)]
+    lib.icd_fusion_destroy.argtypes = [vp]
+    lib.icd_fusion_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_search_hybrid.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.c_double, vp, i32, i32, i32,
+                                            vp, vp, vp, vp, vp, i32, vp]
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -546,6 +555,106 @@ class IcdIndex:
             return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
         return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
 
+    # -- hybrid search (Milvus hybrid_search over dense requests) -----------------------------------------
+    def fusion(self, max_total: int) -> "IcdFusion":
+        """The workspace of this index's hybrid searches (icd_fusion_create) for calls of up to max_total = nq * R sub-lists."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdFusion(self, int(max_total))
+
+    def search_hybrid(self, queries, limits, k: int, fusion: "IcdFusion", *, ranker: str = "rrf", rrf_c: float = 60.0, weights=None,
+                      norm: str = "none", masks=None, radius=None, range_filter=None, mode: int = MODE_AUTO, reweighted: bool = True):
+        """R dense requests per query fused into one hit list on the device (icd_index_search_hybrid). queries: [nq, R, dim] (a
+        numpy array or a torch CUDA tensor); limits: R ints in 1 .. 128 (or one int for every request). ranker "rrf" (rrf_c) or
+        "weighted" (weights: R floats in [0, 1]; norm "none" | "cosine" | "atan"). masks: None, or nq * R entries (nested [nq][R]
+        or flat) of IcdRowMask or None; radius / range_filter: None, or arrays broadcastable to [nq, R] (-inf / +inf leave a
+        sub-list unbounded). reweighted=True: (adj f64, fused f64, ids i64, levels i32, reqbits) in search_reweighted's
+        order; False: (fused, ids, levels, reqbits) best fused score first. reqbits: bit r set iff request r's list held the id
+        (uint32 in numpy; an int32 tensor on the device, the same bit patterns). Padding: -inf, id -1, level 0, bits 0. Device
+        tensors in -> device tensors out on torch's current stream."""
+        if self.closed or fusion is None or fusion.closed:
+            raise IcdError(-5, "index or fusion is closed")
+        on_dev = _is_torch_tensor(queries) and queries.is_cuda
+        if on_dev:
+            import torch
+            q = queries
+            if q.dtype != torch.float32 or not q.is_contiguous():
+                q = q.to(torch.float32).contiguous()
+            if q.device.index != self.device:
+                raise ValueError(f"queries on cuda:{q.device.index}, index on device {self.device}")
+        else:
+            if _is_torch_tensor(queries):
+                queries = queries.detach().cpu().numpy()
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 2:
+            q = q[None]
+        if q.ndim != 3 or q.shape[-1] != self.dim:
+            raise ValueError(f"queries must be [nq, R, {self.dim}], got {tuple(q.shape)}")
+        nq, R = int(q.shape[0]), int(q.shape[1])
+        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.int32).reshape(-1), (R,)) if np.size(limits) == 1
+                                   else np.asarray(limits, dtype=np.int32).reshape(-1))
+        if lim.size != R:
+            raise ValueError(f"limits holds {lim.size} entries for {R} requests")
+        if ranker not in ("rrf", "weighted"):
+            raise ValueError(f"ranker={ranker!r}: 'rrf' or 'weighted'")
+        if norm not in NORMS:
+            raise ValueError(f"norm={norm!r}: one of {sorted(NORMS)}")
+        wts = None
+        if ranker == "weighted":
+            wts = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+            if wts.size != R:
+                raise ValueError(f"weights holds {wts.size} entries for {R} requests")
+        k = int(k)
+        total = nq * R
+        mask_h = None
+        if masks is not None:
+            flat = []
+            for m_ in masks:
+                flat.extend(m_ if isinstance(m_, (list, tuple)) else [m_])
+            if len(flat) != total:
+                raise ValueError(f"masks holds {len(flat)} entries for {nq} x {R} sub-searches")
+            mask_h = np.zeros(max(total, 1), np.uint64)
+            for j, m_ in enumerate(flat):
+                if m_ is None:
+                    continue
+                if not isinstance(m_, IcdRowMask):
+                    raise TypeError("masks: IcdRowMask or None per (query, request)")
+                if m_.closed:
+                    raise IcdError(-5, "a row mask is closed")
+                mask_h[j] = m_._h.value
+            if not mask_h.any():
+                mask_h = None
+
+        def bound(v):
+            if v is None:
+                return None
+            if on_dev:
+                t = torch.as_tensor(v).to(device=q.device, dtype=torch.float32)
+                return t.expand(nq, R).contiguous().reshape(-1) if t.numel() != total else t.contiguous().reshape(-1)
+            if _is_torch_tensor(v):
+                v = v.detach().cpu().numpy()
+            t = np.asarray(v, dtype=np.float32)
+            return np.ascontiguousarray(np.broadcast_to(t, (nq, R)) if t.size != total else t).reshape(-1)
+        lo, hi = bound(radius), bound(range_filter)
+        if on_dev:
+            mk = lambda dt: torch.empty((nq, k), dtype=dt, device=q.device)
+            adj, fused, ids, lv, bits = mk(torch.float64), mk(torch.float64), mk(torch.int64), mk(torch.int32), mk(torch.int32)
+            ptr = lambda t: t.data_ptr()
+            stream = _current_stream_ptr(self.device)
+        else:
+            mk = lambda dt: np.empty((nq, k), dtype=dt)
+            adj, fused, ids, lv, bits = mk(np.float64), mk(np.float64), mk(np.int64), mk(np.int32), mk(np.uint32)
+            ptr = lambda t: t.ctypes.data
+            stream = None
+        rc = self._lib.icd_index_search_hybrid(
+            self._h, fusion._h, ptr(q) if nq else None, nq, R, 1 if on_dev else 0, lim.ctypes.data,
+            None if mask_h is None else mask_h.ctypes.data, None if lo is None else ptr(lo), None if hi is None else ptr(hi),
+            1 if on_dev else 0, int(mode), RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c),
+            None if wts is None else wts.ctypes.data, NORMS[norm], k, 1 if reweighted else 0,
+            ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), 1 if on_dev else 0, stream)
+        _check(self._lib, rc)
+        return (adj, fused, ids, lv, bits) if reweighted else (fused, ids, lv, bits)
+
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""
         import torch
@@ -622,6 +731,39 @@ class IcdGrouping:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.icd_grouping_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def closed(self) -> bool:
+        return not self._h.value
+
+
+class IcdFusion:
+    """The workspace of one IcdIndex's hybrid searches (icd_fusion_*): staging for max_total = nq * R sub-lists of 128 hits and
+    for host callers. Independent of the index's lifetime: either may be closed first (a search with a closed partner raises)."""
+
+    def __init__(self, index: "IcdIndex", max_total: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        self.max_total, self.device = int(max_total), index.device
+        _check(self._lib, self._lib.icd_fusion_create(index._h, self.max_total, C.byref(self._h)))
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "fusion is closed")
+        t, b = C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_fusion_stats(self._h, C.byref(t), C.byref(b)))
+        return {"max_total": t.value, "bytes": b.value}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.icd_fusion_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -1,10 +1,10 @@
-"""FastAPI surface: POST /embed, POST /query, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
 cut to top_k, every match's confidence metrics / factors / level copied as :325-330 does; 503 when services are missing, 500 with a `detail` string on any exception), `/embed`
 (:505-530), `/stats` (:574-599). `/query` takes a Milvus `filter` expression (services/filter_expr.py; a bad one is a 400), `/stats`
-lists the cached filter views, filter masks and groupings; `/query` takes `filter_mode` ("view" / "mask"; anything else is a 400); `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). The LLM, NER, standardisation and resource routes are out of scope.
+lists the cached filter views, filter masks and groupings; `/query` takes `filter_mode` ("view" / "mask"; anything else is a 400); `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). `/hybrid_query` takes several phrasings of one diagnosis and a ranker (Milvus hybrid_search, services/hybrid_search.py; bad arguments are a 400). The LLM, NER, standardisation and resource routes are out of scope.
 
     uvicorn rag_project_icd10_amd.api.app:app --host 0.0.0.0 --port 8005
 """
@@ -18,7 +18,7 @@ from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
 from .icd_models import (DiagnosisMatch, EmbeddingRequest, EmbeddingResponse, HealthCheckResponse,
-                         QueryRequest, QueryResponse, convert_numpy_types)
+                         HybridQueryRequest, QueryRequest, QueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
 
@@ -165,6 +165,51 @@ async def query_similar(request: QueryRequest):
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
 
 
+@app.post("/hybrid_query", response_model=QueryResponse)
+async def hybrid_query(request: HybridQueryRequest):
+    """Several phrasings of ONE diagnosis (the clinician's wording, the NER entity text, a synonym, an English term): encoded in one
+    call, one dense request each, fused on the device by the ranker (MilvusService.hybrid_search). Bad arguments are a 400, also
+    those only the store can judge (a limit above its max_k). The response has /query's hit shape: `score` is the fused score
+    times the level weight, `original_score` the ranker's own value, `similarity_factors.matched_requests` the indices of the
+    texts that found the hit. `score` is non-negative in that shape; a weighted sum of raw inner products (norm_score "none") can
+    be negative, and such a hit carries score 0 with the true value in `enhanced_score`, which always holds the unclamped score."""
+    from ..services import hybrid_search as hybrid
+    try:
+        if not request.texts or any(not isinstance(t, str) or not t.strip() for t in request.texts):
+            raise ValueError("texts: 1 .. 8 non-empty strings")
+        if len(request.texts) > hybrid.MAX_REQUESTS:
+            raise ValueError(f"{len(request.texts)} texts: a hybrid query takes 1 .. {hybrid.MAX_REQUESTS} phrasings")
+        if not 1 <= request.top_k <= 50:
+            raise ValueError(f"top_k={request.top_k}: 1 .. 50")
+        ranker = hybrid.ranker_from_dict(request.ranker)
+        if isinstance(ranker, hybrid.WeightedRanker) and len(ranker.weights) != len(request.texts):
+            raise ValueError(f"the ranker holds {len(ranker.weights)} weights for {len(request.texts)} texts")
+        hybrid.AnnSearchRequest(None, request.req_limit, request.filter)   # (the limit's and the filter's checks)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    if not embedding_service or not milvus_service:
+        raise HTTPException(status_code=500, detail="查询失败: 服务未就绪")   # (as /query: the 503 surfaces as a 500)
+    try:
+        import numpy as np
+        vecs = np.asarray(embedding_service.encode_query_batch(list(request.texts)), dtype=np.float32)
+        reqs = [hybrid.AnnSearchRequest(vecs[i], request.req_limit, request.filter) for i in range(len(request.texts))]
+        try:
+            hits = milvus_service.hybrid_search(reqs, ranker, request.top_k)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+        from .icd_models import Candidate
+        candidates = [Candidate(code=h["code"], title=h["title"] or "", score=max(float(h["score"]), 0.0), enhanced_score=float(h["score"]),
+                                level=h["metadata"].get("level", 1), parent_code=h["metadata"].get("parent_code", ""),
+                                original_score=float(h["fused_score"]), similarity_factors={"matched_requests": h["matched_requests"]})
+                      for h in hits]
+        response = QueryResponse(candidates=candidates, is_multi_diagnosis=False, extracted_diagnoses=[request.texts[0]])
+        return QueryResponse(**convert_numpy_types(response.model_dump()))
+    except HTTPException:
+        raise
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+
+
 @app.post("/embed", response_model=EmbeddingResponse)
 async def embed_texts(request: EmbeddingRequest):
     try:
@@ -189,6 +234,8 @@ async def get_stats():
                 stats["filter_masks"] = milvus_service.filter_masks()
             if hasattr(milvus_service, "groupings"):      # the cached groupings: field, groups, largest group, HBM bytes
                 stats["groupings"] = milvus_service.groupings()
+            if hasattr(milvus_service, "fusions"):        # the hybrid-search workspace: sub-lists per call, HBM bytes
+                stats["fusions"] = milvus_service.fusions()
         if embedding_service:
             stats["embedding"] = embedding_service.get_model_info()
         return stats

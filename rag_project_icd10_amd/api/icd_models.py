@@ -8,7 +8,7 @@ QueryResponse (:141-158), EmbeddingRequest / EmbeddingResponse (:184-192), Healt
 from __future__ import annotations
 
 import dataclasses
-from typing import Any, List, Optional
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 from pydantic import BaseModel, ConfigDict, Field, field_serializer
@@ -220,6 +220,17 @@ class QueryRequest(BaseModel):
     group_size: int = Field(default=1, description="rows returned per group (with group_by_field)", ge=1, le=128)
     radius: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is ABOVE this are ranked")
     range_filter: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is at or below this are ranked (radius < range_filter)")
+
+
+class HybridQueryRequest(BaseModel):
+    """POST /hybrid_query: several phrasings of ONE diagnosis, fused by a ranker (Milvus hybrid_search). The ranges of texts, top_k
+    and req_limit are checked by the route (a 400 with the reason), not by the model (which would answer 422)."""
+    texts: List[str] = Field(..., description="phrasings of one diagnosis (1 .. 8): each becomes one dense request")
+    ranker: Dict[str, Any] = Field(default_factory=lambda: {"strategy": "rrf", "params": {"k": 60}},
+                                   description="{'strategy': 'rrf', 'params': {'k': 60}} or {'strategy': 'weighted', 'params': {'weights': [..], 'norm_score': 'atan'}}")
+    top_k: int = Field(default=5, description="fused hits returned (1 .. 50)")
+    req_limit: int = Field(default=20, description="hits every phrasing contributes (1 .. 128)")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression applied to every request")
 
 
 class QueryResponse(BaseModel):

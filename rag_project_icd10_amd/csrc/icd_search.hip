@@ -21,6 +21,7 @@
 #include "exact_kernel.hpp"
 #include "finalize.hpp"
 #include "group_topk.hpp"
+#include "hybrid_fuse.hpp"
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
@@ -2385,6 +2386,207 @@ int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float
         HIP_TRY(hipMemcpyAsync(out_ids, d_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
         if (out_levels) HIP_TRY(hipMemcpyAsync(out_levels, d_lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
         if (out_groups) HIP_TRY(hipMemcpyAsync(out_groups, d_grp, no * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    if (!out_on_device || !queries_on_device) HIP_TRY(hipStreamSynchronize(s));
+    return ICD_OK;
+}
+
+}  // extern "C"
+
+// ---- hybrid search (hybrid_fuse.hpp) -----------------------------------------------------------------
+// A fusion belongs to the index it was created for but keeps no pointer into it: handle and identity are compared, never
+// followed. Its workspace - the staging of the sub-lists, the staging of host callers - is allocated here, never in a search.
+struct icd_fusion {
+    uint32_t magic = 0x1CDF05EDu;
+    const icd_index *owner = nullptr;
+    unsigned long long owner_uid = 0;
+    int device = 0, dim = 0;
+    int64_t n = 0, max_total = 0;
+    float *st_scores = nullptr; long long *st_ids = nullptr;   // [max_total][ICD_MAX_K] the sub-lists of a call, [nq * R][max limit] used
+    float *qdev = nullptr;                                     // [max_total][dim] a host caller's vectors
+    double *o_adj = nullptr, *o_fused = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr; uint32_t *o_bits = nullptr;   // [FUSION_HOST_CHUNK][ICD_MAX_K] a host caller's outputs, FUSION_HOST_CHUNK queries at a time
+    int limits[ICD_MAX_REQUESTS] = {};                         // of the current call (copied: the caller's arrays are not read again)
+    double weights[ICD_MAX_REQUESTS] = {};
+    size_t bytes = 0;
+    std::mutex mu;
+};
+
+namespace {
+// a HOST caller's outputs leave the device in pieces of this many queries (one fuse launch and its copies per piece, in stream
+// order through one staging block of 256 x 128 slots = 1 MB): the staging does not grow with max_total, and a device caller,
+// who never uses it, does not pay for it
+constexpr int FUSION_HOST_CHUNK = 256;
+bool valid_fusion(icd_fusion *f) { return f && f->magic == 0x1CDF05EDu; }
+void free_fusion(icd_fusion *f) {
+    if (!f) return;
+    hipFree(f->st_scores); hipFree(f->st_ids); hipFree(f->qdev);
+    hipFree(f->o_adj); hipFree(f->o_fused); hipFree(f->o_ids); hipFree(f->o_lv); hipFree(f->o_bits);
+    f->magic = 0;
+    delete f;
+}
+}  // namespace
+
+extern "C" {
+
+int icd_fusion_create(icd_index *idx, int64_t max_total, icd_fusion **out) {
+    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (max_total <= 0 || max_total > 0x7FFFFFFFll / ICD_MAX_K) return fail(ICD_ERR_INVALID, "max_total=%lld", (long long)max_total);
+    if (idx->n >= 0x7FFFFFFFll) return fail(ICD_ERR_UNSUPPORTED, "n=%lld: a fusion addresses rows with 31 bits", (long long)idx->n);
+    HIP_TRY(hipSetDevice(idx->device));
+    icd_fusion *f = new (std::nothrow) icd_fusion();
+    if (!f) return fail(ICD_ERR_NOMEM, "host allocation failed");
+    f->owner = idx; f->owner_uid = idx->uid; f->device = idx->device; f->dim = idx->dim; f->n = idx->n; f->max_total = max_total;
+    const size_t no = (size_t)max_total * ICD_MAX_K;
+#define FU_TRY(expr)                                                                                                       \
+    do {                                                                                                                   \
+        hipError_t e_ = (expr);                                                                                            \
+        if (e_ != hipSuccess) {                                                                                            \
+            free_fusion(f);                                                                                                \
+            return fail(e_ == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+        }                                                                                                                  \
+    } while (0)
+    FU_TRY(dmalloc(&f->st_scores, no)); FU_TRY(dmalloc(&f->st_ids, no));
+    FU_TRY(dmalloc(&f->qdev, (size_t)max_total * idx->dim));
+    const size_t nh = (size_t)std::min<int64_t>(max_total, FUSION_HOST_CHUNK) * ICD_MAX_K;
+    FU_TRY(dmalloc(&f->o_adj, nh)); FU_TRY(dmalloc(&f->o_fused, nh)); FU_TRY(dmalloc(&f->o_ids, nh)); FU_TRY(dmalloc(&f->o_lv, nh)); FU_TRY(dmalloc(&f->o_bits, nh));
+#undef FU_TRY
+    f->bytes = no * (4 + 8) + (size_t)max_total * idx->dim * 4 + nh * (8 + 8 + 8 + 4 + 4);
+    *out = f;
+    return ICD_OK;
+}
+
+int icd_fusion_destroy(icd_fusion *fusion) {
+    if (!valid_fusion(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
+    hipSetDevice(fusion->device);
+    hipDeviceSynchronize();
+    free_fusion(fusion);
+    return ICD_OK;
+}
+
+int icd_fusion_stats(icd_fusion *fusion, int64_t *out_max_total, int64_t *out_bytes) {
+    if (!valid_fusion(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
+    if (out_max_total) *out_max_total = fusion->max_total;
+    if (out_bytes) *out_bytes = (int64_t)fusion->bytes;
+    return ICD_OK;
+}
+
+int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *queries, int64_t nq, int32_t R, int32_t queries_on_device,
+                            const int32_t *limits, icd_rowmask *const *masks, const float *radius, const float *range_filter,
+                            int32_t bounds_on_device, int32_t mode, int32_t ranker, double rrf_c, const double *weights, int32_t norm,
+                            int32_t k, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
+                            uint32_t *out_reqbits, int32_t out_on_device, void *stream) {
+    // every check comes before the first device call
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_fusion(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
+    icd_fusion *f = fusion;
+    if (f->owner != idx || f->owner_uid != idx->uid || f->n != idx->n || f->device != idx->device || f->dim != idx->dim)
+        return fail(ICD_ERR_INVALID, "the fusion was created for another index");
+    if (R < 1 || R > ICD_MAX_REQUESTS) return fail(ICD_ERR_INVALID, "R=%d: a hybrid search takes 1 .. %d requests per query", R, ICD_MAX_REQUESTS);
+    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a hybrid search returns 1 .. %d hits per query", k, ICD_MAX_K);
+    if (!limits) return fail(ICD_ERR_INVALID, "limits is NULL");
+    int lmax = 0;
+    for (int r = 0; r < R; ++r) {
+        if (limits[r] < 1 || limits[r] > ICD_MAX_K) return fail(ICD_ERR_INVALID, "limits[%d]=%d: a request returns 1 .. %d hits", r, limits[r], ICD_MAX_K);
+        lmax = std::max(lmax, (int)limits[r]);
+    }
+    if (lmax > idx->max_k) return fail(ICD_ERR_INVALID, "limit %d exceeds the index's max_k=%d", lmax, idx->max_k);
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    const int64_t total = nq * R;
+    if (total > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)total, (long long)f->max_total);
+    if (total > idx->max_nq) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the index's max_nq=%d", (long long)total, idx->max_nq);
+    if (mode != ICD_MODE_AUTO && mode != ICD_MODE_EXACT) return fail(ICD_ERR_INVALID, "mode=%d", mode);
+    if (ranker == ICD_RANKER_RRF) {
+        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
+    } else if (ranker == ICD_RANKER_WEIGHTED) {
+        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
+        for (int r = 0; r < R; ++r)
+            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
+        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
+    } else {
+        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
+    }
+    if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    const bool banded = radius || range_filter;
+    if (banded && !bounds_on_device) {
+        for (int64_t i = 0; i < total; ++i) {
+            if (radius && std::isnan(radius[i])) return fail(ICD_ERR_INVALID, "radius[%lld] is NaN", (long long)i);
+            if (range_filter && std::isnan(range_filter[i])) return fail(ICD_ERR_INVALID, "range_filter[%lld] is NaN", (long long)i);
+            if (radius && range_filter && !(radius[i] < range_filter[i]))
+                return fail(ICD_ERR_INVALID, "sub-search %lld: radius=%g must be below range_filter=%g", (long long)i, (double)radius[i], (double)range_filter[i]);
+        }
+    }
+    if (masks) {
+        if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a masked hybrid search on a view is not supported: mask the parent");
+        for (int64_t i = 0; i < total; ++i) {
+            const icd_rowmask *m = masks[i];
+            if (!m) continue;
+            if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "masks[%lld]: invalid row mask handle", (long long)i);
+            if (m->owner != idx || m->owner_uid != idx->uid || m->n != idx->n || m->device != idx->device)
+                return fail(ICD_ERR_INVALID, "masks[%lld] was created for another index", (long long)i);
+        }
+    }
+    if (nq == 0) return ICD_OK;
+    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
+    std::lock_guard<std::mutex> guard(f->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const bool capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+        if (capturing && (!queries_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
+        if (capturing && masks) return fail(ICD_ERR_INVALID, "a masked search stages its mask table on the host at call time: it cannot be captured into a graph");
+        if (capturing && banded && !bounds_on_device) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
+    }
+    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
+        f->limits[r] = r < R ? limits[r] : 0;
+        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
+    }
+    const float *dq = queries;
+    if (!queries_on_device) {
+        HIP_TRY(hipMemcpyAsync(f->qdev, queries, (size_t)total * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        dq = f->qdev;
+    }
+    // step 1: ONE existing sub-search over the nq * R vectors at k = the largest limit, into the staging
+    int rc;
+    if (!masks && !banded)
+        rc = icd_index_search(idx, dq, total, lmax, 1, mode, f->st_scores, reinterpret_cast<int64_t *>(f->st_ids), 1, stream);
+    else
+        rc = icd_index_search_masked(idx, masks, dq, total, lmax, 1, radius, range_filter, nullptr, nullptr, bounds_on_device, 0, nullptr,
+                                     f->st_scores, reinterpret_cast<int64_t *>(f->st_ids), nullptr, 1, stream);
+    if (rc) return rc;
+    // step 2: the fuse
+    HybridArgs a{};
+    a.st_scores = f->st_scores; a.st_ids = f->st_ids;
+    a.R = R; a.lmax = lmax; a.k = k;
+    a.slots = 2;
+    while (a.slots < R * lmax) a.slots <<= 1;
+    for (int r = 0; r < HY_MAX_R; ++r) { a.limits[r] = f->limits[r]; a.weights[r] = f->weights[r]; }
+    a.rrf_c = rrf_c; a.ranker = ranker; a.norm = norm; a.reweighted = reweighted ? 1 : 0;
+    a.n = idx->n; a.id_base = idx->id_base; a.row_map = idx->row_map; a.levels = idx->levels;
+    a.out_adj = out_adj; a.out_fused = out_fused; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels; a.out_reqbits = out_reqbits;
+    if (out_on_device) {
+        hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(HY_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // host outputs: FUSION_HOST_CHUNK queries per launch into the staging, copied out behind it (stream order keeps the
+        // next piece's launch behind this piece's copies)
+        a.out_adj = reweighted ? f->o_adj : nullptr; a.out_fused = f->o_fused; a.out_ids = f->o_ids;
+        a.out_levels = out_levels ? f->o_lv : nullptr; a.out_reqbits = out_reqbits ? f->o_bits : nullptr;
+        for (int64_t q0 = 0; q0 < nq; q0 += FUSION_HOST_CHUNK) {
+            const int64_t nb = std::min<int64_t>(FUSION_HOST_CHUNK, nq - q0);
+            a.st_scores = f->st_scores + (size_t)q0 * R * lmax;
+            a.st_ids = f->st_ids + (size_t)q0 * R * lmax;
+            hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, a);
+            HIP_TRY(hipGetLastError());
+            const size_t no = (size_t)nb * k, at = (size_t)q0 * k;
+            if (reweighted) HIP_TRY(hipMemcpyAsync(out_adj + at, a.out_adj, no * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_fused + at, a.out_fused, no * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_ids + at, a.out_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
+            if (out_levels) HIP_TRY(hipMemcpyAsync(out_levels + at, a.out_levels, no * sizeof(int), hipMemcpyDeviceToHost, s));
+            if (out_reqbits) HIP_TRY(hipMemcpyAsync(out_reqbits + at, a.out_reqbits, no * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
     }
     if (!out_on_device || !queries_on_device) HIP_TRY(hipStreamSynchronize(s));
     return ICD_OK;

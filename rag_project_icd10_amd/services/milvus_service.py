@@ -31,7 +31,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..corpus_store import CorpusStore
-from . import filter_expr, range_search
+from . import filter_expr, hybrid_search as hybrid, range_search
 
 logger = logging.getLogger(__name__)
 
@@ -64,6 +64,9 @@ class MilvusService:
         # grouping search: (field, store generation, normalised filter or None) -> (the index or view it belongs to, IcdGrouping)
         self._groupings: "OrderedDict[tuple, Any]" = OrderedDict()
         self._max_groupings = max(1, int(os.getenv("ICD_GROUPINGS", "16")))
+        # hybrid search: (the index it belongs to, IcdFusion, store generation); one handle, regrown when a call needs more
+        # sub-lists, dropped where the views and masks are
+        self._fusion = None
         self._columns = None        # filter_expr.Columns of the store generation they were built from (rebuilt when it moves on)
         self._connect()
         self._setup_collection()
@@ -218,6 +221,7 @@ class MilvusService:
             self._views.clear()
             self._groupings.clear()
             self._masks.clear()
+            self._fusion = None
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
     def _grouping(self, field: str, index, rows, filter_key):
@@ -577,6 +581,79 @@ class MilvusService:
         if hasattr(adj, "cpu"):
             adj, raw, ids = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy()
         return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
+
+    # ---- hybrid search (Milvus hybrid_search over dense requests) ------------------------------------------
+    def _fusion_for(self, index, total: int):
+        """the cached IcdFusion of the store's index with room for `total` sub-lists (per store generation; regrown when short)"""
+        gen = self.client.generation
+        with self._views_lock:
+            hit = self._fusion
+            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_total >= total:
+                return hit[1]
+            fusion = index.fusion(min(index.max_nq, max(int(total), 64)))
+            self._fusion = (index, fusion, gen)
+        return fusion
+
+    def fusions(self) -> List[Dict[str, Any]]:
+        """the cached hybrid-search workspace (at most one): sub-lists per call, HBM bytes"""
+        with self._views_lock:
+            hit = self._fusion
+        if hit is None or hit[1].closed:
+            return []
+        st = hit[1].stats()
+        return [{"max_total": int(st["max_total"]), "generation": hit[2], "bytes": int(st["bytes"])}]
+
+    def hybrid_search_batch(self, reqs, ranker, limit: int = 10, as_dicts: bool = False):
+        """Milvus's hybrid_search for a batch: reqs is a list of 1 .. 8 hybrid_search.AnnSearchRequest whose data share one shape
+        [nq, dim] (request r's vector of every query; numpy arrays, or torch CUDA tensors for device outputs); ranker an RRFRanker
+        or WeightedRanker; limit the fused hits per query (1 .. 128). Every request's sub-list is exact, over its own expr's
+        selection (through the mask cache; a selection of every row passes no mask) and its own param's radius / range_filter,
+        and the lists are fused on the device. Returns (adjusted f64, fused f64, ids i64, levels i32, matched_requests bits), each
+        [nq, limit], in the order `search` returns hits (adjusted = fused * level weight, one stable re-sort); with as_dicts a
+        list of hybrid_search-shaped hit lists. Bad arguments raise ValueError before anything is loaded."""
+        limit = hybrid.check_requests(reqs, ranker, limit)
+        q = hybrid.stack_requests(reqs)
+        index = self._ready_index()
+        if index is None:
+            raise RuntimeError(f"collection {self.collection_name} is empty or missing")
+        nq, R = int(q.shape[0]), len(reqs)
+        if max(r.limit for r in reqs) > index.max_k:
+            raise ValueError(f"a request's limit exceeds the index's max_k={index.max_k} (ICD_GPU_MAX_K)")
+        if nq * R > index.max_nq:
+            raise ValueError(f"{nq} queries x {R} requests exceed the index's batch of {index.max_nq} (ICD_GPU_MAX_BATCH)")
+        per_req = [self._filter_mask(index, r.expr) for r in reqs]
+        masks = [per_req] * nq if any(m is not None for m in per_req) else None
+        lo = hi = None
+        if any(r.radius is not None for r in reqs):
+            lo = np.array([-np.inf if r.radius is None else r.radius for r in reqs], np.float32)
+        if any(r.range_filter is not None for r in reqs):
+            hi = np.array([np.inf if r.range_filter is None else r.range_filter for r in reqs], np.float32)
+        kw = ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
+              else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
+        out = index.search_hybrid(q, [r.limit for r in reqs], limit, self._fusion_for(index, nq * R), masks=masks, radius=lo,
+                                  range_filter=hi, **kw)
+        if not as_dicts:
+            return out
+        adj, fused, ids, _levels, bits = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in out]
+        res = []
+        for qi in range(nq):
+            hits = self._hits_to_dicts(adj[qi], fused[qi], ids[qi])
+            valid = [j for j in range(limit) if ids[qi][j] >= 0]
+            for hit, j in zip(hits, valid):
+                hit["fused_score"] = hit.pop("original_score")
+                hit["matched_requests"] = [r for r in range(R) if (int(bits[qi][j]) >> r) & 1]
+            res.append(hits)
+        return res
+
+    def hybrid_search(self, reqs, ranker, limit: int = 10) -> List[Dict[str, Any]]:
+        """Milvus's hybrid_search for ONE query: every request's data is one vector. Returns a `search`-shaped hit list whose
+        `score` is the reweighted fused score; `fused_score` (the ranker's value) and `matched_requests` (the indices of the
+        requests whose list held the hit) replace `original_score`. Bad arguments raise ValueError."""
+        limit = hybrid.check_requests(reqs, ranker, limit)
+        for r in reqs:
+            if np.ndim(r.data) > 2 or (np.ndim(r.data) == 2 and np.shape(r.data)[0] != 1):
+                raise ValueError("hybrid_search takes one vector per request; hybrid_search_batch takes batches")
+        return self.hybrid_search_batch(reqs, ranker, limit, as_dicts=True)[0]
 
     def _empty_hits(self, query_vectors, k: int, as_dicts: bool):
         nq = 1 if getattr(query_vectors, "ndim", 2) == 1 else int(query_vectors.shape[0])
