@@ -9,6 +9,7 @@ services/milvus_service.py:57-206 and searches at :280-285.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -189,6 +190,108 @@ def _current_stream_ptr(device_index: int) -> int:
     return int(torch.cuda.current_stream(device_index).cuda_stream)
 
 
+# ---- what the search methods share ---------------------------------------------------------------------------------------------
+def _host_ptr(a):
+    return a.ctypes.data
+
+
+def _dev_ptr(t):
+    return t.data_ptr()
+
+
+def _outputs(on_dev: bool, device: int, shape, dtypes):
+    """The uninitialised outputs of one call (numpy dtypes; torch tensors on cuda:device when on_dev), how to take an array's
+    pointer, the stream the call runs on and the C ABI's on_device flag"""
+    if on_dev:
+        import torch
+        where = torch.device("cuda", device)
+        return ([torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=where) for dt in dtypes], _dev_ptr,
+                _current_stream_ptr(device), 1)
+    return [np.empty(shape, dt) for dt in dtypes], _host_ptr, None, 0
+
+
+def _chunked(q, step: int, on_dev: bool, call):
+    """call(queries of the chunk, its first query) -> tuple of arrays, per chunk of at most `step` queries; the chunks joined"""
+    nq = q.shape[0]
+    if nq <= step:   # (the usual call: no slice, no list)
+        return call(q, 0)
+    outs = [call(q[s0:s0 + step], s0) for s0 in range(0, nq, step)]
+    if on_dev:
+        import torch
+        return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
+    return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+
+
+def _bound(v, dtype, shape, on_dev: bool, device: int):
+    """A bound (None, a scalar, or values that fill or broadcast to `shape`) as a flat contiguous array of numpy `dtype`, on
+    cuda:device when on_dev. The one-dimensional form takes ONE value of any rank for every query."""
+    if v is None:
+        return None
+    flat = len(shape) == 1
+    count = shape[0] if flat else math.prod(shape)
+    if on_dev:
+        import torch
+        t = torch.as_tensor(v).to(device=torch.device("cuda", device), dtype=getattr(torch, np.dtype(dtype).name))
+        size = t.numel()
+    else:
+        if _is_torch_tensor(v):
+            v = v.detach().cpu().numpy()
+        t = np.asarray(v, dtype)
+        size = t.size
+    if size != count:
+        if flat:
+            if size != 1:
+                raise ValueError(f"a bound holds {size} values for {count} queries")
+            t = t.reshape(-1)
+        t = t.expand(shape) if on_dev else np.broadcast_to(t, shape)
+    return t.contiguous().reshape(-1) if on_dev else np.ascontiguousarray(t).reshape(-1)
+
+
+def _mask_table(masks, count: int, what: str, per: str) -> np.ndarray:
+    """[entry] -> row-mask handle as a uint64 array (0: unfiltered), for ONE IcdRowMask on every entry or a sequence of `count` of
+    IcdRowMask or None. Built without a Python loop over the entries (10 000 of them cost milliseconds in front of the launch): the
+    distinct mask objects are found by identity and checked once each."""
+    if isinstance(masks, IcdRowMask):
+        uniq, inverse = [masks], np.zeros(count, np.int64)
+    else:
+        masks = list(masks)
+        if len(masks) != count:
+            raise ValueError(f"masks holds {len(masks)} entries for {what}")
+        ident = np.fromiter(map(id, masks), np.int64, count)
+        _, first, inverse = np.unique(ident, return_index=True, return_inverse=True)
+        uniq = [masks[i] for i in first]
+    vals = np.zeros(max(len(uniq), 1), np.uint64)
+    for j, m_ in enumerate(uniq):
+        if m_ is None:
+            continue
+        if not isinstance(m_, IcdRowMask):
+            raise TypeError(f"masks: IcdRowMask or None per {per}")
+        if m_.closed:
+            raise IcdError(-5, "a row mask is closed")
+        vals[j] = m_._h.value
+    return np.ascontiguousarray(vals[inverse.reshape(-1)]) if count else np.zeros(1, np.uint64)
+
+
+class _Handle:
+    """A native workspace handle of an index: `_h`, closed once through the entry point its class names in `_destroy`"""
+    _destroy = ""
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def closed(self) -> bool:
+        return not self._h.value
+
+
 class IcdIndex:
     """Exact inner-product index over a dense fp32 corpus resident in one GPU's HBM.
 
@@ -294,23 +397,23 @@ class IcdIndex:
         return not self._h.value
 
     # -- search --------------------------------------------------------------------------------------
-    def _prep_queries(self, queries):
-        if _is_torch_tensor(queries) and queries.is_cuda:
+    def _prep_queries(self, queries, rank: int = 2):
+        """queries as contiguous float32 of `rank` dimensions (one dimension less: a single entry) -> (array, on_device)"""
+        on_dev = type(queries) is not np.ndarray and _is_torch_tensor(queries) and queries.is_cuda
+        if on_dev:
             import torch
             q = queries
-            if q.dim() == 1:
-                q = q.unsqueeze(0)
             if q.dtype != torch.float32 or not q.is_contiguous():
                 q = q.to(torch.float32).contiguous()
             if q.device.index != self.device:
                 raise ValueError(f"queries on cuda:{q.device.index}, index on device {self.device}")
-            return q, True
-        if _is_torch_tensor(queries):
-            queries = queries.detach().cpu().numpy()
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        return q, False
+        else:
+            if type(queries) is not np.ndarray and _is_torch_tensor(queries):
+                queries = queries.detach().cpu().numpy()
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == rank - 1:
+            q = q[None]
+        return q, on_dev
 
     def _validate(self, q, k):
         if self.closed:
@@ -325,69 +428,29 @@ class IcdIndex:
         Device tensors in -> device tensors out (enqueued on torch's current stream, no sync)."""
         q, on_dev = self._prep_queries(queries)
         self._validate(q, k)
-        nq = int(q.shape[0])
-        out_s, out_i = [], []
-        for s0 in range(0, max(nq, 1), self.max_nq):
-            qs = q[s0:s0 + self.max_nq]
-            m = int(qs.shape[0])
-            if on_dev:
-                import torch
-                sc = torch.empty((m, k), dtype=torch.float32, device=q.device)
-                ids = torch.empty((m, k), dtype=torch.int64, device=q.device)
-                if m:
-                    _check(self._lib, self._lib.icd_index_search(self._h, qs.data_ptr(), m, k, 1, mode, sc.data_ptr(),
-                                                                  ids.data_ptr(), 1, _current_stream_ptr(self.device)))
-            else:
-                sc = np.empty((m, k), dtype=np.float32)
-                ids = np.empty((m, k), dtype=np.int64)
-                if m:
-                    _check(self._lib, self._lib.icd_index_search(self._h, qs.ctypes.data, m, k, 0, mode, sc.ctypes.data,
-                                                                  ids.ctypes.data, 0, None))
-            out_s.append(sc)
-            out_i.append(ids)
-        if len(out_s) == 1:
-            return out_s[0], out_i[0]
-        if on_dev:
-            import torch
-            return torch.cat(out_s), torch.cat(out_i)
-        return np.concatenate(out_s), np.concatenate(out_i)
+
+        def call(qs, s0):
+            m = qs.shape[0]
+            (sc, ids), ptr, stream, dev = _outputs(on_dev, self.device, (m, k), (np.float32, np.int64))
+            if m:
+                _check(self._lib, self._lib.icd_index_search(self._h, ptr(qs), m, k, dev, mode, ptr(sc), ptr(ids), dev, stream))
+            return sc, ids
+        return _chunked(q, self.max_nq, on_dev, call)
 
     def search_reweighted(self, queries, k: int = 10, mode: int = MODE_AUTO):
         """Raw top-k, then adj = float64(score) * w[level] and a stable descending re-sort of the k hits
         (services/milvus_service.py:290-295,314). Returns (adj f64, raw f32, ids i64, levels i32), each [nq,k]."""
         q, on_dev = self._prep_queries(queries)
         self._validate(q, k)
-        nq = int(q.shape[0])
-        outs = []
-        for s0 in range(0, max(nq, 1), self.max_nq):
-            qs = q[s0:s0 + self.max_nq]
-            m = int(qs.shape[0])
-            if on_dev:
-                import torch
-                adj = torch.empty((m, k), dtype=torch.float64, device=q.device)
-                raw = torch.empty((m, k), dtype=torch.float32, device=q.device)
-                ids = torch.empty((m, k), dtype=torch.int64, device=q.device)
-                lv = torch.empty((m, k), dtype=torch.int32, device=q.device)
-                if m:
-                    _check(self._lib, self._lib.icd_index_search_reweighted(
-                        self._h, qs.data_ptr(), m, k, 1, mode, adj.data_ptr(), raw.data_ptr(), ids.data_ptr(),
-                        lv.data_ptr(), 1, _current_stream_ptr(self.device)))
-            else:
-                adj = np.empty((m, k), dtype=np.float64)
-                raw = np.empty((m, k), dtype=np.float32)
-                ids = np.empty((m, k), dtype=np.int64)
-                lv = np.empty((m, k), dtype=np.int32)
-                if m:
-                    _check(self._lib, self._lib.icd_index_search_reweighted(
-                        self._h, qs.ctypes.data, m, k, 0, mode, adj.ctypes.data, raw.ctypes.data, ids.ctypes.data,
-                        lv.ctypes.data, 0, None))
-            outs.append((adj, raw, ids, lv))
-        if len(outs) == 1:
-            return outs[0]
-        if on_dev:
-            import torch
-            return tuple(torch.cat([o[i] for o in outs]) for i in range(4))
-        return tuple(np.concatenate([o[i] for o in outs]) for i in range(4))
+
+        def call(qs, s0):
+            m = qs.shape[0]
+            (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (m, k), (np.float64, np.float32, np.int64, np.int32))
+            if m:
+                _check(self._lib, self._lib.icd_index_search_reweighted(self._h, ptr(qs), m, k, dev, mode, ptr(adj), ptr(raw), ptr(ids),
+                                                                         ptr(lv), dev, stream))
+            return adj, raw, ids, lv
+        return _chunked(q, self.max_nq, on_dev, call)
 
     # -- grouping search (Milvus group_by_field / group_size) ------------------------------------------
     def grouping(self, group_of, *, max_nq: Optional[int] = None) -> "IcdGrouping":
@@ -411,33 +474,17 @@ class IcdIndex:
         k, group_size = int(k), int(group_size)
         if k < 1 or group_size < 1 or k * group_size > MAX_K:
             raise ValueError(f"k={k}, group_size={group_size}: need k >= 1, group_size >= 1 and k * group_size <= {MAX_K}")
-        nq, w = int(q.shape[0]), k * group_size
-        outs = []
-        for s0 in range(0, max(nq, 1), grouping.max_nq):
-            qs = q[s0:s0 + grouping.max_nq]
-            m = int(qs.shape[0])
-            if on_dev:
-                import torch
-                mk = lambda dt: torch.empty((m, w), dtype=dt, device=q.device)
-                adj, raw, ids, lv, grp = mk(torch.float64), mk(torch.float32), mk(torch.int64), mk(torch.int32), mk(torch.int32)
-                ptr = lambda t: t.data_ptr()
-                stream = _current_stream_ptr(self.device)
-            else:
-                mk = lambda dt: np.empty((m, w), dtype=dt)
-                adj, raw, ids, lv, grp = mk(np.float64), mk(np.float32), mk(np.int64), mk(np.int32), mk(np.int32)
-                ptr = lambda t: t.ctypes.data
-                stream = None
+
+        def call(qs, s0):
+            m = qs.shape[0]
+            (adj, raw, ids, lv, grp), ptr, stream, dev = _outputs(on_dev, self.device, (m, k * group_size),
+                                                                  (np.float64, np.float32, np.int64, np.int32, np.int32))
             if m:
                 _check(self._lib, self._lib.icd_index_search_grouped(
-                    self._h, grouping._h, ptr(qs), m, k, group_size, 1 if on_dev else 0, 1 if reweighted else 0,
-                    ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(grp), 1 if on_dev else 0, stream))
-            outs.append((adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp))
-        if len(outs) == 1:
-            return outs[0]
-        if on_dev:
-            import torch
-            return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
-        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+                    self._h, grouping._h, ptr(qs), m, k, group_size, dev, 1 if reweighted else 0,
+                    ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(grp), dev, stream))
+            return (adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp)
+        return _chunked(q, grouping.max_nq, on_dev, call)
 
     # -- range search, offset, iterator pages (Milvus radius / range_filter, offset, search_iterator) ----
     def search_range(self, queries, k: int = 10, *, radius=None, range_filter=None, after=None, reweighted: bool = True):
@@ -469,91 +516,26 @@ class IcdIndex:
         q, on_dev = self._prep_queries(queries)
         self._validate(q, k)
         nq = int(q.shape[0])
-        mask_h = None
-        if masks is not None:
-            # [query] -> handle as a uint64 array, built without a Python loop over the queries (10 000 of them cost milliseconds
-            # in front of the launch): the distinct mask objects are found by identity and checked once each
-            if isinstance(masks, IcdRowMask):
-                uniq, inverse = [masks], np.zeros(nq, np.int64)
-            else:
-                masks = list(masks)
-                if len(masks) != nq:
-                    raise ValueError(f"masks holds {len(masks)} entries for {nq} queries")
-                ident = np.fromiter(map(id, masks), np.int64, nq)
-                _, first, inverse = np.unique(ident, return_index=True, return_inverse=True)
-                uniq = [masks[i] for i in first]
-            vals = np.zeros(max(len(uniq), 1), np.uint64)
-            for j, m_ in enumerate(uniq):
-                if m_ is None:
-                    continue
-                if not isinstance(m_, IcdRowMask):
-                    raise TypeError("masks: IcdRowMask or None per query")
-                if m_.closed:
-                    raise IcdError(-5, "a row mask is closed")
-                vals[j] = m_._h.value
-            mask_h = np.ascontiguousarray(vals[inverse.reshape(-1)]) if nq else np.zeros(1, np.uint64)   # (kept alive over the calls below)
+        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the calls below)
         a_sc, a_id = (None, None) if after is None else after
         if (a_sc is None) != (a_id is None):
             raise ValueError("after = (scores, ids): both or neither")
-        if on_dev:
-            import torch
+        bounds = [None if v is None else _bound(v, dt, (nq,), on_dev, self.device)
+                  for v, dt in ((radius, np.float32), (range_filter, np.float32), (a_sc, np.float32), (a_id, np.int64))]
 
-            def bound(v, dt):
-                if v is None:
-                    return None
-                t = torch.as_tensor(v).to(device=q.device, dtype=dt).reshape(-1)
-                if t.numel() == 1 and nq != 1:
-                    t = t.expand(nq)
-                if t.numel() != nq:
-                    raise ValueError(f"a bound holds {t.numel()} values for {nq} queries")
-                return t.contiguous()
-            f32, i64t = torch.float32, torch.int64
-        else:
-            def bound(v, dt):
-                if v is None:
-                    return None
-                if _is_torch_tensor(v):
-                    v = v.detach().cpu().numpy()
-                t = np.asarray(v, dtype=dt).reshape(-1)
-                if t.size == 1 and nq != 1:
-                    t = np.broadcast_to(t, (nq,))
-                if t.size != nq:
-                    raise ValueError(f"a bound holds {t.size} values for {nq} queries")
-                return np.ascontiguousarray(t)
-            f32, i64t = np.float32, np.int64
-        lo, hi, asc, aid = bound(radius, f32), bound(range_filter, f32), bound(a_sc, f32), bound(a_id, i64t)
-        outs = []
-        for s0 in range(0, max(nq, 1), self.max_nq):
-            qs = q[s0:s0 + self.max_nq]
-            m = int(qs.shape[0])
-            if on_dev:
-                mk = lambda dt: torch.empty((m, k), dtype=dt, device=q.device)
-                adj, raw, ids, lv = mk(torch.float64), mk(torch.float32), mk(torch.int64), mk(torch.int32)
-                ptr = lambda t: t.data_ptr()
-                stream = _current_stream_ptr(self.device)
-            else:
-                mk = lambda dt: np.empty((m, k), dtype=dt)
-                adj, raw, ids, lv = mk(np.float64), mk(np.float32), mk(np.int64), mk(np.int32)
-                ptr = lambda t: t.ctypes.data
-                stream = None
-            part = [None if b is None else b[s0:s0 + self.max_nq] for b in (lo, hi, asc, aid)]   # (kept alive over the call)
-            if m and mask_h is None:
-                _check(self._lib, self._lib.icd_index_search_range(
-                    self._h, ptr(qs), m, k, 1 if on_dev else 0, *[None if b is None else ptr(b) for b in part],
-                    1 if on_dev else 0, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv),
-                    1 if on_dev else 0, stream))
-            elif m:
-                _check(self._lib, self._lib.icd_index_search_masked(
-                    self._h, mask_h.ctypes.data + 8 * s0, ptr(qs), m, k, 1 if on_dev else 0,
-                    *[None if b is None else ptr(b) for b in part],
-                    1 if on_dev else 0, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv),
-                    1 if on_dev else 0, stream))
-            outs.append((adj, raw, ids, lv) if reweighted else (raw, ids, lv))
-        if len(outs) == 1:
-            return outs[0]
-        if on_dev:
-            return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
-        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+        def call(qs, s0):
+            m = qs.shape[0]
+            (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (m, k), (np.float64, np.float32, np.int64, np.int32))
+            if m:
+                part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
+                tail = (ptr(qs), m, k, dev, *[None if b is None else ptr(b) for b in part], dev, 1 if reweighted else 0,
+                        ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
+                if mask_h is None:
+                    _check(self._lib, self._lib.icd_index_search_range(self._h, *tail))
+                else:
+                    _check(self._lib, self._lib.icd_index_search_masked(self._h, mask_h.ctypes.data + 8 * s0, *tail))
+            return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
+        return _chunked(q, self.max_nq, on_dev, call)
 
     # -- hybrid search (Milvus hybrid_search over dense requests) -----------------------------------------
     def fusion(self, max_total: int) -> "IcdFusion":
@@ -574,20 +556,7 @@ class IcdIndex:
         tensors in -> device tensors out on torch's current stream."""
         if self.closed or fusion is None or fusion.closed:
             raise IcdError(-5, "index or fusion is closed")
-        on_dev = _is_torch_tensor(queries) and queries.is_cuda
-        if on_dev:
-            import torch
-            q = queries
-            if q.dtype != torch.float32 or not q.is_contiguous():
-                q = q.to(torch.float32).contiguous()
-            if q.device.index != self.device:
-                raise ValueError(f"queries on cuda:{q.device.index}, index on device {self.device}")
-        else:
-            if _is_torch_tensor(queries):
-                queries = queries.detach().cpu().numpy()
-            q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 2:
-            q = q[None]
+        q, on_dev = self._prep_queries(queries, rank=3)
         if q.ndim != 3 or q.shape[-1] != self.dim:
             raise ValueError(f"queries must be [nq, R, {self.dim}], got {tuple(q.shape)}")
         nq, R = int(q.shape[0]), int(q.shape[1])
@@ -605,53 +574,23 @@ class IcdIndex:
             if wts.size != R:
                 raise ValueError(f"weights holds {wts.size} entries for {R} requests")
         k = int(k)
-        total = nq * R
         mask_h = None
         if masks is not None:
             flat = []
             for m_ in masks:
                 flat.extend(m_ if isinstance(m_, (list, tuple)) else [m_])
-            if len(flat) != total:
-                raise ValueError(f"masks holds {len(flat)} entries for {nq} x {R} sub-searches")
-            mask_h = np.zeros(max(total, 1), np.uint64)
-            for j, m_ in enumerate(flat):
-                if m_ is None:
-                    continue
-                if not isinstance(m_, IcdRowMask):
-                    raise TypeError("masks: IcdRowMask or None per (query, request)")
-                if m_.closed:
-                    raise IcdError(-5, "a row mask is closed")
-                mask_h[j] = m_._h.value
+            mask_h = _mask_table(flat, nq * R, f"{nq} x {R} sub-searches", "(query, request)")
             if not mask_h.any():
                 mask_h = None
-
-        def bound(v):
-            if v is None:
-                return None
-            if on_dev:
-                t = torch.as_tensor(v).to(device=q.device, dtype=torch.float32)
-                return t.expand(nq, R).contiguous().reshape(-1) if t.numel() != total else t.contiguous().reshape(-1)
-            if _is_torch_tensor(v):
-                v = v.detach().cpu().numpy()
-            t = np.asarray(v, dtype=np.float32)
-            return np.ascontiguousarray(np.broadcast_to(t, (nq, R)) if t.size != total else t).reshape(-1)
-        lo, hi = bound(radius), bound(range_filter)
-        if on_dev:
-            mk = lambda dt: torch.empty((nq, k), dtype=dt, device=q.device)
-            adj, fused, ids, lv, bits = mk(torch.float64), mk(torch.float64), mk(torch.int64), mk(torch.int32), mk(torch.int32)
-            ptr = lambda t: t.data_ptr()
-            stream = _current_stream_ptr(self.device)
-        else:
-            mk = lambda dt: np.empty((nq, k), dtype=dt)
-            adj, fused, ids, lv, bits = mk(np.float64), mk(np.float64), mk(np.int64), mk(np.int32), mk(np.uint32)
-            ptr = lambda t: t.ctypes.data
-            stream = None
+        lo, hi = (_bound(v, np.float32, (nq, R), on_dev, self.device) for v in (radius, range_filter))
+        (adj, fused, ids, lv, bits), ptr, stream, dev = _outputs(
+            on_dev, self.device, (nq, k), (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32))
         rc = self._lib.icd_index_search_hybrid(
-            self._h, fusion._h, ptr(q) if nq else None, nq, R, 1 if on_dev else 0, lim.ctypes.data,
+            self._h, fusion._h, ptr(q) if nq else None, nq, R, dev, lim.ctypes.data,
             None if mask_h is None else mask_h.ctypes.data, None if lo is None else ptr(lo), None if hi is None else ptr(hi),
-            1 if on_dev else 0, int(mode), RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c),
+            dev, int(mode), RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c),
             None if wts is None else wts.ctypes.data, NORMS[norm], k, 1 if reweighted else 0,
-            ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), 1 if on_dev else 0, stream)
+            ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), dev, stream)
         _check(self._lib, rc)
         return (adj, fused, ids, lv, bits) if reweighted else (fused, ids, lv, bits)
 
@@ -693,9 +632,10 @@ class IcdIndex:
         return {f: float(getattr(p, f)) for f, _ in _Profile._fields_}
 
 
-class IcdGrouping:
+class IcdGrouping(_Handle):
     """Rows of one IcdIndex ordered by group, with the workspace of the grouped searches (icd_grouping_*). Independent of the
     index's lifetime: either may be closed first (a search with a closed partner raises)."""
+    _destroy = "icd_grouping_destroy"
 
     def __init__(self, index: "IcdIndex", group_of, max_nq: int):
         self._lib = index._lib
@@ -728,25 +668,11 @@ class IcdGrouping:
         _check(self._lib, self._lib.icd_grouping_stats(self._h, C.byref(g), C.byref(m), C.byref(b)))
         return {"groups": g.value, "largest_group": m.value, "bytes": b.value}
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.icd_grouping_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def closed(self) -> bool:
-        return not self._h.value
-
-
-class IcdFusion:
+class IcdFusion(_Handle):
     """The workspace of one IcdIndex's hybrid searches (icd_fusion_*): staging for max_total = nq * R sub-lists of 128 hits and
     for host callers. Independent of the index's lifetime: either may be closed first (a search with a closed partner raises)."""
+    _destroy = "icd_fusion_destroy"
 
     def __init__(self, index: "IcdIndex", max_total: int):
         self._lib = index._lib
@@ -760,21 +686,6 @@ class IcdFusion:
         t, b = C.c_int64(), C.c_int64()
         _check(self._lib, self._lib.icd_fusion_stats(self._h, C.byref(t), C.byref(b)))
         return {"max_total": t.value, "bytes": b.value}
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.icd_fusion_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def closed(self) -> bool:
-        return not self._h.value
 
 
 def rowmask_words(n: int) -> int:
@@ -795,9 +706,10 @@ def pack_rowmask(rows, n: int) -> np.ndarray:
     return out
 
 
-class IcdRowMask:
+class IcdRowMask(_Handle):
     """A set of rows of one IcdIndex as a device bitset (icd_rowmask_*): what search_masked tests inside the scan. Independent
     of the index's lifetime: either may be closed first (a search with a closed partner raises)."""
+    _destroy = "icd_rowmask_destroy"
 
     def __init__(self, index: "IcdIndex", rows):
         self._lib = index._lib
@@ -826,21 +738,6 @@ class IcdRowMask:
         r, b = C.c_int64(), C.c_int64()
         _check(self._lib, self._lib.icd_rowmask_stats(self._h, C.byref(r), C.byref(b)))
         return {"rows": r.value, "bytes": b.value}
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.icd_rowmask_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def closed(self) -> bool:
-        return not self._h.value
 
 
 def group_unique_id() -> bytes:

@@ -537,8 +537,7 @@ int icd_encoder_encode(icd_encoder *e, const int32_t *ids, const int32_t *length
         if (ids[t] < 0 || ids[t] >= d.vocab) return fail(ICD_ERR_INVALID, "token %d: id %d outside the vocabulary of %d", t, ids[t], d.vocab);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+    const bool capturing = stream_capturing(s);
     if (capturing && !out_on_device) return fail(ICD_ERR_INVALID, "a call with a host output synchronises: it cannot be captured into a graph");
     if (capturing) return fail(ICD_ERR_UNSUPPORTED, "icd_encoder_encode reads its token ids from host memory at call time: it cannot be captured into a graph");
     // the previous launch's copy node may not have read h_meta yet (device outputs: the call did not wait)
@@ -581,8 +580,7 @@ int icd_encoder_encode_many(icd_encoder *e, const int32_t *ids, const int32_t *l
         if (ids[t] < 0 || ids[t] >= d.vocab) return fail(ICD_ERR_INVALID, "token %lld: id %d outside the vocabulary of %d", (long long)t, ids[t], d.vocab);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive)
+    if (stream_capturing(s))
         return fail(ICD_ERR_UNSUPPORTED, "icd_encoder_encode_many reads its token ids from host memory at call time: it cannot be captured into a graph");
     // (a device-output call of icd_encoder_encode may still be reading h_meta: not touched here; d_meta and the activations are
     //  protected by stream order, across streams by ev_tail)

@@ -1,0 +1,158 @@
+// icd_grouped.hpp - the grouping search (icd_grouping_*, icd_index_search_grouped). Part of icd_search.hip's translation unit (fail(),
+// HIP_TRY, the owned-handle and host-call helpers); included there and nowhere else.
+#pragma once
+
+// ---- grouping search (group_topk.hpp) ----------------------------------------------------------------
+// A grouping belongs to the index it was created for (n rows, the same device) but keeps no pointer into it: the handle is
+// compared, never followed, outside a search that is given both. Its workspace - the score block S, the per-group keys, the
+// staging of host callers - is allocated here, never inside a search.
+struct icd_grouping : OwnedHandle {
+    static constexpr uint32_t MAGIC = 0x1CD96B0Fu;
+    static constexpr const char *NOUN = "grouping";
+    int G = 0, largest = 0, max_nq = 0, qb = 0;
+    long long ldS = 0;
+    int *group_of = nullptr, *dense_of = nullptr, *order = nullptr, *gpos = nullptr, *seg = nullptr;
+    float *S = nullptr;
+    u64 *best = nullptr;
+    float *qdev = nullptr;
+    double *o_adj = nullptr; float *o_raw = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr, *o_grp = nullptr;
+    std::mutex mu;
+};
+
+namespace {
+constexpr int GROUP_QUERY_BLOCK = 512;   // queries scored per pass: S = 512 x 40 576 x 4 B = 83 MB stays in the 256-MiB Infinity Cache next to the 124-MB corpus
+}  // namespace
+
+extern "C" {
+
+int icd_grouping_create(icd_index *idx, const int32_t *group_of, int64_t n, int32_t on_device, int32_t max_nq, icd_grouping **out) {
+    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!group_of) return fail(ICD_ERR_INVALID, "group_of is NULL");
+    if (n != idx->n) return fail(ICD_ERR_INVALID, "group_of holds %lld ids, the index %lld rows", (long long)n, (long long)idx->n);
+    if (n >= 0x7FFFFFFFll) return fail(ICD_ERR_UNSUPPORTED, "n=%lld: a grouping addresses rows with 31 bits", (long long)n);
+    if (max_nq <= 0) return fail(ICD_ERR_INVALID, "max_nq=%d", max_nq);
+    HIP_TRY(hipSetDevice(idx->device));
+    std::vector<int> ids((size_t)n);
+    if (on_device) HIP_TRY(hipMemcpy(ids.data(), group_of, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    else memcpy(ids.data(), group_of, (size_t)n * sizeof(int));
+    for (int64_t i = 0; i < n; ++i)
+        if (ids[i] < 0) return fail(ICD_ERR_INVALID, "group_of[%lld]=%d: group ids are non-negative (-1 marks padding in the outputs)", (long long)i, ids[i]);
+    // rows in (group, row) order; dense group numbers in the order of the caller's ids
+    std::vector<int> order((size_t)n), gpos((size_t)n), dense((size_t)n), seg;
+    for (int64_t i = 0; i < n; ++i) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ids[a] < ids[b]; });
+    int largest = 0;
+    for (int64_t p = 0; p < n; ++p) {
+        if (p == 0 || ids[order[p]] != ids[order[p - 1]]) {
+            if (!seg.empty()) largest = std::max(largest, (int)p - seg.back());
+            seg.push_back((int)p);
+        }
+        gpos[p] = (int)seg.size() - 1;
+        dense[order[p]] = gpos[p];
+    }
+    largest = std::max(largest, (int)n - seg.back());
+    const int G = (int)seg.size();
+    seg.push_back((int)n);
+
+    icd_grouping *g = new_handle<icd_grouping>(idx);
+    if (!g) return fail(ICD_ERR_NOMEM, "host allocation failed");
+    g->G = G; g->largest = largest; g->max_nq = max_nq;
+    g->qb = std::min(GROUP_QUERY_BLOCK, (max_nq + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE);
+    g->ldS = ((long long)n + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE;
+    const size_t no = (size_t)max_nq * ICD_MAX_K;
+#define GR_TRY(expr) HIP_TRY_OR(free_handle(g), expr)
+    GR_TRY(g->alloc(&g->group_of, (size_t)n)); GR_TRY(g->alloc(&g->dense_of, (size_t)n)); GR_TRY(g->alloc(&g->order, (size_t)n));
+    GR_TRY(g->alloc(&g->gpos, (size_t)n)); GR_TRY(g->alloc(&g->seg, (size_t)G + 1));
+    GR_TRY(g->alloc(&g->S, (size_t)g->qb * g->ldS)); GR_TRY(g->alloc(&g->best, (size_t)g->qb * G));
+    GR_TRY(g->alloc(&g->qdev, (size_t)max_nq * idx->dim));
+    GR_TRY(g->alloc(&g->o_adj, no)); GR_TRY(g->alloc(&g->o_raw, no)); GR_TRY(g->alloc(&g->o_ids, no)); GR_TRY(g->alloc(&g->o_lv, no)); GR_TRY(g->alloc(&g->o_grp, no));
+    GR_TRY(hipMemcpy(g->group_of, ids.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->dense_of, dense.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->order, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->gpos, gpos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    GR_TRY(hipMemcpy(g->seg, seg.data(), ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice));
+#undef GR_TRY
+    g->bytes = (size_t)n * 20 + ((size_t)G + 1) * 4 + (size_t)g->qb * g->ldS * 4 + (size_t)g->qb * G * 8 + (size_t)max_nq * idx->dim * 4 + no * 28;
+    *out = g;
+    return ICD_OK;
+}
+
+int icd_grouping_destroy(icd_grouping *grouping) { return destroy_handle(grouping); }
+
+int icd_grouping_stats(icd_grouping *grouping, int64_t *out_groups, int64_t *out_largest, int64_t *out_bytes) {
+    if (!valid_handle(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    if (out_groups) *out_groups = grouping->G;
+    if (out_largest) *out_largest = grouping->largest;
+    if (out_bytes) *out_bytes = (int64_t)grouping->bytes;
+    return ICD_OK;
+}
+
+int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float *queries, int64_t nq, int32_t k, int32_t group_size,
+                             int32_t queries_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                             int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream) {
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    icd_grouping *g = grouping;
+    if (const int rc = check_owner(g->at, idx, "the grouping")) return rc;
+    if (k < 1 || group_size < 1 || (int64_t)k * group_size > ICD_MAX_K)
+        return fail(ICD_ERR_INVALID, "k=%d group_size=%d: need k >= 1, group_size >= 1 and k * group_size <= %d", k, group_size, ICD_MAX_K);
+    if (nq < 0 || nq > g->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the grouping's max_nq=%d", (long long)nq, g->max_nq);
+    if (!out_ids || !out_raw || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (nq == 0) return ICD_OK;
+    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
+    std::lock_guard<std::mutex> guard(g->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
+    int rc = check_capture(s, !queries_on_device || !out_on_device, false, false);
+    if (rc) return rc;
+    const float *dq;
+    if ((rc = hc.upload(queries, g->qdev, (size_t)nq * idx->dim, &dq))) return rc;
+    double *d_adj = hc.target(out_adj, g->o_adj); float *d_raw = hc.target(out_raw, g->o_raw);
+    long long *d_ids = hc.target(reinterpret_cast<long long *>(out_ids), g->o_ids);
+    int *d_lv = hc.target(out_levels, g->o_lv), *d_grp = hc.target(out_groups, g->o_grp);
+    const int n = (int)g->at.n;
+    const int ks = k * group_size;
+    const int ntiles = (int)(g->ldS / GROUP_TILE);
+    const bool small_kp = k <= 16 && group_size <= 16;
+    for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {
+        const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
+        GroupScoreArgs sa{};
+        sa.corpus = idx->corpus; sa.queries = dq + (size_t)q0 * idx->dim; sa.order = g->order;
+        sa.nq = nb; sa.n = n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
+        sa.S = g->S; sa.ldS = g->ldS;
+        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)(ntiles * sa.mtiles)), dim3(256), 0, s, sa);
+        HIP_TRY(hipGetLastError());
+
+        HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
+        GroupBestArgs ba{};
+        ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
+        ba.nq = nb; ba.n = n; ba.G = g->G; ba.best = g->best;
+        ba.R = nb >= 64 ? 1024 : 128;
+        ba.nranges = (n + ba.R - 1) / ba.R;
+        constexpr int QW = 4;
+        const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
+        hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
+        HIP_TRY(hipGetLastError());
+
+        GroupFinishArgs fa{};
+        fa.best = g->best; fa.S = g->S; fa.ldS = g->ldS; fa.order = g->order; fa.seg = g->seg; fa.dense_of = g->dense_of;
+        fa.nq = nb; fa.G = g->G; fa.k = k; fa.s = group_size; fa.q_base = (int)q0;
+        fa.fin.k = ks; fa.fin.levels = idx->levels; fa.fin.id_base = idx->id_base; fa.fin.row_map = idx->row_map; fa.fin.groups = g->group_of;
+        if (reweighted) {
+            fa.fin.out_adj = d_adj; fa.fin.out_adj_raw = d_raw; fa.fin.out_adj_ids = d_ids; fa.fin.out_adj_levels = d_lv; fa.fin.out_adj_groups = d_grp;
+        } else {
+            fa.fin.out_scores = d_raw; fa.fin.out_ids = d_ids; fa.fin.out_levels = d_lv; fa.fin.out_groups = d_grp;
+        }
+        if (small_kp) hipLaunchKernelGGL((group_finish_kernel<16, 2>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
+        else hipLaunchKernelGGL((group_finish_kernel<128, 4>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = hc.copy_back({{out_adj, d_adj, 8}, {out_raw, d_raw, 4}, {out_ids, d_ids, 8}, {out_levels, d_lv, 4}, {out_groups, d_grp, 4}}, (size_t)nq * ks)))
+        return rc;
+    return hc.finish();
+}
+
+}  // extern "C"

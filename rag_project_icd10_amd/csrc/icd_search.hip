@@ -91,6 +91,16 @@ namespace {
                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                         \
     } while (0)
 
+// ... with something to unwind first: a half-built index or owned handle (the ONE allocate-or-free-everything form)
+#define HIP_TRY_OR(undo, expr)                                                                                             \
+    do {                                                                                                                   \
+        hipError_t e_ = (expr);                                                                                            \
+        if (e_ != hipSuccess) {                                                                                            \
+            undo;                                                                                                          \
+            return fail(e_ == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+        }                                                                                                                  \
+    } while (0)
+
 constexpr float EPS_REL = 1.2e-3f;
 constexpr size_t PACE_WORDS = (size_t)1 << 18;   // arrival counters of a paced coarse sweep: classes x epochs (1 MB)
 constexpr size_t COARSE_CACHED_IMAGE_BYTES = (size_t)96 << 20;   // fp16 images up to this size take CF_CACHED_VAR (both corpus copies then fit the 256 MiB Infinity Cache)
@@ -212,7 +222,7 @@ struct icd_index {
     int prof_every = 1;            // events on every prof_every-th search (a recorded event keeps the next kernel from
     long prof_tick = 0;            // overlapping the previous one's tail: sampling keeps that cost out of a timed region)
     bool prof_now = false;
-    bool capturing = false;        // the current search is being captured into a HIP graph (search_common): no event queries, no host-side adaptation
+    bool capturing = false;        // the current search is being captured into a HIP graph (run_search): no event queries, no host-side adaptation
     hipEvent_t evring[EV_RING][NUM_EV + 1] = {};
     bool evring_valid[EV_RING][NUM_EV + 1] = {};
     long prof_count = 0;           // profiled searches since the last summary
@@ -740,7 +750,7 @@ int run_exact(const SearchCtx &c, const int *qlist, const int *nq_ptr, int px, b
     return rc;
 }
 
-// a host caller's ONE query whose copy search_common left out (host_q): every path but the single-launch kernel wants it
+// a host caller's ONE query whose copy run_search left out (host_q): every path but the single-launch kernel wants it
 // in device memory after all - the copy it would have got, enqueued before anything that reads dq
 int stage_host_query(const SearchCtx &c) {
     icd_index *x = c.x;
@@ -781,13 +791,13 @@ int search_tiny(const SearchCtx &c) {
     if (one) {   // up to four queries (the reference's call shape is ONE; a /query request batches its D diagnoses): ONE launch,
                  // no memset, no reduction, no finalize
         rec(x, 3, s);
-        const float *hq = qb1 == 1 ? x->host_q : nullptr;   // (a host caller's ONE query: search_common left the copy out)
+        const float *hq = qb1 == 1 ? x->host_q : nullptr;   // (a host caller's ONE query: run_search left the copy out)
         if (!hq) { const int rcq = stage_host_query(c); if (rcq) return rcq; }
         const bool poll = x->host_one_call && (x->opt_host_one & 2) != 0;
         if (c.band) {   // a page of a range search: still ONE launch (host-packed bands travel in the arguments)
             BandArgs b = *c.band;
             if (x->band_pending > 0) { b.q = nullptr; x->band_pending = 0; }
-            if (c.mask) {   // (the pointer table is in device memory already: search_common copied it)
+            if (c.mask) {   // (the pointer table is in device memory already: run_search copied it)
                 const int rcm = qb1 == 1 ? launch_stream_one<16, 2, 1, true, true>(x, c.dq, 1, c.f, s, hq, poll, &b, c.mask)
                               : qb1 == 2 ? launch_stream_one<16, 2, 2, true, true>(x, c.dq, 2, c.f, s, nullptr, false, &b, c.mask)
                                          : launch_stream_one<16, 2, 4, true, true>(x, c.dq, (int)nq, c.f, s, nullptr, false, &b, c.mask);
@@ -1227,16 +1237,7 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
     x->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const bool fast_dim = (dim == 768 || dim == 1024);
 
-#define CR_TRY(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            free_all(x);                                                                             \
-            return fail(e_ == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "%s: %s", #expr,    \
-                        hipGetErrorString(e_));                                                      \
-        }                                                                                            \
-    } while (0)
-
+#define CR_TRY(expr) HIP_TRY_OR(free_all(x), expr)
     const size_t nelem = (size_t)n * dim;
     // ST_PAD_ROWS zero rows behind the corpus: the streaming kernel's stages run to the next 256-row boundary
     CR_TRY(dmalloc(&x->corpus, nelem + (size_t)ST_PAD_ROWS * dim));
@@ -1414,28 +1415,136 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
     return ICD_OK;
 }
 
-// The bounds of a range search as the caller gave them (icd_index_search_range): packed into BandQ inside search_common, under
-// the handle's mutex.
-struct RangeBounds {
-    const float *radius, *range_filter, *after_scores;
-    const long long *after_ids;
-    bool on_device;
-};
-static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s, BandArgs *out);
+// ---- what the search entry points share ----------------------------------------------------------------------------------------
+// One body per concern; every entry family (plain, reweighted, range, masked, grouped, hybrid) goes through these.
 
-// ---- row masks (icd_rowmask_create) ---------------------------------------------------------------------
-// A mask belongs to the index it was created for but keeps no pointer into it: handle and identity are compared, never followed.
-struct icd_rowmask {
-    uint32_t magic = 0x1CD3A5C1u;
+// The identity of the index an owned handle (row mask, grouping, fusion) was created for. A handle keeps no pointer INTO the index:
+// address and identity are compared, never followed. The uid tells an index re-created at the address of a closed one from it.
+struct OwnerStamp {
     const icd_index *owner = nullptr;
-    unsigned long long owner_uid = 0;
-    int device = 0;
-    int64_t n = 0, rows = 0;
-    uint32_t *bits = nullptr;   // [rowmask_tile_words(n) + ROWMASK_TAIL_WORDS]
-    size_t bytes = 0;
+    unsigned long long uid = 0;
+    int device = 0, dim = 0;
+    int64_t n = 0;
+    void stamp(const icd_index *idx) { owner = idx; uid = idx->uid; device = idx->device; dim = idx->dim; n = idx->n; }
+    bool belongs_to(const icd_index *idx) const { return owner == idx && uid == idx->uid && device == idx->device && dim == idx->dim && n == idx->n; }
 };
-static bool valid_rowmask(const icd_rowmask *m) { return m && m->magic == 0x1CD3A5C1u; }
-static int stage_masks(icd_index *x, icd_rowmask *const *masks, int nq, hipStream_t s);
+static int check_owner(const OwnerStamp &at, const icd_index *idx, const char *what, long long entry = -1) {
+    if (at.belongs_to(idx)) return ICD_OK;
+    char name[48];
+    if (entry >= 0) { snprintf(name, sizeof name, "%s[%lld]", what, entry); what = name; }   // (an entry of a table)
+    return fail(ICD_ERR_INVALID, "%s was created for another index", what);
+}
+
+// What the three owned handles are made of: magic, stamp, and their device allocations - everything alloc() handed out goes in
+// free_handle. Each handle type adds MAGIC, NOUN (its name in messages) and its own fields.
+struct OwnedHandle {
+    uint32_t magic = 0;
+    OwnerStamp at;
+    std::vector<void *> allocs;
+    size_t bytes = 0;
+    template <typename T>
+    hipError_t alloc(T **p, size_t count) {
+        const hipError_t e = dmalloc(p, count);
+        if (e == hipSuccess) allocs.push_back(*p);
+        return e;
+    }
+};
+template <typename H>
+H *new_handle(const icd_index *idx) {
+    H *h = new (std::nothrow) H();
+    if (h) { h->magic = H::MAGIC; h->at.stamp(idx); }
+    return h;
+}
+template <typename H>
+bool valid_handle(const H *h) { return h && h->magic == H::MAGIC; }
+template <typename H>
+void free_handle(H *h) {
+    if (!h) return;
+    for (void *p : h->allocs) hipFree(p);
+    h->magic = 0;
+    delete h;
+}
+template <typename H>
+int destroy_handle(H *h) {
+    if (!valid_handle(h)) return fail(ICD_ERR_STATE, "invalid %s handle", H::NOUN);
+    hipSetDevice(h->at.device);
+    hipDeviceSynchronize();
+    free_handle(h);
+    return ICD_OK;
+}
+
+// The capture state of a stream and what it forbids. Device-in / device-out searches are graph-capturable (no allocation, no
+// synchronisation, no query while capturing); whatever synchronises or is staged on the host at call time is refused.
+static bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+}
+static int check_capture(hipStream_t s, bool host_buffers, bool host_bounds, bool mask_table, bool *capturing = nullptr) {
+    const bool on = stream_capturing(s);
+    if (capturing) *capturing = on;
+    if (!on) return ICD_OK;
+    if (host_buffers) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
+    if (host_bounds) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
+    if (mask_table) return fail(ICD_ERR_INVALID, "a masked search stages its mask table on the host at call time: it cannot be captured into a graph");
+    return ICD_OK;
+}
+
+// A call whose queries or outputs may be host memory: the queries go to a device staging, the kernels write to device staging in
+// place of host outputs, the outputs are copied back behind them and the call ends with ONE stream synchronisation.
+struct HostOut { void *host; const void *dev; size_t elem; };   // (host == nullptr: an output the caller did not ask for)
+struct HostCall {
+    hipStream_t s;
+    bool q_on_device, out_on_device;
+    int upload(const float *src, float *staging, size_t floats, const float **dq) const {
+        *dq = src;
+        if (q_on_device) return ICD_OK;
+        HIP_TRY(hipMemcpyAsync(staging, src, floats * sizeof(float), hipMemcpyHostToDevice, s));
+        *dq = staging;
+        return ICD_OK;
+    }
+    template <typename T>
+    T *target(T *user, T *staging) const { return (user && !out_on_device) ? staging : user; }   // where the kernels write this output
+    int copy_back(std::initializer_list<HostOut> outs, size_t slots) const {
+        if (out_on_device) return ICD_OK;
+        for (const HostOut &o : outs)
+            if (o.host) HIP_TRY(hipMemcpyAsync(o.host, o.dev, slots * o.elem, hipMemcpyDeviceToHost, s));
+        return ICD_OK;
+    }
+    int finish(bool also = false) const {
+        if (!q_on_device || !out_on_device || also) HIP_TRY(hipStreamSynchronize(s));
+        return ICD_OK;
+    }
+};
+
+struct RangeBounds;
+// ONE dense search as every entry point hands it to run_search, its own arguments already checked.
+struct SearchRequest {
+    const float *queries;
+    int64_t nq;
+    int k;
+    bool q_on_device, out_on_device;
+    int mode;
+    Outs outs;
+    const RangeBounds *range;       // nullptr: no band
+    icd_rowmask *const *masks;      // nullptr: no mask table (never an all-NULL table: that is the range search)
+    hipStream_t stream;
+    const bool *capture_checked = nullptr;   // the stream's capture state when the caller has run check_capture for this very request (hybrid)
+};
+static int run_search(icd_index *x, const SearchRequest &r);
+
+// the outputs of the raw (scores, ids, levels) or the reweighted (adj, raw, ids, levels) form
+static Outs outs_for(bool reweighted, double *adj, float *raw, int64_t *ids, int *levels) {
+    Outs o{};
+    if (reweighted) {
+        o.adj = adj; o.adj_raw = raw; o.adj_ids = reinterpret_cast<long long *>(ids); o.adj_lv = levels;
+    } else {
+        o.scores = raw; o.ids = reinterpret_cast<long long *>(ids); o.lv = levels;
+    }
+    return o;
+}
+
+// range and masked search: the bounds, the row masks, their two entry points
+#include "icd_range_mask.hpp"
 
 extern "C" {
 
@@ -1497,67 +1606,63 @@ static void copy_pinned_out(icd_index *x, const Outs &user, size_t no_small) {
     else if (user.lv) memcpy(user.lv, h, no_small * 4);
 }
 
-static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t k, int32_t q_on_device,
-                         int32_t mode, Outs user, int32_t out_on_device, void *stream, const RangeBounds *range = nullptr,
-                         icd_rowmask *const *masks = nullptr) {
+}  // extern "C"
+
+// The internal search call: takes the handle's mutex, owns the capture flags, packs the bands and stages the mask table. The
+// public entry points and the hybrid search's step 1 call it with a request whose own arguments they have checked; what is
+// checked here is the request against THIS index.
+static int run_search(icd_index *x, const SearchRequest &r) {
     if (!valid(x)) return fail(ICD_ERR_STATE, "invalid handle");
     std::lock_guard<std::mutex> guard(x->mu);
+    const int64_t nq = r.nq;
+    const int k = r.k;
     if (nq < 0 || nq > x->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds max_nq=%d", (long long)nq, x->max_nq);
     if (k <= 0 || k > x->max_k) return fail(ICD_ERR_INVALID, "k=%d exceeds max_k=%d", k, x->max_k);
-    if (mode != ICD_MODE_AUTO && mode != ICD_MODE_EXACT) return fail(ICD_ERR_INVALID, "mode=%d", mode);
+    if (r.mode != ICD_MODE_AUTO && r.mode != ICD_MODE_EXACT) return fail(ICD_ERR_INVALID, "mode=%d", r.mode);
     if (nq == 0) return ICD_OK;
-    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
+    if (!r.queries) return fail(ICD_ERR_INVALID, "queries is NULL");
     HIP_TRY(hipSetDevice(x->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    {   // device-in / device-out searches are graph-capturable (no allocation, no synchronisation, no query while capturing)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        x->capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-        if (x->capturing && (!q_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
-        if (x->capturing && range && !range->on_device) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
-        if (x->capturing && masks) return fail(ICD_ERR_INVALID, "a masked search stages its mask table on the host at call time: it cannot be captured into a graph");
-    }
-    if (masks) { const int rcm = stage_masks(x, masks, (int)nq, s); if (rcm) return rcm; }
+    hipStream_t s = r.stream;
+    const HostCall hc{s, r.q_on_device, r.out_on_device};
+    const bool host_bands = r.range && !r.range->on_device;
+    int rc = ICD_OK;
+    if (r.capture_checked) x->capturing = *r.capture_checked;
+    else if ((rc = check_capture(s, !r.q_on_device || !r.out_on_device, host_bands, r.masks != nullptr, &x->capturing))) return rc;
+    if (r.masks && (rc = stage_masks(x, r.masks, (int)nq, s))) return rc;
     BandArgs band{};
     x->band_pending = 0;
-    if (range) { const int rcb = pack_bands(x, *range, (int)nq, s, &band); if (rcb) return rcb; }
-    const bool host_bands = range && !range->on_device;
-    const float *dq = queries;
-    if (!q_on_device) {
-        const size_t qbytes = (size_t)nq * x->dim * sizeof(float);
-        if (nq == 1 && (x->opt_host_one & 1) && qbytes <= sizeof(StreamInlineQuery) && !x->capturing) {
-            x->host_q = queries;   // ONE query: search_device puts it into the single-launch kernel's arguments (or copies it after all)
-        } else if (qbytes <= PIN_Q_BYTES) {
-            memcpy(x->h_pin, queries, qbytes);
-            HIP_TRY(hipMemcpyAsync(x->qdev, x->h_pin, qbytes, hipMemcpyHostToDevice, s));
-        } else {
-            HIP_TRY(hipMemcpyAsync(x->qdev, queries, qbytes, hipMemcpyHostToDevice, s));
-        }
-        dq = x->qdev;
+    if (r.range && (rc = pack_bands(x, *r.range, (int)nq, s, &band))) return rc;
+    const float *dq = x->qdev;
+    const size_t qbytes = (size_t)nq * x->dim * sizeof(float);
+    if (!r.q_on_device && nq == 1 && (x->opt_host_one & 1) && qbytes <= sizeof(StreamInlineQuery) && !x->capturing) {
+        x->host_q = r.queries;   // ONE query: search_device puts it into the single-launch kernel's arguments (or copies it after all)
+    } else {
+        const float *src = r.queries;
+        if (!r.q_on_device && qbytes <= PIN_Q_BYTES) { memcpy(x->h_pin, src, qbytes); src = reinterpret_cast<const float *>(x->h_pin); }
+        if ((rc = hc.upload(src, x->qdev, (size_t)nq * x->dim, &dq))) return rc;
     }
+    const Outs &user = r.outs;
     Outs dev = user;
-    const size_t no_small = (size_t)nq * k;
-    const bool pinned_out = !out_on_device && no_small * 36 <= PIN_OUT_BYTES;
+    const size_t no = (size_t)nq * k;
+    const bool pinned_out = !r.out_on_device && no * 36 <= PIN_OUT_BYTES;
     if (pinned_out) {   // the six arrays back to back in the mapped block, 8-byte ones first
         char *d = x->h_pin_dev + PIN_Q_BYTES;
-        dev.adj = user.adj ? reinterpret_cast<double *>(d) : nullptr;                          d += no_small * 8;
-        dev.ids = user.ids ? reinterpret_cast<long long *>(d) : nullptr;                       d += no_small * 8;
-        dev.adj_ids = user.adj_ids ? reinterpret_cast<long long *>(d) : nullptr;               d += no_small * 8;
-        dev.scores = user.scores ? reinterpret_cast<float *>(d) : nullptr;                     d += no_small * 4;
-        dev.adj_raw = user.adj_raw ? reinterpret_cast<float *>(d) : nullptr;                   d += no_small * 4;
+        dev.adj = user.adj ? reinterpret_cast<double *>(d) : nullptr;                          d += no * 8;
+        dev.ids = user.ids ? reinterpret_cast<long long *>(d) : nullptr;                       d += no * 8;
+        dev.adj_ids = user.adj_ids ? reinterpret_cast<long long *>(d) : nullptr;               d += no * 8;
+        dev.scores = user.scores ? reinterpret_cast<float *>(d) : nullptr;                     d += no * 4;
+        dev.adj_raw = user.adj_raw ? reinterpret_cast<float *>(d) : nullptr;                   d += no * 4;
         dev.adj_lv = user.adj_lv ? reinterpret_cast<int *>(d) : nullptr;
         dev.lv = (user.lv && !user.adj_lv) ? reinterpret_cast<int *>(d) : nullptr;
-    } else if (!out_on_device) {
-        dev.scores = user.scores ? x->o_scores : nullptr;
-        dev.ids = user.ids ? x->o_ids : nullptr;
-        dev.adj = user.adj ? x->o_adj : nullptr;
-        dev.adj_raw = user.adj_raw ? x->o_adj_raw : nullptr;
-        dev.adj_ids = user.adj_ids ? x->o_adj_ids : nullptr;
-        dev.adj_lv = user.adj_lv ? x->o_adj_lv : nullptr;
-        dev.lv = (user.lv && !user.adj_lv) ? x->o_adj_lv : nullptr;
+    } else {
+        dev.scores = hc.target(user.scores, x->o_scores); dev.ids = hc.target(user.ids, x->o_ids);
+        dev.adj = hc.target(user.adj, x->o_adj); dev.adj_raw = hc.target(user.adj_raw, x->o_adj_raw);
+        dev.adj_ids = hc.target(user.adj_ids, x->o_adj_ids);
+        dev.adj_lv = hc.target(user.adj_lv, x->o_adj_lv); dev.lv = hc.target(user.lv, x->o_adj_lv);   // (never both: Outs)
     }
     x->done_armed = false;
-    x->host_one_call = !q_on_device && nq == 1 && pinned_out && !x->capturing;
-    int rc = search_device(x, dq, (int)nq, k, mode, dev, s, range ? &band : nullptr, masks ? x->mask_dev : nullptr);
+    x->host_one_call = !r.q_on_device && nq == 1 && pinned_out && !x->capturing;
+    rc = search_device(x, dq, (int)nq, k, r.mode, dev, s, r.range ? &band : nullptr, r.masks ? x->mask_dev : nullptr);
     x->band_pending = 0;
     x->host_q = nullptr;
     x->host_one_call = false;
@@ -1575,7 +1680,7 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
             if ((spin & 255u) == 255u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(DONE_POLL_US)) break;
         }
         if (!seen) HIP_TRY(hipStreamSynchronize(s));
-        copy_pinned_out(x, user, no_small);
+        copy_pinned_out(x, user, no);
         return ICD_OK;
     }
     // the search's last kernel has written the fallback counters to pinned host memory: icd_index_stats reads them after
@@ -1583,453 +1688,30 @@ static int search_common(icd_index *x, const float *queries, int64_t nq, int32_t
     if (!x->capturing) HIP_TRY(hipEventRecord(x->ev_nflag, s));   // (an event recorded inside a capture could not be waited for by icd_index_stats)
     if (pinned_out) {
         HIP_TRY(hipStreamSynchronize(s));   // (the kernels' stores to the mapped block are visible behind it, like the counters')
-        copy_pinned_out(x, user, no_small);
+        copy_pinned_out(x, user, no);
         return ICD_OK;
     }
-    if (!out_on_device) {
-        const size_t no = (size_t)nq * k;
-        if (user.scores) HIP_TRY(hipMemcpyAsync(user.scores, dev.scores, no * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (user.ids) HIP_TRY(hipMemcpyAsync(user.ids, dev.ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
-        if (user.adj) HIP_TRY(hipMemcpyAsync(user.adj, dev.adj, no * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (user.adj_raw) HIP_TRY(hipMemcpyAsync(user.adj_raw, dev.adj_raw, no * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (user.adj_ids) HIP_TRY(hipMemcpyAsync(user.adj_ids, dev.adj_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
-        if (user.adj_lv) HIP_TRY(hipMemcpyAsync(user.adj_lv, dev.adj_lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
-        else if (user.lv) HIP_TRY(hipMemcpyAsync(user.lv, dev.lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    if (!out_on_device || !q_on_device || host_bands) HIP_TRY(hipStreamSynchronize(s));   // (host bounds went through the pinned block; the mask table's block is guarded by its own event, stage_masks)
-    return ICD_OK;
-}
-
-}  // extern "C"
-
-// ---- range search: the callers' bounds -> BandQ (topk_select.hpp) --------------------------------------
-// The cursor names a hit by its GLOBAL id; the kernels compare keys of LOCAL rows. cut = the first local row whose id is larger
-// than the cursor's: id - id_base + 1 clamped to [0, n], or on a view the upper bound in its strictly increasing row map - once
-// per query, here, not per score.
-__global__ void band_pack_kernel(const float *radius, const float *range_filter, const float *after_scores, const long long *after_ids,
-                                 int nq, const long long *row_map, long long n, long long id_base, BandQ *out) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    BandQ b;
-    b.lo = radius ? radius[q] : -INFINITY;
-    b.hi = range_filter ? range_filter[q] : INFINITY;
-    b.below = ~0ull;
-    if (b.lo != b.lo || b.hi != b.hi) { b.lo = INFINITY; b.hi = -INFINITY; }   // (NaN bounds, unseen by the host: an empty band)
-    if (after_scores) {
-        const float as = after_scores[q];
-        const long long id = after_ids[q];
-        long long cut;
-        if (row_map) {
-            long long lo = 0, hi = n;   // first local row with row_map[row] > id
-            while (lo < hi) { const long long mid = (lo + hi) >> 1; if (row_map[mid] > id) hi = mid; else lo = mid + 1; }
-            cut = lo;
-        } else {
-            cut = id < id_base ? 0 : (id - id_base >= n ? n : id - id_base + 1);
-        }
-        b.below = as != as ? 0ull : band_below(order_f32(as), (uint32_t)cut);
-    }
-    out[q] = b;
-}
-
-// the [query] -> bitset table of a masked search: filled in the pinned block under the handle's mutex, one copy per call. An
-// event recorded right behind the copy guards the block: the next masked call waits for it before it refills the block, so
-// neither a device-in / device-out call (which only enqueues) nor an error return further down leaves a copy reading a block
-// that is being rewritten.
-static int stage_masks(icd_index *x, icd_rowmask *const *masks, int nq, hipStream_t s) {
-    if (!x->mask_dev) return fail(ICD_ERR_UNSUPPORTED, "a masked search on a view is not supported: mask the parent");
-    if (x->mask_copy_pending) { HIP_TRY(hipEventSynchronize(x->ev_mask)); x->mask_copy_pending = false; }
-    for (int q = 0; q < nq; ++q) x->h_mask[q] = masks[q] ? masks[q]->bits : x->mask_ones;
-    const hipError_t ec = hipMemcpyAsync(x->mask_dev, x->h_mask, (size_t)nq * sizeof(uint32_t *), hipMemcpyHostToDevice, s);
-    const hipError_t ee = hipEventRecord(x->ev_mask, s);   // (also behind a copy that failed to enqueue: whatever did get queued is covered)
-    x->mask_copy_pending = ee == hipSuccess;
-    if (ec != hipSuccess || ee != hipSuccess) {
-        hipStreamSynchronize(s);
-        x->mask_copy_pending = false;
-        return fail(ICD_ERR_HIP, "mask table: %s", hipGetErrorString(ec != hipSuccess ? ec : ee));
-    }
-    return ICD_OK;
-}
-
-static uint32_t host_order_f32(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
-// Host bounds were validated by icd_index_search_range (no NaN, radius < range_filter); device bounds cannot be without a
-// synchronisation: an empty or inverted band simply yields padding.
-static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s, BandArgs *out) {
-    out->q = x->band_dev;
-    if (rb.on_device) {
-        hipLaunchKernelGGL(band_pack_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, rb.radius, rb.range_filter, rb.after_scores,
-                           rb.after_ids, nq, x->row_map, (long long)x->n, (long long)x->id_base, x->band_dev);
-        HIP_TRY(hipGetLastError());
-        return ICD_OK;
-    }
-    for (int q = 0; q < nq; ++q) {
-        BandQ b;
-        b.lo = rb.radius ? rb.radius[q] : -INFINITY;
-        b.hi = rb.range_filter ? rb.range_filter[q] : INFINITY;
-        b.below = ~0ull;
-        if (rb.after_scores) {
-            const long long id = rb.after_ids[q];
-            long long cut;
-            if (x->row_map) cut = std::upper_bound(x->h_row_map.begin(), x->h_row_map.end(), id) - x->h_row_map.begin();
-            else cut = id < x->id_base ? 0 : (id - x->id_base >= x->n ? x->n : id - x->id_base + 1);
-            b.below = band_below(host_order_f32(rb.after_scores[q]), (uint32_t)cut);
-        }
-        x->h_band[q] = b;
-        if (q < 4) out->inl[q] = b;
-    }
-    x->band_pending = nq;
-    return ICD_OK;
+    if ((rc = hc.copy_back({{user.scores, dev.scores, 4}, {user.ids, dev.ids, 8}, {user.adj, dev.adj, 8}, {user.adj_raw, dev.adj_raw, 4},
+                            {user.adj_ids, dev.adj_ids, 8}, {user.adj_lv, dev.adj_lv, 4}, {user.lv, dev.lv, 4}}, no)))
+        return rc;
+    return hc.finish(host_bands);   // (host bounds went through the pinned block; the mask table's block is guarded by its own event, stage_masks)
 }
 
 extern "C" {
 
-int icd_index_search_range(icd_index *idx, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
-                           const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
-                           int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
-                           int32_t *out_levels, int32_t out_on_device, void *stream) {
-    // (the checks that need neither the handle nor the device come first)
-    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a range search returns 1 .. %d hits per query", k, ICD_MAX_K);
-    if ((after_scores == nullptr) != (after_ids == nullptr)) return fail(ICD_ERR_INVALID, "after_scores and after_ids: both or neither (a cursor is a hit's score AND id)");
-    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
-    if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    if (!bounds_on_device) {
-        for (int64_t q = 0; q < nq; ++q) {
-            if (radius && std::isnan(radius[q])) return fail(ICD_ERR_INVALID, "radius[%lld] is NaN", (long long)q);
-            if (range_filter && std::isnan(range_filter[q])) return fail(ICD_ERR_INVALID, "range_filter[%lld] is NaN", (long long)q);
-            if (after_scores && std::isnan(after_scores[q])) return fail(ICD_ERR_INVALID, "after_scores[%lld] is NaN", (long long)q);
-            if (radius && range_filter && !(radius[q] < range_filter[q]))
-                return fail(ICD_ERR_INVALID, "query %lld: radius=%g must be below range_filter=%g (hits have radius < score <= range_filter)", (long long)q, (double)radius[q], (double)range_filter[q]);
-        }
-    }
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    Outs o{};
-    if (reweighted) {
-        o.adj = out_adj; o.adj_raw = out_raw; o.adj_ids = reinterpret_cast<long long *>(out_ids); o.adj_lv = out_levels;
-    } else {
-        o.scores = out_raw; o.ids = reinterpret_cast<long long *>(out_ids); o.lv = out_levels;
-    }
-    RangeBounds rb{radius, range_filter, after_scores, reinterpret_cast<const long long *>(after_ids), bounds_on_device != 0};
-    return search_common(idx, queries, nq, k, queries_on_device, ICD_MODE_EXACT, o, out_on_device, stream, &rb);
-}
-
-// ---- row masks --------------------------------------------------------------------------------------------------------------
-// A row list that already sits on the device -> bitset: one memset in front, then one vector atomicOr per row. The list is
-// checked here as well (inside [0, n), strictly increasing): a bad entry sets *err and writes nothing.
-__global__ void rowmask_build_kernel(const long long *rows, long long n_rows, long long n, uint32_t *bits, int *err) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows) return;
-    const long long r = rows[i];
-    if (r < 0 || r >= n || (i > 0 && rows[i - 1] >= r)) { atomicOr(err, 1); return; }
-    atomicOr(bits + (r >> 5), 1u << (r & 31));
-}
-
-int icd_rowmask_pack(const int64_t *rows, int64_t n_rows, int64_t n, uint32_t *out_words, int64_t out_count) {
-    if (n <= 0 || n_rows < 0 || (n_rows > 0 && !rows) || !out_words) return fail(ICD_ERR_INVALID, "rows / out_words NULL, n=%lld or n_rows=%lld", (long long)n, (long long)n_rows);
-    if (out_count < rowmask_tile_words(n)) return fail(ICD_ERR_INVALID, "out_count=%lld: %lld rows need %lld words", (long long)out_count, (long long)n, rowmask_tile_words(n));
-    for (int64_t i = 0; i < n_rows; ++i) {   // (checked before anything is written)
-        if (rows[i] < 0 || rows[i] >= n) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld outside the index's [0, %lld)", (long long)i, (long long)rows[i], (long long)n);
-        if (i > 0 && rows[i] <= rows[i - 1]) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld: row ids must be strictly increasing", (long long)i, (long long)rows[i]);
-    }
-    memset(out_words, 0, (size_t)out_count * sizeof(uint32_t));
-    for (int64_t i = 0; i < n_rows; ++i) out_words[rows[i] >> 5] |= 1u << (rows[i] & 31);
-    return ICD_OK;
-}
-
-int icd_rowmask_create(icd_index *idx, const int64_t *rows, int64_t n_rows, int32_t rows_on_device, icd_rowmask **out) {
-    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(ICD_ERR_INVALID, "rows NULL or n_rows=%lld", (long long)n_rows);
-    if (n_rows > idx->n) return fail(ICD_ERR_INVALID, "n_rows=%lld exceeds the index's %lld rows", (long long)n_rows, (long long)idx->n);
-    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "row masks on a view are not supported: mask the parent");
-    HIP_TRY(hipSetDevice(idx->device));
-    const size_t words = (size_t)rowmask_tile_words(idx->n) + ROWMASK_TAIL_WORDS;
-    std::vector<uint32_t> packed;
-    if (!rows_on_device) {   // a host list: checked and packed here, one upload
-        packed.resize(words);
-        const int rcp = icd_rowmask_pack(rows, n_rows, idx->n, packed.data(), (int64_t)words);
-        if (rcp) return rcp;
-    }
-    icd_rowmask *m = new (std::nothrow) icd_rowmask();
-    if (!m) return fail(ICD_ERR_NOMEM, "host allocation failed");
-    m->owner = idx; m->owner_uid = idx->uid; m->device = idx->device; m->n = idx->n; m->rows = n_rows; m->bytes = words * sizeof(uint32_t);
-    int *derr = nullptr;
-    int herr = 0;
-    hipError_t e = dmalloc(&m->bits, words);
-    if (e == hipSuccess && !rows_on_device) e = hipMemcpy(m->bits, packed.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && rows_on_device) {
-        e = hipMemset(m->bits, 0, words * sizeof(uint32_t));
-        if (e == hipSuccess && n_rows > 0) {
-            e = dmalloc(&derr, 1);
-            if (e == hipSuccess) e = hipMemset(derr, 0, sizeof(int));
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(rowmask_build_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, 0,
-                                   reinterpret_cast<const long long *>(rows), (long long)n_rows, (long long)idx->n, m->bits, derr);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpy(&herr, derr, sizeof(int), hipMemcpyDeviceToHost);
-            hipFree(derr);
-        }
-    }
-    if (e != hipSuccess || herr) {
-        hipFree(m->bits);
-        m->magic = 0;
-        delete m;
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "row mask: %s", hipGetErrorString(e));
-        return fail(ICD_ERR_INVALID, "rows: row ids must be strictly increasing and inside the index's [0, %lld)", (long long)idx->n);
-    }
-    *out = m;
-    return ICD_OK;
-}
-
-int icd_rowmask_destroy(icd_rowmask *m) {
-    if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "invalid row mask handle");
-    hipSetDevice(m->device);
-    hipDeviceSynchronize();
-    hipFree(m->bits);
-    m->magic = 0;
-    delete m;
-    return ICD_OK;
-}
-
-int icd_rowmask_stats(icd_rowmask *m, int64_t *out_rows, int64_t *out_bytes) {
-    if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "invalid row mask handle");
-    if (out_rows) *out_rows = m->rows;
-    if (out_bytes) *out_bytes = (int64_t)m->bytes;
-    return ICD_OK;
-}
-
-int icd_index_search_masked(icd_index *idx, icd_rowmask *const *masks, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
-                            const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
-                            int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
-                            int32_t *out_levels, int32_t out_on_device, void *stream) {
-    if (!masks)   // (no table at all: the range search, which the all-NULL table equals bit for bit)
-        return icd_index_search_range(idx, queries, nq, k, queries_on_device, radius, range_filter, after_scores, after_ids, bounds_on_device,
-                                      reweighted, out_adj, out_raw, out_ids, out_levels, out_on_device, stream);
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a masked search on a view is not supported: mask the parent");
-    if (nq < 0 || nq > idx->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds max_nq=%d", (long long)nq, idx->max_nq);
-    bool any = false;
-    for (int64_t q = 0; q < nq; ++q) {
-        const icd_rowmask *m = masks[q];
-        if (!m) continue;
-        any = true;
-        if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "masks[%lld]: invalid row mask handle", (long long)q);
-        if (m->owner != idx || m->owner_uid != idx->uid || m->n != idx->n || m->device != idx->device)
-            return fail(ICD_ERR_INVALID, "masks[%lld] was created for another index", (long long)q);
-    }
-    if (!any)
-        return icd_index_search_range(idx, queries, nq, k, queries_on_device, radius, range_filter, after_scores, after_ids, bounds_on_device,
-                                      reweighted, out_adj, out_raw, out_ids, out_levels, out_on_device, stream);
-    // (from here on: icd_index_search_range's checks and call, with the mask table)
-    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a masked search returns 1 .. %d hits per query", k, ICD_MAX_K);
-    if ((after_scores == nullptr) != (after_ids == nullptr)) return fail(ICD_ERR_INVALID, "after_scores and after_ids: both or neither (a cursor is a hit's score AND id)");
-    if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    if (!bounds_on_device) {
-        for (int64_t q = 0; q < nq; ++q) {
-            if (radius && std::isnan(radius[q])) return fail(ICD_ERR_INVALID, "radius[%lld] is NaN", (long long)q);
-            if (range_filter && std::isnan(range_filter[q])) return fail(ICD_ERR_INVALID, "range_filter[%lld] is NaN", (long long)q);
-            if (after_scores && std::isnan(after_scores[q])) return fail(ICD_ERR_INVALID, "after_scores[%lld] is NaN", (long long)q);
-            if (radius && range_filter && !(radius[q] < range_filter[q]))
-                return fail(ICD_ERR_INVALID, "query %lld: radius=%g must be below range_filter=%g (hits have radius < score <= range_filter)", (long long)q, (double)radius[q], (double)range_filter[q]);
-        }
-    }
-    Outs o{};
-    if (reweighted) {
-        o.adj = out_adj; o.adj_raw = out_raw; o.adj_ids = reinterpret_cast<long long *>(out_ids); o.adj_lv = out_levels;
-    } else {
-        o.scores = out_raw; o.ids = reinterpret_cast<long long *>(out_ids); o.lv = out_levels;
-    }
-    RangeBounds rb{radius, range_filter, after_scores, reinterpret_cast<const long long *>(after_ids), bounds_on_device != 0};
-    return search_common(idx, queries, nq, k, queries_on_device, ICD_MODE_EXACT, o, out_on_device, stream, &rb, masks);
-}
-
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
                      int32_t mode, float *out_scores, int64_t *out_ids, int32_t out_on_device, void *stream) {
     if (!out_scores || !out_ids) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    Outs o{};
-    o.scores = out_scores;
-    o.ids = reinterpret_cast<long long *>(out_ids);
-    return search_common(idx, queries, nq, k, queries_on_device, mode, o, out_on_device, stream);
+    return run_search(idx, SearchRequest{queries, nq, k, queries_on_device != 0, out_on_device != 0, mode,
+                                         outs_for(false, nullptr, out_scores, out_ids, nullptr), nullptr, nullptr, reinterpret_cast<hipStream_t>(stream)});
 }
 
 int icd_index_search_reweighted(icd_index *idx, const float *queries, int64_t nq, int32_t k,
                                 int32_t queries_on_device, int32_t mode, double *out_adj, float *out_raw,
                                 int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
     if (!out_adj || !out_ids) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    Outs o{};
-    o.adj = out_adj;
-    o.adj_raw = out_raw;
-    o.adj_ids = reinterpret_cast<long long *>(out_ids);
-    o.adj_lv = out_levels;
-    return search_common(idx, queries, nq, k, queries_on_device, mode, o, out_on_device, stream);
-}
-
-int icd_merge_topk(int32_t device, const float *scores, const int64_t *ids, const int32_t *levels, int32_t G,
-                   int64_t nq, int32_t k, double *out_adj, float *out_raw, int64_t *out_ids,
-                   int32_t *out_levels, void *stream) {
-    if (!scores || !ids || !levels) return fail(ICD_ERR_INVALID, "input pointer is NULL");
-    if (G <= 0 || k <= 0 || k > ICD_MAX_K || (int64_t)G * k > 1024) return fail(ICD_ERR_INVALID, "G=%d k=%d: need G*k <= 1024", G, k);
-    if (nq < 0 || nq > 0x7FFFFFFF) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
-    if (nq == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    MergeArgs a{};
-    a.scores = scores; a.ids = reinterpret_cast<const long long *>(ids); a.levels = levels;
-    a.G = G; a.nq = (int)nq; a.k = k;
-    a.out_adj = out_adj; a.out_raw = out_raw; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels;
-    const size_t lds = 4 * (1024 * 16 + 128 * 24);
-    HIP_TRY(launch_lds<merge_topk_kernel>(device, lds, dim3(((int)nq + 3) / 4), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a));
-    return ICD_OK;
-}
-
-// the two entry points share their checks and arguments; qp_width is the width of a query's row of q_params
-static int hier_rescore_launch(int qp_width, int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
-                               int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
-                               int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
-                               double *out_boost, void *stream) {
-    if (!adj || !ids || !row_tags || !q_params || !weights) return fail(ICD_ERR_INVALID, "input pointer is NULL");
-    if (!out_order || !out_enhanced || !out_score || !out_vs || !out_hb || !out_boost) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    if (k <= 0 || k > HIER_MAX_K) return fail(ICD_ERR_INVALID, "k=%d (1..%d)", k, HIER_MAX_K);
-    if (nq < 0 || nq > 0x7FFFFFFF || n_rows < 0) return fail(ICD_ERR_INVALID, "nq=%lld n_rows=%lld", (long long)nq, (long long)n_rows);
-    if (nq == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    HierArgs a{};
-    a.adj = adj; a.ids = reinterpret_cast<const long long *>(ids); a.nq = (int)nq; a.k = k; a.id_base = id_base; a.n_rows = n_rows;
-    a.row_tags = row_tags; a.q_params = q_params;
-    a.w_hb = weights[0]; a.w_em = weights[1]; a.w_sc = weights[2]; a.w_ca = weights[3]; a.w_cr = weights[4];
-    a.sc_value = weights[5]; a.level_term = weights[6];
-    a.out_order = out_order; a.out_enhanced = out_enhanced; a.out_score = out_score; a.out_vs = out_vs; a.out_hb = out_hb;
-    a.out_boost = out_boost;
-    if (qp_width == HIER_QP_ENT)
-        hipLaunchKernelGGL(hier_rescore_kernel<HIER_QP_ENT>, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    else
-        hipLaunchKernelGGL(hier_rescore_kernel<HIER_QP>, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-int icd_hier_rescore(int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
-                     int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
-                     int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
-                     double *out_boost, void *stream) {
-    return hier_rescore_launch(HIER_QP, device, adj, ids, nq, k, id_base, n_rows, row_tags, q_params, weights, out_order,
-                               out_enhanced, out_score, out_vs, out_hb, out_boost, stream);
-}
-
-int icd_hier_rescore_entities(int32_t device, const double *adj, const int64_t *ids, int64_t nq, int32_t k, int64_t id_base,
-                              int64_t n_rows, const uint8_t *row_tags, const double *q_params, const double *weights,
-                              int32_t *out_order, double *out_enhanced, double *out_score, double *out_vs, double *out_hb,
-                              double *out_boost, void *stream) {
-    return hier_rescore_launch(HIER_QP_ENT, device, adj, ids, nq, k, id_base, n_rows, row_tags, q_params, weights, out_order,
-                               out_enhanced, out_score, out_vs, out_hb, out_boost, stream);
-}
-
-int icd_pack_winners(int32_t device, const int32_t *order, const int64_t *ids, const float *raw, const double *adj, const double *enhanced,
-                     const double *vs, const double *hb, const double *boost, int64_t nq, int32_t k, int32_t kk, double *out, void *stream) {
-    if (!order || !ids || !raw || !adj || !enhanced || !vs || !hb || !boost || !out) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (k <= 0 || kk <= 0 || kk > k || nq < 0 || nq > 0x7FFFFFFF) return fail(ICD_ERR_INVALID, "nq=%lld k=%d kk=%d", (long long)nq, k, kk);
-    if (nq == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    PackWinnersArgs a{};
-    a.order = order; a.ids = reinterpret_cast<const long long *>(ids); a.raw = raw; a.adj = adj; a.enh = enhanced; a.vs = vs; a.hb = hb; a.boost = boost;
-    a.nq = (int)nq; a.k = k; a.kk = kk; a.out = out;
-    const long long per = (long long)nq * kk;
-    hipLaunchKernelGGL(pack_winners_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-int icd_score_stats(int32_t device, const double *scores, const int32_t *order, int64_t nq, int32_t k, int32_t use,
-                    double *out, void *stream) {
-    if (!scores || !out) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (k <= 0 || k > STATS_MAX_K || use <= 0) return fail(ICD_ERR_INVALID, "k=%d (1..%d) use=%d", k, STATS_MAX_K, use);
-    if (nq < 0 || nq > 0x7FFFFFFF) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
-    if (nq == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    StatsArgs a{};
-    a.scores = scores; a.order = order; a.nq = (int)nq; a.k = k; a.use = use; a.out = out;
-    hipLaunchKernelGGL(score_stats_kernel, dim3(((int)nq + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-int icd_cosine_rows(int32_t device, const float *x, const float *y, int64_t y_stride, int64_t nq, int32_t dim,
-                    double *out, void *stream) {
-    if (!x || !y || !out) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (dim <= 0 || (y_stride != 0 && y_stride != dim)) return fail(ICD_ERR_INVALID, "dim=%d y_stride=%lld (0 or dim)", dim, (long long)y_stride);
-    if (nq < 0 || nq > 0x7FFFFFFF) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
-    if (nq == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    CosArgs a{};
-    a.x = x; a.y = y; a.y_stride = y_stride; a.nq = (int)nq; a.dim = dim; a.out = out;
-    hipLaunchKernelGGL(cosine_rows_kernel, dim3(((int)nq + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-int icd_term_first_match(int32_t device, const int32_t *key_cp, const int32_t *key_off, int32_t n_keys, const int32_t *term_cp,
-                         const int32_t *term_off, int32_t n_terms, int32_t *out_first, void *stream_) {
-    if (!key_cp || !key_off || !term_cp || !term_off || !out_first) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (n_keys < 0 || n_terms < 0) return fail(ICD_ERR_INVALID, "n_keys=%d n_terms=%d", n_keys, n_terms);
-    if (n_terms == 0) return ICD_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    HIP_TRY(hipSetDevice(device));
-    // the terms' lengths decide whether the kernel can take them: read the offsets (n_terms + 1 ints) on the stream
-    std::vector<int32_t> off((size_t)n_terms + 1);
-    HIP_TRY(hipMemcpyAsync(off.data(), term_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (off[0] < 0) return fail(ICD_ERR_INVALID, "term_off[0]=%d", off[0]);
-    for (int32_t t = 0; t < n_terms; ++t) {
-        const int32_t len = off[t + 1] - off[t];
-        if (len < 0) return fail(ICD_ERR_INVALID, "term %d: term_off decreases", t);
-        if (len > ICD_TERM_MAX_LEN) return fail(ICD_ERR_UNSUPPORTED, "term %d has %d code points (at most %d)", t, len, ICD_TERM_MAX_LEN);
-    }
-    static_assert(ICD_TERM_MAX_LEN == TERM_MAX_LEN, "ICD_TERM_MAX_LEN and term_lookup.hpp disagree");
-    TermArgs a{};
-    a.key_cp = key_cp; a.key_off = key_off; a.n_keys = n_keys; a.term_cp = term_cp; a.term_off = term_off; a.n_terms = n_terms;
-    a.out_first = out_first;
-    hipLaunchKernelGGL(term_first_match_kernel, dim3((unsigned)n_terms), dim3(TERM_BLOCK), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-int icd_packed_attention(int32_t device, const float *qkv, int64_t ld, const int32_t *starts, int32_t nseq, int32_t heads,
-                         int32_t head_dim, int32_t max_len, float *out, int64_t out_ld, void *stream) {
-    if (!qkv || !starts || !out) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (head_dim != ATT_HEAD_DIM) return fail(ICD_ERR_UNSUPPORTED, "head_dim=%d (this kernel is written for %d)", head_dim, ATT_HEAD_DIM);
-    if (max_len < 1 || max_len > ATT_MAX_SEQ) return fail(ICD_ERR_UNSUPPORTED, "max_len=%d (1..%d tokens per sequence)", max_len, ATT_MAX_SEQ);
-    if (nseq < 0 || heads <= 0 || (int64_t)nseq * heads > 0x7FFFFFF0LL) return fail(ICD_ERR_INVALID, "nseq=%d heads=%d", nseq, heads);
-    const int64_t hidden = (int64_t)heads * head_dim;
-    if (ld < 3 * hidden || out_ld < hidden || ld % 4 != 0) return fail(ICD_ERR_INVALID, "ld=%lld out_ld=%lld for hidden=%lld", (long long)ld, (long long)out_ld, (long long)hidden);
-    if (nseq == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    PackedAttnArgs a{};
-    a.qkv = qkv; a.out = out; a.starts = starts; a.nseq = nseq; a.heads = heads; a.ld = ld; a.out_ld = out_ld; a.hidden = (int)hidden;
-    a.scale = 0.125f;   // 1 / sqrt(64), exact
-    const int tasks = nseq * heads;
-    hipLaunchKernelGGL(packed_attention_kernel, dim3((tasks + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
-}
-
-int icd_split_bf16x3(int32_t device, const float *x, int64_t rows, int32_t cols, int64_t ld, int32_t act, void *out, void *stream) {
-    if (!x || !out) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (rows < 0 || cols < SPLIT_TAIL || cols % 8 != 0 || ld < cols || ld % 4 != 0) return fail(ICD_ERR_INVALID, "rows=%lld cols=%d ld=%lld (cols a multiple of 8, ld >= cols and a multiple of 4)", (long long)rows, cols, (long long)ld);
-    if (act != 0 && act != 1) return fail(ICD_ERR_INVALID, "act=%d (0 none, 1 erf-GELU)", act);
-    if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) return fail(ICD_ERR_INVALID, "x and out must be 16-byte aligned");
-    if (rows == 0) return ICD_OK;
-    HIP_TRY(hipSetDevice(device));
-    SplitArgs a{};
-    a.x = x; a.out = static_cast<unsigned short *>(out); a.rows = rows; a.cols = cols; a.act = act; a.ld = ld;
-    const long long total = rows * (long long)(cols / 8);
-    const int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(split_bf16x3_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    HIP_TRY(hipGetLastError());
-    return ICD_OK;
+    return run_search(idx, SearchRequest{queries, nq, k, queries_on_device != 0, out_on_device != 0, mode,
+                                         outs_for(true, out_adj, out_raw, out_ids, out_levels), nullptr, nullptr, reinterpret_cast<hipStream_t>(stream)});
 }
 
 int icd_index_lookup_levels(icd_index *idx, const int64_t *ids, int64_t count, int32_t *out_levels, void *stream) {
@@ -2074,19 +1756,6 @@ int icd_index_stats(icd_index *idx, icd_stats *out) {
     out->sparse_fallback_armed = idx->pol.sparse_disarmed ? 0 : 1;
     out->centered = idx->cmean ? 1 : 0; out->mean_share = idx->mean_share;
     out->last_chunks = idx->last_chunks; out->last_mode = idx->last_mode;
-    return ICD_OK;
-}
-
-int icd_unpack_query_slices(int32_t device, const void *gathered, int32_t world, int64_t nq, int32_t k, double *out_adj,
-                                  float *out_raw, int64_t *out_ids, int32_t *out_levels, void *stream) {
-    if (!gathered || !out_adj || !out_raw || !out_ids || !out_levels) return fail(ICD_ERR_INVALID, "pointer is NULL");
-    if (world < 1 || nq < 0 || k <= 0) return fail(ICD_ERR_INVALID, "world=%d nq=%lld k=%d", world, (long long)nq, k);
-    HIP_TRY(hipSetDevice(device));
-    const size_t width = ((size_t)nq + world - 1) / world, per = width * k;
-    const char *rb = static_cast<const char *>(gathered);
-    if (icd_internal_unpack_query_slices(rb, rb + per * world * 8, rb + per * world * 16, rb + per * world * 20, world, nq, k,
-                                         (long long)width, out_adj, out_raw, out_ids, out_levels, stream))
-        return fail(ICD_ERR_HIP, "the unpack launch failed");
     return ICD_OK;
 }
 
@@ -2203,396 +1872,11 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
     return ICD_OK;
 }
 
-// ---- grouping search (group_topk.hpp) ----------------------------------------------------------------
-// A grouping belongs to the index it was created for (n rows, the same device) but keeps no pointer into it: the handle is
-// compared, never followed, outside a search that is given both. Its workspace - the score block S, the per-group keys, the
-// staging of host callers - is allocated here, never inside a search.
-struct icd_grouping {
-    uint32_t magic = 0x1CD96B0Fu;
-    const icd_index *owner = nullptr;
-    int device = 0;
-    int n = 0, G = 0, largest = 0, max_nq = 0, qb = 0, dim = 0;
-    long long ldS = 0;
-    int *group_of = nullptr, *dense_of = nullptr, *order = nullptr, *gpos = nullptr, *seg = nullptr;
-    float *S = nullptr;
-    u64 *best = nullptr;
-    float *qdev = nullptr;
-    double *o_adj = nullptr; float *o_raw = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr, *o_grp = nullptr;
-    size_t bytes = 0;
-    std::mutex mu;
-};
-
-namespace {
-constexpr int GROUP_QUERY_BLOCK = 512;   // queries scored per pass: S = 512 x 40 576 x 4 B = 83 MB stays in the 256-MiB Infinity Cache next to the 124-MB corpus
-bool valid_grouping(icd_grouping *g) { return g && g->magic == 0x1CD96B0Fu; }
-void free_grouping(icd_grouping *g) {
-    if (!g) return;
-    hipFree(g->group_of); hipFree(g->dense_of); hipFree(g->order); hipFree(g->gpos); hipFree(g->seg); hipFree(g->S); hipFree(g->best);
-    hipFree(g->qdev); hipFree(g->o_adj); hipFree(g->o_raw); hipFree(g->o_ids); hipFree(g->o_lv); hipFree(g->o_grp);
-    g->magic = 0;
-    delete g;
-}
-}  // namespace
-
-int icd_grouping_create(icd_index *idx, const int32_t *group_of, int64_t n, int32_t on_device, int32_t max_nq, icd_grouping **out) {
-    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (!group_of) return fail(ICD_ERR_INVALID, "group_of is NULL");
-    if (n != idx->n) return fail(ICD_ERR_INVALID, "group_of holds %lld ids, the index %lld rows", (long long)n, (long long)idx->n);
-    if (n >= 0x7FFFFFFFll) return fail(ICD_ERR_UNSUPPORTED, "n=%lld: a grouping addresses rows with 31 bits", (long long)n);
-    if (max_nq <= 0) return fail(ICD_ERR_INVALID, "max_nq=%d", max_nq);
-    HIP_TRY(hipSetDevice(idx->device));
-    std::vector<int> ids((size_t)n);
-    if (on_device) HIP_TRY(hipMemcpy(ids.data(), group_of, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    else memcpy(ids.data(), group_of, (size_t)n * sizeof(int));
-    for (int64_t i = 0; i < n; ++i)
-        if (ids[i] < 0) return fail(ICD_ERR_INVALID, "group_of[%lld]=%d: group ids are non-negative (-1 marks padding in the outputs)", (long long)i, ids[i]);
-    // rows in (group, row) order; dense group numbers in the order of the caller's ids
-    std::vector<int> order((size_t)n), gpos((size_t)n), dense((size_t)n), seg;
-    for (int64_t i = 0; i < n; ++i) order[i] = (int)i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ids[a] < ids[b]; });
-    int largest = 0;
-    for (int64_t p = 0; p < n; ++p) {
-        if (p == 0 || ids[order[p]] != ids[order[p - 1]]) {
-            if (!seg.empty()) largest = std::max(largest, (int)p - seg.back());
-            seg.push_back((int)p);
-        }
-        gpos[p] = (int)seg.size() - 1;
-        dense[order[p]] = gpos[p];
-    }
-    largest = std::max(largest, (int)n - seg.back());
-    const int G = (int)seg.size();
-    seg.push_back((int)n);
-
-    icd_grouping *g = new (std::nothrow) icd_grouping();
-    if (!g) return fail(ICD_ERR_NOMEM, "host allocation failed");
-    g->owner = idx; g->device = idx->device; g->n = (int)n; g->G = G; g->largest = largest; g->max_nq = max_nq; g->dim = idx->dim;
-    g->qb = std::min(GROUP_QUERY_BLOCK, (max_nq + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE);
-    g->ldS = ((long long)n + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE;
-    const size_t no = (size_t)max_nq * ICD_MAX_K;
-#define GR_TRY(expr)                                                                                                       \
-    do {                                                                                                                   \
-        hipError_t e_ = (expr);                                                                                            \
-        if (e_ != hipSuccess) {                                                                                            \
-            free_grouping(g);                                                                                              \
-            return fail(e_ == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-        }                                                                                                                  \
-    } while (0)
-    GR_TRY(dmalloc(&g->group_of, (size_t)n)); GR_TRY(dmalloc(&g->dense_of, (size_t)n)); GR_TRY(dmalloc(&g->order, (size_t)n));
-    GR_TRY(dmalloc(&g->gpos, (size_t)n)); GR_TRY(dmalloc(&g->seg, (size_t)G + 1));
-    GR_TRY(dmalloc(&g->S, (size_t)g->qb * g->ldS)); GR_TRY(dmalloc(&g->best, (size_t)g->qb * G));
-    GR_TRY(dmalloc(&g->qdev, (size_t)max_nq * idx->dim));
-    GR_TRY(dmalloc(&g->o_adj, no)); GR_TRY(dmalloc(&g->o_raw, no)); GR_TRY(dmalloc(&g->o_ids, no)); GR_TRY(dmalloc(&g->o_lv, no)); GR_TRY(dmalloc(&g->o_grp, no));
-    GR_TRY(hipMemcpy(g->group_of, ids.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    GR_TRY(hipMemcpy(g->dense_of, dense.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    GR_TRY(hipMemcpy(g->order, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    GR_TRY(hipMemcpy(g->gpos, gpos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    GR_TRY(hipMemcpy(g->seg, seg.data(), ((size_t)G + 1) * sizeof(int), hipMemcpyHostToDevice));
-#undef GR_TRY
-    g->bytes = (size_t)n * 20 + ((size_t)G + 1) * 4 + (size_t)g->qb * g->ldS * 4 + (size_t)g->qb * G * 8 + (size_t)max_nq * idx->dim * 4 + no * 28;
-    *out = g;
-    return ICD_OK;
-}
-
-int icd_grouping_destroy(icd_grouping *grouping) {
-    if (!valid_grouping(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
-    hipSetDevice(grouping->device);
-    hipDeviceSynchronize();
-    free_grouping(grouping);
-    return ICD_OK;
-}
-
-int icd_grouping_stats(icd_grouping *grouping, int64_t *out_groups, int64_t *out_largest, int64_t *out_bytes) {
-    if (!valid_grouping(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
-    if (out_groups) *out_groups = grouping->G;
-    if (out_largest) *out_largest = grouping->largest;
-    if (out_bytes) *out_bytes = (int64_t)grouping->bytes;
-    return ICD_OK;
-}
-
-int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float *queries, int64_t nq, int32_t k, int32_t group_size,
-                             int32_t queries_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
-                             int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream) {
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (!valid_grouping(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
-    icd_grouping *g = grouping;
-    if (g->owner != idx || g->n != idx->n || g->device != idx->device || g->dim != idx->dim)
-        return fail(ICD_ERR_INVALID, "the grouping was created for another index");
-    if (k < 1 || group_size < 1 || (int64_t)k * group_size > ICD_MAX_K)
-        return fail(ICD_ERR_INVALID, "k=%d group_size=%d: need k >= 1, group_size >= 1 and k * group_size <= %d", k, group_size, ICD_MAX_K);
-    if (nq < 0 || nq > g->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the grouping's max_nq=%d", (long long)nq, g->max_nq);
-    if (!out_ids || !out_raw || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    if (nq == 0) return ICD_OK;
-    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
-    std::lock_guard<std::mutex> guard(g->mu);
-    HIP_TRY(hipSetDevice(idx->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-        if (capturing && (!queries_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
-    }
-    const float *dq = queries;
-    if (!queries_on_device) {
-        HIP_TRY(hipMemcpyAsync(g->qdev, queries, (size_t)nq * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-        dq = g->qdev;
-    }
-    double *d_adj = out_adj; float *d_raw = out_raw; long long *d_ids = reinterpret_cast<long long *>(out_ids); int *d_lv = out_levels, *d_grp = out_groups;
-    if (!out_on_device) {
-        d_adj = out_adj ? g->o_adj : nullptr; d_raw = g->o_raw; d_ids = g->o_ids;
-        d_lv = out_levels ? g->o_lv : nullptr; d_grp = out_groups ? g->o_grp : nullptr;
-    }
-    const int ks = k * group_size;
-    const int ntiles = (int)(g->ldS / GROUP_TILE);
-    const bool small_kp = k <= 16 && group_size <= 16;
-    for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {
-        const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
-        GroupScoreArgs sa{};
-        sa.corpus = idx->corpus; sa.queries = dq + (size_t)q0 * idx->dim; sa.order = g->order;
-        sa.nq = nb; sa.n = g->n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
-        sa.S = g->S; sa.ldS = g->ldS;
-        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)(ntiles * sa.mtiles)), dim3(256), 0, s, sa);
-        HIP_TRY(hipGetLastError());
-
-        HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
-        GroupBestArgs ba{};
-        ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
-        ba.nq = nb; ba.n = g->n; ba.G = g->G; ba.best = g->best;
-        ba.R = nb >= 64 ? 1024 : 128;
-        ba.nranges = (g->n + ba.R - 1) / ba.R;
-        constexpr int QW = 4;
-        const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
-        hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
-        HIP_TRY(hipGetLastError());
-
-        GroupFinishArgs fa{};
-        fa.best = g->best; fa.S = g->S; fa.ldS = g->ldS; fa.order = g->order; fa.seg = g->seg; fa.dense_of = g->dense_of;
-        fa.nq = nb; fa.G = g->G; fa.k = k; fa.s = group_size; fa.q_base = (int)q0;
-        fa.fin.k = ks; fa.fin.levels = idx->levels; fa.fin.id_base = idx->id_base; fa.fin.row_map = idx->row_map; fa.fin.groups = g->group_of;
-        if (reweighted) {
-            fa.fin.out_adj = d_adj; fa.fin.out_adj_raw = d_raw; fa.fin.out_adj_ids = d_ids; fa.fin.out_adj_levels = d_lv; fa.fin.out_adj_groups = d_grp;
-        } else {
-            fa.fin.out_scores = d_raw; fa.fin.out_ids = d_ids; fa.fin.out_levels = d_lv; fa.fin.out_groups = d_grp;
-        }
-        if (small_kp) hipLaunchKernelGGL((group_finish_kernel<16, 2>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
-        else hipLaunchKernelGGL((group_finish_kernel<128, 4>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!out_on_device) {
-        const size_t no = (size_t)nq * ks;
-        if (out_adj) HIP_TRY(hipMemcpyAsync(out_adj, d_adj, no * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_raw, d_raw, no * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_ids, d_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
-        if (out_levels) HIP_TRY(hipMemcpyAsync(out_levels, d_lv, no * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (out_groups) HIP_TRY(hipMemcpyAsync(out_groups, d_grp, no * sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    if (!out_on_device || !queries_on_device) HIP_TRY(hipStreamSynchronize(s));
-    return ICD_OK;
-}
-
 }  // extern "C"
 
-// ---- hybrid search (hybrid_fuse.hpp) -----------------------------------------------------------------
-// A fusion belongs to the index it was created for but keeps no pointer into it: handle and identity are compared, never
-// followed. Its workspace - the staging of the sub-lists, the staging of host callers - is allocated here, never in a search.
-struct icd_fusion {
-    uint32_t magic = 0x1CDF05EDu;
-    const icd_index *owner = nullptr;
-    unsigned long long owner_uid = 0;
-    int device = 0, dim = 0;
-    int64_t n = 0, max_total = 0;
-    float *st_scores = nullptr; long long *st_ids = nullptr;   // [max_total][ICD_MAX_K] the sub-lists of a call, [nq * R][max limit] used
-    float *qdev = nullptr;                                     // [max_total][dim] a host caller's vectors
-    double *o_adj = nullptr, *o_fused = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr; uint32_t *o_bits = nullptr;   // [FUSION_HOST_CHUNK][ICD_MAX_K] a host caller's outputs, FUSION_HOST_CHUNK queries at a time
-    int limits[ICD_MAX_REQUESTS] = {};                         // of the current call (copied: the caller's arrays are not read again)
-    double weights[ICD_MAX_REQUESTS] = {};
-    size_t bytes = 0;
-    std::mutex mu;
-};
-
-namespace {
-// a HOST caller's outputs leave the device in pieces of this many queries (one fuse launch and its copies per piece, in stream
-// order through one staging block of 256 x 128 slots = 1 MB): the staging does not grow with max_total, and a device caller,
-// who never uses it, does not pay for it
-constexpr int FUSION_HOST_CHUNK = 256;
-bool valid_fusion(icd_fusion *f) { return f && f->magic == 0x1CDF05EDu; }
-void free_fusion(icd_fusion *f) {
-    if (!f) return;
-    hipFree(f->st_scores); hipFree(f->st_ids); hipFree(f->qdev);
-    hipFree(f->o_adj); hipFree(f->o_fused); hipFree(f->o_ids); hipFree(f->o_lv); hipFree(f->o_bits);
-    f->magic = 0;
-    delete f;
-}
-}  // namespace
-
-extern "C" {
-
-int icd_fusion_create(icd_index *idx, int64_t max_total, icd_fusion **out) {
-    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (max_total <= 0 || max_total > 0x7FFFFFFFll / ICD_MAX_K) return fail(ICD_ERR_INVALID, "max_total=%lld", (long long)max_total);
-    if (idx->n >= 0x7FFFFFFFll) return fail(ICD_ERR_UNSUPPORTED, "n=%lld: a fusion addresses rows with 31 bits", (long long)idx->n);
-    HIP_TRY(hipSetDevice(idx->device));
-    icd_fusion *f = new (std::nothrow) icd_fusion();
-    if (!f) return fail(ICD_ERR_NOMEM, "host allocation failed");
-    f->owner = idx; f->owner_uid = idx->uid; f->device = idx->device; f->dim = idx->dim; f->n = idx->n; f->max_total = max_total;
-    const size_t no = (size_t)max_total * ICD_MAX_K;
-#define FU_TRY(expr)                                                                                                       \
-    do {                                                                                                                   \
-        hipError_t e_ = (expr);                                                                                            \
-        if (e_ != hipSuccess) {                                                                                            \
-            free_fusion(f);                                                                                                \
-            return fail(e_ == hipErrorOutOfMemory ? ICD_ERR_NOMEM : ICD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-        }                                                                                                                  \
-    } while (0)
-    FU_TRY(dmalloc(&f->st_scores, no)); FU_TRY(dmalloc(&f->st_ids, no));
-    FU_TRY(dmalloc(&f->qdev, (size_t)max_total * idx->dim));
-    const size_t nh = (size_t)std::min<int64_t>(max_total, FUSION_HOST_CHUNK) * ICD_MAX_K;
-    FU_TRY(dmalloc(&f->o_adj, nh)); FU_TRY(dmalloc(&f->o_fused, nh)); FU_TRY(dmalloc(&f->o_ids, nh)); FU_TRY(dmalloc(&f->o_lv, nh)); FU_TRY(dmalloc(&f->o_bits, nh));
-#undef FU_TRY
-    f->bytes = no * (4 + 8) + (size_t)max_total * idx->dim * 4 + nh * (8 + 8 + 8 + 4 + 4);
-    *out = f;
-    return ICD_OK;
-}
-
-int icd_fusion_destroy(icd_fusion *fusion) {
-    if (!valid_fusion(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
-    hipSetDevice(fusion->device);
-    hipDeviceSynchronize();
-    free_fusion(fusion);
-    return ICD_OK;
-}
-
-int icd_fusion_stats(icd_fusion *fusion, int64_t *out_max_total, int64_t *out_bytes) {
-    if (!valid_fusion(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
-    if (out_max_total) *out_max_total = fusion->max_total;
-    if (out_bytes) *out_bytes = (int64_t)fusion->bytes;
-    return ICD_OK;
-}
-
-int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *queries, int64_t nq, int32_t R, int32_t queries_on_device,
-                            const int32_t *limits, icd_rowmask *const *masks, const float *radius, const float *range_filter,
-                            int32_t bounds_on_device, int32_t mode, int32_t ranker, double rrf_c, const double *weights, int32_t norm,
-                            int32_t k, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
-                            uint32_t *out_reqbits, int32_t out_on_device, void *stream) {
-    // every check comes before the first device call
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (!valid_fusion(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
-    icd_fusion *f = fusion;
-    if (f->owner != idx || f->owner_uid != idx->uid || f->n != idx->n || f->device != idx->device || f->dim != idx->dim)
-        return fail(ICD_ERR_INVALID, "the fusion was created for another index");
-    if (R < 1 || R > ICD_MAX_REQUESTS) return fail(ICD_ERR_INVALID, "R=%d: a hybrid search takes 1 .. %d requests per query", R, ICD_MAX_REQUESTS);
-    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a hybrid search returns 1 .. %d hits per query", k, ICD_MAX_K);
-    if (!limits) return fail(ICD_ERR_INVALID, "limits is NULL");
-    int lmax = 0;
-    for (int r = 0; r < R; ++r) {
-        if (limits[r] < 1 || limits[r] > ICD_MAX_K) return fail(ICD_ERR_INVALID, "limits[%d]=%d: a request returns 1 .. %d hits", r, limits[r], ICD_MAX_K);
-        lmax = std::max(lmax, (int)limits[r]);
-    }
-    if (lmax > idx->max_k) return fail(ICD_ERR_INVALID, "limit %d exceeds the index's max_k=%d", lmax, idx->max_k);
-    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
-    const int64_t total = nq * R;
-    if (total > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)total, (long long)f->max_total);
-    if (total > idx->max_nq) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the index's max_nq=%d", (long long)total, idx->max_nq);
-    if (mode != ICD_MODE_AUTO && mode != ICD_MODE_EXACT) return fail(ICD_ERR_INVALID, "mode=%d", mode);
-    if (ranker == ICD_RANKER_RRF) {
-        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
-    } else if (ranker == ICD_RANKER_WEIGHTED) {
-        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
-        for (int r = 0; r < R; ++r)
-            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
-        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
-    } else {
-        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
-    }
-    if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    const bool banded = radius || range_filter;
-    if (banded && !bounds_on_device) {
-        for (int64_t i = 0; i < total; ++i) {
-            if (radius && std::isnan(radius[i])) return fail(ICD_ERR_INVALID, "radius[%lld] is NaN", (long long)i);
-            if (range_filter && std::isnan(range_filter[i])) return fail(ICD_ERR_INVALID, "range_filter[%lld] is NaN", (long long)i);
-            if (radius && range_filter && !(radius[i] < range_filter[i]))
-                return fail(ICD_ERR_INVALID, "sub-search %lld: radius=%g must be below range_filter=%g", (long long)i, (double)radius[i], (double)range_filter[i]);
-        }
-    }
-    if (masks) {
-        if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a masked hybrid search on a view is not supported: mask the parent");
-        for (int64_t i = 0; i < total; ++i) {
-            const icd_rowmask *m = masks[i];
-            if (!m) continue;
-            if (!valid_rowmask(m)) return fail(ICD_ERR_STATE, "masks[%lld]: invalid row mask handle", (long long)i);
-            if (m->owner != idx || m->owner_uid != idx->uid || m->n != idx->n || m->device != idx->device)
-                return fail(ICD_ERR_INVALID, "masks[%lld] was created for another index", (long long)i);
-        }
-    }
-    if (nq == 0) return ICD_OK;
-    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
-    std::lock_guard<std::mutex> guard(f->mu);
-    HIP_TRY(hipSetDevice(idx->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-        if (capturing && (!queries_on_device || !out_on_device)) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
-        if (capturing && masks) return fail(ICD_ERR_INVALID, "a masked search stages its mask table on the host at call time: it cannot be captured into a graph");
-        if (capturing && banded && !bounds_on_device) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
-    }
-    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
-        f->limits[r] = r < R ? limits[r] : 0;
-        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
-    }
-    const float *dq = queries;
-    if (!queries_on_device) {
-        HIP_TRY(hipMemcpyAsync(f->qdev, queries, (size_t)total * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-        dq = f->qdev;
-    }
-    // step 1: ONE existing sub-search over the nq * R vectors at k = the largest limit, into the staging
-    int rc;
-    if (!masks && !banded)
-        rc = icd_index_search(idx, dq, total, lmax, 1, mode, f->st_scores, reinterpret_cast<int64_t *>(f->st_ids), 1, stream);
-    else
-        rc = icd_index_search_masked(idx, masks, dq, total, lmax, 1, radius, range_filter, nullptr, nullptr, bounds_on_device, 0, nullptr,
-                                     f->st_scores, reinterpret_cast<int64_t *>(f->st_ids), nullptr, 1, stream);
-    if (rc) return rc;
-    // step 2: the fuse
-    HybridArgs a{};
-    a.st_scores = f->st_scores; a.st_ids = f->st_ids;
-    a.R = R; a.lmax = lmax; a.k = k;
-    a.slots = 2;
-    while (a.slots < R * lmax) a.slots <<= 1;
-    for (int r = 0; r < HY_MAX_R; ++r) { a.limits[r] = f->limits[r]; a.weights[r] = f->weights[r]; }
-    a.rrf_c = rrf_c; a.ranker = ranker; a.norm = norm; a.reweighted = reweighted ? 1 : 0;
-    a.n = idx->n; a.id_base = idx->id_base; a.row_map = idx->row_map; a.levels = idx->levels;
-    a.out_adj = out_adj; a.out_fused = out_fused; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels; a.out_reqbits = out_reqbits;
-    if (out_on_device) {
-        hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(HY_THREADS), 0, s, a);
-        HIP_TRY(hipGetLastError());
-    } else {
-        // host outputs: FUSION_HOST_CHUNK queries per launch into the staging, copied out behind it (stream order keeps the
-        // next piece's launch behind this piece's copies)
-        a.out_adj = reweighted ? f->o_adj : nullptr; a.out_fused = f->o_fused; a.out_ids = f->o_ids;
-        a.out_levels = out_levels ? f->o_lv : nullptr; a.out_reqbits = out_reqbits ? f->o_bits : nullptr;
-        for (int64_t q0 = 0; q0 < nq; q0 += FUSION_HOST_CHUNK) {
-            const int64_t nb = std::min<int64_t>(FUSION_HOST_CHUNK, nq - q0);
-            a.st_scores = f->st_scores + (size_t)q0 * R * lmax;
-            a.st_ids = f->st_ids + (size_t)q0 * R * lmax;
-            hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, a);
-            HIP_TRY(hipGetLastError());
-            const size_t no = (size_t)nb * k, at = (size_t)q0 * k;
-            if (reweighted) HIP_TRY(hipMemcpyAsync(out_adj + at, a.out_adj, no * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_fused + at, a.out_fused, no * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_ids + at, a.out_ids, no * sizeof(long long), hipMemcpyDeviceToHost, s));
-            if (out_levels) HIP_TRY(hipMemcpyAsync(out_levels + at, a.out_levels, no * sizeof(int), hipMemcpyDeviceToHost, s));
-            if (out_reqbits) HIP_TRY(hipMemcpyAsync(out_reqbits + at, a.out_reqbits, no * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        }
-    }
-    if (!out_on_device || !queries_on_device) HIP_TRY(hipStreamSynchronize(s));
-    return ICD_OK;
-}
-
-}  // extern "C"
-
+// the other entry families, each its own file in this translation unit (launch_lds's per-kernel state and the kernel templates exist once)
+#include "icd_utility.hpp"   // the stateless utility entry points
+#include "icd_grouped.hpp"   // the grouping search
+#include "icd_hybrid.hpp"    // the hybrid search
 // the small-input sentence encoder (icd_encoder_*): its own file, this translation unit (fail(), HIP_TRY, packed_attention_kernel)
 #include "icd_encoder.hpp"

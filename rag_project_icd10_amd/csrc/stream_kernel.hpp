@@ -65,7 +65,7 @@ struct StreamArgs {
     u64 *wg_keys;         // [slot][nwg][KP] one merged best-first list per work-group (keys, 0 = empty)
     u64 *ticket;          // monotonic arrival counter (zeroed once, at index create)
     FinArgs fin;          // the outputs, levels, id_base and k of the search (emit_outputs), counters / host_counters
-    // a host caller's ONE query (icd_search.hip, search_common): the last work-group stores done_value to *done - a word of the
+    // a host caller's ONE query (icd_search.hip, run_search): the last work-group stores done_value to *done - a word of the
     // index's mapped host block - behind its outputs (system-scope release); nullptr = nobody polls
     u64 *done;
     u64 done_value;
