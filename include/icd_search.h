@@ -333,6 +333,73 @@ int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *que
                             int32_t bounds_on_device, int32_t mode, int32_t ranker, double rrf_c, const double *weights, int32_t norm,
                             int32_t k, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
                             uint32_t *out_reqbits, int32_t out_on_device, void *stream);
+/*
+ * icd_fusion_fuse_lists: step 2 of icd_index_search_hybrid alone, on the caller's lists - the seam that lets a request be
+ * anything that yields a best-first list (a sparse search next to a dense one). scores / ids: DEVICE arrays [nq * R][lmax], list
+ * (q, r) at row q * R + r, fp32 scores and global ids of `idx`, best first, padding id -1 (an id outside the index is skipped like
+ * padding); list r is read up to limits[r] <= lmax <= ICD_MAX_K. Rankers, answer, outputs, the host-output staging and
+ * the errors are icd_index_search_hybrid's; nq * R is bound by the fusion's max_total alone. With device outputs the call only
+ * enqueues on `stream` (graph-capturable).
+ */
+int icd_fusion_fuse_lists(icd_index *idx, icd_fusion *fusion, const float *scores, const int64_t *ids, int64_t nq, int32_t R,
+                          int32_t lmax, const int32_t *limits, int32_t ranker, double rrf_c, const double *weights, int32_t norm,
+                          int32_t k, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids,
+                          int32_t *out_levels, uint32_t *out_reqbits, int32_t out_on_device, void *stream);
+
+/*
+ * Sparse-vector search: Milvus's SPARSE_FLOAT_VECTOR field searched with metric IP (usually filled by its BM25 function), alone
+ * or as one request of a hybrid search through icd_fusion_fuse_lists. DESIGN.md section 14.
+ *   index             row i of an index of n rows carries a set of (term, value) pairs in CSR form (row_off[n + 1], terms, vals):
+ *                     term a uint32 in [0, vocab), strictly increasing within a row, value a finite non-zero fp32; a row may be
+ *                     empty. Not on a view, not on the row-sharded path (icd_group_*), n < 2^31. A built sparse index is not
+ *                     mutated: rebuild it.
+ *   query             0 .. ICD_SPARSE_MAX_QUERY_TERMS pairs under the same rules (q_off[nq + 1], q_terms, q_vals); a query
+ *                     without pairs yields padding.
+ *   score(q, i)       the sum over the terms t present in both, ascending t, of q_t * d_it: every product rounded once to
+ *                     fp32, the sum fp32 from 0.0f left to right, no FMA. A row that shares no term with the query is NOT a hit,
+ *                     whatever k is (Milvus's behaviour); a shared term makes the row a hit even when the sum is 0 or below.
+ *                     Sums that overflow fp32 are outside the contract.
+ *   answer            the min(k, hits) best rows by (score desc, id asc), 1 <= k <= ICD_MAX_K, then padding (score -inf, id -1,
+ *                     level 0); ids are global (id_base + row). masks: NULL, or a HOST array of nq row-mask handles of `idx`
+ *                     (NULL entries: unmasked) that restrict a query's hits to the mask's rows.
+ *   reweighted = 0    out_raw, out_ids, out_levels in that order; out_adj is not written.
+ *   reweighted = 1    icd_index_search_reweighted's step: out_adj = (double)raw * w[level], ONE stable descending re-sort.
+ *                     out_levels may be NULL.
+ *
+ * icd_sparse_pack (host only: no device, no handle): checks the rows and builds the inverted index the kernels walk -
+ * post_off[vocab + 1], post_row / post_val [row_off[n]], every term's postings by ascending row (a stable counting sort).
+ * Nothing is written when the input is refused.
+ *
+ * icd_sparse_create: packs the host CSR rows (n = the index's n), uploads the postings and allocates every workspace of the
+ * searches for up to max_nq queries at k <= max_k: a host caller's query and output staging and the [tiles][max_nq][max_k]
+ * partial lists (tiles of icd_sparse_tile_rows() rows). Nothing is allocated in a search. The handle keeps no pointer into its
+ * index - it is compared, never followed - and either may be destroyed first; it serves one stream at a time. A masked
+ * search reads the index's mask table and so also falls under the index's own one-stream-at-a-time rule, like every masked search.
+ *
+ * icd_sparse_search: one launch of sparse_accumulate_select_kernel over (query, tile) and one of sparse_merge_kernel. Every check
+ * comes before the first device call. ICD_ERR_INVALID: unsorted or duplicate terms, a term >= vocab, a non-finite or zero
+ * value, a query longer than ICD_SPARSE_MAX_QUERY_TERMS, k or nq above the handle's limits (nq above the index's max_nq with
+ * masks), a sparse index or a mask created for another index. ICD_ERR_UNSUPPORTED: a view, n >= 2^31. ICD_ERR_STATE: a
+ * destroyed handle. With queries_on_device = 1 the pairs cannot be read on the host: the call TRUSTS strictly increasing terms
+ * (a term >= vocab is skipped, a query is cut at ICD_SPARSE_MAX_QUERY_TERMS pairs; unsorted or repeated terms give sums in
+ * another order). With device queries and outputs and no masks the call only enqueues on `stream` (graph-capturable); with masks
+ * it is not, for the reason icd_index_search_masked gives. Range bounds, offset, iterator and grouping do not exist for a
+ * sparse search.
+ */
+typedef struct icd_sparse icd_sparse;
+#define ICD_SPARSE_MAX_QUERY_TERMS 64
+/* rows per tile of the sparse search kernel (a build constant; tests place their shapes around it) */
+int icd_sparse_tile_rows(void);
+int icd_sparse_pack(const int64_t *row_off, const uint32_t *terms, const float *vals, int64_t n, int64_t vocab,
+                    int64_t *post_off, uint32_t *post_row, float *post_val);
+int icd_sparse_create(icd_index *idx, const int64_t *row_off, const uint32_t *terms, const float *vals, int64_t vocab,
+                      int32_t max_nq, int32_t max_k, icd_sparse **out);
+int icd_sparse_destroy(icd_sparse *sp);
+/* vocabulary size, postings, device bytes held (any pointer may be NULL) */
+int icd_sparse_stats(icd_sparse *sp, int64_t *out_vocab, int64_t *out_nnz, int64_t *out_bytes);
+int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals,
+                      int64_t nq, int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, int32_t reweighted,
+                      double *out_adj, float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream);
 
 /*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by

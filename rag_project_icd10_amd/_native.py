@@ -38,8 +38,10 @@ EXPORTED_SYMBOLS = (
     "icd_grouping_create", "icd_grouping_destroy", "icd_grouping_stats", "icd_index_search_grouped",
     "icd_index_search_range",
     "icd_rowmask_create", "icd_rowmask_destroy", "icd_rowmask_stats", "icd_rowmask_pack", "icd_index_search_masked",
-    "icd_fusion_create", "icd_fusion_destroy", "icd_fusion_stats", "icd_index_search_hybrid",
+    "icd_fusion_create", "icd_fusion_destroy", "icd_fusion_stats", "icd_index_search_hybrid", "icd_fusion_fuse_lists",
+    "icd_sparse_tile_rows", "icd_sparse_pack", "icd_sparse_create", "icd_sparse_destroy", "icd_sparse_stats", "icd_sparse_search",
 )
+SPARSE_MAX_QUERY_TERMS = 64   # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
 RANKER_RRF, RANKER_WEIGHTED = 0, 1
 NORMS = {"none": 0, "cosine": 1, "atan": 2}   # ICD_NORM_*
@@ -129,6 +131,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_fusion_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_hybrid.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, i32, C.c_double, vp, i32, i32, i32,
                                             vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_fusion_fuse_lists.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_sparse_tile_rows.restype = C.c_int
+    lib.icd_sparse_pack.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp]
+    lib.icd_sparse_create.argtypes = [vp, vp, vp, vp, i64, i32, i32, C.POINTER(vp)]
+    lib.icd_sparse_destroy.argtypes = [vp]
+    lib.icd_sparse_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_sparse_search.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -594,6 +603,99 @@ class IcdIndex:
         _check(self._lib, rc)
         return (adj, fused, ids, lv, bits) if reweighted else (fused, ids, lv, bits)
 
+    def fuse_lists(self, fusion: "IcdFusion", scores, ids, limits, k: int, *, ranker: str = "rrf", rrf_c: float = 60.0, weights=None,
+                   norm: str = "none", reweighted: bool = True, to_host: bool = False):
+        """Step 2 of search_hybrid on the caller's lists (icd_fusion_fuse_lists): scores [nq, R, lmax] float32 and ids
+        [nq, R, lmax] int64 (this index's ids, -1 = padding), best first - numpy arrays (uploaded) or torch CUDA tensors. limits,
+        rankers and outputs as search_hybrid; device tensors out unless to_host."""
+        if self.closed or fusion is None or fusion.closed:
+            raise IcdError(-5, "index or fusion is closed")
+        import torch
+        where = torch.device("cuda", self.device)
+        sc = torch.as_tensor(scores).to(device=where, dtype=torch.float32).contiguous()
+        idt = torch.as_tensor(ids).to(device=where, dtype=torch.int64).contiguous()
+        if sc.ndim != 3 or tuple(idt.shape) != tuple(sc.shape):
+            raise ValueError(f"scores and ids must both be [nq, R, lmax], got {tuple(sc.shape)} and {tuple(idt.shape)}")
+        nq, R, lmax = (int(v) for v in sc.shape)
+        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.int32).reshape(-1), (R,)) if np.size(limits) == 1
+                                   else np.asarray(limits, dtype=np.int32).reshape(-1))
+        if lim.size != R:
+            raise ValueError(f"limits holds {lim.size} entries for {R} requests")
+        if ranker not in ("rrf", "weighted"):
+            raise ValueError(f"ranker={ranker!r}: 'rrf' or 'weighted'")
+        if norm not in NORMS:
+            raise ValueError(f"norm={norm!r}: one of {sorted(NORMS)}")
+        wts = None
+        if ranker == "weighted":
+            wts = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+            if wts.size != R:
+                raise ValueError(f"weights holds {wts.size} entries for {R} requests")
+        k = int(k)
+        on_dev = not to_host
+        (adj, fused, out_ids, lv, bits), ptr, stream, dev = _outputs(
+            on_dev, self.device, (nq, k), (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32))
+        if stream is None:
+            stream = _current_stream_ptr(self.device)   # (the lists are device tensors of torch's current stream)
+        rc = self._lib.icd_fusion_fuse_lists(
+            self._h, fusion._h, sc.data_ptr() if nq else None, idt.data_ptr() if nq else None, nq, R, lmax, lim.ctypes.data,
+            RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
+            1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(out_ids), ptr(lv), ptr(bits), dev, stream)
+        _check(self._lib, rc)
+        return (adj, fused, out_ids, lv, bits) if reweighted else (fused, out_ids, lv, bits)
+
+    # -- sparse-vector search (Milvus SPARSE_FLOAT_VECTOR, metric IP) --------------------------------------
+    def sparse(self, row_off, terms, vals, vocab: int, max_nq: int = 1024, max_k: int = MAX_K) -> "IcdSparse":
+        """A sparse index over this index's rows (icd_sparse_create): CSR rows (row_off int64 [n + 1], terms uint32, vals
+        float32; strictly increasing terms below vocab, finite non-zero values), with the workspace of searches of up to max_nq
+        queries at k <= max_k."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdSparse(self, row_off, terms, vals, int(vocab), int(max_nq), int(max_k))
+
+    def search_sparse(self, sp: "IcdSparse", q_off, q_terms, q_vals, k: int, masks=None, reweighted: bool = False, validate: bool = True):
+        """The best k rows by sparse inner product among the rows that share a term with the query (icd_sparse_search). Queries
+        in CSR form (q_off int64 [nq + 1], q_terms uint32, q_vals float32; at most 64 strictly increasing terms each): numpy
+        arrays - checked by the library, host outputs - or torch CUDA tensors (int64 / int32 holding the uint32 bit patterns /
+        float32), device tensors out on torch's current stream. The library cannot read device queries, so with validate=True
+        (the default) they are copied to the host and checked there first: that SYNCHRONISES, and the call is not
+        graph-capturable. validate=False skips the copy for queries the caller has already checked (check_sparse_rows): the
+        call then only enqueues and, without masks, can be captured; the kernel trusts strictly increasing terms. masks: None, ONE IcdRowMask for
+        every query, or nq of IcdRowMask or None. reweighted: (adj f64, raw f32, ids i64, levels i32) in search_reweighted's
+        order, else (raw, ids, levels) best first; padding -inf, -1, 0."""
+        if self.closed or sp is None or sp.closed:
+            raise IcdError(-5, "index or sparse index is closed")
+        on_dev = _is_torch_tensor(q_off) and q_off.is_cuda
+        if on_dev:
+            import torch
+            off = q_off.to(torch.int64).contiguous().reshape(-1)
+            tr = q_terms.contiguous().reshape(-1)
+            if tr.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                tr = tr.to(torch.int64).to(torch.int32)   # (values up to 2^32 - 1 wrap into the same bit patterns)
+            vl = q_vals.to(torch.float32).contiguous().reshape(-1)
+            nq, n_terms = int(off.numel()) - 1, int(tr.numel())
+            if nq < 0 or n_terms != int(vl.numel()):
+                raise ValueError("q_off must hold nq + 1 offsets; q_terms and q_vals one entry per pair")
+            if validate:   # (device -> host copies: a synchronisation)
+                check_sparse_rows(off.cpu().numpy(), tr.cpu().numpy().view(np.uint32), vl.cpu().numpy(), sp.vocab, SPARSE_MAX_QUERY_TERMS, "query")
+        else:   # (a host caller's queries are checked by icd_sparse_search itself)
+            off = np.ascontiguousarray(np.asarray(q_off).reshape(-1), dtype=np.int64)
+            tr = np.ascontiguousarray(np.asarray(q_terms).reshape(-1), dtype=np.uint32)
+            vl = np.ascontiguousarray(np.asarray(q_vals).reshape(-1), dtype=np.float32)
+            nq, n_terms = int(off.size) - 1, int(tr.size)
+            if nq < 0 or n_terms != vl.size or (nq > 0 and int(off[-1]) != n_terms):
+                raise ValueError("q_off must hold nq + 1 offsets that end at the number of terms and values")
+        k = int(k)
+        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")
+        (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (nq, k), (np.float64, np.float32, np.int64, np.int32))
+        if nq:
+            rc = self._lib.icd_sparse_search(self._h, sp._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k,
+                                             dev, None if mask_h is None else mask_h.ctypes.data, 1 if reweighted else 0,
+                                             ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
+            if rc == -1:
+                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+            _check(self._lib, rc)
+        return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
+
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""
         import torch
@@ -686,6 +788,87 @@ class IcdFusion(_Handle):
         t, b = C.c_int64(), C.c_int64()
         _check(self._lib, self._lib.icd_fusion_stats(self._h, C.byref(t), C.byref(b)))
         return {"max_total": t.value, "bytes": b.value}
+
+
+def sparse_tile_rows() -> int:
+    """Rows per tile of the sparse search kernel (icd_sparse_tile_rows: a constant of the build)"""
+    return int(load_library().icd_sparse_tile_rows())
+
+
+def check_sparse_rows(row_off, terms, vals, vocab: int, max_terms: int = 0, unit: str = "row"):
+    """The rules of sparse rows / queries in CSR form, in numpy (what icd_sparse_pack and icd_sparse_search check on the host):
+    offsets from 0 that never decrease, terms strictly increasing within a row and below vocab, values finite and non-zero, at
+    most max_terms (> 0) pairs per row. Raises ValueError."""
+    off = np.asarray(row_off, np.int64).reshape(-1)
+    t = np.asarray(terms).reshape(-1).astype(np.int64)
+    v = np.asarray(vals, np.float32).reshape(-1)
+    if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != t.size or t.size != v.size:
+        raise ValueError(f"{unit} offsets must start at 0, never decrease and end at the number of terms and values")
+    if max_terms > 0 and off.size > 1 and int(np.diff(off).max()) > max_terms:
+        raise ValueError(f"a {unit} carries at most {max_terms} terms")
+    if t.size == 0:
+        return
+    if t.min() < 0 or t.max() >= vocab:
+        raise ValueError(f"{unit}: a term lies outside the vocabulary's [0, {vocab})")
+    inner = np.ones(t.size, bool)
+    inner[off[:-1][off[:-1] < t.size]] = False   # the first pair of every row has no predecessor
+    if (np.diff(t, prepend=t[0])[inner] <= 0).any():
+        raise ValueError(f"{unit}: terms must be strictly increasing")
+    if not np.isfinite(v).all() or (v == 0).any():
+        raise ValueError(f"{unit}: values must be finite and non-zero")
+
+
+def sparse_pack(row_off, terms, vals, n: int, vocab: int):
+    """The inverted index CSR rows become (icd_sparse_pack, the packer icd_sparse_create runs; no device needed):
+    (post_off int64 [vocab + 1], post_row uint32 [nnz], post_val float32 [nnz]), every term's postings by ascending row. Raises
+    ValueError for rows the rules refuse."""
+    lib = load_library()
+    off = np.ascontiguousarray(np.asarray(row_off).reshape(-1), dtype=np.int64)
+    t = np.ascontiguousarray(np.asarray(terms).reshape(-1), dtype=np.uint32)
+    v = np.ascontiguousarray(np.asarray(vals).reshape(-1), dtype=np.float32)
+    if off.size != int(n) + 1 or int(vocab) < 1:
+        raise ValueError(f"row_off holds {off.size} offsets for {n} rows (vocab={vocab})")
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != t.size or t.size != v.size:
+        raise ValueError("row offsets must start at 0, never decrease and end at the number of terms and values")
+    post_off = np.empty(int(vocab) + 1, np.int64)
+    post_row = np.empty(max(t.size, 1), np.uint32)
+    post_val = np.empty(max(t.size, 1), np.float32)
+    rc = lib.icd_sparse_pack(off.ctypes.data, t.ctypes.data if t.size else None, v.ctypes.data if t.size else None, int(n), int(vocab),
+                             post_off.ctypes.data, post_row.ctypes.data, post_val.ctypes.data)
+    if rc == -1:
+        raise ValueError(lib.icd_last_error().decode("utf-8", "replace"))
+    _check(lib, rc)
+    return post_off, post_row[:t.size], post_val[:t.size]
+
+
+class IcdSparse(_Handle):
+    """A sparse index over the rows of one IcdIndex (icd_sparse_*): postings on the device and the workspace of its searches.
+    Independent of the index's lifetime: either may be closed first (a search with a closed partner raises)."""
+    _destroy = "icd_sparse_destroy"
+
+    def __init__(self, index: "IcdIndex", row_off, terms, vals, vocab: int, max_nq: int, max_k: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        off = np.ascontiguousarray(np.asarray(row_off).reshape(-1), dtype=np.int64)
+        t = np.ascontiguousarray(np.asarray(terms).reshape(-1), dtype=np.uint32)
+        v = np.ascontiguousarray(np.asarray(vals).reshape(-1), dtype=np.float32)
+        if off.size != index.n + 1:
+            raise ValueError(f"row_off holds {off.size} offsets, the index {index.n} rows")
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != t.size or t.size != v.size:
+            raise ValueError("row offsets must start at 0, never decrease and end at the number of terms and values")
+        self.n, self.vocab, self.max_nq, self.max_k, self.device = index.n, int(vocab), int(max_nq), int(max_k), index.device
+        rc = self._lib.icd_sparse_create(index._h, off.ctypes.data, t.ctypes.data if t.size else None, v.ctypes.data if t.size else None,
+                                         self.vocab, self.max_nq, self.max_k, C.byref(self._h))
+        if rc == -1:
+            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+        _check(self._lib, rc)
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "sparse index is closed")
+        vv, nn, bb = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_sparse_stats(self._h, C.byref(vv), C.byref(nn), C.byref(bb)))
+        return {"vocab": vv.value, "nnz": nn.value, "bytes": bb.value}
 
 
 def rowmask_words(n: int) -> int:

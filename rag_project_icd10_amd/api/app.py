@@ -182,8 +182,11 @@ async def hybrid_query(request: HybridQueryRequest):
         if not 1 <= request.top_k <= 50:
             raise ValueError(f"top_k={request.top_k}: 1 .. 50")
         ranker = hybrid.ranker_from_dict(request.ranker)
-        if isinstance(ranker, hybrid.WeightedRanker) and len(ranker.weights) != len(request.texts):
-            raise ValueError(f"the ranker holds {len(ranker.weights)} weights for {len(request.texts)} texts")
+        n_reqs = len(request.texts) * (2 if request.sparse else 1)   # sparse: the dense requests first, then one sparse request per text
+        if n_reqs > hybrid.MAX_REQUESTS:
+            raise ValueError(f"{len(request.texts)} texts with sparse requests: at most {hybrid.MAX_REQUESTS // 2} phrasings")
+        if isinstance(ranker, hybrid.WeightedRanker) and len(ranker.weights) != n_reqs:
+            raise ValueError(f"the ranker holds {len(ranker.weights)} weights for {n_reqs} requests")
         hybrid.AnnSearchRequest(None, request.req_limit, request.filter)   # (the limit's and the filter's checks)
     except ValueError as exc:
         raise HTTPException(status_code=400, detail=str(exc))
@@ -193,6 +196,8 @@ async def hybrid_query(request: HybridQueryRequest):
         import numpy as np
         vecs = np.asarray(embedding_service.encode_query_batch(list(request.texts)), dtype=np.float32)
         reqs = [hybrid.AnnSearchRequest(vecs[i], request.req_limit, request.filter) for i in range(len(request.texts))]
+        if request.sparse:
+            reqs += [hybrid.AnnSearchRequest(t, request.req_limit, request.filter, anns_field="sparse") for t in request.texts]
         try:
             hits = milvus_service.hybrid_search(reqs, ranker, request.top_k)
         except ValueError as exc:
@@ -236,6 +241,8 @@ async def get_stats():
                 stats["groupings"] = milvus_service.groupings()
             if hasattr(milvus_service, "fusions"):        # the hybrid-search workspace: sub-lists per call, HBM bytes
                 stats["fusions"] = milvus_service.fusions()
+            if hasattr(milvus_service, "sparse_indexes"):   # the sparse (BM25) index: field, vocabulary, postings, HBM bytes
+                stats["sparse_indexes"] = milvus_service.sparse_indexes()
         if embedding_service:
             stats["embedding"] = embedding_service.get_model_info()
         return stats

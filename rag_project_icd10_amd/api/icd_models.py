@@ -231,6 +231,7 @@ class HybridQueryRequest(BaseModel):
     top_k: int = Field(default=5, description="fused hits returned (1 .. 50)")
     req_limit: int = Field(default=20, description="hits every phrasing contributes (1 .. 128)")
     filter: Optional[str] = Field(default=None, description="Milvus filter expression applied to every request")
+    sparse: bool = Field(default=False, description="every text also contributes a sparse (BM25) request next to its dense one (at most 4 texts then)")
 
 
 class QueryResponse(BaseModel):

@@ -24,6 +24,46 @@ namespace {
 constexpr int FUSION_HOST_CHUNK = 256;
 }  // namespace
 
+// Step 2 of a hybrid search: ONE launch of hybrid_fuse_kernel over the [nq * R][lmax] sub-lists at st_scores / st_ids (device memory;
+// the fusion's staging, or a caller's lists: icd_fusion_fuse_lists), limits and weights taken from the fusion, where the caller
+// has put them. Host outputs leave through the fusion's staging, FUSION_HOST_CHUNK queries at a time.
+static int fuse_lists_step(icd_index *idx, icd_fusion *f, const float *st_scores, const long long *st_ids, int64_t nq, int32_t R, int lmax,
+                           int32_t ranker, double rrf_c, int32_t norm, int32_t k, int32_t reweighted, double *out_adj, double *out_fused,
+                           int64_t *out_ids, int32_t *out_levels, uint32_t *out_reqbits, const HostCall &hc, hipStream_t s) {
+    int rc;
+    HybridArgs a{};
+    a.st_scores = st_scores; a.st_ids = st_ids;
+    a.R = R; a.lmax = lmax; a.k = k;
+    a.slots = 2;
+    while (a.slots < R * lmax) a.slots <<= 1;
+    for (int r = 0; r < HY_MAX_R; ++r) { a.limits[r] = f->limits[r]; a.weights[r] = f->weights[r]; }
+    a.rrf_c = rrf_c; a.ranker = ranker; a.norm = norm; a.reweighted = reweighted ? 1 : 0;
+    a.n = idx->n; a.id_base = idx->id_base; a.row_map = idx->row_map; a.levels = idx->levels;
+    a.out_adj = out_adj; a.out_fused = out_fused; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels; a.out_reqbits = out_reqbits;
+    if (hc.out_on_device) {
+        hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(HY_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // host outputs: FUSION_HOST_CHUNK queries per launch into the staging, copied out behind it (stream order keeps the
+        // next piece's launch behind this piece's copies)
+        a.out_adj = reweighted ? f->o_adj : nullptr; a.out_fused = f->o_fused; a.out_ids = f->o_ids;
+        a.out_levels = out_levels ? f->o_lv : nullptr; a.out_reqbits = out_reqbits ? f->o_bits : nullptr;
+        for (int64_t q0 = 0; q0 < nq; q0 += FUSION_HOST_CHUNK) {
+            const int64_t nb = std::min<int64_t>(FUSION_HOST_CHUNK, nq - q0);
+            a.st_scores = st_scores + (size_t)q0 * R * lmax;
+            a.st_ids = st_ids + (size_t)q0 * R * lmax;
+            hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, a);
+            HIP_TRY(hipGetLastError());
+            const size_t at = (size_t)q0 * k;
+            if ((rc = hc.copy_back({{reweighted ? out_adj + at : nullptr, a.out_adj, 8}, {out_fused + at, a.out_fused, 8}, {out_ids + at, a.out_ids, 8},
+                                    {out_levels ? out_levels + at : nullptr, a.out_levels, 4}, {out_reqbits ? out_reqbits + at : nullptr, a.out_reqbits, 4}},
+                                   (size_t)nb * k)))
+                return rc;
+        }
+    }
+    return ICD_OK;
+}
+
 extern "C" {
 
 int icd_fusion_create(icd_index *idx, int64_t max_total, icd_fusion **out) {
@@ -120,36 +160,9 @@ int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *que
                                        plain ? nullptr : &rb, any_mask ? masks : nullptr, s, &capturing});
     if (rc) return rc;
     // step 2: the fuse
-    HybridArgs a{};
-    a.st_scores = f->st_scores; a.st_ids = f->st_ids;
-    a.R = R; a.lmax = lmax; a.k = k;
-    a.slots = 2;
-    while (a.slots < R * lmax) a.slots <<= 1;
-    for (int r = 0; r < HY_MAX_R; ++r) { a.limits[r] = f->limits[r]; a.weights[r] = f->weights[r]; }
-    a.rrf_c = rrf_c; a.ranker = ranker; a.norm = norm; a.reweighted = reweighted ? 1 : 0;
-    a.n = idx->n; a.id_base = idx->id_base; a.row_map = idx->row_map; a.levels = idx->levels;
-    a.out_adj = out_adj; a.out_fused = out_fused; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels; a.out_reqbits = out_reqbits;
-    if (out_on_device) {
-        hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(HY_THREADS), 0, s, a);
-        HIP_TRY(hipGetLastError());
-    } else {
-        // host outputs: FUSION_HOST_CHUNK queries per launch into the staging, copied out behind it (stream order keeps the
-        // next piece's launch behind this piece's copies)
-        a.out_adj = reweighted ? f->o_adj : nullptr; a.out_fused = f->o_fused; a.out_ids = f->o_ids;
-        a.out_levels = out_levels ? f->o_lv : nullptr; a.out_reqbits = out_reqbits ? f->o_bits : nullptr;
-        for (int64_t q0 = 0; q0 < nq; q0 += FUSION_HOST_CHUNK) {
-            const int64_t nb = std::min<int64_t>(FUSION_HOST_CHUNK, nq - q0);
-            a.st_scores = f->st_scores + (size_t)q0 * R * lmax;
-            a.st_ids = f->st_ids + (size_t)q0 * R * lmax;
-            hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, a);
-            HIP_TRY(hipGetLastError());
-            const size_t at = (size_t)q0 * k;
-            if ((rc = hc.copy_back({{reweighted ? out_adj + at : nullptr, a.out_adj, 8}, {out_fused + at, a.out_fused, 8}, {out_ids + at, a.out_ids, 8},
-                                    {out_levels ? out_levels + at : nullptr, a.out_levels, 4}, {out_reqbits ? out_reqbits + at : nullptr, a.out_reqbits, 4}},
-                                   (size_t)nb * k)))
-                return rc;
-        }
-    }
+    if ((rc = fuse_lists_step(idx, f, f->st_scores, f->st_ids, nq, R, lmax, ranker, rrf_c, norm, k, reweighted, out_adj, out_fused, out_ids,
+                              out_levels, out_reqbits, hc, s)))
+        return rc;
     return hc.finish();
 }
 

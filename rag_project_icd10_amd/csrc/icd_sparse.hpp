@@ -1,0 +1,201 @@
+// icd_sparse.hpp - the sparse-vector search (icd_sparse_*) and the fuse of caller-provided lists (icd_fusion_fuse_lists). Part of
+// icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle, mask and host-call helpers, the fusion); included there and
+// nowhere else.
+#pragma once
+#include "sparse_pack.hpp"
+
+// ---- sparse search (sparse_kernel.hpp) ------------------------------------------------------------------
+// A sparse index belongs to the index it was created for but keeps no pointer into it: handle and identity are compared, never
+// followed. Postings, the staging of a host caller's queries and outputs and the tiles' partial lists are allocated here, never
+// in a search.
+struct icd_sparse : OwnedHandle {
+    static constexpr uint32_t MAGIC = 0x1CD5BA25u;
+    static constexpr const char *NOUN = "sparse index";
+    int64_t vocab = 0, nnz = 0;
+    int tiles = 0, max_nq = 0, max_k = 0;
+    long long *post_off = nullptr; uint32_t *post_row = nullptr; float *post_val = nullptr;   // [vocab + 1], [nnz], [nnz]
+    long long *q_off = nullptr; uint32_t *q_terms = nullptr; float *q_vals = nullptr;         // a host caller's queries: [max_nq + 1], [max_nq][64] each
+    icd::u64 *part = nullptr;                                                                  // [tiles][max_nq][max_k] keys, best first
+    double *o_adj = nullptr; float *o_raw = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr;   // [max_nq][max_k] a host caller's outputs
+    std::mutex mu;
+};
+
+static_assert(ICD_SPARSE_MAX_QUERY_TERMS == SP_MAX_TERMS, "ICD_SPARSE_MAX_QUERY_TERMS and sparse_kernel.hpp disagree");
+
+extern "C" {
+
+int icd_sparse_tile_rows(void) { return SP_TILE; }
+
+int icd_sparse_pack(const int64_t *row_off, const uint32_t *terms, const float *vals, int64_t n, int64_t vocab, int64_t *post_off,
+                    uint32_t *post_row, float *post_val) {
+    char msg[200];
+    if (sparse_pack_rows(row_off, terms, vals, n, vocab, post_off, post_row, post_val, msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);
+    return ICD_OK;
+}
+
+int icd_sparse_create(icd_index *idx, const int64_t *row_off, const uint32_t *terms, const float *vals, int64_t vocab, int32_t max_nq,
+                      int32_t max_k, icd_sparse **out) {
+    if (!out) return fail(ICD_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a sparse index on a view is not supported: build it on the parent and mask");
+    if (idx->n > 0x7FFFFFFFll) return fail(ICD_ERR_UNSUPPORTED, "n=%lld: a sparse index addresses rows with 31 bits (n < 2^31)", (long long)idx->n);
+    if (max_nq < 1 || max_k < 1 || max_k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "max_nq=%d max_k=%d (max_k in 1 .. %d)", max_nq, max_k, ICD_MAX_K);
+    const int64_t tiles = (idx->n + SP_TILE - 1) / SP_TILE;
+    if (tiles * max_nq > 0x7FFFFFFFll) return fail(ICD_ERR_INVALID, "max_nq=%d: %lld tiles of rows times max_nq exceed 2^31 - 1 work-groups", max_nq, (long long)tiles);
+    char msg[200];
+    if (sparse_check_rows(row_off, terms, vals, idx->n, vocab, msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);   // (the one pass over the rows' rules)
+    const int64_t nnz = row_off[idx->n];
+    std::vector<int64_t> h_off;
+    std::vector<uint32_t> h_row;
+    std::vector<float> h_val;
+    try {
+        h_off.resize((size_t)vocab + 1); h_row.resize((size_t)nnz); h_val.resize((size_t)nnz);
+    } catch (const std::bad_alloc &) {
+        return fail(ICD_ERR_NOMEM, "host allocation failed");
+    }
+    sparse_pack_checked(row_off, terms, vals, idx->n, vocab, h_off.data(), h_row.data(), h_val.data());
+    HIP_TRY(hipSetDevice(idx->device));
+    icd_sparse *sp = new_handle<icd_sparse>(idx);
+    if (!sp) return fail(ICD_ERR_NOMEM, "host allocation failed");
+    sp->vocab = vocab; sp->nnz = nnz; sp->tiles = (int)tiles; sp->max_nq = max_nq; sp->max_k = max_k;
+    const size_t nt = (size_t)max_nq * SP_MAX_TERMS, no = (size_t)max_nq * max_k, np_ = (size_t)tiles * no;
+#define SP_TRY(expr) HIP_TRY_OR(free_handle(sp), expr)
+    SP_TRY(sp->alloc(&sp->post_off, (size_t)vocab + 1)); SP_TRY(sp->alloc(&sp->post_row, (size_t)nnz)); SP_TRY(sp->alloc(&sp->post_val, (size_t)nnz));
+    SP_TRY(sp->alloc(&sp->q_off, (size_t)max_nq + 1)); SP_TRY(sp->alloc(&sp->q_terms, nt)); SP_TRY(sp->alloc(&sp->q_vals, nt));
+    SP_TRY(sp->alloc(&sp->part, np_));
+    SP_TRY(sp->alloc(&sp->o_adj, no)); SP_TRY(sp->alloc(&sp->o_raw, no)); SP_TRY(sp->alloc(&sp->o_ids, no)); SP_TRY(sp->alloc(&sp->o_lv, no));
+    SP_TRY(hipMemcpy(sp->post_off, h_off.data(), ((size_t)vocab + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz) {
+        SP_TRY(hipMemcpy(sp->post_row, h_row.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+        SP_TRY(hipMemcpy(sp->post_val, h_val.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+    }
+#undef SP_TRY
+    sp->bytes = ((size_t)vocab + 1) * 8 + (size_t)nnz * 8 + ((size_t)max_nq + 1) * 8 + nt * 8 + np_ * 8 + no * (8 + 4 + 8 + 4);
+    *out = sp;
+    return ICD_OK;
+}
+
+int icd_sparse_destroy(icd_sparse *sp) { return destroy_handle(sp); }
+
+int icd_sparse_stats(icd_sparse *sp, int64_t *out_vocab, int64_t *out_nnz, int64_t *out_bytes) {
+    if (!valid_handle(sp)) return fail(ICD_ERR_STATE, "invalid sparse index handle");
+    if (out_vocab) *out_vocab = sp->vocab;
+    if (out_nnz) *out_nnz = sp->nnz;
+    if (out_bytes) *out_bytes = (int64_t)sp->bytes;
+    return ICD_OK;
+}
+
+int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals, int64_t nq,
+                      int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, int32_t reweighted, double *out_adj, float *out_raw,
+                      int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
+    // every check comes before the first device call
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(sp)) return fail(ICD_ERR_STATE, "invalid sparse index handle");
+    int rc = check_owner(sp->at, idx, "the sparse index");
+    if (rc) return rc;
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a sparse search on a view is not supported");
+    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a sparse search returns 1 .. %d hits per query", k, ICD_MAX_K);
+    if (k > sp->max_k) return fail(ICD_ERR_INVALID, "k=%d exceeds the sparse index's max_k=%d", k, sp->max_k);
+    if (nq < 0 || nq > sp->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the sparse index's max_nq=%d", (long long)nq, sp->max_nq);
+    if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    bool any_mask = false;
+    if (masks && (rc = check_masks(idx, masks, nq, "masked sparse search", &any_mask))) return rc;
+    if (nq == 0) return ICD_OK;
+    if (!q_off) return fail(ICD_ERR_INVALID, "q_off is NULL");
+    int64_t q_nnz = 0;
+    if (!queries_on_device) {
+        char msg[200];
+        if (sparse_check_csr(q_off, q_terms, q_vals, nq, sp->vocab, SP_MAX_TERMS, "query", msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);
+        q_nnz = q_off[nq];
+    } else if (!q_terms || !q_vals) {
+        return fail(ICD_ERR_INVALID, "q_terms / q_vals NULL");
+    }
+    std::lock_guard<std::mutex> guard(sp->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
+    if ((rc = check_capture(s, !queries_on_device || !out_on_device, false, any_mask))) return rc;
+    // a masked call reads section 12's table of the index: it holds the index's mutex from the table's fill to its last launch, as
+    // every masked dense search does (an unmasked call touches nothing of the index's workspace and takes only its own)
+    std::unique_lock<std::mutex> table(idx->mu, std::defer_lock);
+    if (any_mask) {
+        table.lock();
+        if ((rc = stage_masks(idx, masks, (int)nq, s))) return rc;
+    }
+    SparseArgs a{};
+    a.post_off = sp->post_off; a.post_row = sp->post_row; a.post_val = sp->post_val; a.vocab = sp->vocab;
+    a.q_off = reinterpret_cast<const long long *>(q_off); a.q_terms = q_terms; a.q_vals = q_vals;
+    if (!queries_on_device) {
+        HIP_TRY(hipMemcpyAsync(sp->q_off, q_off, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, s));
+        if (q_nnz) {
+            HIP_TRY(hipMemcpyAsync(sp->q_terms, q_terms, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(sp->q_vals, q_vals, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
+        }
+        a.q_off = sp->q_off; a.q_terms = sp->q_terms; a.q_vals = sp->q_vals;
+    }
+    a.masks = any_mask ? idx->mask_dev : nullptr;
+    a.mask_words = rowmask_tile_words(idx->n);
+    a.tiles = sp->tiles; a.nq = (int)nq; a.k = k; a.part = sp->part;
+    hipLaunchKernelGGL(sparse_accumulate_select_kernel, dim3((unsigned)(nq * sp->tiles)), dim3(SP_THREADS), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    SparseMergeArgs m{};
+    m.part = sp->part; m.tiles = sp->tiles; m.nq = (int)nq; m.k = k; m.reweighted = reweighted ? 1 : 0;
+    m.id_base = idx->id_base; m.levels = idx->levels;
+    m.out_adj = reweighted ? hc.target(out_adj, sp->o_adj) : nullptr; m.out_raw = hc.target(out_raw, sp->o_raw);
+    m.out_ids = hc.target(reinterpret_cast<long long *>(out_ids), sp->o_ids); m.out_levels = hc.target(out_levels, sp->o_lv);
+    hipLaunchKernelGGL(sparse_merge_kernel, dim3((unsigned)nq), dim3(SP_THREADS), 0, s, m);
+    HIP_TRY(hipGetLastError());
+    if ((rc = hc.copy_back({{reweighted ? out_adj : nullptr, m.out_adj, 8}, {out_raw, m.out_raw, 4}, {out_ids, m.out_ids, 8}, {out_levels, m.out_levels, 4}},
+                           (size_t)nq * k)))
+        return rc;
+    return hc.finish();
+}
+
+int icd_fusion_fuse_lists(icd_index *idx, icd_fusion *fusion, const float *scores, const int64_t *ids, int64_t nq, int32_t R, int32_t lmax,
+                          const int32_t *limits, int32_t ranker, double rrf_c, const double *weights, int32_t norm, int32_t k,
+                          int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
+                          uint32_t *out_reqbits, int32_t out_on_device, void *stream) {
+    // the checks of icd_index_search_hybrid that concern its step 2, before the first device call
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
+    icd_fusion *f = fusion;
+    int rc = check_owner(f->at, idx, "the fusion");
+    if (rc) return rc;
+    if (R < 1 || R > ICD_MAX_REQUESTS) return fail(ICD_ERR_INVALID, "R=%d: a hybrid search takes 1 .. %d requests per query", R, ICD_MAX_REQUESTS);
+    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a hybrid search returns 1 .. %d hits per query", k, ICD_MAX_K);
+    if (lmax < 1 || lmax > ICD_MAX_K) return fail(ICD_ERR_INVALID, "lmax=%d: a list holds 1 .. %d hits", lmax, ICD_MAX_K);
+    if (!limits) return fail(ICD_ERR_INVALID, "limits is NULL");
+    for (int r = 0; r < R; ++r)
+        if (limits[r] < 1 || limits[r] > lmax) return fail(ICD_ERR_INVALID, "limits[%d]=%d: a request returns 1 .. lmax=%d hits", r, limits[r], lmax);
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    if (nq * R > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)(nq * R), (long long)f->max_total);
+    if (ranker == ICD_RANKER_RRF) {
+        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
+    } else if (ranker == ICD_RANKER_WEIGHTED) {
+        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
+        for (int r = 0; r < R; ++r)
+            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
+        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
+    } else {
+        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
+    }
+    if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (nq == 0) return ICD_OK;
+    if (!scores || !ids) return fail(ICD_ERR_INVALID, "scores / ids NULL");
+    std::lock_guard<std::mutex> guard(f->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, true, out_on_device != 0};
+    if ((rc = check_capture(s, !out_on_device, false, false))) return rc;
+    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
+        f->limits[r] = r < R ? limits[r] : 0;
+        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
+    }
+    if ((rc = fuse_lists_step(idx, f, scores, reinterpret_cast<const long long *>(ids), nq, R, lmax, ranker, rrf_c, norm, k, reweighted, out_adj,
+                              out_fused, out_ids, out_levels, out_reqbits, hc, s)))
+        return rc;
+    return hc.finish();
+}
+
+}  // extern "C"

@@ -19,14 +19,26 @@ from . import filter_expr, range_search
 MAX_REQUESTS = 8    # include/icd_search.h ICD_MAX_REQUESTS
 MAX_LIMIT = 128     # ICD_MAX_K
 NORMS = ("none", "cosine", "atan")
+ANNS_FIELDS = ("vector", "sparse")   # the dense field; the sparse (BM25) field of DESIGN.md section 14
 
 
 class AnnSearchRequest:
-    """One dense request of a hybrid search. data: the query vector(s) - [dim] or [nq, dim]; limit: hits this request contributes
-    (1 .. 128); expr: a Milvus filter expression (services/filter_expr.py) or None; param: Milvus search params, of which
-    {"params": {"radius": .., "range_filter": ..}} (or the two keys at the top level) are used."""
+    """One request of a hybrid search.
 
-    def __init__(self, data, limit: int, expr: Optional[str] = None, param: Optional[Dict[str, Any]] = None):
+    anns_field "vector" (the default), a dense request. data: the query vector(s) - [dim] or [nq, dim]; limit: hits this request
+    contributes (1 .. 128); expr: a Milvus filter expression (services/filter_expr.py) or None; param: Milvus search params, of
+    which {"params": {"radius": .., "range_filter": ..}} (or the two keys at the top level) are used.
+
+    anns_field "sparse": data is a text or a {term_id: weight} dict (or a list of nq of them), searched in the store's sparse
+    (BM25) index (MilvusService.build_sparse_index); limit and expr as above, no bounds."""
+
+    def __init__(self, data, limit: int, expr: Optional[str] = None, param: Optional[Dict[str, Any]] = None, *, anns_field: str = "vector"):
+        if anns_field not in ANNS_FIELDS:
+            raise ValueError(f"anns_field={anns_field!r}: one of {ANNS_FIELDS}")
+        if anns_field == "sparse":
+            for d in (data if isinstance(data, (list, tuple)) else [data]):
+                if not isinstance(d, (str, dict)):
+                    raise ValueError(f"a sparse request's data is a text or a {{term_id: weight}} dict (or a list of them), not {type(d).__name__}")
         if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)):
             raise ValueError(f"limit={limit!r}: an int in 1 .. {MAX_LIMIT}")
         if not 1 <= int(limit) <= MAX_LIMIT:
@@ -38,10 +50,13 @@ class AnnSearchRequest:
         if param is not None and not isinstance(param, dict):
             raise ValueError(f"param={param!r}: a dict or None")
         self.data, self.limit, self.expr, self.param = data, int(limit), expr, param
+        self.anns_field = anns_field
         self.radius, self.range_filter = range_search.check_bounds(None, None, param)
+        if anns_field == "sparse" and (self.radius is not None or self.range_filter is not None):
+            raise ValueError("a sparse request takes no radius / range_filter")
 
     def __repr__(self):
-        return f"AnnSearchRequest(limit={self.limit}, expr={self.expr!r}, param={self.param!r})"
+        return f"AnnSearchRequest(anns_field={self.anns_field!r}, limit={self.limit}, expr={self.expr!r}, param={self.param!r})"
 
 
 class RRFRanker:
@@ -123,8 +138,15 @@ def check_requests(reqs, ranker, limit):
     return int(limit)
 
 
+def sparse_queries(req):
+    """a sparse request's data as a list of nq texts / {term_id: weight} dicts"""
+    return list(req.data) if isinstance(req.data, (list, tuple)) else [req.data]
+
+
 def stack_requests(reqs):
-    """the requests' vectors as ONE [nq, R, dim] array (numpy, or a torch CUDA tensor when every request's data is one)"""
+    """the DENSE requests' vectors as ONE [nq, R, dim] array (numpy, or a torch CUDA tensor when every request's data is one)"""
+    if any(r.anns_field != "vector" for r in reqs):
+        raise ValueError("stack_requests takes dense requests only")
     datas = [r.data for r in reqs]
     if all(hasattr(d, "is_cuda") and d.is_cuda for d in datas):
         import torch

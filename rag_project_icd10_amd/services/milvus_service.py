@@ -31,7 +31,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..corpus_store import CorpusStore
-from . import filter_expr, hybrid_search as hybrid, range_search
+from . import filter_expr, hybrid_search as hybrid, range_search, sparse_text
 
 logger = logging.getLogger(__name__)
 
@@ -67,6 +67,8 @@ class MilvusService:
         # hybrid search: (the index it belongs to, IcdFusion, store generation); one handle, regrown when a call needs more
         # sub-lists, dropped where the views and masks are
         self._fusion = None
+        # sparse search: (the index it belongs to, IcdSparse, SparseTextIndex, field, store generation); built lazily, one handle
+        self._sparse = None
         self._columns = None        # filter_expr.Columns of the store generation they were built from (rebuilt when it moves on)
         self._connect()
         self._setup_collection()
@@ -222,6 +224,7 @@ class MilvusService:
             self._groupings.clear()
             self._masks.clear()
             self._fusion = None
+            self._sparse = None
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
     def _grouping(self, field: str, index, rows, filter_key):
@@ -603,6 +606,154 @@ class MilvusService:
         st = hit[1].stats()
         return [{"max_total": int(st["max_total"]), "generation": hit[2], "bytes": int(st["bytes"])}]
 
+    # ---- sparse search (BM25 over a text field) ---------------------------------------------------------------
+    SPARSE_MAX_NQ = 1024   # queries per icd_sparse_search call (longer batches are sent in pieces)
+
+    def build_sparse_index(self, field: str = "preferred_zh"):
+        """(IcdSparse, SparseTextIndex) over `field` of the store's records: analyzer + BM25 on the host, postings on the device.
+        Built lazily, cached per store generation and field, dropped where the views, masks and fusions are."""
+        index = self._ready_index()
+        if index is None:
+            raise RuntimeError(f"collection {self.collection_name} is empty or missing")
+        gen = self.client.generation
+        with self._views_lock:
+            hit = self._sparse
+            if hit is not None and hit[0] is index and hit[3] == field and hit[4] == gen and not index.closed and not hit[1].closed:
+                return hit[1], hit[2]
+        recs = self.client.records
+        if recs and field not in recs[0]:
+            raise ValueError(f"field={field!r}: not a field of the store's records")
+        tx = sparse_text.SparseTextIndex([str(r.get(field) or "") for r in recs])
+        sp = index.sparse(tx.row_off, tx.terms, tx.vals, tx.vocab_size, max_nq=min(index.max_nq, self.SPARSE_MAX_NQ), max_k=index.max_k)
+        with self._views_lock:
+            self._sparse = (index, sp, tx, field, gen)
+        return sp, tx
+
+    def sparse_indexes(self) -> List[Dict[str, Any]]:
+        """the cached sparse index (at most one): field, vocabulary, postings, HBM bytes"""
+        with self._views_lock:
+            hit = self._sparse
+        if hit is None or hit[1].closed:
+            return []
+        st = hit[1].stats()
+        return [{"field": hit[3], "vocab": int(st["vocab"]), "nnz": int(st["nnz"]), "generation": hit[4], "bytes": int(st["bytes"])}]
+
+    def _sparse_lists(self, index, sp, q_off, q_terms, q_vals, k: int, masks, reweighted: bool):
+        """search_sparse over a batch of any length, SPARSE_MAX_NQ queries per call; host arrays in and out"""
+        q_off = np.asarray(q_off, np.int64)
+        nq = len(q_off) - 1
+        outs = []
+        for s0 in range(0, max(nq, 1), sp.max_nq):
+            s1 = min(nq, s0 + sp.max_nq)
+            a, b = int(q_off[s0]), int(q_off[s1])
+            outs.append(index.search_sparse(sp, q_off[s0:s1 + 1] - a, q_terms[a:b], q_vals[a:b], k,
+                                            masks=None if masks is None else masks[s0:s1], reweighted=reweighted))
+        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+
+    def search_sparse_batch(self, q_off, q_terms, q_vals, top_k: int = 10, filter=None, as_dicts: bool = False):   # noqa: A002
+        """Many sparse queries in CSR form (q_off int64 [nq + 1], q_terms uint32 term ids of the sparse index's vocabulary, q_vals
+        float32; at most 64 strictly increasing terms per query) against the store's sparse index. Only rows that share a term
+        with the query are hits. filter: a Milvus filter expression, or a list with one expression (or None) per query, through
+        the mask cache. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order `search` returns
+        hits; with as_dicts a list of `search`-shaped hit lists (`original_score` the sparse inner product). Bad arguments raise
+        ValueError."""
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 128:
+            raise ValueError(f"top_k={top_k!r}: an int in 1 .. 128")
+        nq = len(np.asarray(q_off).reshape(-1)) - 1
+        if nq < 0:
+            raise ValueError("q_off holds nq + 1 offsets")
+        if isinstance(filter, (list, tuple)) and len(filter) != nq:
+            raise ValueError(f"filter holds {len(filter)} expressions for {nq} queries")
+        for e in (filter if isinstance(filter, (list, tuple)) else [filter]):
+            if e is not None:
+                filter_expr.compile(e)
+        sp, _tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        index = self._index
+        if int(top_k) > index.max_k:
+            raise ValueError(f"top_k={top_k} exceeds the index's max_k={index.max_k} (ICD_GPU_MAX_K)")
+        masks = None
+        if filter is not None:
+            masks = self._masks_for(index, filter, nq)
+            if all(m is None for m in masks):
+                masks = None
+        adj, raw, ids, levels = self._sparse_lists(index, sp, q_off, np.asarray(q_terms, np.uint32).reshape(-1),
+                                                   np.asarray(q_vals, np.float32).reshape(-1), int(top_k), masks, True)
+        if not as_dicts:
+            return adj, raw, ids, levels
+        return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(nq)]
+
+    def search_text(self, text: str, top_k: int = 10, filter: Optional[str] = None) -> List[Dict[str, Any]]:   # noqa: A002
+        """BM25 full-text search of ONE text over the sparse index's field: `search`-shaped hits, `original_score` the BM25 score,
+        `score` the reweighted one. A text without a term of the vocabulary finds nothing. Bad arguments raise ValueError."""
+        if not isinstance(text, str):
+            raise ValueError("text: a string")
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("a list of filters needs a batch: search_sparse_batch")
+        _sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        return self.search_sparse_batch(*tx.encode_queries([text]), top_k, filter=filter, as_dicts=True)[0]
+
+    def _hybrid_mixed(self, reqs, ranker, limit: int):
+        """hybrid_search_batch with at least one sparse request: the dense requests as ONE search_batch-style sub-search, the
+        sparse ones as ONE search_sparse_batch-style call, their raw lists interleaved into [nq, R, lmax] on the device, fused by
+        fuse_lists. Returns device tensors."""
+        import torch
+        index = self._ready_index()
+        if index is None:
+            raise RuntimeError(f"collection {self.collection_name} is empty or missing")
+        sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        dense = [r for r in reqs if r.anns_field == "vector"]
+        sparse = [r for r in reqs if r.anns_field == "sparse"]
+        sq = [hybrid.sparse_queries(r) for r in sparse]
+        counts = {len(x) for x in sq}
+        qd = None
+        if dense:
+            qd = hybrid.stack_requests(dense)
+            counts.add(int(qd.shape[0]))
+        if len(counts) != 1:
+            raise ValueError("the requests' data must share one number of queries")
+        nq, R = counts.pop(), len(reqs)
+        lmax = max(r.limit for r in reqs)
+        if lmax > index.max_k:
+            raise ValueError(f"a request's limit exceeds the index's max_k={index.max_k} (ICD_GPU_MAX_K)")
+        if nq * R > index.max_nq:
+            raise ValueError(f"{nq} queries x {R} requests exceed the index's batch of {index.max_nq} (ICD_GPU_MAX_BATCH)")
+        where = torch.device("cuda", index.device)
+        scores = torch.full((nq, R, lmax), float("-inf"), dtype=torch.float32, device=where)
+        ids = torch.full((nq, R, lmax), -1, dtype=torch.int64, device=where)
+        dense_at = [i for i, r in enumerate(reqs) if r.anns_field == "vector"]
+        sparse_at = [i for i, r in enumerate(reqs) if r.anns_field == "sparse"]
+        if dense:   # ONE banded / masked / plain sub-search over the nq * Rd vectors, as search_hybrid's step 1
+            Rd, ld = len(dense), max(r.limit for r in dense)
+            flat = qd.reshape(nq * Rd, -1) if hasattr(qd, "is_cuda") else np.ascontiguousarray(qd.reshape(nq * Rd, -1))
+            per = [self._filter_mask(index, r.expr) for r in dense]
+            lo = [r.radius for r in dense]
+            hi = [r.range_filter for r in dense]
+            if any(m is not None for m in per) or any(v is not None for v in lo + hi):
+                bound = lambda vs, fill: None if all(v is None for v in vs) else np.tile(np.array([fill if v is None else v for v in vs], np.float32), nq)   # noqa: E731
+                d_raw, d_ids, _lv = index.search_masked(flat, ld, per * nq, radius=bound(lo, -np.inf), range_filter=bound(hi, np.inf), reweighted=False)
+            else:
+                d_raw, d_ids = index.search(flat, ld)   # (AUTO: the same hits as EXACT, as search_hybrid's plain step 1)
+            d_raw = torch.as_tensor(d_raw).to(where).reshape(nq, Rd, ld)
+            d_ids = torch.as_tensor(d_ids).to(where).reshape(nq, Rd, ld)
+            for j, at in enumerate(dense_at):
+                scores[:, at, :ld], ids[:, at, :ld] = d_raw[:, j], d_ids[:, j]
+        if sparse:  # ONE sparse call over the nq * Rs queries
+            Rs, ls = len(sparse), max(r.limit for r in sparse)
+            pairs = []
+            for q in range(nq):
+                for x in sq:
+                    pairs.append(tx.encode_query(x[q]) if isinstance(x[q], str) else sparse_text.query_from_dict(x[q], tx.vocab_size))
+            per = [self._filter_mask(index, r.expr) for r in sparse]
+            masks = per * nq if any(m is not None for m in per) else None
+            s_raw, s_ids, _lv = self._sparse_lists(index, sp, *sparse_text.csr_from_pairs(pairs), ls, masks, False)
+            s_raw = torch.from_numpy(s_raw).to(where).reshape(nq, Rs, ls)
+            s_ids = torch.from_numpy(s_ids).to(where).reshape(nq, Rs, ls)
+            for j, at in enumerate(sparse_at):
+                scores[:, at, :ls], ids[:, at, :ls] = s_raw[:, j], s_ids[:, j]
+        kw = ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
+              else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
+        return index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, **kw), nq, R
+
     def hybrid_search_batch(self, reqs, ranker, limit: int = 10, as_dicts: bool = False):
         """Milvus's hybrid_search for a batch: reqs is a list of 1 .. 8 hybrid_search.AnnSearchRequest whose data share one shape
         [nq, dim] (request r's vector of every query; numpy arrays, or torch CUDA tensors for device outputs); ranker an RRFRanker
@@ -612,6 +763,9 @@ class MilvusService:
         [nq, limit], in the order `search` returns hits (adjusted = fused * level weight, one stable re-sort); with as_dicts a
         list of hybrid_search-shaped hit lists. Bad arguments raise ValueError before anything is loaded."""
         limit = hybrid.check_requests(reqs, ranker, limit)
+        if any(r.anns_field == "sparse" for r in reqs):   # (DESIGN.md section 14; with dense requests only the path below is untouched)
+            out, nq, R = self._hybrid_mixed(reqs, ranker, limit)
+            return self._hybrid_dicts(out, nq, R, limit) if as_dicts else out
         q = hybrid.stack_requests(reqs)
         index = self._ready_index()
         if index is None:
@@ -634,6 +788,9 @@ class MilvusService:
                                   range_filter=hi, **kw)
         if not as_dicts:
             return out
+        return self._hybrid_dicts(out, nq, R, limit)
+
+    def _hybrid_dicts(self, out, nq: int, R: int, limit: int):
         adj, fused, ids, _levels, bits = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in out]
         res = []
         for qi in range(nq):
@@ -651,7 +808,10 @@ class MilvusService:
         requests whose list held the hit) replace `original_score`. Bad arguments raise ValueError."""
         limit = hybrid.check_requests(reqs, ranker, limit)
         for r in reqs:
-            if np.ndim(r.data) > 2 or (np.ndim(r.data) == 2 and np.shape(r.data)[0] != 1):
+            if r.anns_field == "sparse":
+                if isinstance(r.data, (list, tuple)) and len(r.data) != 1:
+                    raise ValueError("hybrid_search takes one text per sparse request; hybrid_search_batch takes batches")
+            elif np.ndim(r.data) > 2 or (np.ndim(r.data) == 2 and np.shape(r.data)[0] != 1):
                 raise ValueError("hybrid_search takes one vector per request; hybrid_search_batch takes batches")
         return self.hybrid_search_batch(reqs, ranker, limit, as_dicts=True)[0]
 

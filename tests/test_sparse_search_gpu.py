@@ -1,0 +1,313 @@
+"""icd_sparse_search on the device against tests/sparse_oracle.py, bit for bit: ids, raw scores, levels and
+adj. The arithmetic is fully specified, so there is no tolerance. Shapes sit around the kernel's tile (T rows, from the build)."""
+import csv
+import ctypes
+import io
+import lzma
+import os
+
+import numpy as np
+import pytest
+
+import sparse_oracle as so
+from rag_project_icd10_amd import _native
+from rag_project_icd10_amd.services import sparse_text
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DIM = 32
+
+
+def tile():
+    """T: rows per tile of the build (read at run time: the library is loaded by the first test, not by the collection)"""
+    return _native.sparse_tile_rows()
+
+
+def make_rows(n, vocab, seed):
+    """Adversarial rows. Term 0 sits in EVERY row (a tile's select sees T candidates) with few distinct values (ties); with a
+    vocabulary of 37 or more: term 1 in exactly one row per tile, term 2 in rows that straddle every tile boundary, term 3 in
+    no row, terms 4 / 5 / 6 carry 1e8 / 1 / -1e8 on every 7th row (the fp32 sum depends on the order), the rest random with
+    either sign. Rows 100 .. 599 are identical (ties ordered by id)."""
+    rng = np.random.default_rng(seed)
+    T = tile()
+    r = [np.arange(n)]
+    t = [np.zeros(n, np.int64)]
+    v = [rng.choice(np.array([0.5, 1.0, 1.0, -2.0, 3.0], np.float32), n)]
+    if vocab >= 37:
+        one = np.arange(5, n, T)
+        edge = np.unique(np.clip(np.concatenate([np.arange(b - 3, b + 3) for b in range(T, n + T, T)]), 0, n - 1))
+        sev = np.arange(0, n, 7)
+        for rows_, term, val in ((one, 1, 2.5), (edge, 2, -1.5), (sev, 4, 1e8), (sev, 5, 1.0), (sev, 6, -1e8)):
+            r.append(rows_); t.append(np.full(len(rows_), term)); v.append(np.full(len(rows_), val, np.float32))
+        m = 3 * n
+        r.append(rng.integers(0, n, m)); t.append(rng.integers(7, vocab, m))
+        v.append((rng.integers(1, 64, m) / 8.0 * rng.choice([-1.0, 1.0], m)).astype(np.float32))
+    r, t, v = np.concatenate(r), np.concatenate(t), np.concatenate(v).astype(np.float32)
+    _, first = np.unique(r * vocab + t, return_index=True)   # (sorted by row, then term; duplicates dropped)
+    r, t, v = r[first], t[first], v[first]
+    if n >= 600:   # rows 100 .. 599 become copies of row 100
+        keep = (r < 101) | (r >= 600)
+        t0, v0 = t[r == 100], v[r == 100]
+        r = np.concatenate([r[keep], np.repeat(np.arange(101, 600), len(t0))])
+        t = np.concatenate([t[keep], np.tile(t0, 499)])
+        v = np.concatenate([v[keep], np.tile(v0, 499)])
+        order = np.argsort(r * vocab + t, kind="stable")
+        r, t, v = r[order], t[order], v[order]
+    row_off = np.zeros(n + 1, np.int64)
+    np.add.at(row_off, r + 1, 1)
+    return np.cumsum(row_off), t.astype(np.uint32), v.astype(np.float32)
+
+
+def make_queries(nq, vocab, seed):
+    rng = np.random.default_rng(seed)
+    fixed = [([0], [1.0]), ([], []), ([0], [-1.0])]
+    if vocab >= 37:
+        wide = np.arange(min(vocab, 64))
+        fixed += [([1], [1.0]), ([2], [2.0]), ([3], [1.0]), ([4, 5, 6], [1.0, 1.0, 1.0]), ([0, 4, 5, 6], [1.0, 1.0, 1.0, 1.0]),
+                  (wide, np.where(wide % 3 == 0, -0.75, 1.25)), ([1, 2, 3], [1.0, -1.0, 1.0])]
+    pairs = []
+    for q in range(nq):
+        if q < len(fixed):
+            tt, ww = fixed[q]
+        else:
+            m = int(rng.integers(1, min(vocab, 8) + 1))
+            tt = np.sort(rng.choice(vocab, m, replace=False))
+            ww = rng.integers(1, 32, m) / 4.0 * rng.choice([-1.0, 1.0], m)
+        pairs.append((np.asarray(tt, np.uint32), np.asarray(ww, np.float32)))
+    return sparse_text.csr_from_pairs(pairs)
+
+
+def build(n, vocab, seed, id_base=0, max_nq=320):
+    rng = np.random.default_rng(seed)
+    corpus = rng.standard_normal((n, DIM), dtype=np.float32)
+    levels = rng.integers(1, 4, n).astype(np.int32)
+    index = _native.IcdIndex(corpus, levels, device=0, max_nq=max_nq, max_k=128, id_base=id_base, probe=False)
+    rows = make_rows(n, vocab, seed)
+    return index, index.sparse(*rows, vocab, max_nq=max_nq, max_k=128), rows, levels
+
+
+def same(got, want, what):
+    for g, w, name in zip(got, want, ("adj", "raw", "ids", "levels")[4 - len(want):]):
+        g = g.cpu().numpy() if hasattr(g, "cpu") else g
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name)
+        bad = np.flatnonzero((g.view(np.uint8).reshape(g.shape[0], -1) != w.view(np.uint8).reshape(w.shape[0], -1)).any(axis=1))
+        assert bad.size == 0, f"{what}: {name} differs in queries {bad[:8].tolist()}: {g[bad[0]][:6]} vs {w[bad[0]][:6]}"
+
+
+# ((a, b): n = a * T + b, vocabulary, k, batch)
+CASES = [((0, 1), 1, 1, 1), ((1, -1), 37, 10, 4), ((1, 0), 5000, 128, 17), ((1, 1), 37, 128, 4), ((2, 5), 5000, 10, 300), ((2, 5), 37, 1, 17),
+         ((2, 5), 1, 128, 4), ((1, 1), 5000, 1, 1)]
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_sparse_search_equals_the_oracle(case):
+    import torch
+    (a, b), vocab, k, nq = CASES[case]
+    T = tile()
+    n = a * T + b
+    id_base = 1000 if case % 2 else 0
+    index, sp, rows, levels = build(n, vocab, 40 + case, id_base)
+    q = make_queries(nq, vocab, 90 + case)
+    assert sp.stats()["vocab"] == vocab and sp.stats()["nnz"] == len(rows[1])
+    for rw in (False, True):
+        want = so.search(*rows, vocab, *q, k, levels=levels, id_base=id_base, reweighted=rw)
+        same(index.search_sparse(sp, *q, k, reweighted=rw), want, f"host call, reweighted={rw}")
+        dq = (torch.from_numpy(q[0]).cuda(), torch.from_numpy(q[1].view(np.int32)).cuda(), torch.from_numpy(q[2]).cuda())
+        got = index.search_sparse(sp, *dq, k, reweighted=rw)
+        assert all(g.is_cuda for g in got)
+        same(got, want, f"device call, reweighted={rw}")
+    if vocab >= 37 and nq >= 5:   # what the adversarial queries are there for
+        raw, ids, _ = so.search(*rows, vocab, *q, k, levels=levels, id_base=id_base)
+        assert (ids[1] == -1).all() and np.isneginf(raw[1]).all()           # no terms: padding
+        assert (ids[4] >= 0).any() and (raw[4][ids[4] >= 0] < 0).all()   # hits below zero are hits, above padding
+        assert ((ids[3] >= 0).sum() == min(k, -(-max(n - 5, 0) // T))) or n <= 5   # one row per tile: fewer hits than k
+    sp.close()
+    index.close()
+
+
+def test_order_dependent_sums_and_ties():
+    """1e8 + 1 - 1e8 over three terms is 0 in the canonical order and 1 in another; 500 identical rows come back in id order"""
+    n, vocab = tile() + 700, 37
+    index, sp, rows, levels = build(n, vocab, 7)
+    q = sparse_text.csr_from_pairs([(np.array([4, 5, 6], np.uint32), np.ones(3, np.float32)), (np.array([0], np.uint32), np.ones(1, np.float32))])
+    raw, ids, lv = index.search_sparse(sp, *q, 128)
+    want = so.search(*rows, vocab, *q, 128, levels=levels)
+    same((raw, ids, lv), want, "order")
+    sevenths = np.arange(0, n, 7)
+    assert (raw[0] == 0.0).all() and np.array_equal(ids[0], sevenths[(sevenths <= 100) | (sevenths >= 600)][:128])
+    d = so.rows_as_dicts(*rows)
+    assert all(d[i] == d[100] for i in range(100, 600))
+    block = index.rowmask(np.arange(100, 600))
+    raw_t, ids_t, _ = index.search_sparse(sp, *q, 128, masks=block)
+    assert np.array_equal(ids_t[1], np.arange(100, 228)) and (raw_t[1] == raw_t[1][0]).all()
+    block.close()
+    sp.close()
+    index.close()
+
+
+def test_masks():
+    n, vocab, k, nq = 2 * tile() + 5, 37, 10, 17
+    index, sp, rows, levels = build(n, vocab, 11)
+    q = make_queries(nq, vocab, 12)
+    free = so.search(*rows, vocab, *q, k, levels=levels)
+    rng = np.random.default_rng(3)
+    dense = []
+    for i in range(nq):
+        if i % 5 == 1:
+            dense.append(None)                                   # a NULL among them
+        elif i == 4:
+            dense.append(np.zeros(n, bool))                      # an empty mask
+        elif i % 5 == 0 and free[1][i][0] >= 0:
+            m = np.ones(n, bool); m[free[1][i][0]] = False       # removes the unmasked winner
+            dense.append(m)
+        else:
+            dense.append(rng.random(n) < (0.5 if i % 2 else 0.01))
+    masks = [None if m is None else index.rowmask(np.flatnonzero(m)) for m in dense]
+    for rw in (False, True):
+        want = so.search(*rows, vocab, *q, k, levels=levels, masks=dense, reweighted=rw)
+        same(index.search_sparse(sp, *q, k, masks=masks, reweighted=rw), want, f"masked, reweighted={rw}")
+    got = index.search_sparse(sp, *q, k, masks=masks)
+    assert (got[1][4] == -1).all() and got[1][0][0] != free[1][0][0]
+    same(index.search_sparse(sp, *q, k, masks=[None] * nq), free, "an all-NULL table")
+    one = index.search_sparse(sp, *q, k, masks=masks[2])   # ONE mask on every query
+    same(one, so.search(*rows, vocab, *q, k, levels=levels, masks=[dense[2]] * nq), "one mask")
+    for m in masks:
+        if m is not None:
+            m.close()
+    sp.close()
+    index.close()
+
+
+def test_errors_of_the_abi_in_one_process():
+    lib = _native.load_library()
+    index, sp, rows, levels = build(300, 37, 21, max_nq=8)
+    other, sp_other, _, _ = build(300, 37, 22, max_nq=8)
+    view = index.view(np.arange(0, 300, 2))
+    row_off, terms, vals = rows
+    h = ctypes.c_void_p()
+
+    def create(idx, off, t, v, vocab=37, max_nq=8, max_k=16):
+        return lib.icd_sparse_create(idx._h, off.ctypes.data, t.ctypes.data, v.ctypes.data, vocab, max_nq, max_k, ctypes.byref(h))
+    first = int(np.flatnonzero(np.diff(row_off) >= 2)[0])
+    at = int(row_off[first])
+    for mutate, word in ((lambda t, v: t.__setitem__(at + 1, t[at]), b"strictly increasing"), (lambda t, v: t.__setitem__(slice(at, at + 2), t[at:at + 2][::-1].copy()), b"strictly increasing"),
+                         (lambda t, v: t.__setitem__(at, 37), b"vocabulary"), (lambda t, v: v.__setitem__(at, 0.0), b"non-zero"),
+                         (lambda t, v: v.__setitem__(at, np.inf), b"finite")):
+        t2, v2 = terms.copy(), vals.copy()
+        mutate(t2, v2)
+        assert create(index, row_off, t2, v2) == -1 and word in lib.icd_last_error() and not h.value
+    assert create(index, row_off, terms, vals, max_k=129) == -1 and create(index, row_off, terms, vals, max_nq=0) == -1
+    assert create(view, row_off[:151], terms[:row_off[150]], vals[:row_off[150]]) == -4 and b"view" in lib.icd_last_error()   # ICD_ERR_UNSUPPORTED
+
+    q_off = np.array([0, 2], np.int64)
+    q_t = np.array([0, 5], np.uint32)
+    q_v = np.array([1.0, 2.0], np.float32)
+    raw, ids, lv, adj = np.empty((8, 16), np.float32), np.empty((8, 16), np.int64), np.empty((8, 16), np.int32), np.empty((8, 16), np.float64)
+
+    def search(idx_h, sp_h, off=q_off, t=q_t, v=q_v, nq=1, k=4, masks=None, rw=0, a=adj):
+        return lib.icd_sparse_search(idx_h, sp_h, off.ctypes.data, t.ctypes.data, v.ctypes.data, nq, k, 0, masks, rw,
+                                     a.ctypes.data if a is not None else None, raw.ctypes.data, ids.ctypes.data, lv.ctypes.data, 0, None)
+    assert search(index._h, sp._h) == 0
+    assert search(index._h, sp._h, t=np.array([5, 0], np.uint32)) == -1 and b"strictly increasing" in lib.icd_last_error()
+    assert search(index._h, sp._h, t=np.array([5, 5], np.uint32)) == -1
+    assert search(index._h, sp._h, t=np.array([0, 37], np.uint32)) == -1 and b"vocabulary" in lib.icd_last_error()
+    assert search(index._h, sp._h, v=np.array([1.0, 0.0], np.float32)) == -1 and search(index._h, sp._h, v=np.array([np.nan, 1.0], np.float32)) == -1
+    long_off = np.array([0, 65], np.int64)
+    assert search(index._h, sp._h, off=long_off, t=np.arange(65, dtype=np.uint32), v=np.ones(65, np.float32)) == -1 and b"at most 64" in lib.icd_last_error()
+    assert search(index._h, sp._h, k=0) == -1 and search(index._h, sp._h, k=129) == -1
+    sp16 = index.sparse(row_off, terms, vals, 37, max_nq=8, max_k=16)
+    assert search(index._h, sp16._h, k=17) == -1 and b"max_k" in lib.icd_last_error()
+    assert search(index._h, sp._h, off=np.zeros(10, np.int64), nq=9) == -1 and b"max_nq" in lib.icd_last_error()
+    assert search(index._h, sp._h, rw=1, a=None) == -1
+    assert search(index._h, sp_other._h) == -1 and b"another index" in lib.icd_last_error()
+    assert search(view._h, sp._h) == -1   # (a view is another index)
+    foreign = other.rowmask(np.arange(10))
+    table = (ctypes.c_void_p * 1)(foreign._h.value)
+    assert search(index._h, sp._h, masks=table) == -1 and b"another index" in lib.icd_last_error()
+    mine = index.rowmask(np.arange(10))
+    table = (ctypes.c_void_p * 1)(mine._h.value)
+    assert search(index._h, sp._h, masks=table) == 0
+    dead = ctypes.c_void_p(sp16._h.value)
+    sp16.close()
+    assert search(index._h, dead) == -5 and lib.icd_sparse_destroy(dead) == -5   # ICD_ERR_STATE
+    mine_dead = (ctypes.c_void_p * 1)(mine._h.value)
+    mine.close()
+    assert search(index._h, sp._h, masks=mine_dead) == -5
+    with pytest.raises(ValueError):
+        index.search_sparse(sp, q_off, np.array([5, 0], np.uint32), q_v, 4)
+    with pytest.raises(ValueError):
+        index.sparse(row_off[:-1], terms, vals, 37)
+    for x in (foreign, sp_other, other, view, sp, index):
+        x.close()
+
+
+def test_index_destroyed_first_then_the_sparse_handle():
+    index, sp, rows, levels = build(500, 37, 31, max_nq=8)
+    q = make_queries(4, 37, 32)
+    index.search_sparse(sp, *q, 5)
+    index.close()
+    with pytest.raises(_native.IcdError):
+        index.search_sparse(sp, *q, 5)
+    assert sp.stats()["vocab"] == 37
+    sp.close()
+    assert sp.closed
+    # an index re-created (possibly at the same address) is another index
+    index2, sp2, _, _ = build(500, 37, 31, max_nq=8)
+    sp_old = index2.sparse(*rows, 37, max_nq=8, max_k=8)
+    index2.close()
+    index3, sp3, _, _ = build(500, 37, 31, max_nq=8)
+    with pytest.raises((ValueError, _native.IcdError)):
+        index3.search_sparse(sp_old, *q, 5)
+    for x in (sp_old, sp2, sp3, index3):
+        x.close()
+
+
+def test_golden_titles_bm25_at_csv_size():
+    """the 40 474 titles of the golden CSV through the analyzer and BM25, k = 10, a batch of 17 golden diagnosis strings: every
+    hit equals the oracle's, and a query that IS a title finds that row first"""
+    rd = csv.DictReader(io.StringIO(lzma.open(os.path.join(GOLDEN, "ICD_10v601.csv.xz")).read().decode("utf-8-sig")))
+    titles = [r["disease"] for r in rd]
+    assert len(titles) == 40474
+    tx = sparse_text.SparseTextIndex(titles)
+    strings = [l.rstrip("\n") for l in open(os.path.join(GOLDEN, "diagnosis_strings.txt"), encoding="utf-8")][:14]
+    picked = [3, 20000, 40473]
+    q = tx.encode_queries(strings + [titles[i] for i in picked])
+    rng = np.random.default_rng(1)
+    levels = rng.integers(1, 4, len(titles)).astype(np.int32)
+    index = _native.IcdIndex(rng.standard_normal((len(titles), DIM), dtype=np.float32), levels, device=0, max_nq=32, max_k=16, probe=False)
+    sp = index.sparse(tx.row_off, tx.terms, tx.vals, tx.vocab_size, max_nq=32, max_k=16)
+    want = so.search(tx.row_off, tx.terms, tx.vals, tx.vocab_size, *q, 10, levels=levels, reweighted=True)
+    same(index.search_sparse(sp, *q, 10, reweighted=True), want, "golden titles")
+    raw, ids, _ = index.search_sparse(sp, *q, 10)
+    for j, i in enumerate(picked):
+        assert titles[int(ids[14 + j][0])] == titles[i]
+    sp.close()
+    index.close()
+
+
+def test_device_queries_without_the_host_check_only_enqueue():
+    """validate=False: no copy to the host, so the call can be captured into a graph; the replay gives the validated call's bits"""
+    import torch
+    n, vocab, k, nq = tile() + 1, 37, 10, 17
+    index, sp, rows, levels = build(n, vocab, 51)
+    q = make_queries(nq, vocab, 52)
+    want = so.search(*rows, vocab, *q, k, levels=levels, reweighted=True)
+    dq = (torch.from_numpy(q[0]).cuda(), torch.from_numpy(q[1].view(np.int32)).cuda(), torch.from_numpy(q[2]).cuda())
+    same(index.search_sparse(sp, *dq, k, reweighted=True, validate=False), want, "validate=False")
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        index.search_sparse(sp, *dq, k, reweighted=True, validate=False)   # warm-up on the capture stream
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        cap = index.search_sparse(sp, *dq, k, reweighted=True, validate=False)
+    for t in cap:
+        t.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    same(cap, want, "graph replay")
+    del graph
+    sp.close()
+    index.close()
