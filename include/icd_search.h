@@ -347,6 +347,37 @@ int icd_fusion_fuse_lists(icd_index *idx, icd_fusion *fusion, const float *score
                           int32_t *out_levels, uint32_t *out_reqbits, int32_t out_on_device, void *stream);
 
 /*
+ * Grouped hybrid search: group_by_field / group_size on hybrid_search. DESIGN.md section 15 (rules H1 - H6).
+ *   sub-lists         list (q, r) is icd_index_search_grouped's RAW output for that vector at k = limits[r] GROUPS and group_size
+ *                     members; limits[r] >= 1, limits[r] * group_size <= ICD_MAX_K. One sub-search runs at the largest limit and
+ *                     list r is cut in front of its (limits[r] + 1)-th RUN of equal group ids; rank j is the slot index.
+ *   fused(id)         icd_index_search_hybrid's rules (RRF, Weighted with none / cosine / atan), unchanged.
+ *   answer            the distinct fused ids grouped by the grouping; members rank by (fused desc, id asc), a group by its best
+ *                     member: the min(k, groups present) best groups times the min(group_size, members) best rows,
+ *                     group-rank-major, hits contiguous, [nq][k * group_size]; padding -inf, -1, 0, 0, -1. k * group_size <=
+ *                     ICD_MAX_K. reweighted = 1: adj = fused * w[level], ONE stable descending re-sort; group id and request
+ *                     bits travel with the hit. Every row its own group and group_size = 1 IS icd_index_search_hybrid in
+ *                     ICD_MODE_EXACT, bit for bit.
+ * icd_fusion_fuse_lists_grouped: the same cut by runs and the same fuse on caller-provided device lists [nq * R][lmax]; a hit's
+ * group is read from the grouping by row (a slot whose id is no row of the index is a run of its own and no hit).
+ * Every check comes before the first device call. ICD_ERR_INVALID: what icd_index_search_hybrid refuses, k * group_size or
+ * limits[r] * group_size above ICD_MAX_K, nq * R above the grouping's max_nq or the fusion's max_total, a fusion or grouping of
+ * another index, ANY mask table or bound (filter with a view: the grouping is then the view's). ICD_ERR_STATE: a destroyed handle.
+ * Lock order: fusion, grouping. With device buffers the calls only enqueue. A host caller's groups leave through the grouping's
+ * staging.
+ */
+int icd_index_search_hybrid_grouped(icd_index *idx, icd_fusion *fusion, icd_grouping *grouping, const float *queries, int64_t nq, int32_t R,
+                                    int32_t queries_on_device, const int32_t *limits, icd_rowmask *const *masks, const float *radius,
+                                    const float *range_filter, int32_t ranker, double rrf_c, const double *weights, int32_t norm, int32_t k,
+                                    int32_t group_size, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids,
+                                    int32_t *out_levels, uint32_t *out_reqbits, int32_t *out_groups, int32_t out_on_device, void *stream);
+int icd_fusion_fuse_lists_grouped(icd_index *idx, icd_fusion *fusion, icd_grouping *grouping, const float *scores, const int64_t *ids,
+                                  int64_t nq, int32_t R, int32_t lmax, const int32_t *limits, int32_t ranker, double rrf_c,
+                                  const double *weights, int32_t norm, int32_t k, int32_t group_size, int32_t reweighted, double *out_adj,
+                                  double *out_fused, int64_t *out_ids, int32_t *out_levels, uint32_t *out_reqbits, int32_t *out_groups,
+                                  int32_t out_on_device, void *stream);
+
+/*
  * Sparse-vector search: Milvus's SPARSE_FLOAT_VECTOR field searched with metric IP (usually filled by its BM25 function), alone
  * or as one request of a hybrid search through icd_fusion_fuse_lists. DESIGN.md section 14.
  *   index             row i of an index of n rows carries a set of (term, value) pairs in CSR form (row_off[n + 1], terms, vals):
@@ -383,8 +414,8 @@ int icd_fusion_fuse_lists(icd_index *idx, icd_fusion *fusion, const float *score
  * destroyed handle. With queries_on_device = 1 the pairs cannot be read on the host: the call TRUSTS strictly increasing terms
  * (a term >= vocab is skipped, a query is cut at ICD_SPARSE_MAX_QUERY_TERMS pairs; unsorted or repeated terms give sums in
  * another order). With device queries and outputs and no masks the call only enqueues on `stream` (graph-capturable); with masks
- * it is not, for the reason icd_index_search_masked gives. Range bounds, offset, iterator and grouping do not exist for a
- * sparse search.
+ * it is not, for the reason icd_index_search_masked gives. Range bounds, offset and iterator do not exist for a sparse
+ * search; grouping is icd_sparse_search_grouped below.
  */
 typedef struct icd_sparse icd_sparse;
 #define ICD_SPARSE_MAX_QUERY_TERMS 64
@@ -400,6 +431,34 @@ int icd_sparse_stats(icd_sparse *sp, int64_t *out_vocab, int64_t *out_nnz, int64
 int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals,
                       int64_t nq, int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, int32_t reweighted,
                       double *out_adj, float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream);
+
+/*
+ * Grouped sparse search: group_by_field / group_size on a sparse field. DESIGN.md section 15.
+ *   hits, scores      icd_sparse_search's: only rows that share a term with the query and lie inside the query's row mask
+ *                     (masks ARE allowed here: the sparse index has no views, a mask is its only filter).
+ *   answer            among the hits, a group's members rank by (score desc, id asc), a group by its best member's key: the
+ *                     min(k, groups with a hit) best groups and of each its min(group_size, hit members) best rows; layout,
+ *                     padding (-inf, -1, 0, -1) and the reweighted form are icd_index_search_grouped's. k >= 1,
+ *                     group_size >= 1, k * group_size <= ICD_MAX_K. Every row its own group and group_size = 1 IS
+ *                     icd_sparse_search at the same k, bit for bit; one group at group_size = m IS icd_sparse_search at k = m.
+ *
+ * icd_grouping_pair_sparse: once per (grouping, sparse index of the same index), outside any search: builds the grouping's
+ * row -> position table (n * 4 bytes the grouping owns, counted in icd_grouping_stats from then on; a grouping that is never
+ * paired reports what it always did). Idempotent. A grouped sparse search with an unpaired grouping is ICD_ERR_STATE.
+ *
+ * icd_sparse_search_grouped: per pass of the grouping's query block one launch of sparse_store_kernel (the accumulate phase of
+ * icd_sparse_search, the tile's sums stored into the grouping's score block, a NaN for a row that is no hit) and the two
+ * reduction kernels of icd_index_search_grouped. Every check comes before the first device call. ICD_ERR_INVALID: what
+ * icd_sparse_search refuses, k * group_size > ICD_MAX_K, nq above the sparse index's or the grouping's max_nq, a sparse index,
+ * grouping or mask created for another index. ICD_ERR_STATE: a destroyed handle. The handles may be destroyed in any order.
+ * Nothing is allocated. With device queries and outputs and no masks the call only enqueues on `stream`. The call holds the
+ * sparse index's, then the grouping's, then (masked) the index's lock: one stream at a time per handle.
+ */
+int icd_grouping_pair_sparse(icd_index *idx, icd_grouping *grouping, icd_sparse *sp);
+int icd_sparse_search_grouped(icd_index *idx, icd_sparse *sp, icd_grouping *grouping, const int64_t *q_off, const uint32_t *q_terms,
+                              const float *q_vals, int64_t nq, int32_t k, int32_t group_size, int32_t queries_on_device,
+                              icd_rowmask *const *masks, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                              int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream);
 
 /*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "icd_rowmask_create", "icd_rowmask_destroy", "icd_rowmask_stats", "icd_rowmask_pack", "icd_index_search_masked",
     "icd_fusion_create", "icd_fusion_destroy", "icd_fusion_stats", "icd_index_search_hybrid", "icd_fusion_fuse_lists",
     "icd_sparse_tile_rows", "icd_sparse_pack", "icd_sparse_create", "icd_sparse_destroy", "icd_sparse_stats", "icd_sparse_search",
+    "icd_grouping_pair_sparse", "icd_sparse_search_grouped", "icd_index_search_hybrid_grouped", "icd_fusion_fuse_lists_grouped",
 )
 SPARSE_MAX_QUERY_TERMS = 64   # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
@@ -138,6 +139,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_sparse_destroy.argtypes = [vp]
     lib.icd_sparse_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_sparse_search.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
+    lib.icd_grouping_pair_sparse.argtypes = [vp, vp, vp]
+    lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
+                                                    vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
+                                                  vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_sparse_search_grouped.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -254,6 +261,20 @@ def _bound(v, dtype, shape, on_dev: bool, device: int):
             t = t.reshape(-1)
         t = t.expand(shape) if on_dev else np.broadcast_to(t, shape)
     return t.contiguous().reshape(-1) if on_dev else np.ascontiguousarray(t).reshape(-1)
+
+
+def _check_group_args(grouping, k, group_size) -> int:
+    """group_size of a call that may carry a grouping, checked (ValueError / IcdError) before anything else happens"""
+    group_size = int(group_size)
+    if grouping is None:
+        if group_size != 1:
+            raise ValueError("group_size needs a grouping")
+        return 1
+    if grouping.closed:
+        raise IcdError(-5, "grouping is closed")
+    if int(k) < 1 or group_size < 1 or int(k) * group_size > MAX_K:
+        raise ValueError(f"k={k}, group_size={group_size}: need k >= 1, group_size >= 1 and k * group_size <= {MAX_K}")
+    return group_size
 
 
 def _mask_table(masks, count: int, what: str, per: str) -> np.ndarray:
@@ -554,7 +575,8 @@ class IcdIndex:
         return IcdFusion(self, int(max_total))
 
     def search_hybrid(self, queries, limits, k: int, fusion: "IcdFusion", *, ranker: str = "rrf", rrf_c: float = 60.0, weights=None,
-                      norm: str = "none", masks=None, radius=None, range_filter=None, mode: int = MODE_AUTO, reweighted: bool = True):
+                      norm: str = "none", masks=None, radius=None, range_filter=None, mode: int = MODE_AUTO, reweighted: bool = True,
+                      grouping: Optional["IcdGrouping"] = None, group_size: int = 1):
         """R dense requests per query fused into one hit list on the device (icd_index_search_hybrid). queries: [nq, R, dim] (a
         numpy array or a torch CUDA tensor); limits: R ints in 1 .. 128 (or one int for every request). ranker "rrf" (rrf_c) or
         "weighted" (weights: R floats in [0, 1]; norm "none" | "cosine" | "atan"). masks: None, or nq * R entries (nested [nq][R]
@@ -562,9 +584,16 @@ class IcdIndex:
         sub-list unbounded). reweighted=True: (adj f64, fused f64, ids i64, levels i32, reqbits) in search_reweighted's
         order; False: (fused, ids, levels, reqbits) best fused score first. reqbits: bit r set iff request r's list held the id
         (uint32 in numpy; an int32 tensor on the device, the same bit patterns). Padding: -inf, id -1, level 0, bits 0. Device
-        tensors in -> device tensors out on torch's current stream."""
+        tensors in -> device tensors out on torch's current stream.
+        grouping (an IcdGrouping of this index) / group_size: the grouped form (icd_index_search_hybrid_grouped) - limits then
+        count GROUPS per request (limit * group_size <= 128), k the fused groups (k * group_size <= 128); every sub-list is the
+        grouped search's, the fused hits are grouped again; outputs [nq, k * group_size] with the hits' group ids as one more
+        array (padding -1). Masks and bounds cannot be combined with it (ValueError); `mode` does not apply."""
         if self.closed or fusion is None or fusion.closed:
             raise IcdError(-5, "index or fusion is closed")
+        group_size = _check_group_args(grouping, k, group_size)
+        if grouping is not None and (masks is not None or radius is not None or range_filter is not None):
+            raise ValueError("masks and radius / range_filter cannot be combined with grouping")
         q, on_dev = self._prep_queries(queries, rank=3)
         if q.ndim != 3 or q.shape[-1] != self.dim:
             raise ValueError(f"queries must be [nq, R, {self.dim}], got {tuple(q.shape)}")
@@ -591,6 +620,17 @@ class IcdIndex:
             mask_h = _mask_table(flat, nq * R, f"{nq} x {R} sub-searches", "(query, request)")
             if not mask_h.any():
                 mask_h = None
+        if grouping is not None:
+            (adj, fused, ids, lv, bits, grp), ptr, stream, dev = _outputs(
+                on_dev, self.device, (nq, k * group_size), (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32, np.int32))
+            rc = self._lib.icd_index_search_hybrid_grouped(
+                self._h, fusion._h, grouping._h, ptr(q) if nq else None, nq, R, dev, lim.ctypes.data, None, None, None,
+                RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
+                group_size, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), ptr(grp), dev, stream)
+            if rc == -1:
+                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+            _check(self._lib, rc)
+            return (adj, fused, ids, lv, bits, grp) if reweighted else (fused, ids, lv, bits, grp)
         lo, hi = (_bound(v, np.float32, (nq, R), on_dev, self.device) for v in (radius, range_filter))
         (adj, fused, ids, lv, bits), ptr, stream, dev = _outputs(
             on_dev, self.device, (nq, k), (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32))
@@ -604,12 +644,16 @@ class IcdIndex:
         return (adj, fused, ids, lv, bits) if reweighted else (fused, ids, lv, bits)
 
     def fuse_lists(self, fusion: "IcdFusion", scores, ids, limits, k: int, *, ranker: str = "rrf", rrf_c: float = 60.0, weights=None,
-                   norm: str = "none", reweighted: bool = True, to_host: bool = False):
+                   norm: str = "none", reweighted: bool = True, to_host: bool = False, grouping: Optional["IcdGrouping"] = None,
+                   group_size: int = 1):
         """Step 2 of search_hybrid on the caller's lists (icd_fusion_fuse_lists): scores [nq, R, lmax] float32 and ids
         [nq, R, lmax] int64 (this index's ids, -1 = padding), best first - numpy arrays (uploaded) or torch CUDA tensors. limits,
-        rankers and outputs as search_hybrid; device tensors out unless to_host."""
+        rankers and outputs as search_hybrid; device tensors out unless to_host. grouping / group_size: the grouped form
+        (icd_fusion_fuse_lists_grouped) as in search_hybrid - list r is cut in front of its (limit + 1)-th run of equal group ids,
+        a hit's group is read from the grouping by row."""
         if self.closed or fusion is None or fusion.closed:
             raise IcdError(-5, "index or fusion is closed")
+        group_size = _check_group_args(grouping, k, group_size)
         import torch
         where = torch.device("cuda", self.device)
         sc = torch.as_tensor(scores).to(device=where, dtype=torch.float32).contiguous()
@@ -632,10 +676,22 @@ class IcdIndex:
                 raise ValueError(f"weights holds {wts.size} entries for {R} requests")
         k = int(k)
         on_dev = not to_host
-        (adj, fused, out_ids, lv, bits), ptr, stream, dev = _outputs(
-            on_dev, self.device, (nq, k), (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32))
+        dtypes = (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32) + ((np.int32,) if grouping is not None else ())
+        outs, ptr, stream, dev = _outputs(on_dev, self.device, (nq, k * group_size), dtypes)
+        adj, fused, out_ids, lv, bits = outs[:5]
         if stream is None:
             stream = _current_stream_ptr(self.device)   # (the lists are device tensors of torch's current stream)
+        if grouping is not None:
+            grp = outs[5]
+            rc = self._lib.icd_fusion_fuse_lists_grouped(
+                self._h, fusion._h, grouping._h, sc.data_ptr() if nq else None, idt.data_ptr() if nq else None, nq, R, lmax, lim.ctypes.data,
+                RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
+                group_size, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(out_ids), ptr(lv), ptr(bits), ptr(grp),
+                dev, stream)
+            if rc == -1:
+                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+            _check(self._lib, rc)
+            return (adj, fused, out_ids, lv, bits, grp) if reweighted else (fused, out_ids, lv, bits, grp)
         rc = self._lib.icd_fusion_fuse_lists(
             self._h, fusion._h, sc.data_ptr() if nq else None, idt.data_ptr() if nq else None, nq, R, lmax, lim.ctypes.data,
             RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
@@ -652,7 +708,8 @@ class IcdIndex:
             raise IcdError(-5, "index is closed")
         return IcdSparse(self, row_off, terms, vals, int(vocab), int(max_nq), int(max_k))
 
-    def search_sparse(self, sp: "IcdSparse", q_off, q_terms, q_vals, k: int, masks=None, reweighted: bool = False, validate: bool = True):
+    def search_sparse(self, sp: "IcdSparse", q_off, q_terms, q_vals, k: int, masks=None, reweighted: bool = False, validate: bool = True,
+                      grouping: Optional["IcdGrouping"] = None, group_size: int = 1):
         """The best k rows by sparse inner product among the rows that share a term with the query (icd_sparse_search). Queries
         in CSR form (q_off int64 [nq + 1], q_terms uint32, q_vals float32; at most 64 strictly increasing terms each): numpy
         arrays - checked by the library, host outputs - or torch CUDA tensors (int64 / int32 holding the uint32 bit patterns /
@@ -661,9 +718,14 @@ class IcdIndex:
         graph-capturable. validate=False skips the copy for queries the caller has already checked (check_sparse_rows): the
         call then only enqueues and, without masks, can be captured; the kernel trusts strictly increasing terms. masks: None, ONE IcdRowMask for
         every query, or nq of IcdRowMask or None. reweighted: (adj f64, raw f32, ids i64, levels i32) in search_reweighted's
-        order, else (raw, ids, levels) best first; padding -inf, -1, 0."""
+        order, else (raw, ids, levels) best first; padding -inf, -1, 0.
+        grouping (an IcdGrouping of this index) / group_size: the grouped form (icd_sparse_search_grouped) - the k best GROUPS
+        among the hits and the group_size best hit rows of each, outputs [nq, k * group_size] with the hits' group ids as one
+        more array at the end, layout and padding (-inf, -1, 0, -1) as search_grouped. Masks are allowed. The first grouped call
+        of a grouping pairs it with the sparse index (one launch, n * 4 bytes the grouping then owns)."""
         if self.closed or sp is None or sp.closed:
             raise IcdError(-5, "index or sparse index is closed")
+        group_size = _check_group_args(grouping, k, group_size)
         on_dev = _is_torch_tensor(q_off) and q_off.is_cuda
         if on_dev:
             import torch
@@ -686,6 +748,19 @@ class IcdIndex:
                 raise ValueError("q_off must hold nq + 1 offsets that end at the number of terms and values")
         k = int(k)
         mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")
+        if grouping is not None:
+            grouping.pair_sparse(self, sp)   # (behind every argument check of this layer: a refused call leaves the grouping as it was)
+            (adj, raw, ids, lv, grp), ptr, stream, dev = _outputs(on_dev, self.device, (nq, k * group_size),
+                                                                  (np.float64, np.float32, np.int64, np.int32, np.int32))
+            if nq:
+                rc = self._lib.icd_sparse_search_grouped(
+                    self._h, sp._h, grouping._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k, group_size,
+                    dev, None if mask_h is None else mask_h.ctypes.data, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw),
+                    ptr(ids), ptr(lv), ptr(grp), dev, stream)
+                if rc == -1:
+                    raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+                _check(self._lib, rc)
+            return (adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp)
         (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (nq, k), (np.float64, np.float32, np.int64, np.int32))
         if nq:
             rc = self._lib.icd_sparse_search(self._h, sp._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k,
@@ -762,6 +837,17 @@ class IcdGrouping(_Handle):
             raise ValueError(f"group_of holds {n} ids, the index {index.n} rows")
         self.n, self.max_nq, self.device = n, int(max_nq), index.device
         _check(self._lib, self._lib.icd_grouping_create(index._h, ptr, n, on_dev, self.max_nq, C.byref(self._h)))
+        self._paired = False
+
+    def pair_sparse(self, index: "IcdIndex", sp: "IcdSparse"):
+        """The one-time pairing with a sparse index of the same IcdIndex (icd_grouping_pair_sparse): the grouping's row ->
+        position table. search_sparse issues it at a grouping's first grouped call; later calls return at once."""
+        if self._paired:
+            return
+        if self.closed or index.closed or sp.closed:
+            raise IcdError(-5, "index, grouping or sparse index is closed")
+        _check(self._lib, self._lib.icd_grouping_pair_sparse(index._h, self._h, sp._h))
+        self._paired = True
 
     def stats(self) -> dict:
         if self.closed:

@@ -4,7 +4,7 @@ Mirrors the reference's main.py for these routes: lifespan-owned service globals
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
 cut to top_k, every match's confidence metrics / factors / level copied as :325-330 does; 503 when services are missing, 500 with a `detail` string on any exception), `/embed`
 (:505-530), `/stats` (:574-599). `/query` takes a Milvus `filter` expression (services/filter_expr.py; a bad one is a 400), `/stats`
-lists the cached filter views, filter masks and groupings; `/query` takes `filter_mode` ("view" / "mask"; anything else is a 400); `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). `/hybrid_query` takes several phrasings of one diagnosis and a ranker (Milvus hybrid_search, services/hybrid_search.py; bad arguments are a 400). The LLM, NER, standardisation and resource routes are out of scope.
+lists the cached filter views, filter masks and groupings; `/query` takes `filter_mode` ("view" / "mask"; anything else is a 400); `/query` also takes Milvus's `group_by_field` / `group_size` and `radius` / `range_filter` (a bad pair is a 400). `/hybrid_query` takes several phrasings of one diagnosis and a ranker (Milvus hybrid_search, services/hybrid_search.py; bad arguments are a 400), and `group_by_field` / `group_size` as `/query` does (a bad combination is a 400). The LLM, NER, standardisation and resource routes are out of scope.
 
     uvicorn rag_project_icd10_amd.api.app:app --host 0.0.0.0 --port 8005
 """
@@ -188,6 +188,12 @@ async def hybrid_query(request: HybridQueryRequest):
         if isinstance(ranker, hybrid.WeightedRanker) and len(ranker.weights) != n_reqs:
             raise ValueError(f"the ranker holds {len(ranker.weights)} weights for {n_reqs} requests")
         hybrid.AnnSearchRequest(None, request.req_limit, request.filter)   # (the limit's and the filter's checks)
+        if request.group_by_field is not None:   # Milvus's grouping on hybrid_search: the limits count groups
+            from ..services import filter_expr
+            filter_expr.check_grouping(request.group_by_field, request.top_k, request.group_size)
+            filter_expr.check_grouping(request.group_by_field, request.req_limit, request.group_size)
+        elif request.group_size != 1:
+            raise ValueError("group_size needs group_by_field")
     except ValueError as exc:
         raise HTTPException(status_code=400, detail=str(exc))
     if not embedding_service or not milvus_service:
@@ -199,7 +205,10 @@ async def hybrid_query(request: HybridQueryRequest):
         if request.sparse:
             reqs += [hybrid.AnnSearchRequest(t, request.req_limit, request.filter, anns_field="sparse") for t in request.texts]
         try:
-            hits = milvus_service.hybrid_search(reqs, ranker, request.top_k)
+            if request.group_by_field is not None:
+                hits = milvus_service.hybrid_search(reqs, ranker, request.top_k, group_by_field=request.group_by_field, group_size=request.group_size)
+            else:
+                hits = milvus_service.hybrid_search(reqs, ranker, request.top_k)
         except ValueError as exc:
             raise HTTPException(status_code=400, detail=str(exc))
         from .icd_models import Candidate

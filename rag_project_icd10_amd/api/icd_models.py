@@ -232,6 +232,8 @@ class HybridQueryRequest(BaseModel):
     req_limit: int = Field(default=20, description="hits every phrasing contributes (1 .. 128)")
     filter: Optional[str] = Field(default=None, description="Milvus filter expression applied to every request")
     sparse: bool = Field(default=False, description="every text also contributes a sparse (BM25) request next to its dense one (at most 4 texts then)")
+    group_by_field: Optional[str] = Field(default=None, description="Milvus grouping search: top_k and req_limit count groups of this field")
+    group_size: int = Field(default=1, description="rows returned per group (top_k * group_size and req_limit * group_size <= 128)")
 
 
 class QueryResponse(BaseModel):

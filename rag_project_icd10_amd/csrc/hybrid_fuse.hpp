@@ -194,6 +194,165 @@ __global__ __launch_bounds__(HY_THREADS) void hybrid_fuse_kernel(const HybridArg
     if (a.out_levels) a.out_levels[w] = lvl;
     if (a.out_reqbits) a.out_reqbits[w] = bits;
 }
+// ---- grouped fuse (rules H1 - H4) ----------------------------------------------------------------------------
+struct HybridGroupedArgs {
+    HybridArgs h;             // k = the number of GROUPS; limits[r] = L_r in runs of equal group ids; lmax <= HY_MAX_L slots per list
+    const int *dense_of;      // [n] dense group (0 .. G-1) of every local row
+    const int *group_of;      // [n] the caller's group id of every local row
+    int s;                    // members per group; k * s <= FIN_MAX_K
+    int *out_groups;          // [nq][k * s], nullable
+};
+
+// One work-group per query. List r is cut in front of its (L_r + 1)-th run of equal group ids (a slot without a row of the index is
+// a run of its own and no hit), then hybrid_fuse_kernel's (row, r) network and run sums give the fused heads, ordered by
+// (fused desc, row asc): a head's place p in that order stands for its key from there on. The heads are ordered again by
+// (dense group, p) - each group's first head is its best - the group heads by p, and the first k groups' first s members are
+// written group-rank-major, hits contiguous; the reweighted form ranks the winners as hybrid_fuse_kernel does.
+// LDS: four u64 arrays of 1024 slots, 1024 ints, the winners and their adjusted scores = 38.5 KB, static; no scratch.
+__global__ __launch_bounds__(HY_THREADS) void hybrid_fuse_grouped_kernel(const HybridGroupedArgs g) {
+    __shared__ u64 ka[HY_SLOTS];
+    __shared__ u64 kb[HY_SLOTS];
+    __shared__ u64 kc[HY_SLOTS];
+    __shared__ u64 kd[HY_SLOTS];
+    __shared__ int sg[HY_SLOTS];          // dense group of every staged slot, -1 = no row
+    __shared__ double adjbuf[FIN_MAX_K];
+    __shared__ int win[FIN_MAX_K], gcnt[FIN_MAX_K];
+    __shared__ int nheads, ngroups;
+    const HybridArgs &a = g.h;
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x;
+    const int slots = a.slots;
+    const size_t base = (size_t)q * a.R * a.lmax;
+    if (tid == 0) { nheads = 0; ngroups = 0; }
+
+    // 0. the staged slots' rows (kept in kc until the gather) and groups
+    for (int i = tid; i < slots; i += HY_THREADS) {
+        const int r = i / a.lmax, j = i - r * a.lmax;
+        int row = -1;
+        if (r < a.R) row = hybrid_local_row(a, a.st_ids[base + (size_t)r * a.lmax + j]);
+        kc[i] = (u64)(uint32_t)row;
+        sg[i] = row >= 0 ? g.dense_of[row] : -1;
+    }
+    __syncthreads();
+    // 1. gather with the cut by runs: slot (r, j) lies in run number 1 + #{1 <= i <= j : group(i) != group(i - 1) or no row at i}
+    for (int i = tid; i < slots; i += HY_THREADS) {
+        const int r = i / a.lmax, j = i - r * a.lmax;
+        u64 key = ~0ull;
+        const int row = (int)(uint32_t)kc[i];
+        if (r < a.R && row >= 0) {
+            const int *lg = sg + r * a.lmax;
+            int runs = 1;
+            for (int t = 1; t <= j; ++t) runs += (lg[t] != lg[t - 1] || lg[t] < 0) ? 1 : 0;
+            if (runs <= a.limits[r]) key = ((u64)(uint32_t)row << 10) | ((u64)r << 7) | (u64)j;
+        }
+        ka[i] = key;
+    }
+    // 2. order by (row, r)
+    hybrid_bitonic<false>(ka, kb, slots, tid);
+
+    // 3. the first entry of every run of equal rows sums the run (hybrid_fuse_kernel's step 3)
+    constexpr int PER = HY_SLOTS / HY_THREADS;
+    u64 fa[PER], fb[PER];
+    int mine = 0;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+        const int p = tid + e * HY_THREADS;
+        fa[e] = ~0ull; fb[e] = ~0ull;
+        if (p >= slots) continue;
+        const u64 key = ka[p];
+        if (key == ~0ull) continue;
+        const uint32_t row = (uint32_t)(key >> 10);
+        if (p > 0 && (uint32_t)(ka[p - 1] >> 10) == row) continue;
+        double fused = 0.0;
+        uint32_t bits = 0;
+        for (int t = p; t < slots; ++t) {
+            const u64 kt = ka[t];
+            if (kt == ~0ull || (uint32_t)(kt >> 10) != row) break;
+            const int r = (int)(kt >> 7) & 7, j = (int)kt & 127;
+            fused = fused + hybrid_term(a, r, j, a.st_scores[base + (size_t)r * a.lmax + j]);
+            bits |= 1u << r;
+        }
+        fa[e] = ~order_f64(fused);
+        fb[e] = ((u64)row << 8) | (u64)bits;
+        ++mine;
+    }
+    if (mine) atomicAdd(&nheads, mine);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+        const int p = tid + e * HY_THREADS;
+        if (p < slots) { ka[p] = fa[e]; kb[p] = fb[e]; }
+    }
+    // 4. the heads by (fused desc, row asc): head p of that order keeps its data at ka[p] / kb[p] to the end
+    hybrid_bitonic<true>(ka, kb, slots, tid);
+    const int nh = min(nheads, slots);
+
+    // 5. the heads by (dense group, p)
+    for (int i = tid; i < slots; i += HY_THREADS)
+        kc[i] = i < nh ? (((u64)(uint32_t)g.dense_of[(int)(kb[i] >> 8)] << 10) | (u64)i) : ~0ull;
+    hybrid_bitonic<false>(kc, kc, slots, tid);
+    // 6. every group's first head is its best: the group heads by p, with where the group starts
+    int heads_here = 0;
+    for (int t = tid; t < slots; t += HY_THREADS) {
+        u64 key = ~0ull;
+        if (t < nh && (t == 0 || (kc[t - 1] >> 10) != (kc[t] >> 10))) { key = ((kc[t] & 1023ull) << 10) | (u64)t; ++heads_here; }
+        kd[t] = key;
+    }
+    if (heads_here) atomicAdd(&ngroups, heads_here);
+    hybrid_bitonic<false>(kd, kd, slots, tid);
+
+    // 7. the first k groups' first s members, group-rank-major, hits contiguous
+    const int kg = min(a.k, ngroups), ks = a.k * g.s;
+    if (tid < kg) {
+        const int t0 = (int)(kd[tid] & 1023ull);
+        const u64 grp = kc[t0] >> 10;
+        int c = 1;
+        while (c < g.s && t0 + c < nh && (kc[t0 + c] >> 10) == grp) ++c;
+        gcnt[tid] = c;
+    }
+    __syncthreads();
+    int nres = 0;
+    for (int i = 0; i < kg; ++i) nres += gcnt[i];
+    if (tid < kg) {
+        int off = 0;
+        for (int i = 0; i < tid; ++i) off += gcnt[i];
+        const int t0 = (int)(kd[tid] & 1023ull);
+        for (int m = 0; m < gcnt[tid]; ++m) win[off + m] = (int)(kc[t0 + m] & 1023ull);
+    }
+    __syncthreads();
+
+    // 8. outputs: raw order, or the level weight in double and ONE stable descending re-sort (hybrid_fuse_kernel's step 5)
+    const size_t o = (size_t)q * ks;
+    double fused = -INFINITY, adj = -INFINITY;
+    int row = -1, lvl = 0;
+    uint32_t bits = 0;
+    if (tid < nres) {
+        const int p = win[tid];
+        fused = unorder_f64(~ka[p]);
+        row = (int)(kb[p] >> 8);
+        bits = (uint32_t)kb[p] & 0xFFu;
+        lvl = a.levels ? a.levels[row] : 1;
+        adj = fused * level_weight(lvl);
+        adjbuf[tid] = adj;
+    }
+    __syncthreads();
+    if (tid >= ks) return;
+    int pos = tid;
+    if (a.reweighted && tid < nres) {
+        pos = 0;
+        for (int i = 0; i < nres; ++i) {
+            const double ai = adjbuf[i];
+            pos += (ai > adj || (ai == adj && i < tid)) ? 1 : 0;
+        }
+    }
+    const size_t w = o + pos;
+    if (a.reweighted) a.out_adj[w] = adj;
+    a.out_fused[w] = fused;
+    a.out_ids[w] = row >= 0 ? (a.row_map ? a.row_map[row] : a.id_base + row) : -1ll;
+    if (a.out_levels) a.out_levels[w] = lvl;
+    if (a.out_reqbits) a.out_reqbits[w] = bits;
+    if (g.out_groups) g.out_groups[w] = row >= 0 ? g.group_of[row] : -1;
+}
 #pragma clang fp contract(fast)
 
 }  // namespace icd

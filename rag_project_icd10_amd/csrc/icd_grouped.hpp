@@ -12,6 +12,7 @@ struct icd_grouping : OwnedHandle {
     int G = 0, largest = 0, max_nq = 0, qb = 0;
     long long ldS = 0;
     int *group_of = nullptr, *dense_of = nullptr, *order = nullptr, *gpos = nullptr, *seg = nullptr;
+    int *pos_of = nullptr;   // [n] the inverse of `order`; built by icd_grouping_pair_sparse, absent before
     float *S = nullptr;
     u64 *best = nullptr;
     float *qdev = nullptr;
@@ -22,6 +23,59 @@ struct icd_grouping : OwnedHandle {
 namespace {
 constexpr int GROUP_QUERY_BLOCK = 512;   // queries scored per pass: S = 512 x 40 576 x 4 B = 83 MB stays in the 256-MiB Infinity Cache next to the 124-MB corpus
 }  // namespace
+
+// where a grouped search writes: the reweighted form fills all five, the raw form all but d_adj
+struct GroupedOuts { double *d_adj; float *d_raw; long long *d_ids; int *d_lv, *d_grp; };
+
+// Steps 2 and 3 of a grouped search for ONE pass of nb <= g->qb queries whose scores of all rows sit in g->S (queries q0 .. of
+// the call): group_best_kernel, group_finish_kernel. Whoever filled S - the dense scoring pass or the sparse store - calls this.
+static int grouped_reduce_pass(icd_index *idx, icd_grouping *g, int nb, int64_t q0, int k, int group_size, bool reweighted, const GroupedOuts &o,
+                               hipStream_t s) {
+    const int n = (int)g->at.n;
+    HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
+    GroupBestArgs ba{};
+    ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
+    ba.nq = nb; ba.n = n; ba.G = g->G; ba.best = g->best;
+    ba.R = nb >= 64 ? 1024 : 128;
+    ba.nranges = (n + ba.R - 1) / ba.R;
+    constexpr int QW = 4;
+    const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
+    hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
+    HIP_TRY(hipGetLastError());
+
+    GroupFinishArgs fa{};
+    fa.best = g->best; fa.S = g->S; fa.ldS = g->ldS; fa.order = g->order; fa.seg = g->seg; fa.dense_of = g->dense_of;
+    fa.nq = nb; fa.G = g->G; fa.k = k; fa.s = group_size; fa.q_base = (int)q0;
+    fa.fin.k = k * group_size; fa.fin.levels = idx->levels; fa.fin.id_base = idx->id_base; fa.fin.row_map = idx->row_map; fa.fin.groups = g->group_of;
+    if (reweighted) {
+        fa.fin.out_adj = o.d_adj; fa.fin.out_adj_raw = o.d_raw; fa.fin.out_adj_ids = o.d_ids; fa.fin.out_adj_levels = o.d_lv; fa.fin.out_adj_groups = o.d_grp;
+    } else {
+        fa.fin.out_scores = o.d_raw; fa.fin.out_ids = o.d_ids; fa.fin.out_levels = o.d_lv; fa.fin.out_groups = o.d_grp;
+    }
+    if (k <= 16 && group_size <= 16) hipLaunchKernelGGL((group_finish_kernel<16, 2>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
+    else hipLaunchKernelGGL((group_finish_kernel<128, 4>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
+    HIP_TRY(hipGetLastError());
+    return ICD_OK;
+}
+
+// icd_index_search_grouped's body for device queries and device outputs: per pass of the grouping's query block the scoring pass
+// and the reduction. The hybrid grouped search runs it on the fusion's staged vectors. The caller holds the grouping's lock.
+static int grouped_search_device(icd_index *idx, icd_grouping *g, const float *dq, int64_t nq, int k, int group_size, bool reweighted,
+                                 const GroupedOuts &o, hipStream_t s) {
+    const int n = (int)g->at.n;
+    const int ntiles = (int)(g->ldS / GROUP_TILE);
+    for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {
+        const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
+        GroupScoreArgs sa{};
+        sa.corpus = idx->corpus; sa.queries = dq + (size_t)q0 * idx->dim; sa.order = g->order;
+        sa.nq = nb; sa.n = n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
+        sa.S = g->S; sa.ldS = g->ldS;
+        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)(ntiles * sa.mtiles)), dim3(256), 0, s, sa);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = grouped_reduce_pass(idx, g, nb, q0, k, group_size, reweighted, o, s)) return rc;
+    }
+    return ICD_OK;
+}
 
 extern "C" {
 
@@ -113,43 +167,8 @@ int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float
     double *d_adj = hc.target(out_adj, g->o_adj); float *d_raw = hc.target(out_raw, g->o_raw);
     long long *d_ids = hc.target(reinterpret_cast<long long *>(out_ids), g->o_ids);
     int *d_lv = hc.target(out_levels, g->o_lv), *d_grp = hc.target(out_groups, g->o_grp);
-    const int n = (int)g->at.n;
     const int ks = k * group_size;
-    const int ntiles = (int)(g->ldS / GROUP_TILE);
-    const bool small_kp = k <= 16 && group_size <= 16;
-    for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {
-        const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
-        GroupScoreArgs sa{};
-        sa.corpus = idx->corpus; sa.queries = dq + (size_t)q0 * idx->dim; sa.order = g->order;
-        sa.nq = nb; sa.n = n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
-        sa.S = g->S; sa.ldS = g->ldS;
-        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)(ntiles * sa.mtiles)), dim3(256), 0, s, sa);
-        HIP_TRY(hipGetLastError());
-
-        HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
-        GroupBestArgs ba{};
-        ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
-        ba.nq = nb; ba.n = n; ba.G = g->G; ba.best = g->best;
-        ba.R = nb >= 64 ? 1024 : 128;
-        ba.nranges = (n + ba.R - 1) / ba.R;
-        constexpr int QW = 4;
-        const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
-        hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
-        HIP_TRY(hipGetLastError());
-
-        GroupFinishArgs fa{};
-        fa.best = g->best; fa.S = g->S; fa.ldS = g->ldS; fa.order = g->order; fa.seg = g->seg; fa.dense_of = g->dense_of;
-        fa.nq = nb; fa.G = g->G; fa.k = k; fa.s = group_size; fa.q_base = (int)q0;
-        fa.fin.k = ks; fa.fin.levels = idx->levels; fa.fin.id_base = idx->id_base; fa.fin.row_map = idx->row_map; fa.fin.groups = g->group_of;
-        if (reweighted) {
-            fa.fin.out_adj = d_adj; fa.fin.out_adj_raw = d_raw; fa.fin.out_adj_ids = d_ids; fa.fin.out_adj_levels = d_lv; fa.fin.out_adj_groups = d_grp;
-        } else {
-            fa.fin.out_scores = d_raw; fa.fin.out_ids = d_ids; fa.fin.out_levels = d_lv; fa.fin.out_groups = d_grp;
-        }
-        if (small_kp) hipLaunchKernelGGL((group_finish_kernel<16, 2>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
-        else hipLaunchKernelGGL((group_finish_kernel<128, 4>), dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, fa);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = grouped_search_device(idx, g, dq, nq, k, group_size, reweighted != 0, GroupedOuts{d_adj, d_raw, d_ids, d_lv, d_grp}, s))) return rc;
     if ((rc = hc.copy_back({{out_adj, d_adj, 8}, {out_raw, d_raw, 4}, {out_ids, d_ids, 8}, {out_levels, d_lv, 4}, {out_groups, d_grp, 4}}, (size_t)nq * ks)))
         return rc;
     return hc.finish();

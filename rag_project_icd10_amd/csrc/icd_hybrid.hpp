@@ -29,9 +29,14 @@ constexpr int FUSION_HOST_CHUNK = 256;
 // has put them. Host outputs leave through the fusion's staging, FUSION_HOST_CHUNK queries at a time.
 static int fuse_lists_step(icd_index *idx, icd_fusion *f, const float *st_scores, const long long *st_ids, int64_t nq, int32_t R, int lmax,
                            int32_t ranker, double rrf_c, int32_t norm, int32_t k, int32_t reweighted, double *out_adj, double *out_fused,
-                           int64_t *out_ids, int32_t *out_levels, uint32_t *out_reqbits, const HostCall &hc, hipStream_t s) {
+                           int64_t *out_ids, int32_t *out_levels, uint32_t *out_reqbits, const HostCall &hc, hipStream_t s,
+                           icd_grouping *grp = nullptr, int group_size = 1, int32_t *out_groups = nullptr) {
     int rc;
-    HybridArgs a{};
+    // grouped (grp != nullptr): hybrid_fuse_grouped_kernel, k groups of group_size members, k * group_size slots per query, the
+    // hits' group ids as one more output (a host caller's through the grouping's staging)
+    const int kk = grp ? k * group_size : k;
+    HybridGroupedArgs ga{};
+    HybridArgs &a = ga.h;
     a.st_scores = st_scores; a.st_ids = st_ids;
     a.R = R; a.lmax = lmax; a.k = k;
     a.slots = 2;
@@ -40,24 +45,30 @@ static int fuse_lists_step(icd_index *idx, icd_fusion *f, const float *st_scores
     a.rrf_c = rrf_c; a.ranker = ranker; a.norm = norm; a.reweighted = reweighted ? 1 : 0;
     a.n = idx->n; a.id_base = idx->id_base; a.row_map = idx->row_map; a.levels = idx->levels;
     a.out_adj = out_adj; a.out_fused = out_fused; a.out_ids = reinterpret_cast<long long *>(out_ids); a.out_levels = out_levels; a.out_reqbits = out_reqbits;
+    if (grp) { ga.dense_of = grp->dense_of; ga.group_of = grp->group_of; ga.s = group_size; ga.out_groups = out_groups; }
+    auto launch = [&](int64_t nb) {
+        if (grp) hipLaunchKernelGGL(hybrid_fuse_grouped_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, ga);
+        else hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, a);
+        return hipGetLastError();
+    };
     if (hc.out_on_device) {
-        hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nq), dim3(HY_THREADS), 0, s, a);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(nq));
     } else {
         // host outputs: FUSION_HOST_CHUNK queries per launch into the staging, copied out behind it (stream order keeps the
         // next piece's launch behind this piece's copies)
         a.out_adj = reweighted ? f->o_adj : nullptr; a.out_fused = f->o_fused; a.out_ids = f->o_ids;
         a.out_levels = out_levels ? f->o_lv : nullptr; a.out_reqbits = out_reqbits ? f->o_bits : nullptr;
+        if (grp) ga.out_groups = out_groups ? grp->o_grp : nullptr;   // (a piece is at most FUSION_HOST_CHUNK <= nq <= the grouping's max_nq queries)
         for (int64_t q0 = 0; q0 < nq; q0 += FUSION_HOST_CHUNK) {
             const int64_t nb = std::min<int64_t>(FUSION_HOST_CHUNK, nq - q0);
             a.st_scores = st_scores + (size_t)q0 * R * lmax;
             a.st_ids = st_ids + (size_t)q0 * R * lmax;
-            hipLaunchKernelGGL(hybrid_fuse_kernel, dim3((unsigned)nb), dim3(HY_THREADS), 0, s, a);
-            HIP_TRY(hipGetLastError());
-            const size_t at = (size_t)q0 * k;
+            HIP_TRY(launch(nb));
+            const size_t at = (size_t)q0 * kk;
             if ((rc = hc.copy_back({{reweighted ? out_adj + at : nullptr, a.out_adj, 8}, {out_fused + at, a.out_fused, 8}, {out_ids + at, a.out_ids, 8},
-                                    {out_levels ? out_levels + at : nullptr, a.out_levels, 4}, {out_reqbits ? out_reqbits + at : nullptr, a.out_reqbits, 4}},
-                                   (size_t)nb * k)))
+                                    {out_levels ? out_levels + at : nullptr, a.out_levels, 4}, {out_reqbits ? out_reqbits + at : nullptr, a.out_reqbits, 4},
+                                    {out_groups ? out_groups + at : nullptr, ga.out_groups, 4}},
+                                   (size_t)nb * kk)))
                 return rc;
         }
     }
@@ -162,6 +173,113 @@ int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *que
     // step 2: the fuse
     if ((rc = fuse_lists_step(idx, f, f->st_scores, f->st_ids, nq, R, lmax, ranker, rrf_c, norm, k, reweighted, out_adj, out_fused, out_ids,
                               out_levels, out_reqbits, hc, s)))
+        return rc;
+    return hc.finish();
+}
+
+}  // extern "C"
+
+// ---- grouped hybrid search (rules H1 - H6) -----------------------------------------------------------------
+// the checks the two grouped entry points share (section 13's and section 10's), before the first device call; *lmax_groups: max L_r
+static int check_grouped_fuse(icd_index *idx, icd_fusion *f, icd_grouping *g, int64_t nq, int32_t R, const int32_t *limits, int32_t ranker,
+                              double rrf_c, const double *weights, int32_t norm, int32_t k, int32_t group_size, int32_t reweighted,
+                              const double *out_adj, const double *out_fused, const int64_t *out_ids, int *lmax_groups) {
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(f)) return fail(ICD_ERR_STATE, "invalid fusion handle");
+    if (!valid_handle(g)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    int rc = check_owner(f->at, idx, "the fusion");
+    if (rc) return rc;
+    if ((rc = check_owner(g->at, idx, "the grouping"))) return rc;
+    if (R < 1 || R > ICD_MAX_REQUESTS) return fail(ICD_ERR_INVALID, "R=%d: a hybrid search takes 1 .. %d requests per query", R, ICD_MAX_REQUESTS);
+    if (k < 1 || group_size < 1 || (int64_t)k * group_size > ICD_MAX_K)
+        return fail(ICD_ERR_INVALID, "k=%d group_size=%d: need k >= 1, group_size >= 1 and k * group_size <= %d", k, group_size, ICD_MAX_K);
+    if (!limits) return fail(ICD_ERR_INVALID, "limits is NULL");
+    int lmax = 0;
+    for (int r = 0; r < R; ++r) {
+        if (limits[r] < 1 || (int64_t)limits[r] * group_size > ICD_MAX_K)
+            return fail(ICD_ERR_INVALID, "limits[%d]=%d group_size=%d: a request returns 1 .. %d / group_size groups", r, limits[r], group_size, ICD_MAX_K);
+        lmax = std::max(lmax, (int)limits[r]);
+    }
+    *lmax_groups = lmax;
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    if (nq * R > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)(nq * R), (long long)f->max_total);
+    if (nq * R > g->max_nq) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the grouping's max_nq=%d", (long long)(nq * R), g->max_nq);
+    if (ranker == ICD_RANKER_RRF) {
+        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
+    } else if (ranker == ICD_RANKER_WEIGHTED) {
+        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
+        for (int r = 0; r < R; ++r)
+            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
+        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
+    } else {
+        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
+    }
+    if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    return ICD_OK;
+}
+
+static void stage_fuse_params(icd_fusion *f, int32_t R, const int32_t *limits, int32_t ranker, const double *weights) {
+    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
+        f->limits[r] = r < R ? limits[r] : 0;
+        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
+    }
+}
+
+extern "C" {
+
+int icd_fusion_fuse_lists_grouped(icd_index *idx, icd_fusion *fusion, icd_grouping *grouping, const float *scores, const int64_t *ids, int64_t nq,
+                                  int32_t R, int32_t lmax, const int32_t *limits, int32_t ranker, double rrf_c, const double *weights, int32_t norm,
+                                  int32_t k, int32_t group_size, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids,
+                                  int32_t *out_levels, uint32_t *out_reqbits, int32_t *out_groups, int32_t out_on_device, void *stream) {
+    int lg = 0;
+    int rc = check_grouped_fuse(idx, fusion, grouping, nq, R, limits, ranker, rrf_c, weights, norm, k, group_size, reweighted, out_adj, out_fused, out_ids, &lg);
+    if (rc) return rc;
+    if (lmax < 1 || lmax > ICD_MAX_K) return fail(ICD_ERR_INVALID, "lmax=%d: a list holds 1 .. %d hits", lmax, ICD_MAX_K);
+    if (nq == 0) return ICD_OK;
+    if (!scores || !ids) return fail(ICD_ERR_INVALID, "scores / ids NULL");
+    // lock order: fusion, grouping, index
+    std::lock_guard<std::mutex> guard(fusion->mu);
+    std::lock_guard<std::mutex> guard_g(grouping->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, true, out_on_device != 0};
+    if ((rc = check_capture(s, !out_on_device, false, false))) return rc;
+    stage_fuse_params(fusion, R, limits, ranker, weights);
+    if ((rc = fuse_lists_step(idx, fusion, scores, reinterpret_cast<const long long *>(ids), nq, R, lmax, ranker, rrf_c, norm, k, reweighted, out_adj,
+                              out_fused, out_ids, out_levels, out_reqbits, hc, s, grouping, group_size, out_groups)))
+        return rc;
+    return hc.finish();
+}
+
+int icd_index_search_hybrid_grouped(icd_index *idx, icd_fusion *fusion, icd_grouping *grouping, const float *queries, int64_t nq, int32_t R,
+                                    int32_t queries_on_device, const int32_t *limits, icd_rowmask *const *masks, const float *radius,
+                                    const float *range_filter, int32_t ranker, double rrf_c, const double *weights, int32_t norm, int32_t k,
+                                    int32_t group_size, int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids,
+                                    int32_t *out_levels, uint32_t *out_reqbits, int32_t *out_groups, int32_t out_on_device, void *stream) {
+    int lg = 0;
+    int rc = check_grouped_fuse(idx, fusion, grouping, nq, R, limits, ranker, rrf_c, weights, norm, k, group_size, reweighted, out_adj, out_fused, out_ids, &lg);
+    if (rc) return rc;
+    if (masks || radius || range_filter)
+        return fail(ICD_ERR_INVALID, "row masks and radius / range_filter cannot be combined with grouping (filter with a view and its grouping)");
+    if (nq == 0) return ICD_OK;
+    if (!queries) return fail(ICD_ERR_INVALID, "queries is NULL");
+    icd_fusion *f = fusion;
+    std::lock_guard<std::mutex> guard(f->mu);
+    std::lock_guard<std::mutex> guard_g(grouping->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
+    if ((rc = check_capture(s, !queries_on_device || !out_on_device, false, false))) return rc;
+    stage_fuse_params(f, R, limits, ranker, weights);
+    const int64_t total = nq * R;
+    const float *dq;
+    if ((rc = hc.upload(queries, f->qdev, (size_t)total * idx->dim, &dq))) return rc;
+    // step 1: ONE grouped sub-search over the nq * R vectors at max L_r groups of group_size members, raw form, into the staging
+    if ((rc = grouped_search_device(idx, grouping, dq, total, lg, group_size, false, GroupedOuts{nullptr, f->st_scores, f->st_ids, nullptr, nullptr}, s)))
+        return rc;
+    // step 2: the grouped fuse; list r is cut in front of its (L_r + 1)-th group
+    if ((rc = fuse_lists_step(idx, f, f->st_scores, f->st_ids, nq, R, lg * group_size, ranker, rrf_c, norm, k, reweighted, out_adj, out_fused, out_ids,
+                              out_levels, out_reqbits, hc, s, grouping, group_size, out_groups)))
         return rc;
     return hc.finish();
 }

@@ -1,5 +1,6 @@
-// icd_sparse.hpp - the sparse-vector search (icd_sparse_*) and the fuse of caller-provided lists (icd_fusion_fuse_lists). Part of
-// icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle, mask and host-call helpers, the fusion); included there and
+// icd_sparse.hpp - the sparse-vector search (icd_sparse_*), its grouped form (icd_grouping_pair_sparse, icd_sparse_search_grouped)
+// and the fuse of caller-provided lists (icd_fusion_fuse_lists). Part of
+// icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle, mask and host-call helpers, the grouping, the fusion); included there and
 // nowhere else.
 #pragma once
 #include "sparse_pack.hpp"
@@ -148,6 +149,116 @@ int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, cons
     HIP_TRY(hipGetLastError());
     if ((rc = hc.copy_back({{reweighted ? out_adj : nullptr, m.out_adj, 8}, {out_raw, m.out_raw, 4}, {out_ids, m.out_ids, 8}, {out_levels, m.out_levels, 4}},
                            (size_t)nq * k)))
+        return rc;
+    return hc.finish();
+}
+
+// ---- grouped sparse search -------------------------------------------------------------------------------
+// The one-time pairing of a grouping with a sparse index of the same index: builds the grouping's row -> position table (one
+// launch over `order`, memory the grouping owns) so that no search allocates. Idempotent; a grouping that is never paired keeps
+// the bytes icd_grouping_stats has always reported.
+int icd_grouping_pair_sparse(icd_index *idx, icd_grouping *grouping, icd_sparse *sp) {
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    if (!valid_handle(sp)) return fail(ICD_ERR_STATE, "invalid sparse index handle");
+    int rc = check_owner(grouping->at, idx, "the grouping");
+    if (rc) return rc;
+    if ((rc = check_owner(sp->at, idx, "the sparse index"))) return rc;
+    std::lock_guard<std::mutex> guard(grouping->mu);
+    if (grouping->pos_of) return ICD_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    const int n = (int)grouping->at.n;
+    // a stream of its own (a NULL-stream launch or a device-wide wait would collide with a capture elsewhere on the device); the
+    // table joins the handle's allocations only once it is built, so a failure leaves nothing behind
+    int *pos = nullptr;
+    hipStream_t st = nullptr;
+    HIP_TRY(dmalloc(&pos, (size_t)n));
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(grouping_invert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, grouping->order, pos, n);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        hipStreamDestroy(st);
+    }
+    if (e != hipSuccess) {
+        hipFree(pos);
+        return fail(ICD_ERR_HIP, "pairing a grouping with a sparse index: %s", hipGetErrorString(e));
+    }
+    grouping->allocs.push_back(pos);
+    grouping->pos_of = pos;
+    grouping->bytes += (size_t)n * sizeof(int);
+    return ICD_OK;
+}
+
+int icd_sparse_search_grouped(icd_index *idx, icd_sparse *sp, icd_grouping *grouping, const int64_t *q_off, const uint32_t *q_terms,
+                              const float *q_vals, int64_t nq, int32_t k, int32_t group_size, int32_t queries_on_device,
+                              icd_rowmask *const *masks, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                              int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream) {
+    // every check comes before the first device call
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(sp)) return fail(ICD_ERR_STATE, "invalid sparse index handle");
+    if (!valid_handle(grouping)) return fail(ICD_ERR_STATE, "invalid grouping handle");
+    icd_grouping *g = grouping;
+    int rc = check_owner(sp->at, idx, "the sparse index");
+    if (rc) return rc;
+    if ((rc = check_owner(g->at, idx, "the grouping"))) return rc;
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "a sparse search on a view is not supported");
+    if (k < 1 || group_size < 1 || (int64_t)k * group_size > ICD_MAX_K)
+        return fail(ICD_ERR_INVALID, "k=%d group_size=%d: need k >= 1, group_size >= 1 and k * group_size <= %d", k, group_size, ICD_MAX_K);
+    if (nq < 0 || nq > sp->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the sparse index's max_nq=%d", (long long)nq, sp->max_nq);
+    if (nq > g->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the grouping's max_nq=%d", (long long)nq, g->max_nq);
+    if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    bool any_mask = false;
+    if (masks && (rc = check_masks(idx, masks, nq, "masked sparse search", &any_mask))) return rc;
+    if (nq == 0) return ICD_OK;
+    if (!q_off) return fail(ICD_ERR_INVALID, "q_off is NULL");
+    int64_t q_nnz = 0;
+    if (!queries_on_device) {
+        char msg[200];
+        if (sparse_check_csr(q_off, q_terms, q_vals, nq, sp->vocab, SP_MAX_TERMS, "query", msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);
+        q_nnz = q_off[nq];
+    } else if (!q_terms || !q_vals) {
+        return fail(ICD_ERR_INVALID, "q_terms / q_vals NULL");
+    }
+    // lock order: sparse index, grouping, index
+    std::lock_guard<std::mutex> guard_sp(sp->mu);
+    std::lock_guard<std::mutex> guard_g(g->mu);
+    if (!g->pos_of) return fail(ICD_ERR_STATE, "the grouping was never paired with a sparse index (icd_grouping_pair_sparse)");
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
+    if ((rc = check_capture(s, !queries_on_device || !out_on_device, false, any_mask))) return rc;
+    std::unique_lock<std::mutex> table(idx->mu, std::defer_lock);   // (a masked call reads the index's mask table: icd_sparse_search)
+    if (any_mask) {
+        table.lock();
+        if ((rc = stage_masks(idx, masks, (int)nq, s))) return rc;
+    }
+    SparseStoreArgs a{};
+    a.sp.post_off = sp->post_off; a.sp.post_row = sp->post_row; a.sp.post_val = sp->post_val; a.sp.vocab = sp->vocab;
+    a.sp.q_off = reinterpret_cast<const long long *>(q_off); a.sp.q_terms = q_terms; a.sp.q_vals = q_vals;
+    if (!queries_on_device) {
+        HIP_TRY(hipMemcpyAsync(sp->q_off, q_off, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, s));
+        if (q_nnz) {
+            HIP_TRY(hipMemcpyAsync(sp->q_terms, q_terms, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(sp->q_vals, q_vals, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
+        }
+        a.sp.q_off = sp->q_off; a.sp.q_terms = sp->q_terms; a.sp.q_vals = sp->q_vals;
+    }
+    a.sp.masks = any_mask ? idx->mask_dev : nullptr;
+    a.sp.mask_words = rowmask_tile_words(idx->n);
+    a.sp.tiles = sp->tiles;
+    a.n = (int)idx->n; a.pos_of = g->pos_of; a.S = g->S; a.ldS = g->ldS;
+    const GroupedOuts o{hc.target(out_adj, g->o_adj), hc.target(out_raw, g->o_raw), hc.target(reinterpret_cast<long long *>(out_ids), g->o_ids),
+                        hc.target(out_levels, g->o_lv), hc.target(out_groups, g->o_grp)};
+    for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {   // passes of the grouping's query block
+        const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
+        a.sp.nq = nb; a.q_base = (int)q0;
+        hipLaunchKernelGGL(sparse_store_kernel, dim3((unsigned)((int64_t)nb * sp->tiles)), dim3(SP_THREADS), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        if ((rc = grouped_reduce_pass(idx, g, nb, q0, k, group_size, reweighted != 0, o, s))) return rc;
+    }
+    if ((rc = hc.copy_back({{reweighted ? out_adj : nullptr, o.d_adj, 8}, {out_raw, o.d_raw, 4}, {out_ids, o.d_ids, 8}, {out_levels, o.d_lv, 4},
+                            {out_groups, o.d_grp, 4}}, (size_t)nq * k * group_size)))
         return rc;
     return hc.finish();
 }

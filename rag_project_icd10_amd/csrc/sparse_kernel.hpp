@@ -20,6 +20,10 @@
 //
 // LDS: 32 KB accumulators + 1 KB bitset + 1 KB histogram + 1 KB survivors + 1.5 KB of the query = 36.6 KB: four work-groups per
 // CU. No scratch.
+//
+// sparse_store_kernel (grouped sparse search): the same accumulate phase (sparse_accumulate_tile), then the
+// tile's sums - a NaN where a row is no hit - go to the score block of a grouping, where group_topk.hpp's reduction kernels pick
+// the k best groups and their s best rows. grouping_invert_kernel builds the row -> position table that store needs, once.
 #pragma once
 #include "hybrid_fuse.hpp"
 
@@ -49,19 +53,10 @@ struct SparseArgs {
 };
 
 #pragma clang fp contract(off)
-__global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(const SparseArgs a) {
-    __shared__ float acc[SP_TILE];
-    __shared__ uint32_t touched[SP_TILE / 32];
-    __shared__ uint32_t hist[256];
-    __shared__ u64 skey[FIN_MAX_K];
-    __shared__ long long seg[2 * SP_MAX_TERMS];
-    __shared__ uint32_t qt[SP_MAX_TERMS];
-    __shared__ float qv[SP_MAX_TERMS];
-    __shared__ int sh_cnt, sh_kept, sh_sel, sh_left, sh_bucket;
-    const int tid = threadIdx.x;
-    const int q = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x - (unsigned)q * (unsigned)a.tiles);
-    const uint32_t tile0 = (uint32_t)tile * (uint32_t)SP_TILE;
-
+// The accumulate phase both kernels run: on return (behind a barrier) acc[l] holds the canonical sum of row tile0 + l and touched
+// its hit bit. The arrays are the caller's LDS.
+__device__ __forceinline__ void sparse_accumulate_tile(const SparseArgs &a, int q, uint32_t tile0, float *acc, uint32_t *touched, long long *seg,
+                                                       uint32_t *qt, float *qv, int tid) {
     // 0. an empty tile; the query's terms (a device caller's offsets are clamped: never more than SP_MAX_TERMS, never backwards)
     for (int i = tid; i < SP_TILE; i += SP_THREADS) acc[i] = 0.0f;
     touched[tid] = 0u;
@@ -70,7 +65,6 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(co
     qn = qn < 0 ? 0 : (qn > SP_MAX_TERMS ? SP_MAX_TERMS : qn);
     const int nt = (int)qn;
     if (tid < nt) { qt[tid] = a.q_terms[qa + tid]; qv[tid] = a.q_vals[qa + tid]; }
-    if (tid == 0) { sh_cnt = 0; sh_kept = 0; }
     __syncthreads();
 
     // 1. the tile's segment of every term's postings: lane 2 t finds its begin, lane 2 t + 1 its end (a term outside the
@@ -102,6 +96,22 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(co
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(const SparseArgs a) {
+    __shared__ float acc[SP_TILE];
+    __shared__ uint32_t touched[SP_TILE / 32];
+    __shared__ uint32_t hist[256];
+    __shared__ u64 skey[FIN_MAX_K];
+    __shared__ long long seg[2 * SP_MAX_TERMS];
+    __shared__ uint32_t qt[SP_MAX_TERMS];
+    __shared__ float qv[SP_MAX_TERMS];
+    __shared__ int sh_cnt, sh_kept, sh_sel, sh_left, sh_bucket;
+    const int tid = threadIdx.x;
+    const int q = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x - (unsigned)q * (unsigned)a.tiles);
+    const uint32_t tile0 = (uint32_t)tile * (uint32_t)SP_TILE;
+    if (tid == 0) { sh_cnt = 0; sh_kept = 0; }
+    sparse_accumulate_tile(a, q, tile0, acc, touched, seg, qt, qv, tid);
 
     // 3. candidates = touched rows inside the query's mask; bit j of `mine` = row tid + SP_THREADS * j of the tile
     const uint32_t *mask = a.masks ? a.masks[q] : nullptr;
@@ -166,6 +176,54 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(co
         out[rank] = key;
     } else if (tid < k) {
         out[tid] = 0ull;
+    }
+}
+
+// ---- grouped sparse search: the tile's sums go to the grouping's score block, not to a top-k ----------------
+struct SparseStoreArgs {
+    SparseArgs sp;        // part / k unused; nq = the queries of this pass; q_off, masks indexed by q_base + query
+    int q_base;           // first query of the pass
+    int n;                // rows of the index
+    const int *pos_of;    // [n] position of every row in the grouping's (group, row) order
+    float *S;             // [queries of the pass][ldS] the grouping's score block
+    long long ldS;
+};
+
+// position -> row becomes row -> position: one launch when a grouping first meets a sparse index
+__global__ void grouping_invert_kernel(const int *order, int *pos_of, int n) {
+    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p < n) pos_of[order[p]] = p;
+}
+
+// One work-group per (query of the pass, tile): the accumulate phase, then S[query][pos_of[row]] for EVERY row of the tile below
+// n - the sum of a hit inside the query's mask, a quiet NaN otherwise (group_topk.hpp reads NaN as "no hit": key 0). The block is
+// reused between passes, so nothing of it is assumed. LDS: 32 KB + 1 KB + 1.5 KB of the query; no scratch.
+__global__ __launch_bounds__(SP_THREADS) void sparse_store_kernel(const SparseStoreArgs a) {
+    __shared__ float acc[SP_TILE];
+    __shared__ uint32_t touched[SP_TILE / 32];
+    __shared__ long long seg[2 * SP_MAX_TERMS];
+    __shared__ uint32_t qt[SP_MAX_TERMS];
+    __shared__ float qv[SP_MAX_TERMS];
+    const int tid = threadIdx.x;
+    const int ql = (int)(blockIdx.x / (unsigned)a.sp.tiles), tile = (int)(blockIdx.x - (unsigned)ql * (unsigned)a.sp.tiles);
+    const int q = a.q_base + ql;
+    const uint32_t tile0 = (uint32_t)tile * (uint32_t)SP_TILE;
+    sparse_accumulate_tile(a.sp, q, tile0, acc, touched, seg, qt, qv, tid);
+
+    const uint32_t *mask = a.sp.masks ? a.sp.masks[q] : nullptr;
+    float *srow = a.S + (size_t)ql * a.ldS;
+#pragma unroll 4
+    for (int j = 0; j < SP_PER; ++j) {
+        const int l = tid + SP_THREADS * j;   // consecutive lanes, consecutive rows: pos_of is read coalesced
+        const long long row = (long long)tile0 + l;
+        if (row >= a.n) break;
+        const int wi = l >> 5;
+        uint32_t word = touched[wi];
+        if (mask && word) {
+            const long long mw = (long long)(tile0 >> 5) + wi;
+            word &= mw < a.sp.mask_words ? mask[mw] : 0u;
+        }
+        srow[a.pos_of[row]] = ((word >> (l & 31)) & 1u) ? acc[l] : __int_as_float(0x7FC00000);
     }
 }
 

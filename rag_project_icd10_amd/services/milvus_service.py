@@ -638,25 +638,37 @@ class MilvusService:
         st = hit[1].stats()
         return [{"field": hit[3], "vocab": int(st["vocab"]), "nnz": int(st["nnz"]), "generation": hit[4], "bytes": int(st["bytes"])}]
 
-    def _sparse_lists(self, index, sp, q_off, q_terms, q_vals, k: int, masks, reweighted: bool):
-        """search_sparse over a batch of any length, SPARSE_MAX_NQ queries per call; host arrays in and out"""
+    def _sparse_lists(self, index, sp, q_off, q_terms, q_vals, k: int, masks, reweighted: bool, grouping=None, group_size: int = 1):
+        """search_sparse over a batch of any length, SPARSE_MAX_NQ queries per call (fewer where the grouping of a grouped call
+        holds fewer); host arrays in and out"""
         q_off = np.asarray(q_off, np.int64)
         nq = len(q_off) - 1
+        step = sp.max_nq if grouping is None else min(sp.max_nq, grouping.max_nq)
         outs = []
-        for s0 in range(0, max(nq, 1), sp.max_nq):
-            s1 = min(nq, s0 + sp.max_nq)
+        for s0 in range(0, max(nq, 1), step):
+            s1 = min(nq, s0 + step)
             a, b = int(q_off[s0]), int(q_off[s1])
             outs.append(index.search_sparse(sp, q_off[s0:s1 + 1] - a, q_terms[a:b], q_vals[a:b], k,
-                                            masks=None if masks is None else masks[s0:s1], reweighted=reweighted))
+                                            masks=None if masks is None else masks[s0:s1], reweighted=reweighted,
+                                            grouping=grouping, group_size=group_size))
         return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
 
-    def search_sparse_batch(self, q_off, q_terms, q_vals, top_k: int = 10, filter=None, as_dicts: bool = False):   # noqa: A002
+    def search_sparse_batch(self, q_off, q_terms, q_vals, top_k: int = 10, filter=None, as_dicts: bool = False,   # noqa: A002
+                            group_by_field: Optional[str] = None, group_size: int = 1):
         """Many sparse queries in CSR form (q_off int64 [nq + 1], q_terms uint32 term ids of the sparse index's vocabulary, q_vals
         float32; at most 64 strictly increasing terms per query) against the store's sparse index. Only rows that share a term
         with the query are hits. filter: a Milvus filter expression, or a list with one expression (or None) per query, through
         the mask cache. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order `search` returns
         hits; with as_dicts a list of `search`-shaped hit lists (`original_score` the sparse inner product). Bad arguments raise
-        ValueError."""
+        ValueError.
+        group_by_field / group_size: as in `search` - the top_k best groups among the hits and the group_size best hit rows of
+        each; the arrays are then [nq, top_k * group_size] and a fifth one follows, the hits' group values'
+        ids; hit dicts carry the group value under metadata[group_by_field]. A filter stays a mask here (also a per-query list):
+        the grouping is the whole store's."""
+        if group_by_field is not None:
+            filter_expr.check_grouping(group_by_field, top_k, group_size)
+        elif group_size != 1:
+            raise ValueError("group_size needs group_by_field")
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 128:
             raise ValueError(f"top_k={top_k!r}: an int in 1 .. 128")
         nq = len(np.asarray(q_off).reshape(-1)) - 1
@@ -676,21 +688,34 @@ class MilvusService:
             masks = self._masks_for(index, filter, nq)
             if all(m is None for m in masks):
                 masks = None
-        adj, raw, ids, levels = self._sparse_lists(index, sp, q_off, np.asarray(q_terms, np.uint32).reshape(-1),
-                                                   np.asarray(q_vals, np.float32).reshape(-1), int(top_k), masks, True)
+        q_terms, q_vals = np.asarray(q_terms, np.uint32).reshape(-1), np.asarray(q_vals, np.float32).reshape(-1)
+        if group_by_field is not None:
+            grouping, values = self._grouping(group_by_field, index, None, None)
+            adj, raw, ids, levels, groups = self._sparse_lists(index, sp, q_off, q_terms, q_vals, int(top_k), masks, True, grouping, int(group_size))
+            if not as_dicts:
+                return adj, raw, ids, levels, groups
+            return [self._hits_to_dicts(adj[q], raw[q], ids[q], (group_by_field, groups[q], values)) for q in range(nq)]
+        adj, raw, ids, levels = self._sparse_lists(index, sp, q_off, q_terms, q_vals, int(top_k), masks, True)
         if not as_dicts:
             return adj, raw, ids, levels
         return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(nq)]
 
-    def search_text(self, text: str, top_k: int = 10, filter: Optional[str] = None) -> List[Dict[str, Any]]:   # noqa: A002
+    def search_text(self, text: str, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002
+                    group_by_field: Optional[str] = None, group_size: int = 1) -> List[Dict[str, Any]]:
         """BM25 full-text search of ONE text over the sparse index's field: `search`-shaped hits, `original_score` the BM25 score,
-        `score` the reweighted one. A text without a term of the vocabulary finds nothing. Bad arguments raise ValueError."""
+        `score` the reweighted one. A text without a term of the vocabulary finds nothing. group_by_field / group_size: as in
+        search_sparse_batch. Bad arguments raise ValueError."""
+        if group_by_field is not None:
+            filter_expr.check_grouping(group_by_field, top_k, group_size)
+        elif group_size != 1:
+            raise ValueError("group_size needs group_by_field")
         if not isinstance(text, str):
             raise ValueError("text: a string")
         if isinstance(filter, (list, tuple)):
             raise ValueError("a list of filters needs a batch: search_sparse_batch")
         _sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
-        return self.search_sparse_batch(*tx.encode_queries([text]), top_k, filter=filter, as_dicts=True)[0]
+        return self.search_sparse_batch(*tx.encode_queries([text]), top_k, filter=filter, as_dicts=True,
+                                        group_by_field=group_by_field, group_size=group_size)[0]
 
     def _hybrid_mixed(self, reqs, ranker, limit: int):
         """hybrid_search_batch with at least one sparse request: the dense requests as ONE search_batch-style sub-search, the
@@ -754,15 +779,109 @@ class MilvusService:
               else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
         return index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, **kw), nq, R
 
-    def hybrid_search_batch(self, reqs, ranker, limit: int = 10, as_dicts: bool = False):
+    @staticmethod
+    def _check_hybrid_grouping(reqs, limit, field, group_size):
+        """the checks of a grouped hybrid search that need no store and no device (ValueError): the grouping arguments against the
+        fused limit and every request's limit (groups times group_size fill at most 128 slots), no `param` band on any request, and
+        ONE expression (or none) on all of them. Returns that expression."""
+        filter_expr.check_grouping(field, limit, group_size)
+        for i, r in enumerate(reqs):
+            if r.radius is not None or r.range_filter is not None:
+                raise ValueError(f"request {i}: radius / range_filter cannot be combined with group_by_field")
+            if int(r.limit) * int(group_size) > filter_expr.MAX_GROUPED_HITS:
+                raise ValueError(f"request {i}: limit * group_size = {int(r.limit) * int(group_size)} exceeds {filter_expr.MAX_GROUPED_HITS} hits "
+                                 f"(limit={r.limit} groups of group_size={group_size})")
+        keys = {None if r.expr is None else filter_expr.compile(r.expr) for r in reqs}
+        if len(keys) != 1:
+            raise ValueError("with group_by_field every request must carry the same expr (or none)")
+        return reqs[0].expr
+
+    def _hybrid_grouped(self, reqs, ranker, limit: int, field: str, group_size: int):
+        """hybrid_search_batch with group_by_field. Dense requests only: search_hybrid with the grouping, on
+        the expression's view with the view's grouping. With a sparse request: the dense side as ONE grouped search on the view,
+        the sparse side as ONE grouped sparse search on the parent under the expression's mask, the raw lists interleaved on the
+        device and fused on the parent with the parent's grouping. Returns ((adj, fused, ids, levels, bits, groups), nq, R, values)."""
+        expr = self._check_hybrid_grouping(reqs, limit, field, group_size)
+        s = int(group_size)
+        index = self._ready_index()
+        if index is None:
+            raise RuntimeError(f"collection {self.collection_name} is empty or missing")
+        dense = [r for r in reqs if r.anns_field == "vector"]
+        sparse = [r for r in reqs if r.anns_field == "sparse"]
+        R = len(reqs)
+        kw = ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
+              else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
+        qd = hybrid.stack_requests(dense) if dense else None
+        sq = [hybrid.sparse_queries(r) for r in sparse]
+        counts = {len(x) for x in sq} | ({int(qd.shape[0])} if dense else set())
+        if len(counts) != 1:
+            raise ValueError("the requests' data must share one number of queries")
+        nq = counts.pop()
+        target, rows, fkey = index, None, None
+        if expr is not None:
+            target, rows = self._filtered_index(expr)
+            if target is not index:
+                fkey = filter_expr.compile(expr)
+        g_parent, values = self._grouping(field, index, None, None)
+        if nq * R > min(index.max_nq, g_parent.max_nq):
+            raise ValueError(f"{nq} queries x {R} requests exceed the grouped batch of {min(index.max_nq, g_parent.max_nq)}")
+        if target is None:   # the expression selects no row: padding
+            kk = limit * s
+            return ((np.full((nq, kk), -np.inf), np.full((nq, kk), -np.inf), np.full((nq, kk), -1, np.int64), np.zeros((nq, kk), np.int32),
+                     np.zeros((nq, kk), np.uint32), np.full((nq, kk), -1, np.int32)), nq, R, values)
+        g_target = g_parent if target is index else self._grouping(field, target, rows, fkey)[0]
+        if not sparse:
+            out = target.search_hybrid(qd, [r.limit for r in reqs], limit, self._fusion_for(target, nq * R), grouping=g_target, group_size=s, **kw)
+            return out, nq, R, values
+        import torch
+        sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        lmax = max(r.limit for r in reqs) * s
+        where = torch.device("cuda", index.device)
+        scores = torch.full((nq, R, lmax), float("-inf"), dtype=torch.float32, device=where)
+        ids = torch.full((nq, R, lmax), -1, dtype=torch.int64, device=where)
+        if dense:   # ONE grouped search over the nq * Rd vectors, on the view with the view's grouping (global ids come back)
+            Rd, ld = len(dense), max(r.limit for r in dense)
+            flat = qd.reshape(nq * Rd, -1) if hasattr(qd, "is_cuda") else np.ascontiguousarray(qd.reshape(nq * Rd, -1))
+            d_raw, d_ids, _lv, _g = target.search_grouped(flat, ld, s, g_target, reweighted=False)
+            d_raw = torch.as_tensor(d_raw).to(where).reshape(nq, Rd, ld * s)
+            d_ids = torch.as_tensor(d_ids).to(where).reshape(nq, Rd, ld * s)
+            for j, at in enumerate(i for i, r in enumerate(reqs) if r.anns_field == "vector"):
+                scores[:, at, :ld * s], ids[:, at, :ld * s] = d_raw[:, j], d_ids[:, j]
+        Rs, ls = len(sparse), max(r.limit for r in sparse)   # ONE grouped sparse call over the nq * Rs queries, on the parent with the mask
+        pairs = []
+        for q in range(nq):
+            for x in sq:
+                pairs.append(tx.encode_query(x[q]) if isinstance(x[q], str) else sparse_text.query_from_dict(x[q], tx.vocab_size))
+        mask = self._filter_mask(index, expr)
+        s_raw, s_ids, _lv, _g = self._sparse_lists(index, sp, *sparse_text.csr_from_pairs(pairs), ls, None if mask is None else [mask] * (nq * Rs),
+                                                   False, g_parent, s)
+        s_raw = torch.from_numpy(s_raw).to(where).reshape(nq, Rs, ls * s)
+        s_ids = torch.from_numpy(s_ids).to(where).reshape(nq, Rs, ls * s)
+        for j, at in enumerate(i for i, r in enumerate(reqs) if r.anns_field == "sparse"):
+            scores[:, at, :ls * s], ids[:, at, :ls * s] = s_raw[:, j], s_ids[:, j]
+        out = index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, grouping=g_parent, group_size=s, **kw)
+        return out, nq, R, values
+
+    def hybrid_search_batch(self, reqs, ranker, limit: int = 10, as_dicts: bool = False, group_by_field: Optional[str] = None,
+                            group_size: int = 1):
         """Milvus's hybrid_search for a batch: reqs is a list of 1 .. 8 hybrid_search.AnnSearchRequest whose data share one shape
         [nq, dim] (request r's vector of every query; numpy arrays, or torch CUDA tensors for device outputs); ranker an RRFRanker
         or WeightedRanker; limit the fused hits per query (1 .. 128). Every request's sub-list is exact, over its own expr's
         selection (through the mask cache; a selection of every row passes no mask) and its own param's radius / range_filter,
         and the lists are fused on the device. Returns (adjusted f64, fused f64, ids i64, levels i32, matched_requests bits), each
         [nq, limit], in the order `search` returns hits (adjusted = fused * level weight, one stable re-sort); with as_dicts a
-        list of hybrid_search-shaped hit lists. Bad arguments raise ValueError before anything is loaded."""
+        list of hybrid_search-shaped hit lists. Bad arguments raise ValueError before anything is loaded.
+        group_by_field / group_size: Milvus's grouping on hybrid_search - every request's limit then counts
+        GROUPS (limit * group_size <= 128), the sub-lists are grouped lists and the fused hits are grouped again: the `limit` best
+        groups' group_size best rows, arrays [nq, limit * group_size] with a sixth one, the hits' group values' ids; hit dicts carry
+        the group value under metadata[group_by_field]. Every request must then carry the same expr (or none) - the dense side runs
+        on that expression's view with the view's grouping - and no `param` band; otherwise ValueError."""
         limit = hybrid.check_requests(reqs, ranker, limit)
+        if group_by_field is not None:
+            out, nq, R, values = self._hybrid_grouped(reqs, ranker, limit, group_by_field, group_size)
+            return self._hybrid_dicts(out, nq, R, limit, (group_by_field, values)) if as_dicts else out
+        if group_size != 1:
+            raise ValueError("group_size needs group_by_field")
         if any(r.anns_field == "sparse" for r in reqs):   # (DESIGN.md section 14; with dense requests only the path below is untouched)
             out, nq, R = self._hybrid_mixed(reqs, ranker, limit)
             return self._hybrid_dicts(out, nq, R, limit) if as_dicts else out
@@ -790,30 +909,37 @@ class MilvusService:
             return out
         return self._hybrid_dicts(out, nq, R, limit)
 
-    def _hybrid_dicts(self, out, nq: int, R: int, limit: int):
-        adj, fused, ids, _levels, bits = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in out]
+    def _hybrid_dicts(self, out, nq: int, R: int, limit: int, group=None):
+        """group: None, or (field, the field's sorted distinct values) of a grouped hybrid search (a sixth array holds the group ids)"""
+        adj, fused, ids, _levels, bits = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in out[:5]]
+        groups = None if group is None else (out[5].cpu().numpy() if hasattr(out[5], "cpu") else out[5])
         res = []
         for qi in range(nq):
-            hits = self._hits_to_dicts(adj[qi], fused[qi], ids[qi])
-            valid = [j for j in range(limit) if ids[qi][j] >= 0]
+            hits = self._hits_to_dicts(adj[qi], fused[qi], ids[qi], None if group is None else (group[0], groups[qi], group[1]))
+            valid = [j for j in range(ids.shape[1]) if ids[qi][j] >= 0]
             for hit, j in zip(hits, valid):
                 hit["fused_score"] = hit.pop("original_score")
                 hit["matched_requests"] = [r for r in range(R) if (int(bits[qi][j]) >> r) & 1]
             res.append(hits)
         return res
 
-    def hybrid_search(self, reqs, ranker, limit: int = 10) -> List[Dict[str, Any]]:
+    def hybrid_search(self, reqs, ranker, limit: int = 10, group_by_field: Optional[str] = None, group_size: int = 1) -> List[Dict[str, Any]]:
         """Milvus's hybrid_search for ONE query: every request's data is one vector. Returns a `search`-shaped hit list whose
         `score` is the reweighted fused score; `fused_score` (the ranker's value) and `matched_requests` (the indices of the
-        requests whose list held the hit) replace `original_score`. Bad arguments raise ValueError."""
+        requests whose list held the hit) replace `original_score`. group_by_field / group_size: as in hybrid_search_batch. Bad
+        arguments raise ValueError."""
         limit = hybrid.check_requests(reqs, ranker, limit)
+        if group_by_field is not None:
+            self._check_hybrid_grouping(reqs, limit, group_by_field, group_size)
+        elif group_size != 1:
+            raise ValueError("group_size needs group_by_field")
         for r in reqs:
             if r.anns_field == "sparse":
                 if isinstance(r.data, (list, tuple)) and len(r.data) != 1:
                     raise ValueError("hybrid_search takes one text per sparse request; hybrid_search_batch takes batches")
             elif np.ndim(r.data) > 2 or (np.ndim(r.data) == 2 and np.shape(r.data)[0] != 1):
                 raise ValueError("hybrid_search takes one vector per request; hybrid_search_batch takes batches")
-        return self.hybrid_search_batch(reqs, ranker, limit, as_dicts=True)[0]
+        return self.hybrid_search_batch(reqs, ranker, limit, as_dicts=True, group_by_field=group_by_field, group_size=group_size)[0]
 
     def _empty_hits(self, query_vectors, k: int, as_dicts: bool):
         nq = 1 if getattr(query_vectors, "ndim", 2) == 1 else int(query_vectors.shape[0])
