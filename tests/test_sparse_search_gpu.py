@@ -1,5 +1,6 @@
 """icd_sparse_search on the device against tests/sparse_oracle.py, bit for bit: ids, raw scores, levels and
-adj. The arithmetic is fully specified, so there is no tolerance. Shapes sit around the kernel's tile (T rows, from the build)."""
+adj. The arithmetic is fully specified, so there is no tolerance. Shapes sit around the kernel's tile (T rows, from the build);
+the shapes around the merge's round (tiles * k keys against the 896 a round takes) are in tests/test_sparse_merge_rounds_gpu.py."""
 import csv
 import ctypes
 import io
