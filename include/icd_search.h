@@ -414,8 +414,23 @@ int icd_fusion_fuse_lists_grouped(icd_index *idx, icd_fusion *fusion, icd_groupi
  * destroyed handle. With queries_on_device = 1 the pairs cannot be read on the host: the call TRUSTS strictly increasing terms
  * (a term >= vocab is skipped, a query is cut at ICD_SPARSE_MAX_QUERY_TERMS pairs; unsorted or repeated terms give sums in
  * another order). With device queries and outputs and no masks the call only enqueues on `stream` (graph-capturable); with masks
- * it is not, for the reason icd_index_search_masked gives. Range bounds, offset and iterator do not exist for a sparse
- * search; grouping is icd_sparse_search_grouped below.
+ * it is not, for the reason icd_index_search_masked gives. Range bounds and the cursor of offset and iterator pages are
+ * icd_sparse_search_range; grouping is icd_sparse_search_grouped below.
+ *
+ * icd_sparse_search_range: icd_index_search_range's band on the sparse ranking, exact. DESIGN.md section 16. Of a query's hits
+ * (the rows that share a term with it, inside its row mask) only those with radius[q] < score <= range_filter[q] (plain float
+ * compares on the canonical sum) that rank strictly behind the cursor (after_scores[q], after_ids[q]) - a smaller score, or equal
+ * score bits and a larger global id - are ranked; the answer is the min(k, hits in the band) best of them, best first, then
+ * padding. Any bound array may be NULL (no such bound); after_scores and after_ids come together. A row without a shared term
+ * is no hit under any band (radius = -inf admits none). reweighted = 1 reweights and re-sorts those k; the band is on the raw
+ * score. With all four bound arrays NULL the call IS icd_sparse_search (the same kernel instantiations, bit for bit); otherwise
+ * one launch of sparse_accumulate_select_kernel<true>, which applies the band before the tile's k best are selected, and
+ * sparse_merge_kernel. bounds_on_device = 0: [nq] host arrays, checked (ICD_ERR_INVALID: a NaN bound, radius >= range_filter)
+ * and packed on the host into the handle's pinned block - the call synchronises; 1: [nq] device arrays, packed by one launch
+ * (a NaN or inverted band there is an empty band: padding). Every check icd_sparse_search makes is made here too, and
+ * ICD_ERR_INVALID when only one of after_scores / after_ids is given; all before the first device call. The bands' staging
+ * (max_nq entries on the device, as many in pinned host memory) belongs to the sparse handle: nothing is allocated in a search.
+ * With device queries, bounds and outputs and no masks the call only enqueues (graph-capturable); with masks it is not.
  */
 typedef struct icd_sparse icd_sparse;
 #define ICD_SPARSE_MAX_QUERY_TERMS 64
@@ -431,6 +446,11 @@ int icd_sparse_stats(icd_sparse *sp, int64_t *out_vocab, int64_t *out_nnz, int64
 int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals,
                       int64_t nq, int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, int32_t reweighted,
                       double *out_adj, float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream);
+int icd_sparse_search_range(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals,
+                            int64_t nq, int32_t k, int32_t queries_on_device, icd_rowmask *const *masks,
+                            const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
+                            int32_t bounds_on_device, int32_t reweighted,
+                            double *out_adj, float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream);
 
 /*
  * Grouped sparse search: group_by_field / group_size on a sparse field. DESIGN.md section 15.

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "icd_fusion_create", "icd_fusion_destroy", "icd_fusion_stats", "icd_index_search_hybrid", "icd_fusion_fuse_lists",
     "icd_sparse_tile_rows", "icd_sparse_pack", "icd_sparse_create", "icd_sparse_destroy", "icd_sparse_stats", "icd_sparse_search",
     "icd_grouping_pair_sparse", "icd_sparse_search_grouped", "icd_index_search_hybrid_grouped", "icd_fusion_fuse_lists_grouped",
+    "icd_sparse_search_range",
 )
 SPARSE_MAX_QUERY_TERMS = 64   # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
@@ -139,6 +140,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_sparse_destroy.argtypes = [vp]
     lib.icd_sparse_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_sparse_search.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
+    lib.icd_sparse_search_range.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_grouping_pair_sparse.argtypes = [vp, vp, vp]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
@@ -709,7 +711,7 @@ class IcdIndex:
         return IcdSparse(self, row_off, terms, vals, int(vocab), int(max_nq), int(max_k))
 
     def search_sparse(self, sp: "IcdSparse", q_off, q_terms, q_vals, k: int, masks=None, reweighted: bool = False, validate: bool = True,
-                      grouping: Optional["IcdGrouping"] = None, group_size: int = 1):
+                      grouping: Optional["IcdGrouping"] = None, group_size: int = 1, radius=None, range_filter=None, after=None):
         """The best k rows by sparse inner product among the rows that share a term with the query (icd_sparse_search). Queries
         in CSR form (q_off int64 [nq + 1], q_terms uint32, q_vals float32; at most 64 strictly increasing terms each): numpy
         arrays - checked by the library, host outputs - or torch CUDA tensors (int64 / int32 holding the uint32 bit patterns /
@@ -722,10 +724,20 @@ class IcdIndex:
         grouping (an IcdGrouping of this index) / group_size: the grouped form (icd_sparse_search_grouped) - the k best GROUPS
         among the hits and the group_size best hit rows of each, outputs [nq, k * group_size] with the hits' group ids as one
         more array at the end, layout and padding (-inf, -1, 0, -1) as search_grouped. Masks are allowed. The first grouped call
-        of a grouping pairs it with the sparse index (one launch, n * 4 bytes the grouping then owns)."""
+        of a grouping pairs it with the sparse index (one launch, n * 4 bytes the grouping then owns).
+        radius / range_filter / after=(scores, ids): search_range's band on the sparse ranking (icd_sparse_search_range) - only hits
+        with radius < score <= range_filter ranked strictly behind the cursor hit; scalars (broadcast) or one value per query
+        (arrays / CUDA tensors; with device queries the bounds are moved to the device). A row without a shared term is no hit
+        under any band. Any bound next to `grouping` is a ValueError; with no bound the call above runs untouched."""
         if self.closed or sp is None or sp.closed:
             raise IcdError(-5, "index or sparse index is closed")
         group_size = _check_group_args(grouping, k, group_size)
+        a_sc, a_id = (None, None) if after is None else after
+        if (a_sc is None) != (a_id is None):
+            raise ValueError("after = (scores, ids): both or neither")
+        banded = radius is not None or range_filter is not None or a_sc is not None
+        if banded and grouping is not None:
+            raise ValueError("radius / range_filter / after cannot be combined with grouping")
         on_dev = _is_torch_tensor(q_off) and q_off.is_cuda
         if on_dev:
             import torch
@@ -762,6 +774,18 @@ class IcdIndex:
                 _check(self._lib, rc)
             return (adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp)
         (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (nq, k), (np.float64, np.float32, np.int64, np.int32))
+        if banded:
+            bounds = [None if v is None else _bound(v, dt, (nq,), on_dev, self.device)   # (kept alive over the call)
+                      for v, dt in ((radius, np.float32), (range_filter, np.float32), (a_sc, np.float32), (a_id, np.int64))]
+            if nq:
+                rc = self._lib.icd_sparse_search_range(
+                    self._h, sp._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k, dev,
+                    None if mask_h is None else mask_h.ctypes.data, *[None if b is None else ptr(b) for b in bounds], dev,
+                    1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
+                if rc == -1:
+                    raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+                _check(self._lib, rc)
+            return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
         if nq:
             rc = self._lib.icd_sparse_search(self._h, sp._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k,
                                              dev, None if mask_h is None else mask_h.ctypes.data, 1 if reweighted else 0,

@@ -60,6 +60,19 @@ static uint32_t host_order_f32(float v) {
     return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
+// One query's host bounds -> BandQ, for an index without a row map (row_map == nullptr in band_pack_kernel's terms): the dense
+// range search off a view and the sparse range search (icd_sparse.hpp) share it.
+static long long band_cut_plain(long long id, long long id_base, long long n) {
+    return id < id_base ? 0 : (id - id_base >= n ? n : id - id_base + 1);
+}
+static BandQ pack_band_host(const RangeBounds &rb, int64_t q, long long cut) {   // cut: read only with a cursor
+    BandQ b;
+    b.lo = rb.radius ? rb.radius[q] : -INFINITY;
+    b.hi = rb.range_filter ? rb.range_filter[q] : INFINITY;
+    b.below = rb.after_scores ? band_below(host_order_f32(rb.after_scores[q]), (uint32_t)cut) : ~0ull;
+    return b;
+}
+
 // Host bounds were validated by check_bands; device bounds are packed as they are.
 static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s, BandArgs *out) {
     out->q = x->band_dev;
@@ -70,17 +83,13 @@ static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s
         return ICD_OK;
     }
     for (int q = 0; q < nq; ++q) {
-        BandQ b;
-        b.lo = rb.radius ? rb.radius[q] : -INFINITY;
-        b.hi = rb.range_filter ? rb.range_filter[q] : INFINITY;
-        b.below = ~0ull;
+        long long cut = 0;
         if (rb.after_scores) {
             const long long id = rb.after_ids[q];
-            long long cut;
             if (x->row_map) cut = std::upper_bound(x->h_row_map.begin(), x->h_row_map.end(), id) - x->h_row_map.begin();
-            else cut = id < x->id_base ? 0 : (id - x->id_base >= x->n ? x->n : id - x->id_base + 1);
-            b.below = band_below(host_order_f32(rb.after_scores[q]), (uint32_t)cut);
+            else cut = band_cut_plain(id, x->id_base, x->n);
         }
+        const BandQ b = pack_band_host(rb, q, cut);
         x->h_band[q] = b;
         if (q < 4) out->inl[q] = b;
     }

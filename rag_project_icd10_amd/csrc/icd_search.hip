@@ -1442,6 +1442,7 @@ struct OwnedHandle {
     uint32_t magic = 0;
     OwnerStamp at;
     std::vector<void *> allocs;
+    std::vector<void *> pinned;   // pinned host blocks (hipHostMalloc), freed with the handle
     size_t bytes = 0;
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -1462,6 +1463,7 @@ template <typename H>
 void free_handle(H *h) {
     if (!h) return;
     for (void *p : h->allocs) hipFree(p);
+    for (void *p : h->pinned) hipHostFree(p);
     h->magic = 0;
     delete h;
 }

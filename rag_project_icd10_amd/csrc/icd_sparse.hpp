@@ -7,8 +7,9 @@
 
 // ---- sparse search (sparse_kernel.hpp) ------------------------------------------------------------------
 // A sparse index belongs to the index it was created for but keeps no pointer into it: handle and identity are compared, never
-// followed. Postings, the staging of a host caller's queries and outputs and the tiles' partial lists are allocated here, never
-// in a search.
+// followed. Postings, the staging of a host caller's queries and outputs, the tiles' partial lists and the bands of a range
+// search (max_nq BandQ on the device, and a pinned host block host bounds are packed in) are allocated
+// here, never in a search.
 struct icd_sparse : OwnedHandle {
     static constexpr uint32_t MAGIC = 0x1CD5BA25u;
     static constexpr const char *NOUN = "sparse index";
@@ -18,6 +19,7 @@ struct icd_sparse : OwnedHandle {
     long long *q_off = nullptr; uint32_t *q_terms = nullptr; float *q_vals = nullptr;         // a host caller's queries: [max_nq + 1], [max_nq][64] each
     icd::u64 *part = nullptr;                                                                  // [tiles][max_nq][max_k] keys, best first
     double *o_adj = nullptr; float *o_raw = nullptr; long long *o_ids = nullptr; int *o_lv = nullptr;   // [max_nq][max_k] a host caller's outputs
+    BandQ *band_dev = nullptr, *h_band = nullptr;                                              // [max_nq] each; h_band pinned host memory
     std::mutex mu;
 };
 
@@ -66,13 +68,17 @@ int icd_sparse_create(icd_index *idx, const int64_t *row_off, const uint32_t *te
     SP_TRY(sp->alloc(&sp->q_off, (size_t)max_nq + 1)); SP_TRY(sp->alloc(&sp->q_terms, nt)); SP_TRY(sp->alloc(&sp->q_vals, nt));
     SP_TRY(sp->alloc(&sp->part, np_));
     SP_TRY(sp->alloc(&sp->o_adj, no)); SP_TRY(sp->alloc(&sp->o_raw, no)); SP_TRY(sp->alloc(&sp->o_ids, no)); SP_TRY(sp->alloc(&sp->o_lv, no));
+    SP_TRY(sp->alloc(&sp->band_dev, (size_t)max_nq));
+    SP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sp->h_band), (size_t)max_nq * sizeof(BandQ), hipHostMallocDefault));
+    sp->pinned.push_back(sp->h_band);
     SP_TRY(hipMemcpy(sp->post_off, h_off.data(), ((size_t)vocab + 1) * 8, hipMemcpyHostToDevice));
     if (nnz) {
         SP_TRY(hipMemcpy(sp->post_row, h_row.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
         SP_TRY(hipMemcpy(sp->post_val, h_val.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
     }
 #undef SP_TRY
-    sp->bytes = ((size_t)vocab + 1) * 8 + (size_t)nnz * 8 + ((size_t)max_nq + 1) * 8 + nt * 8 + np_ * 8 + no * (8 + 4 + 8 + 4);
+    sp->bytes = ((size_t)vocab + 1) * 8 + (size_t)nnz * 8 + ((size_t)max_nq + 1) * 8 + nt * 8 + np_ * 8 + no * (8 + 4 + 8 + 4) +
+                (size_t)max_nq * sizeof(BandQ);
     *out = sp;
     return ICD_OK;
 }
@@ -87,9 +93,12 @@ int icd_sparse_stats(icd_sparse *sp, int64_t *out_vocab, int64_t *out_nnz, int64
     return ICD_OK;
 }
 
-int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals, int64_t nq,
-                      int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, int32_t reweighted, double *out_adj, float *out_raw,
-                      int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
+}  // extern "C"
+
+// icd_sparse_search and icd_sparse_search_range: rb = nullptr is the search without a band, through the BAND = false kernel.
+static int sparse_search_lists(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals, int64_t nq,
+                               int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, const RangeBounds *rb, int32_t reweighted,
+                               double *out_adj, float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
     // every check comes before the first device call
     if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
     if (!valid_handle(sp)) return fail(ICD_ERR_STATE, "invalid sparse index handle");
@@ -100,6 +109,11 @@ int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, cons
     if (k > sp->max_k) return fail(ICD_ERR_INVALID, "k=%d exceeds the sparse index's max_k=%d", k, sp->max_k);
     if (nq < 0 || nq > sp->max_nq) return fail(ICD_ERR_INVALID, "nq=%lld exceeds the sparse index's max_nq=%d", (long long)nq, sp->max_nq);
     if (!out_raw || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (rb) {
+        if ((rb->after_scores == nullptr) != (rb->after_ids == nullptr))
+            return fail(ICD_ERR_INVALID, "after_scores and after_ids: both or neither (a cursor is a hit's score AND id)");
+        if ((rc = check_bands(*rb, nq, "query"))) return rc;
+    }
     bool any_mask = false;
     if (masks && (rc = check_masks(idx, masks, nq, "masked sparse search", &any_mask))) return rc;
     if (nq == 0) return ICD_OK;
@@ -116,7 +130,8 @@ int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, cons
     HIP_TRY(hipSetDevice(idx->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
-    if ((rc = check_capture(s, !queries_on_device || !out_on_device, false, any_mask))) return rc;
+    const bool host_bands = rb && !rb->on_device;
+    if ((rc = check_capture(s, !queries_on_device || !out_on_device, host_bands, any_mask))) return rc;
     // a masked call reads section 12's table of the index: it holds the index's mutex from the table's fill to its last launch, as
     // every masked dense search does (an unmasked call touches nothing of the index's workspace and takes only its own)
     std::unique_lock<std::mutex> table(idx->mu, std::defer_lock);
@@ -138,7 +153,20 @@ int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, cons
     a.masks = any_mask ? idx->mask_dev : nullptr;
     a.mask_words = rowmask_tile_words(idx->n);
     a.tiles = sp->tiles; a.nq = (int)nq; a.k = k; a.part = sp->part;
-    hipLaunchKernelGGL(sparse_accumulate_select_kernel, dim3((unsigned)(nq * sp->tiles)), dim3(SP_THREADS), 0, s, a);
+    if (rb) {   // the bounds -> BandQ (a sparse index has no views: row_map = nullptr), then the BAND = true form
+        if (rb->on_device) {
+            hipLaunchKernelGGL(band_pack_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, rb->radius, rb->range_filter, rb->after_scores,
+                               rb->after_ids, (int)nq, (const long long *)nullptr, (long long)idx->n, (long long)idx->id_base, sp->band_dev);
+            HIP_TRY(hipGetLastError());
+        } else {
+            for (int64_t q = 0; q < nq; ++q)
+                sp->h_band[q] = pack_band_host(*rb, q, rb->after_ids ? band_cut_plain(rb->after_ids[q], idx->id_base, idx->n) : 0);
+            HIP_TRY(hipMemcpyAsync(sp->band_dev, sp->h_band, (size_t)nq * sizeof(BandQ), hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(sparse_accumulate_select_kernel<true>, dim3((unsigned)(nq * sp->tiles)), dim3(SP_THREADS), 0, s, a, SparseBands<true>{sp->band_dev});
+    } else {
+        hipLaunchKernelGGL(sparse_accumulate_select_kernel<false>, dim3((unsigned)(nq * sp->tiles)), dim3(SP_THREADS), 0, s, a, SparseBands<false>{});
+    }
     HIP_TRY(hipGetLastError());
     SparseMergeArgs m{};
     m.part = sp->part; m.tiles = sp->tiles; m.nq = (int)nq; m.k = k; m.reweighted = reweighted ? 1 : 0;
@@ -150,7 +178,27 @@ int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, cons
     if ((rc = hc.copy_back({{reweighted ? out_adj : nullptr, m.out_adj, 8}, {out_raw, m.out_raw, 4}, {out_ids, m.out_ids, 8}, {out_levels, m.out_levels, 4}},
                            (size_t)nq * k)))
         return rc;
-    return hc.finish();
+    return hc.finish(host_bands);   // (host bounds went through the pinned block: the next call may repack it)
+}
+
+extern "C" {
+
+int icd_sparse_search(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals, int64_t nq,
+                      int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, int32_t reweighted, double *out_adj, float *out_raw,
+                      int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
+    return sparse_search_lists(idx, sp, q_off, q_terms, q_vals, nq, k, queries_on_device, masks, nullptr, reweighted, out_adj, out_raw, out_ids,
+                               out_levels, out_on_device, stream);
+}
+
+// (no bound at all IS icd_sparse_search: the same kernel instantiations, nothing packed)
+int icd_sparse_search_range(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals, int64_t nq,
+                            int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, const float *radius, const float *range_filter,
+                            const float *after_scores, const int64_t *after_ids, int32_t bounds_on_device, int32_t reweighted, double *out_adj,
+                            float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
+    const RangeBounds rb{radius, range_filter, after_scores, reinterpret_cast<const long long *>(after_ids), bounds_on_device != 0};
+    const bool any = radius || range_filter || after_scores || after_ids;
+    return sparse_search_lists(idx, sp, q_off, q_terms, q_vals, nq, k, queries_on_device, masks, any ? &rb : nullptr, reweighted, out_adj, out_raw,
+                               out_ids, out_levels, out_on_device, stream);
 }
 
 // ---- grouped sparse search -------------------------------------------------------------------------------

@@ -10,7 +10,8 @@
 // lanes stride over the term's postings inside the tile (found by a binary search per bound, all terms' bounds searched at once)
 // and do acc[row] = acc[row] + q_t * d_t - a plain LDS read-modify-write (rows are distinct within a term), product and sum
 // rounded separately (contract off). That order IS the canonical summation order. The touched rows that pass the query's row
-// mask are the candidates; lane l owns rows l, l + 256, ... of the tile (conflict-free LDS reads), one bit each. The k-th best
+// mask - and, in the BAND = true form (section 16), lie inside the query's band - are the candidates; lane l owns rows l, l + 256,
+// ... of the tile (conflict-free LDS reads), one bit each. The k-th best
 // 64-bit key (make_key: score desc, row asc) is found by a radix select over the keys' bytes, most significant first - an LDS
 // histogram per byte, at most eight passes, correct for any number of candidates up to SP_TILE - and the at most k keys at or
 // above it are ranked by counting. Output: [tile][query][k] keys best first, 0 = padding.
@@ -98,7 +99,19 @@ __device__ __forceinline__ void sparse_accumulate_tile(const SparseArgs &a, int 
     }
 }
 
-__global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(const SparseArgs a) {
+// The bands of a banded launch's queries: an argument of the BAND = true form only - the BAND = false form
+// takes SparseArgs as it always has.
+template <bool BAND>
+struct SparseBands {};
+template <>
+struct SparseBands<true> {
+    const BandQ *q;   // [nq] in device memory (topk_select.hpp)
+};
+
+// BAND: only touched rows inside the query's band (lo < score <= hi, ranked strictly behind the cursor) are candidates: the band is
+// applied where `mine` is built, so the radix select, the counting rank and the output see band candidates only.
+template <bool BAND>
+__global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(const SparseArgs a, const SparseBands<BAND> bands) {
     __shared__ float acc[SP_TILE];
     __shared__ uint32_t touched[SP_TILE / 32];
     __shared__ uint32_t hist[256];
@@ -125,6 +138,17 @@ __global__ __launch_bounds__(SP_THREADS) void sparse_accumulate_select_kernel(co
             word &= mw < a.mask_words ? mask[mw] : 0u;
         }
         mine |= ((word >> (tid & 31)) & 1u) << j;
+    }
+    if constexpr (BAND) {   // the query's band, uniform across the work-group: loaded once; lo < NaN is false, a NaN sum is no hit
+        const BandQ b = bands.q[q];
+        uint32_t in = 0;
+        for (uint32_t m = mine; m; m &= m - 1) {
+            const int j = __ffs((int)m) - 1;
+            const int l = tid + SP_THREADS * j;
+            const float v = acc[l];
+            in |= (uint32_t)((b.lo < v) & band_under(v, tile0 + (uint32_t)l, b.hi, b.below)) << j;
+        }
+        mine = in;
     }
     if (mine) atomicAdd(&sh_cnt, __popc(mine));
     __syncthreads();

@@ -654,7 +654,7 @@ class MilvusService:
         return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
 
     def search_sparse_batch(self, q_off, q_terms, q_vals, top_k: int = 10, filter=None, as_dicts: bool = False,   # noqa: A002
-                            group_by_field: Optional[str] = None, group_size: int = 1):
+                            group_by_field: Optional[str] = None, group_size: int = 1, radius=None, range_filter=None, offset: int = 0):
         """Many sparse queries in CSR form (q_off int64 [nq + 1], q_terms uint32 term ids of the sparse index's vocabulary, q_vals
         float32; at most 64 strictly increasing terms per query) against the store's sparse index. Only rows that share a term
         with the query are hits. filter: a Milvus filter expression, or a list with one expression (or None) per query, through
@@ -664,7 +664,11 @@ class MilvusService:
         group_by_field / group_size: as in `search` - the top_k best groups among the hits and the group_size best hit rows of
         each; the arrays are then [nq, top_k * group_size] and a fifth one follows, the hits' group values'
         ids; hit dicts carry the group value under metadata[group_by_field]. A filter stays a mask here (also a per-query list):
-        the grouping is the whole store's."""
+        the grouping is the whole store's.
+        radius / range_filter / offset: as in `search`, on the sparse ranking - only hits with radius <
+        score <= range_filter are ranked, the hits of ranks offset .. offset + top_k of that ranking are returned, then re-sorted
+        by adjusted score. A bound is one number for every query or an array with one number per query. A row that shares no
+        term with the query is no hit under any band. A bad bound, or one next to group_by_field, raises ValueError."""
         if group_by_field is not None:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
@@ -674,6 +678,11 @@ class MilvusService:
         nq = len(np.asarray(q_off).reshape(-1)) - 1
         if nq < 0:
             raise ValueError("q_off holds nq + 1 offsets")
+        radius, range_filter = range_search.check_bounds_per_query(radius, range_filter, nq)
+        offset = range_search.check_offset(offset, top_k)
+        banded = radius is not None or range_filter is not None or offset > 0
+        if banded and group_by_field is not None:
+            raise ValueError("radius / range_filter / offset cannot be combined with group_by_field")
         if isinstance(filter, (list, tuple)) and len(filter) != nq:
             raise ValueError(f"filter holds {len(filter)} expressions for {nq} queries")
         for e in (filter if isinstance(filter, (list, tuple)) else [filter]):
@@ -695,16 +704,25 @@ class MilvusService:
             if not as_dicts:
                 return adj, raw, ids, levels, groups
             return [self._hits_to_dicts(adj[q], raw[q], ids[q], (group_by_field, groups[q], values)) for q in range(nq)]
-        adj, raw, ids, levels = self._sparse_lists(index, sp, q_off, q_terms, q_vals, int(top_k), masks, True)
+        if banded and nq > 0:
+            band = range_search.SparseBandIndex(index, sp, masks)
+            adj, raw, ids, levels = range_search.search_band(band, (np.asarray(q_off, np.int64).reshape(-1), q_terms, q_vals), int(top_k),
+                                                             radius, range_filter, offset)
+        else:
+            adj, raw, ids, levels = self._sparse_lists(index, sp, q_off, q_terms, q_vals, int(top_k), masks, True)
         if not as_dicts:
             return adj, raw, ids, levels
         return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(nq)]
 
     def search_text(self, text: str, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002
-                    group_by_field: Optional[str] = None, group_size: int = 1) -> List[Dict[str, Any]]:
+                    group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
+                    range_filter: Optional[float] = None, offset: int = 0,
+                    search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
         """BM25 full-text search of ONE text over the sparse index's field: `search`-shaped hits, `original_score` the BM25 score,
         `score` the reweighted one. A text without a term of the vocabulary finds nothing. group_by_field / group_size: as in
-        search_sparse_batch. Bad arguments raise ValueError."""
+        search_sparse_batch. radius / range_filter (also search_params={"params": {...}}) / offset: as in `search`, on the BM25
+        score - a score floor, a ceiling to look under a crowd of titles that share a common term, a window deeper than 128.
+        Bad arguments, or a bound next to group_by_field, raise ValueError."""
         if group_by_field is not None:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
@@ -713,9 +731,40 @@ class MilvusService:
             raise ValueError("text: a string")
         if isinstance(filter, (list, tuple)):
             raise ValueError("a list of filters needs a batch: search_sparse_batch")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 128:
+            raise ValueError(f"top_k={top_k!r}: an int in 1 .. 128")
+        radius, range_filter, offset, _banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         _sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
         return self.search_sparse_batch(*tx.encode_queries([text]), top_k, filter=filter, as_dicts=True,
-                                        group_by_field=group_by_field, group_size=group_size)[0]
+                                        group_by_field=group_by_field, group_size=group_size, radius=radius, range_filter=range_filter,
+                                        offset=offset)[0]
+
+    def search_text_iterator(self, text: str, batch_size: int = 10, limit: int = -1, filter: Optional[str] = None,   # noqa: A002
+                             radius: Optional[float] = None, range_filter: Optional[float] = None,
+                             search_params: Optional[Dict[str, Any]] = None) -> "range_search.SearchIterator":
+        """search_iterator over the BM25 ranking of ONE text: next() returns the following batch_size hits
+        of the text's hit ranking (inside the band, inside the filter's row mask) as a `search_text`-shaped list, [] when
+        exhausted or after `limit` hits. Pages are disjoint and exact at any depth; batch_size <= 128. The iterator keeps the
+        index, the sparse index, the mask and the store generation it started on: next() raises RuntimeError after the store
+        changed. A text without a term of the vocabulary gives an exhausted iterator. Bad arguments raise ValueError."""
+        radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
+        if not isinstance(text, str):
+            raise ValueError("text: a string")
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("search_text_iterator takes one filter expression")
+        if filter is not None:
+            filter_expr.compile(filter)
+        band, query = None, None
+        if self.client is not None and self.client.exists() and self._ready_index() is not None:
+            sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+            index = self._index
+            query = tx.encode_queries([text])
+            mask = self._filter_mask(index, filter)
+            if int(query[0][-1]) > 0 and (mask is None or mask.rows > 0):
+                band = range_search.SparseBandIndex(index, sp, mask)
+        client = self.client
+        return range_search.SearchIterator(band, query, batch_size, limit, radius, range_filter, self._hits_to_dicts,
+                                           lambda: (id(self.client), None if client is None else (client.generation, client.count)))
 
     def _hybrid_mixed(self, reqs, ranker, limit: int):
         """hybrid_search_batch with at least one sparse request: the dense requests as ONE search_batch-style sub-search, the

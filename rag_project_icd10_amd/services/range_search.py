@@ -118,6 +118,68 @@ class MaskedIndex:
         return self.index.search_masked(queries, k, self.masks, **kw)
 
 
+class SparseBandIndex:
+    """An (index, sparse index, masks) triple with an index's band-search surface: search_range runs
+    IcdIndex.search_sparse with the band, its `queries` are the CSR triple (q_off, q_terms, q_vals) of host arrays. masks: None,
+    ONE IcdRowMask for every query, or one entry (IcdRowMask or None) per query. A batch longer than the sparse index's max_nq
+    is sent in pieces, per-query bounds sliced with it. Holds references to the sparse index and the masks it pages over."""
+
+    def __init__(self, index, sparse, masks=None):
+        self.index, self.sparse, self.masks = index, sparse, masks
+
+    @property
+    def max_k(self) -> int:
+        return min(int(self.index.max_k), int(self.sparse.max_k))
+
+    @property
+    def closed(self) -> bool:
+        ms = self.masks if isinstance(self.masks, (list, tuple)) else [self.masks]
+        return self.index.closed or self.sparse.closed or any(m is not None and m.closed for m in ms)
+
+    def search_range(self, queries, k, *, radius=None, range_filter=None, after=None, reweighted: bool = True):
+        q_off, q_terms, q_vals = queries
+        q_off = np.asarray(q_off, np.int64).reshape(-1)
+        nq, step = len(q_off) - 1, int(self.sparse.max_nq)
+        if nq <= step:
+            return self.index.search_sparse(self.sparse, q_off, q_terms, q_vals, k, masks=self.masks, reweighted=reweighted,
+                                            radius=radius, range_filter=range_filter, after=after)
+        per_query = isinstance(self.masks, (list, tuple))
+
+        def part(v, s0, s1):   # a per-query bound's slice (a scalar serves every piece)
+            return v if v is None or np.ndim(v) == 0 or np.size(v) == 1 else np.asarray(v).reshape(-1)[s0:s1]
+        outs = []
+        for s0 in range(0, nq, step):
+            s1 = min(nq, s0 + step)
+            a, b = int(q_off[s0]), int(q_off[s1])
+            outs.append(self.index.search_sparse(
+                self.sparse, q_off[s0:s1 + 1] - a, q_terms[a:b], q_vals[a:b], k, masks=self.masks[s0:s1] if per_query else self.masks,
+                reweighted=reweighted, radius=part(radius, s0, s1), range_filter=part(range_filter, s0, s1),
+                after=None if after is None else (part(after[0], s0, s1), part(after[1], s0, s1))))
+        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+
+
+def check_bounds_per_query(radius, range_filter, nq: int, search_params: Optional[Dict[str, Any]] = None):
+    """check_bounds for bounds that may hold one value PER QUERY (arrays of nq numbers): every query's pair goes through
+    check_bounds. -> (radius, range_filter), each None, a float, or a float32 array [nq]."""
+    def scalar(v):
+        return v is None or np.ndim(v) == 0
+    if scalar(radius) and scalar(range_filter):
+        return check_bounds(radius, range_filter, search_params)
+    if search_params is not None:
+        raise ValueError("per-query bounds are given as radius / range_filter arrays, not through search_params")
+    cols = []
+    for name, v in (("radius", radius), ("range_filter", range_filter)):
+        if not scalar(v):
+            v = _host(v).reshape(-1)
+            if len(v) != nq:
+                raise ValueError(f"{name} holds {len(v)} values for {nq} queries")
+            v = [x.item() if isinstance(x, np.generic) else x for x in v]
+        cols.append(v)
+    pairs = [check_bounds(cols[0] if scalar(cols[0]) else cols[0][q], cols[1] if scalar(cols[1]) else cols[1][q]) for q in range(nq)]
+    return tuple(None if cols[i] is None else (pairs[0][i] if scalar(cols[i]) and pairs else np.array([p[i] for p in pairs], np.float32))
+                 for i in range(2))
+
+
 def _band_index(index):
     """an index, a view, or the pair (index, masks) -> the object whose search_range serves it"""
     return MaskedIndex(*index) if isinstance(index, tuple) else index
@@ -157,7 +219,8 @@ class SearchIterator:
     """pymilvus's iterator surface: next() -> a `search`-shaped hit list of up to batch_size hits ([] when exhausted), close().
     Page i + 1 is the band search behind the raw-order LAST hit of page i, so pages are disjoint and their raw-order concatenation
     is the band's full ranking; every page is handed out re-sorted by adjusted score like any hit list. The iterator pins the
-    index (or filter view, or the pair (index, mask) of a masked search) and the store generation it started on: after a mutation
+    index (or filter view, or the pair (index, mask) of a masked search, or the SparseBandIndex of a sparse search - the query
+    is then the CSR triple of ONE query) and the store generation it started on: after a mutation
     of the store next() raises RuntimeError instead of paging through two different corpora. One launch per next() at
     batch_size <= 16."""
 
@@ -171,7 +234,12 @@ class SearchIterator:
         if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or (limit < 0 and limit != -1):
             raise ValueError("limit must be -1 (no limit) or a non-negative integer")
         self._index = index
-        self._q = None if index is None else np.ascontiguousarray(query_vector, dtype=np.float32).reshape(1, -1)
+        if index is None:
+            self._q = None
+        elif isinstance(query_vector, tuple):   # ONE sparse query as its CSR triple (q_off, q_terms, q_vals): SparseBandIndex
+            self._q = query_vector
+        else:
+            self._q = np.ascontiguousarray(query_vector, dtype=np.float32).reshape(1, -1)
         self._batch, self._left = int(batch_size), (None if limit == -1 else int(limit))
         self._radius, self._range_filter = radius, range_filter
         self._to_hits, self._generation_of = to_hits, generation_of
