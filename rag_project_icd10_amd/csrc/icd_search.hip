@@ -1573,8 +1573,9 @@ int icd_index_create_view(icd_index *parent, const int64_t *rows, int64_t n_rows
     for (int64_t i = 0; i < n_rows; ++i) {
         if (map[i] < 0 || map[i] >= parent->n) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld outside the parent's [0, %lld)", (long long)i, map[i], (long long)parent->n);
         if (i > 0 && map[i] <= map[i - 1]) return fail(ICD_ERR_INVALID, "rows[%lld]=%lld: row ids must be strictly increasing", (long long)i, map[i]);
-        map[i] += parent->id_base;
     }
+    // (behind the check, not inside it: rows[i] was compared with rows[i - 1] + id_base, and no view of an index with an id_base could be made)
+    for (int64_t i = 0; i < n_rows; ++i) map[i] += parent->id_base;
     long long *dmap = nullptr;
     HIP_TRY(dmalloc(&dmap, (size_t)n_rows));
     hipError_t e = hipMemcpy(dmap, map.data(), (size_t)n_rows * sizeof(long long), hipMemcpyHostToDevice);

@@ -25,7 +25,11 @@ def as_bool(mask, n):
 def restrict(scores, ids, mask, id_base=0):
     """one query's ranking restricted to its mask: (scores, ids) of the kept positions, order unchanged"""
     ids = np.asarray(ids, np.int64)
-    keep = as_bool(mask, len(ids))[ids - id_base]
+    m = None if mask is None else np.asarray(mask)
+    if m is not None and m.dtype == bool:   # one entry per ROW of the index: a ranking that left NaN rows out is shorter than that
+        keep = m[ids - id_base]
+    else:
+        keep = as_bool(mask, len(ids))[ids - id_base]
     return np.asarray(scores, np.float32)[keep], ids[keep]
 
 
@@ -36,17 +40,17 @@ def _per_query(v, q):
     return v.reshape(-1)[q] if v.size > 1 else v.reshape(-1)[0]
 
 
-def masked_batch(scores, ids, levels, masks, k, radius=None, range_filter=None, after=None, offset=0):
-    """a batch: masks is one entry per query (None, boolean array or row list); bounds are None, scalars or one value per query;
-    after = (scores [nq], ids [nq]) or None. Returns ((raw, ids, levels) in raw order, (adj, raw, ids, levels) reweighted),
+def masked_batch(scores, ids, levels, masks, k, radius=None, range_filter=None, after=None, offset=0, id_base=0):
+    """a batch: masks is one entry per query (None, boolean array or row list, over ROWS: id - id_base); bounds are None, scalars
+    or one value per query; after = (scores [nq], ids [nq]) or None. Returns ((raw, ids, levels) in raw order, (adj, raw, ids, levels) reweighted),
     each [nq, k], padded (-inf, -1, level 0)."""
     nq = len(scores)
     assert len(masks) == nq
     raws, adjs = [], []
     for q in range(nq):
-        s, i = restrict(scores[q], ids[q], masks[q])
+        s, i = restrict(scores[q], ids[q], masks[q], id_base)
         a = None if after is None else (_per_query(after[0], q), _per_query(after[1], q))
-        r, a2 = band_query(s, i, levels, k, _per_query(radius, q), _per_query(range_filter, q), a, offset)
+        r, a2 = band_query(s, i, levels, k, _per_query(radius, q), _per_query(range_filter, q), a, offset, id_base)
         raws.append(r)
         adjs.append(a2)
     return tuple(np.stack([r[j] for r in raws]) for j in range(3)), tuple(np.stack([a[j] for a in adjs]) for j in range(4))

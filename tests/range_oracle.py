@@ -38,9 +38,9 @@ def reweight(raw, ids, levels_of_hits):
     return o_adj, o_raw, o_ids, o_lv
 
 
-def band_query(scores, ids, levels, k, radius=None, range_filter=None, after=None, offset=0):
+def band_query(scores, ids, levels, k, radius=None, range_filter=None, after=None, offset=0, id_base=0):
     """one query: ((raw, ids, levels) in raw order, (adj, raw, ids, levels) reweighted), each of length k, padded. `ids` are the
-    ids searches return (global); levels is indexed by them."""
+    ids searches return (global: id_base + row; on a view the parent's); levels is indexed by id - id_base."""
     scores = np.asarray(scores, np.float32)
     ids = np.asarray(ids, np.int64)
     pos = np.nonzero(in_band(scores, ids, radius, range_filter, after))[0][offset:offset + k]
@@ -48,7 +48,7 @@ def band_query(scores, ids, levels, k, radius=None, range_filter=None, after=Non
     rid = np.full(k, -1, np.int64)
     lv = np.zeros(k, np.int32)
     raw[:len(pos)], rid[:len(pos)] = scores[pos], ids[pos]
-    lv[:len(pos)] = np.asarray(levels)[ids[pos]]
+    lv[:len(pos)] = np.asarray(levels)[ids[pos] - id_base]
     return (raw, rid, lv), reweight(raw, rid, lv)
 
 
@@ -59,13 +59,13 @@ def _per_query(v, q):
     return v.reshape(-1)[q] if v.size > 1 else v.reshape(-1)[0]
 
 
-def band_batch(scores, ids, levels, k, radius=None, range_filter=None, after=None, offset=0):
+def band_batch(scores, ids, levels, k, radius=None, range_filter=None, after=None, offset=0, id_base=0):
     """a batch: bounds are None, scalars or one value per query; after = (scores [nq], ids [nq]) or None"""
     nq = len(scores)
     raws, adjs = [], []
     for q in range(nq):
         a = None if after is None else (_per_query(after[0], q), _per_query(after[1], q))
-        r, a2 = band_query(scores[q], ids[q], levels, k, _per_query(radius, q), _per_query(range_filter, q), a, offset)
+        r, a2 = band_query(scores[q], ids[q], levels, k, _per_query(radius, q), _per_query(range_filter, q), a, offset, id_base)
         raws.append(r)
         adjs.append(a2)
     return tuple(np.stack([r[i] for r in raws]) for i in range(3)), tuple(np.stack([a[i] for a in adjs]) for i in range(4))

@@ -134,3 +134,28 @@ def test_native_symbols_of_the_grouping_search():
     lib = _native.load_library()
     assert lib.icd_abi_version() == 6 and hasattr(lib, "icd_index_search_grouped")
     assert hasattr(_native.IcdIndex, "grouping") and hasattr(_native.IcdIndex, "search_grouped")
+
+
+@pytest.mark.parametrize("id_base", [1000, 2**32 + 12345])
+def test_a_ranking_shifted_by_id_base_gives_the_same_outputs_with_the_ids_shifted(oracle, id_base):
+    n = 40
+    rng = np.random.default_rng(6)
+    scores = rng.integers(0, 6, (5, n)).astype(np.float32) / 4
+    levels = rng.integers(1, 4, n).astype(np.int32)
+    ids = np.stack([np.array(sorted(range(n), key=lambda i: (-float(r[i]), i)), np.int64) for r in scores])
+    ranked = np.take_along_axis(scores, ids, 1)
+    shift = lambda a: np.where(a >= 0, a + id_base, a)
+    for group_of in (np.arange(n) // 5, (np.arange(n) * 7) % 3, np.arange(n)):
+        for k, s in ((1, 1), (3, 2), (10, 3), (2, 40), (40, 1)):
+            want = expected(oracle, Ranking(ranked, ids, group_of), levels, k, s)
+            got = expected(oracle, Ranking(ranked, ids + id_base, group_of, id_base=id_base), levels, k, s, id_base=id_base)
+            for j, (g, w) in enumerate(zip(got[0] + got[1], want[0] + want[1])):
+                assert g.dtype == w.dtype and g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes(), (k, s, j)
+    # a view: the view's own ranking (rows of the view, no base) through its row map, then the parent's id_base
+    rows = np.arange(0, 2 * n, 2)
+    plevels = rng.integers(1, 4, 2 * n).astype(np.int32)
+    rk = Ranking(ranked, ids, np.arange(n) // 5)
+    want = expected(oracle, rk, plevels, 3, 2, row_map=rows)
+    got = expected(oracle, rk, plevels, 3, 2, row_map=rows, id_base=id_base)
+    for j, (g, w) in enumerate(zip(got[0] + got[1], want[0] + want[1])):
+        assert g.dtype == w.dtype and g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes(), j

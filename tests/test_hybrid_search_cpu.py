@@ -256,3 +256,31 @@ def test_hybrid_query_endpoint_argument_checks():
     finally:
         appmod.install_services(None, None, None)
     assert math.isclose(1.0 / 61, 1.0 / (60.0 + 0 + 1))
+
+
+@pytest.mark.parametrize("id_base", [1000, 2**32 + 12345])
+@pytest.mark.parametrize("ranker,kw", [("rrf", {}), ("weighted", {"weights": [1.0, 0.5, 0.25], "norm": "none"}),
+                                       ("weighted", {"weights": [0.9, 0.8, 0.7], "norm": "cosine"})])
+def test_a_ranking_shifted_by_id_base_gives_the_same_outputs_with_the_ids_shifted(ranker, kw, id_base):
+    corpus, pool, levels, s_all, i_all = _tiny()
+    n = len(corpus)
+    rows = np.arange(n)
+    R, limits = 3, [7, 64, 1]
+    sel = np.array([[(4 * q + r) % len(pool) for r in range(R)] for q in range(6)])
+    masks = [[None if (q + r) % 3 else rows % 5 == r for r in range(R)] for q in range(6)]   # masks stay over ROWS
+    lo = np.full((6, R), -np.inf, np.float32)
+    lo[:, 1] = s_all[sel[:, 1], 30]
+    shift = lambda a: np.where(a >= 0, a + id_base, a)
+    for k in (5, 128):
+        for extra in (dict(), dict(masks=masks), dict(masks=masks, radius=lo)):
+            want = hybrid_batch(s_all, i_all, levels, sel, limits, k, ranker, **kw, **extra)
+            got = hybrid_batch(s_all, i_all + id_base, levels, sel, limits, k, ranker, id_base=id_base, **kw, **extra)
+            for j, (g, w) in enumerate(zip(got[0] + got[1], want[0] + want[1])):
+                assert g.dtype == w.dtype and g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes(), (k, sorted(extra), j)
+    lists = [sub_list(s_all[p], i_all[p], 10) for p in (0, 1)]
+    moved = [(s, i + id_base) for s, i in lists]
+    kw2 = {**kw, "weights": kw["weights"][:2]} if kw else {}
+    want = fuse_query(lists, levels, 10, ranker, **kw2)
+    got = fuse_query(moved, levels, 10, ranker, id_base=id_base, **kw2)
+    for g, w in zip(got[0] + got[1], want[0] + want[1]):
+        assert g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes()

@@ -191,3 +191,24 @@ def test_query_endpoint_rejects_a_bad_filter_mode():
             assert client.get("/stats").json()["filter_masks"] == mil.filter_masks()
     finally:
         appmod.install_services(None, None, None)
+
+
+@pytest.mark.parametrize("id_base", [1000, 2**32 + 12345])
+def test_a_ranking_shifted_by_id_base_gives_the_same_outputs_with_the_ids_shifted(id_base):
+    corpus, q, levels, s_all, i_all = _tiny()
+    n, nq = corpus.shape[0], q.shape[0]
+    rows = np.arange(n)
+    sels = [None, rows % 7 == 3, rows < 40, np.zeros(n, bool), rows >= 490, np.nonzero(rows % 2 == 1)[0]] * 2   # masks stay over ROWS
+    shift = lambda a: np.where(a >= 0, a + id_base, a)
+    cur = (s_all[:, 9].copy(), i_all[:, 9].copy())
+    for case in (dict(), dict(radius=s_all[:, 60].copy()), dict(range_filter=s_all[:, 20].copy(), after=cur), dict(offset=2)):
+        for k in (1, 10, 64):
+            want_raw, want_adj = masked_batch(s_all, i_all, levels, sels, k, **case)
+            moved = dict(case)
+            if "after" in case:
+                moved["after"] = (cur[0], cur[1] + id_base)
+            got_raw, got_adj = masked_batch(s_all, i_all + id_base, levels, sels, k, id_base=id_base, **moved)
+            for j, (g, w) in enumerate(zip(got_raw + got_adj, want_raw + want_adj)):
+                assert g.dtype == w.dtype and g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes(), (sorted(case), k, j)
+    s_r, i_r = restrict(s_all[0], i_all[0] + id_base, sels[1], id_base)
+    assert np.array_equal(i_r - id_base, restrict(s_all[0], i_all[0], sels[1])[1]) and np.array_equal(s_r, restrict(s_all[0], i_all[0], sels[1])[0])

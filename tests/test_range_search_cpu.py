@@ -231,3 +231,29 @@ def test_iterator_and_offset_bookkeeping_against_a_stub_index():
             want = band_batch(ranked[None], ids[None], levels, k, offset=o)[1]
             assert [np.asarray(g).tobytes() for g in got] == [w.tobytes() for w in want], (o, k)
             assert len(stub.calls) == (1 if o + k <= 128 else 1 + -(-o // 128))
+
+
+@pytest.mark.parametrize("id_base", [1000, 2**32 + 12345])
+def test_a_ranking_shifted_by_id_base_gives_the_same_outputs_with_the_ids_shifted(id_base):
+    rng = np.random.default_rng(21)
+    n, nq = 300, 5
+    sc = np.round(rng.standard_normal((nq, n)), 1).astype(np.float32)   # many ties
+    ids = np.stack([np.array(sorted(range(n), key=lambda i: (-float(r[i]), i)), np.int64) for r in sc])
+    ranked = np.take_along_axis(sc, ids, 1)
+    levels = rng.integers(1, 4, n).astype(np.int32)
+    shift = lambda a: np.where(a >= 0, a + id_base, a)
+    lo, hi = ranked[:, 120].copy(), ranked[:, 30].copy()
+    cur = (ranked[:, 40].copy(), ids[:, 40].copy())
+    below, above = (ranked[:, 40].copy(), np.full(nq, -3, np.int64)), (ranked[:, 40].copy(), np.full(nq, n + 7, np.int64))
+    for case in (dict(), dict(radius=lo), dict(range_filter=hi), dict(radius=lo, range_filter=hi, after=cur), dict(after=cur, offset=3),
+                 dict(after=below), dict(after=above)):
+        for k in (1, 10, 128):
+            want_raw, want_adj = band_batch(ranked, ids, levels, k, **case)
+            moved = dict(case)
+            if "after" in case:   # the cursor names a global id; one outside [0, n) lands outside [id_base, id_base + n) on the same side
+                moved["after"] = (case["after"][0], case["after"][1] + id_base)
+            got_raw, got_adj = band_batch(ranked, ids + id_base, levels, k, id_base=id_base, **moved)
+            for j, (g, w) in enumerate(zip(got_raw + got_adj, want_raw + want_adj)):
+                assert g.dtype == w.dtype and g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes(), (sorted(case), k, j)
+    # the pages name their rows by the shifted ids
+    assert pages(ranked[0], ids[0] + id_base, 7, radius=lo[0]) == [[i + id_base for i in p] for p in pages(ranked[0], ids[0], 7, radius=lo[0])]
