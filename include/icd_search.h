@@ -481,6 +481,37 @@ int icd_sparse_search_grouped(icd_index *idx, icd_sparse *sp, icd_grouping *grou
                               int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream);
 
 /*
+ * Keyword match filters: Milvus's TEXT_MATCH(field, "tokens") predicate as row masks, one per query of a batch, built on the
+ * device from the sparse index's postings. DESIGN.md section 17.
+ *   query q           its distinct known terms q_terms[q_off[q] .. q_off[q + 1]) - icd_sparse_search's rules: strictly increasing,
+ *                     below the vocabulary, at most ICD_SPARSE_MAX_QUERY_TERMS - and min_match[q] in 1 .. 64.
+ *   mask q            row r is set iff it holds at least min_match[q] of the query's terms AND (base_masks[q] != NULL) lies in
+ *                     that base mask. A query without terms, or with min_match above its number of terms, gives the empty mask.
+ *
+ * icd_sparse_match_rowmasks: creates nq masks of `idx` with one launch of text_match_mask_kernel over (query, tile) on `stream`.
+ * out_masks: a HOST array of nq handles. The masks are ordinary icd_rowmask handles in icd_rowmask_create's layout: every masked
+ * entry point accepts them, icd_rowmask_stats reports their row count (counted by the kernel and read back by the first such
+ * call, which synchronises the device), icd_rowmask_read their words, icd_rowmask_destroy frees them - each alone, in any order,
+ * before or after the index (the bitsets of one call share one allocation, released with the last of them). Creation allocates;
+ * it is not a search and not graph-capturable (ICD_ERR_INVALID while `stream` is capturing). Masked searches enqueued later on the
+ * same stream see the finished bitsets. base_masks: NULL, or a HOST array of nq handles of `idx` (NULL entries: no base); a base
+ * mask must outlive the call's kernel, as a mask outlives its searches. With host queries or any base mask the call synchronises
+ * the stream before it returns; with queries_on_device = 1 (q_off, q_terms AND min_match are device pointers) and no base mask
+ * it only enqueues, and trusts the queries as icd_sparse_search does (a term >= vocab is skipped, a query is cut at 64 terms, a
+ * min_match outside 1 .. 64 matches nothing).
+ * Every check comes before the first device call; on any error no mask is created and every out_masks[q] is NULL.
+ * ICD_ERR_INVALID: unsorted or duplicate terms, a term >= vocab, a query longer than 64 terms, min_match outside 1 .. 64, a sparse
+ * index or a base mask created for another index, NULL arrays. ICD_ERR_STATE: a destroyed index, sparse index or base mask.
+ * ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 creates nothing.
+ *
+ * icd_rowmask_read: a mask's words on the host, in icd_rowmask_pack's layout, for every mask however it was made; out_count >=
+ * 4 * ceil(n / 128) (else ICD_ERR_INVALID). Synchronises the device.
+ */
+int icd_sparse_match_rowmasks(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const int32_t *min_match,
+                              int64_t nq, int32_t queries_on_device, icd_rowmask *const *base_masks, icd_rowmask **out_masks, void *stream);
+int icd_rowmask_read(icd_rowmask *m, uint32_t *out_words, int64_t out_count);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "icd_sparse_tile_rows", "icd_sparse_pack", "icd_sparse_create", "icd_sparse_destroy", "icd_sparse_stats", "icd_sparse_search",
     "icd_grouping_pair_sparse", "icd_sparse_search_grouped", "icd_index_search_hybrid_grouped", "icd_fusion_fuse_lists_grouped",
     "icd_sparse_search_range",
+    "icd_sparse_match_rowmasks", "icd_rowmask_read",
 )
 SPARSE_MAX_QUERY_TERMS = 64   # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
@@ -142,6 +143,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_sparse_search.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_sparse_search_range.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_grouping_pair_sparse.argtypes = [vp, vp, vp]
+    lib.icd_sparse_match_rowmasks.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    lib.icd_rowmask_read.argtypes = [vp, vp, i64]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
@@ -795,6 +798,32 @@ class IcdIndex:
             _check(self._lib, rc)
         return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
 
+    def match_masks(self, sp: "IcdSparse", q_off, q_terms, min_match, base_masks=None) -> list:
+        """The row masks of a batch of keyword matches (icd_sparse_match_rowmasks), one IcdRowMask per query,
+        built on the device from the sparse index's postings in one launch: row r is in mask q iff it holds at least
+        min_match[q] (1 .. 64) of the terms q_terms[q_off[q] : q_off[q + 1]] (uint32, strictly increasing, below the vocabulary,
+        at most 64) and lies in base_masks[q] (None, ONE IcdRowMask for every query, or nq of IcdRowMask or None). Host arrays,
+        checked by the library (ValueError). The masks are ordinary row masks of this index: every masked search takes them;
+        close() them (or drop them) when the search they were made for is done."""
+        if self.closed or sp is None or sp.closed:
+            raise IcdError(-5, "index or sparse index is closed")
+        off = np.ascontiguousarray(np.asarray(q_off).reshape(-1), dtype=np.int64)
+        tr = np.ascontiguousarray(np.asarray(q_terms).reshape(-1), dtype=np.uint32)
+        mm = np.ascontiguousarray(np.asarray(min_match).reshape(-1), dtype=np.int32)
+        nq = int(off.size) - 1
+        if nq < 0 or mm.size != nq or (nq > 0 and int(off[-1]) != tr.size):
+            raise ValueError("q_off must hold nq + 1 offsets that end at the number of terms; min_match one entry per query")
+        base_h = None if base_masks is None else _mask_table(base_masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
+        if nq == 0:
+            return []
+        out = (C.c_void_p * nq)()
+        rc = self._lib.icd_sparse_match_rowmasks(self._h, sp._h, off.ctypes.data, tr.ctypes.data if tr.size else off.ctypes.data, mm.ctypes.data,
+                                                 nq, 0, None if base_h is None else base_h.ctypes.data, C.cast(out, C.c_void_p), None)
+        if rc == -1:
+            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+        _check(self._lib, rc)
+        return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
+
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""
         import torch
@@ -1025,12 +1054,30 @@ class IcdRowMask(_Handle):
             raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
         _check(self._lib, rc)
 
+    @classmethod
+    def _adopt(cls, index: "IcdIndex", handle: int) -> "IcdRowMask":
+        """a mask the library created itself (IcdIndex.match_masks); `rows` is None until stats() reads the device's count"""
+        m = cls.__new__(cls)
+        m._lib, m._h = index._lib, C.c_void_p(handle)
+        m.n, m.rows, m.device = index.n, None, index.device
+        return m
+
     def stats(self) -> dict:
         if self.closed:
             raise IcdError(-5, "row mask is closed")
         r, b = C.c_int64(), C.c_int64()
         _check(self._lib, self._lib.icd_rowmask_stats(self._h, C.byref(r), C.byref(b)))
+        if self.rows is None:
+            self.rows = r.value
         return {"rows": r.value, "bytes": b.value}
+
+    def words(self) -> np.ndarray:
+        """The mask's bitset on the host (icd_rowmask_read; synchronises): uint32[rowmask_words(n)] in pack_rowmask's layout"""
+        if self.closed:
+            raise IcdError(-5, "row mask is closed")
+        out = np.empty(rowmask_words(self.n), dtype=np.uint32)
+        _check(self._lib, self._lib.icd_rowmask_read(self._h, out.ctypes.data, int(out.size)))
+        return out
 
 
 def group_unique_id() -> bytes:

@@ -101,8 +101,13 @@ static int pack_bands(icd_index *x, const RangeBounds &rb, int nq, hipStream_t s
 struct icd_rowmask : OwnedHandle {
     static constexpr uint32_t MAGIC = 0x1CD3A5C1u;
     static constexpr const char *NOUN = "row mask";
-    int64_t rows = 0;
+    int64_t rows = 0;           // -1: counted on the device (count_dev), read back by the first icd_rowmask_stats
     uint32_t *bits = nullptr;   // [rowmask_tile_words(n) + ROWMASK_TAIL_WORDS]
+    // a mask icd_sparse_match_rowmasks produced: bits and count_dev point into ONE allocation the masks of
+    // that call share; the last of them to be destroyed frees it
+    struct SharedBlock { void *dev = nullptr; std::atomic<int> refs{0}; };
+    SharedBlock *block = nullptr;
+    const int *count_dev = nullptr;
 };
 
 // The mask table of a call, over `count` entries against an index: no table on a view, every entry NULL or a live mask of THIS
@@ -235,12 +240,34 @@ int icd_rowmask_create(icd_index *idx, const int64_t *rows, int64_t n_rows, int3
     return ICD_OK;
 }
 
-int icd_rowmask_destroy(icd_rowmask *m) { return destroy_handle(m); }
+int icd_rowmask_destroy(icd_rowmask *m) {
+    icd_rowmask::SharedBlock *b = valid_handle(m) ? m->block : nullptr;
+    const int rc = destroy_handle(m);   // (synchronises the mask's device first)
+    if (b && b->refs.fetch_sub(1) == 1) { hipFree(b->dev); delete b; }
+    return rc;
+}
 
 int icd_rowmask_stats(icd_rowmask *m, int64_t *out_rows, int64_t *out_bytes) {
     if (!valid_handle(m)) return fail(ICD_ERR_STATE, "invalid row mask handle");
+    if (m->rows < 0 && out_rows) {   // a produced mask: its kernel counted the rows; wait for it, once
+        int cnt = 0;
+        HIP_TRY(hipSetDevice(m->at.device));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(&cnt, m->count_dev, sizeof(int), hipMemcpyDeviceToHost));
+        m->rows = cnt;
+    }
     if (out_rows) *out_rows = m->rows;
     if (out_bytes) *out_bytes = (int64_t)m->bytes;
+    return ICD_OK;
+}
+
+int icd_rowmask_read(icd_rowmask *m, uint32_t *out_words, int64_t out_count) {
+    if (!valid_handle(m)) return fail(ICD_ERR_STATE, "invalid row mask handle");
+    const int64_t words = rowmask_tile_words(m->at.n);
+    if (!out_words || out_count < words) return fail(ICD_ERR_INVALID, "out_words NULL or out_count=%lld: %lld rows need %lld words", (long long)out_count, (long long)m->at.n, (long long)words);
+    HIP_TRY(hipSetDevice(m->at.device));
+    HIP_TRY(hipDeviceSynchronize());   // (whatever stream the mask was built on)
+    HIP_TRY(hipMemcpy(out_words, m->bits, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return ICD_OK;
 }
 

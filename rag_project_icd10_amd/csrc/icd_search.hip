@@ -23,6 +23,7 @@
 #include "group_topk.hpp"
 #include "hybrid_fuse.hpp"
 #include "sparse_kernel.hpp"
+#include "text_match_kernel.hpp"
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
@@ -1883,5 +1884,6 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
 #include "icd_grouped.hpp"   // the grouping search
 #include "icd_hybrid.hpp"    // the hybrid search
 #include "icd_sparse.hpp"    // the sparse-vector search, the fuse of caller-provided lists
+#include "icd_text_match.hpp" // keyword match filters: row masks from the sparse index's postings
 // the small-input sentence encoder (icd_encoder_*): its own file, this translation unit (fail(), HIP_TRY, packed_attention_kernel)
 #include "icd_encoder.hpp"

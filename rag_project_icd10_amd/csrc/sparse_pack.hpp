@@ -47,6 +47,41 @@ inline int sparse_check_csr(const int64_t *row_off, const uint32_t *terms, const
     return SPARSE_OK;
 }
 
+// The queries of a keyword match: `count` term lists without values (q_off[count + 1], terms) under
+// sparse_check_csr's rules for offsets and terms, at most max_terms terms each, and min_match[q] in 1 .. max_terms.
+inline int sparse_check_match_queries(const int64_t *q_off, const uint32_t *terms, const int32_t *min_match, int64_t count, int64_t vocab,
+                                      int64_t max_terms, char *msg, size_t msg_len) {
+    if (count < 0 || vocab < 1 || vocab > 0xFFFFFFFFll || !q_off || !min_match) {
+        snprintf(msg, msg_len, "query offsets or min_match NULL, count=%lld or vocab=%lld", (long long)count, (long long)vocab);
+        return SPARSE_BAD;
+    }
+    if (q_off[0] != 0) { snprintf(msg, msg_len, "query offsets start at %lld, not 0", (long long)q_off[0]); return SPARSE_BAD; }
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t a = q_off[i], b = q_off[i + 1];
+        if (b < a) { snprintf(msg, msg_len, "query %lld: offsets decrease", (long long)i); return SPARSE_BAD; }
+        if (b - a > max_terms) {
+            snprintf(msg, msg_len, "query %lld carries %lld terms (at most %lld)", (long long)i, (long long)(b - a), (long long)max_terms);
+            return SPARSE_BAD;
+        }
+        if (min_match[i] < 1 || min_match[i] > max_terms) {
+            snprintf(msg, msg_len, "query %lld: min_match=%d outside 1 .. %lld", (long long)i, min_match[i], (long long)max_terms);
+            return SPARSE_BAD;
+        }
+        if (b > a && !terms) { snprintf(msg, msg_len, "terms NULL"); return SPARSE_BAD; }
+        for (int64_t p = a; p < b; ++p) {
+            if ((int64_t)terms[p] >= vocab) {
+                snprintf(msg, msg_len, "query %lld: term %u outside the vocabulary's [0, %lld)", (long long)i, terms[p], (long long)vocab);
+                return SPARSE_BAD;
+            }
+            if (p > a && terms[p] <= terms[p - 1]) {
+                snprintf(msg, msg_len, "query %lld: terms must be strictly increasing (%u after %u)", (long long)i, terms[p], terms[p - 1]);
+                return SPARSE_BAD;
+            }
+        }
+    }
+    return SPARSE_OK;
+}
+
 // CSR rows that sparse_check_csr has passed -> postings: post_off[vocab + 1], post_row / post_val [nnz]. A stable counting sort by
 // term: rows are visited in ascending order, so every term's postings come out with ascending rows.
 inline void sparse_pack_checked(const int64_t *row_off, const uint32_t *terms, const float *vals, int64_t n, int64_t vocab,

@@ -9,12 +9,17 @@ The documented subset of Milvus's boolean expression grammar that the scalar fie
     predicate := FIELD ("==" | "!=" | "<" | "<=" | ">" | ">=") LITERAL
                | FIELD ["not"] "in" "[" [LITERAL ("," LITERAL)*] "]"
                | FIELD "like" STRING
+               | "TEXT_MATCH" "(" FIELD "," STRING ["," "minimum_should_match" "=" INT] ")"
 
 * FIELD: code, main_code, secondary_code, parent_code, category_path, preferred_zh (strings), level (int), has_complication
   (bool). Strings and bools take `==` and `!=` only; `like` takes strings only.
 * LITERAL: a single- or double-quoted string (backslash escapes the next character), an int, true / false in any case.
   Keywords (and, or, not, in, like) are matched in any case too.
 * like: "P%" prefix, "%S" suffix, "%X%" infix, no `%` = equality; `_` is an ordinary character.
+
+* TEXT_MATCH (the name and the option keyword in any case): the rows whose text holds at least
+  minimum_should_match (default 1, 1 .. 64) of the distinct terms `sparse_text.analyze` makes of STRING. FIELD is the text-indexed
+  field (TEXT_FIELDS). Parsing needs no index; evaluating needs a matcher (`Columns.set_text_matcher`). No PHRASE_MATCH.
 
 A syntax error, an unknown field or a type mismatch raises ValueError with the position (0-based, in characters) and the reason.
 Nothing is evaluated by `eval`: the expression is parsed into a small tree and the tree is evaluated over whole column arrays.
@@ -41,6 +46,10 @@ FIELDS = STRING_FIELDS + INT_FIELDS + BOOL_FIELDS
 # (the three-character category a code belongs to), the code itself where the path is empty
 GROUP_FIELDS = FIELDS + ("category",)
 MAX_GROUPED_HITS = 128   # include/icd_search.h ICD_MAX_K: top_k * group_size of one query
+# keyword match (Milvus TEXT_MATCH): the field that carries the text index (MilvusService.build_sparse_index's default), and the
+# bounds of minimum_should_match (include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS)
+TEXT_FIELDS = ("preferred_zh",)
+TEXT_MATCH_MAX_TERMS = 64
 _CMP = ("==", "!=", "<", "<=", ">", ">=")
 _KEYWORDS = ("and", "or", "not", "in", "like", "true", "false")
 
@@ -49,6 +58,7 @@ _TOKEN = re.compile(r"""
   | (?P<str>"(?:[^"\\]|\\.)*"|'(?:[^'\\]|\\.)*')
   | (?P<int>-?\d+)
   | (?P<op>==|!=|<=|>=|&&|\|\||<|>|!|\(|\)|\[|\]|,)
+  | (?P<opt>(?i:minimum_should_match)\s*=(?!=))
   | (?P<name>[A-Za-z_][A-Za-z0-9_]*)
 """, re.X | re.S)
 
@@ -73,6 +83,8 @@ def _tokenize(expr: str) -> List[Tuple[str, Any, int]]:
             out.append(("int", int(text), pos))
         elif kind == "op":
             out.append(("op", text, pos))
+        elif kind == "opt":   # TEXT_MATCH's option keyword with its '=' (a lone '=' is no operator of the grammar)
+            out.append(("opt", "minimum_should_match=", pos))
         elif kind == "name":
             low = text.lower()
             if low in ("true", "false"):
@@ -153,10 +165,51 @@ class _Parser:
             raise _error(t[2], f"type mismatch: {field} is {name[want]}, the literal {self._show(t)} is {name[t[0]]}")
         return t[1]
 
+    def expect_op(self, value: str, where: str):
+        t = self.take()
+        if t[:2] != ("op", value):
+            raise _error(t[2], f"expected '{value}' {where}, found {self._show(t)}")
+
+    def text_match(self):
+        """TEXT_MATCH "(" FIELD "," STRING ["," minimum_should_match "=" INT] ")" -> ("text_match", field, sorted distinct terms, m)"""
+        from .sparse_text import analyze
+        self.expect_op("(", "after TEXT_MATCH")
+        t = self.take()
+        if t[0] != "name":
+            raise _error(t[2], f"TEXT_MATCH takes a field name first, found {self._show(t)}")
+        field = t[1]
+        if field not in FIELDS:
+            raise _error(t[2], f"unknown field {field!r} (fields: {', '.join(FIELDS)})")
+        if field not in STRING_FIELDS:
+            raise _error(t[2], f"type mismatch: TEXT_MATCH is not defined on {field} (strings only)")
+        if field not in TEXT_FIELDS:
+            raise _error(t[2], f"TEXT_MATCH: {field} carries no text index (text-indexed: {', '.join(TEXT_FIELDS)})")
+        self.expect_op(",", f"after TEXT_MATCH({field}")
+        t = self.take()
+        if t[0] != "str":
+            raise _error(t[2], f"TEXT_MATCH takes a quoted text, found {self._show(t)}")
+        terms = tuple(sorted(set(analyze(t[1]))))
+        m = 1
+        if self.at("op", ","):
+            self.take()
+            t = self.take()
+            if t[0] != "opt":
+                raise _error(t[2], f"expected minimum_should_match=, found {self._show(t)}")
+            t = self.take()
+            if t[0] != "int":
+                raise _error(t[2], f"minimum_should_match takes an int, found {self._show(t)}")
+            m = t[1]
+            if not 1 <= m <= TEXT_MATCH_MAX_TERMS:
+                raise _error(t[2], f"minimum_should_match={m}: must lie in 1 .. {TEXT_MATCH_MAX_TERMS}")
+        self.expect_op(")", "to close TEXT_MATCH")
+        return ("text_match", field, terms, m)
+
     def predicate(self):
         t = self.take()
         if t[0] != "name":
             raise _error(t[2], f"expected a field name, found {self._show(t)}")
+        if t[1].lower() == "text_match" and self.at("op", "("):
+            return self.text_match()
         field, fpos = t[1], t[2]
         if field not in FIELDS:
             raise _error(fpos, f"unknown field {field!r} (fields: {', '.join(FIELDS)})")
@@ -230,6 +283,8 @@ def _key(node) -> str:
     if kind == "like":
         pat = {"prefix": "{}%", "suffix": "%{}", "infix": "%{}%"}[node[2]].format(node[3])
         return f"{node[1]} like {_quote(pat)}"
+    if kind == "text_match":   # (the analysed terms hold no quote and no space: the key is an expression again)
+        return f"TEXT_MATCH({node[1]}, {_quote(' '.join(node[2]))}, minimum_should_match={node[3]})"
     if kind == "not":
         return f"not ({_key(node[1])})"
     return f" {kind} ".join(f"({_key(t)})" for t in node[1])
@@ -251,6 +306,36 @@ def parse(expr: str):
 def compile(expr: str) -> str:   # noqa: A001 (the name the issue gives the entry point)
     """the normalised key of `expr`; raises ValueError on a syntax error, an unknown field or a type mismatch"""
     return _parse(expr)[1]
+
+
+def _has_text_match(node) -> bool:
+    if node[0] in ("and", "or"):
+        return any(_has_text_match(t) for t in node[1])
+    if node[0] == "not":
+        return _has_text_match(node[1])
+    return node[0] == "text_match"
+
+
+def has_text_match(expr: str) -> bool:
+    """whether `expr` holds a TEXT_MATCH predicate anywhere (evaluating it then needs a matcher)"""
+    return _has_text_match(_parse(expr)[0])
+
+
+def text_match_shape(expr: str):
+    """The shapes a TEXT_MATCH expression's mask is built on the device for: a lone TEXT_MATCH(...), or a
+    top-level conjunction with exactly one TEXT_MATCH among predicates S that hold none. Returns (S, field, terms, m) - S the
+    normalised expression of the other conjuncts, None for a lone TEXT_MATCH - or None for every other expression (no
+    TEXT_MATCH at all, one under `or` / `not` or in a nested conjunction, two of them): those are evaluated on the host."""
+    node = _parse(expr)[0]
+    if node[0] == "text_match":
+        return None, node[1], node[2], node[3]
+    if node[0] != "and":
+        return None
+    text = [t for t in node[1] if t[0] == "text_match"]
+    rest = [t for t in node[1] if t[0] != "text_match"]
+    if len(text) != 1 or any(_has_text_match(t) for t in rest):
+        return None
+    return _key(rest[0] if len(rest) == 1 else ("and", tuple(rest))), text[0][1], text[0][2], text[0][3]
 
 
 def check_grouping(field, top_k, group_size) -> None:
@@ -278,6 +363,7 @@ class Columns:
         self.n = len(next(iter(arrays.values()))) if arrays else 0
         self._sel: "OrderedDict[str, np.ndarray]" = OrderedDict()
         self._groups: Dict[str, Any] = {}
+        self._matchers: Dict[str, Any] = {}
         self._lock = threading.Lock()
 
     @classmethod
@@ -315,6 +401,17 @@ class Columns:
             self._groups[field] = out
         return out
 
+    def set_text_matcher(self, field: str, fn) -> None:
+        """The matcher TEXT_MATCH(field, ...) is evaluated with: fn(terms, m) -> bool[n], terms the analysed distinct terms of
+        the predicate's text, m its minimum_should_match (sparse_text.SparseTextIndex.match_rows over the same rows). Selections
+        cached under another matcher are dropped."""
+        with self._lock:
+            if self._matchers.get(field) is fn:
+                return
+            self._matchers[field] = fn
+            for key in [k for k in self._sel if "TEXT_MATCH(" in k]:
+                del self._sel[key]
+
     def select(self, expr: str) -> np.ndarray:
         node, key = _parse(expr)
         with self._lock:
@@ -322,7 +419,7 @@ class Columns:
             if hit is not None:
                 self._sel.move_to_end(key)
                 return hit
-        rows = np.flatnonzero(_eval(node, self.arrays, self.n)).astype(np.int64)
+        rows = np.flatnonzero(_eval(node, self.arrays, self.n, self._matchers)).astype(np.int64)
         rows.setflags(write=False)
         with self._lock:
             self._sel[key] = rows
@@ -331,20 +428,25 @@ class Columns:
         return rows
 
 
-def _eval(node, cols, n: int) -> np.ndarray:
+def _eval(node, cols, n: int, matchers=None) -> np.ndarray:
     kind = node[0]
     if kind == "and":
-        m = _eval(node[1][0], cols, n)
+        m = _eval(node[1][0], cols, n, matchers)
         for t in node[1][1:]:
-            m = m & _eval(t, cols, n)
+            m = m & _eval(t, cols, n, matchers)
         return m
     if kind == "or":
-        m = _eval(node[1][0], cols, n)
+        m = _eval(node[1][0], cols, n, matchers)
         for t in node[1][1:]:
-            m = m | _eval(t, cols, n)
+            m = m | _eval(t, cols, n, matchers)
         return m
     if kind == "not":
-        return ~_eval(node[1], cols, n)
+        return ~_eval(node[1], cols, n, matchers)
+    if kind == "text_match":
+        fn = (matchers or {}).get(node[1])
+        if fn is None:
+            raise ValueError(f"TEXT_MATCH: no sparse index on {node[1]}: call build_sparse_index")
+        return np.asarray(fn(node[2], node[3]), dtype=bool).reshape(n)
     col = cols[node[1]]
     if kind == "cmp":
         op, v = node[2], node[3]
@@ -377,7 +479,7 @@ def select(expr: str, columns: Union[Columns, Dict[str, np.ndarray]]) -> np.ndar
     missing = [f for f in _fields_of(node) if f not in cols]
     if missing:
         raise ValueError(f"filter expression needs column(s) {missing} that were not given")
-    return np.flatnonzero(_eval(node, cols, n)).astype(np.int64)
+    return np.flatnonzero(_eval(node, cols, n)).astype(np.int64)   # (a TEXT_MATCH needs a Columns with its matcher: ValueError here)
 
 
 def _fields_of(node) -> List[str]:
@@ -385,4 +487,4 @@ def _fields_of(node) -> List[str]:
         return [f for t in node[1] for f in _fields_of(t)]
     if node[0] == "not":
         return _fields_of(node[1])
-    return [node[1]]
+    return [] if node[0] == "text_match" else [node[1]]

@@ -279,7 +279,11 @@ class MilvusService:
         filter_expr.compile(expr)
         if self.client is None or not self.client.exists():
             return np.zeros(0, np.int64)
-        return self._filter_columns().select(expr)
+        cols = self._filter_columns()
+        if filter_expr.has_text_match(expr):   # (the host route of TEXT_MATCH: the sparse index's rows, built lazily as search_text does)
+            _sp, tx, field = self._text_index()
+            cols.set_text_matcher(field, tx.match_rows)
+        return cols.select(expr)
 
     def _filtered_index(self, expr: str):
         """(index, rows) to search for `expr`: the index itself when every row is selected, None when none is, else the
@@ -344,12 +348,54 @@ class MilvusService:
             raise ValueError("a per-query filter list / filter_mode='mask' cannot be combined with group_by_field")
         return masked
 
+    # ---- keyword match filters (TEXT_MATCH) ------------------------------------------------------------------
+    TEXT_MATCH_ON_DEVICE = True   # False: every TEXT_MATCH expression takes the host route (tests compare the two routes' bits)
+
+    def _text_index(self):
+        """(IcdSparse, SparseTextIndex, field) of the store's sparse index, built on the first TEXT_MATCH as search_text builds it"""
+        field = self._sparse[3] if self._sparse is not None else "preferred_zh"
+        sp, tx = self.build_sparse_index(field)
+        return sp, tx, field
+
+    def _match_masks(self, index, shapes):
+        """The masks of a batch of device-shaped TEXT_MATCH expressions (filter_expr.text_match_shape: (S, field, terms, m) each) in
+        ONE IcdIndex.match_masks call, S's cached mask as the base. They belong to the search they were made for: not cached (the
+        text is the query's own words), released by whoever asked (mask.transient marks them)."""
+        sp, tx, field = self._text_index()
+        pairs, mm, bases = [], [], []
+        for rest, f, terms, m in shapes:
+            if f != field:
+                raise ValueError(f"TEXT_MATCH: no sparse index on {f}: call build_sparse_index")
+            known, _total = tx.match_terms(terms)
+            pairs.append((known, known))
+            mm.append(m)
+            bases.append(None if rest is None else self._filter_mask(index, rest))
+        q_off, q_terms, _ = sparse_text.csr_from_pairs(pairs)
+        masks = index.match_masks(sp, q_off, q_terms, mm, bases if any(b is not None for b in bases) else None)
+        for m_ in masks:
+            m_.transient = True
+        return masks
+
+    @staticmethod
+    def _release_masks(masks):
+        """close the per-search masks of a finished search (the cached ones stay)"""
+        for m_ in masks or ():
+            if m_ is not None and getattr(m_, "transient", False):
+                m_.close()
+
     def _filter_mask(self, index, expr):
         """the row mask of `expr` on the store's index: None when the expression is None or selects every row, else the
-        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation)"""
+        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation). A
+        device-shaped TEXT_MATCH expression gets a mask of its own from the device, uncached."""
         if expr is None:
             return None
         key = filter_expr.compile(expr)
+        if self.TEXT_MATCH_ON_DEVICE:
+            shape = filter_expr.text_match_shape(expr)
+            if shape is not None:
+                mask = self._match_masks(index, [shape])[0]
+                mask.stats()   # (one mask: its row count is read now, for the callers that ask whether it is empty)
+                return mask
         ck = (key, self.client.generation)
         with self._views_lock:
             hit = self._masks.get(ck)
@@ -370,12 +416,18 @@ class MilvusService:
         """one entry per query: None (unfiltered) or the expression's mask; equal expressions share one mask"""
         exprs = list(filter) if isinstance(filter, (list, tuple)) else [filter] * nq
         seen: Dict[Any, Any] = {}
-        out = []
+        device: Dict[Any, Any] = {}   # expression -> its device shape: the text parts of ALL such queries are one match_masks call
         for e in exprs:
-            if e not in seen:
+            if e is None or e in seen or e in device:
+                continue
+            shape = filter_expr.text_match_shape(e) if self.TEXT_MATCH_ON_DEVICE else None
+            if shape is not None:
+                device[e] = shape
+            else:
                 seen[e] = self._filter_mask(index, e)
-            out.append(seen[e])
-        return out
+        if device:
+            seen.update(zip(device, self._match_masks(index, list(device.values()))))
+        return [None if e is None else seen[e] for e in exprs]
 
     def filter_masks(self) -> List[Dict[str, Any]]:
         """the cached filter masks, least recently used first: expression (normalised), rows, HBM bytes"""
@@ -437,7 +489,10 @@ class MilvusService:
                 query_vector.tolist  # noqa: B018
                 q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
                 pair = (index, self._masks_for(index, filter, 1))
-                adj, raw, ids, levels = range_search.search_band(pair, q, int(top_k), radius, range_filter, offset)
+                try:
+                    adj, raw, ids, levels = range_search.search_band(pair, q, int(top_k), radius, range_filter, offset)
+                finally:
+                    self._release_masks(pair[1])
                 return self._hits_to_dicts(adj[0], raw[0], ids[0])
             if filter is not None:
                 index, rows = self._filtered_index(filter)
@@ -552,7 +607,10 @@ class MilvusService:
         rows = None
         if masked:
             pair = (index, self._masks_for(index, filter, nq))
-            adj, raw, ids, levels = range_search.search_band(pair, query_vectors, int(top_k), radius, range_filter, offset)
+            try:
+                adj, raw, ids, levels = range_search.search_band(pair, query_vectors, int(top_k), radius, range_filter, offset)
+            finally:
+                self._release_masks(pair[1])   # (closing synchronises the device: the search has run)
             if not as_dicts:
                 return adj, raw, ids, levels
             if hasattr(adj, "cpu"):

@@ -87,6 +87,31 @@ class SparseTextIndex:
         keep = w != 0   # (a weight that rounds to zero in fp32 is no pair)
         return t[keep], w[keep]
 
+    def match_terms(self, terms: Iterable[str]) -> Tuple[np.ndarray, int]:
+        """(known term ids uint32 ascending, |T|) of the distinct analysed terms T of a TEXT_MATCH predicate (DESIGN.md section
+        17): terms outside the vocabulary are dropped for matching but still count in |T|. More than MAX_QUERY_TERMS known terms:
+        ValueError - dropping any would change a set predicate."""
+        distinct = set(analyze(terms)) if isinstance(terms, str) else set(terms)
+        known = sorted(self.term_id[t] for t in distinct if t in self.term_id)
+        if len(known) > MAX_QUERY_TERMS:
+            raise ValueError(f"TEXT_MATCH: the text holds {len(known)} distinct known terms (at most {MAX_QUERY_TERMS})")
+        return np.asarray(known, np.uint32), len(distinct)
+
+    def match_rows(self, terms: Iterable[str], m=1) -> np.ndarray:
+        """bool[n]: the rows that hold at least m of the distinct terms T (analysed term strings, or one text to analyse); m an int
+        in 1 .. 64 or "all" = |T|, unknown terms included - an unknown term under "all" matches nothing. The host evaluation of
+        TEXT_MATCH (filter_expr.Columns.set_text_matcher), over the rows' CSR."""
+        known, total = self.match_terms(terms)
+        need = total if m == "all" else m
+        if isinstance(need, bool) or not isinstance(need, (int, np.integer)) or (m != "all" and not 1 <= need <= MAX_QUERY_TERMS):
+            raise ValueError(f"minimum_should_match={m!r}: an int in 1 .. {MAX_QUERY_TERMS} or 'all'")
+        if known.size == 0 or need > known.size or need < 1:
+            return np.zeros(self.n, bool)
+        hit = np.isin(self.terms, known)
+        count = np.add.reduceat(np.append(hit, False).astype(np.int64), self.row_off[:-1]) if self.n else np.zeros(0, np.int64)
+        count[self.row_off[:-1] == self.row_off[1:]] = 0   # (reduceat on an empty row reads its neighbour's first entry)
+        return count >= need
+
     def encode_queries(self, texts: Iterable[str]):
         """CSR (q_off int64, q_terms uint32, q_vals float32) of several query texts"""
         enc = [self.encode_query(t) for t in texts]
@@ -114,3 +139,19 @@ def query_from_dict(weights: Dict[int, float], vocab: int) -> Tuple[np.ndarray, 
         if not math.isfinite(w) or np.float32(w) == 0:
             raise ValueError(f"the weight of term {t} must be finite and non-zero")
     return np.array([t for t, _ in items], np.uint32), np.array([w for _, w in items], np.float32)
+
+
+def text_match_expr(field: str, text: str, minimum_should_match=1) -> str:
+    """The filter expression TEXT_MATCH(field, text, minimum_should_match=m) (services/filter_expr.py). minimum_should_match: an
+    int in 1 .. 64, or "all": m = the number of distinct terms the analyzer makes of `text`, so that a caller need not count them
+    (every term must then be in the row; a word the corpus does not know matches nothing)."""
+    if minimum_should_match == "all":
+        m = max(len(set(analyze(text))), 1)
+    elif isinstance(minimum_should_match, bool) or not isinstance(minimum_should_match, (int, np.integer)):
+        raise ValueError(f"minimum_should_match={minimum_should_match!r}: an int in 1 .. {MAX_QUERY_TERMS} or 'all'")
+    else:
+        m = int(minimum_should_match)
+    if not 1 <= m <= MAX_QUERY_TERMS:
+        raise ValueError(f"minimum_should_match={m}: must lie in 1 .. {MAX_QUERY_TERMS} (the text holds {len(set(analyze(text)))} distinct terms)")
+    quoted = '"' + text.replace("\\", "\\\\").replace('"', '\\"') + '"'
+    return f"TEXT_MATCH({field}, {quoted}, minimum_should_match={m})"
