@@ -669,6 +669,14 @@ int icd_split_bf16x3(int32_t device, const float *x, int64_t rows, int32_t cols,
  *  for the last search of this handle - an event on that stream - and for nothing else on the device) */
 int icd_index_stats(icd_index *idx, icd_stats *out);
 
+/* Diagnostic / test hook: the MEASURED terms of finalize's certificate, in the fp16 image's scaled
+ * units 2^cexp (queries: each in its own scale): *cmax = the largest norm of the scaled corpus rows (of the centred rows
+ * when the image is centred), *dcmax = the largest | scaled row - its fp16 image |, both rounded up at index creation;
+ * qnorm / qres (host memory, [count], either may be NULL) = the same two norms of the first `count` queries of the last
+ * AUTO search of this handle that ran the coarse pass (count <= that search's batch). Waits for the device. An index
+ * without an fp16 image: ICD_ERR_INVALID. */
+int icd_index_cert_terms(icd_index *idx, float *cmax, float *dcmax, int32_t *cexp, float *qnorm, float *qres, int64_t count);
+
 /* Tuning knob / test hook (0 = automatic): aim for about `chunks` candidate lists per query in the coarse pass
  * (the automatic choice gives every CU the same number of 128 x 128 tiles). */
 int icd_index_set_chunks(icd_index *idx, int32_t chunks);

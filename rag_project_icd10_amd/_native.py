@@ -26,7 +26,7 @@ ABI_VERSION = 6   # include/icd_search.h ICD_ABI_VERSION: a stale libicdsearch.s
 EXPORTED_SYMBOLS = (
     "icd_abi_version", "icd_last_error", "icd_device_count", "icd_index_create", "icd_index_create_view", "icd_index_destroy",
     "icd_index_search", "icd_index_search_reweighted", "icd_merge_topk", "icd_index_lookup_levels",
-    "icd_index_stats", "icd_index_set_chunks", "icd_index_debug_counters", "icd_index_set_profiling",
+    "icd_index_stats", "icd_index_cert_terms", "icd_index_set_chunks", "icd_index_debug_counters", "icd_index_set_profiling",
     "icd_index_last_profile", "icd_index_profile_summary", "icd_index_set_option", "icd_packed_attention",
     "icd_hier_rescore", "icd_hier_rescore_entities",
     "icd_score_stats",
@@ -153,6 +153,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_merge_topk.argtypes = [i32, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     lib.icd_index_lookup_levels.argtypes = [vp, vp, i64, vp, vp]
     lib.icd_index_stats.argtypes = [vp, C.POINTER(_Stats)]
+    lib.icd_index_cert_terms.argtypes = [vp, vp, vp, vp, vp, vp, i64]
     lib.icd_index_set_chunks.argtypes = [vp, i32]
     lib.icd_index_set_second_pass.argtypes = [vp, i32]
     lib.icd_index_set_option.argtypes = [vp, i32, i32]
@@ -838,6 +839,15 @@ class IcdIndex:
         st = _Stats()
         _check(self._lib, self._lib.icd_index_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _Stats._fields_}
+
+    def cert_terms(self, count: int = 0) -> dict:
+        """the measured terms of the certificate's error bound, in the fp16 image's scaled units: `cmax`
+        and `dcmax` of the corpus, `cexp`, and `qnorm` / `qres` of the first `count` queries of the last AUTO batch search"""
+        cmax, dcmax, cexp = C.c_float(), C.c_float(), C.c_int32()
+        qnorm, qres = np.zeros(max(count, 1), np.float32), np.zeros(max(count, 1), np.float32)
+        _check(self._lib, self._lib.icd_index_cert_terms(self._h, C.addressof(cmax), C.addressof(dcmax), C.addressof(cexp),
+                                                        qnorm.ctypes.data, qres.ctypes.data, int(count)))
+        return {"cmax": cmax.value, "dcmax": dcmax.value, "cexp": cexp.value, "qnorm": qnorm[:count], "qres": qres[:count]}
 
     def set_chunks(self, chunks: int):
         _check(self._lib, self._lib.icd_index_set_chunks(self._h, int(chunks)))

@@ -82,6 +82,8 @@ struct ConvertArgs {
     int perm_mod;
     const float *mu;         // nullable [dim]: subtracted from every row before anything else (the corpus's column mean, see below)
     float *norm_raw_max;     // nullable: atomicMax (as bits) of the L2 norm of the UNcentred, unscaled row (rounded up)
+    float *res;              // nullable [rows]: | scaled row - its fp16 image |, rounded up (cert_bound.hpp: the certificate's measured rounding error)
+    unsigned int *resmax_bits;   // nullable: atomicMax of that norm's bits
 };
 
 // ---- the corpus's fp16 image is CENTRED when its rows share a large common component ------------------------------------------
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(256) void convert_rows_kernel(ConvertArgs a) {
         return;
     }
     const int e = anybad ? 0 : (a.mode == 1 ? a.fixed_exp : scale_exp_for(m));
-    float ss = 0.0f;
+    float ss = 0.0f, rs = 0.0f;
     typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int t = 0; t < NV; ++t) {
@@ -209,15 +211,26 @@ __global__ __launch_bounds__(256) void convert_rows_kernel(ConvertArgs a) {
                 const float x = ldexpf(f[j], e);   // exact (a component 2^126 below the row's largest flushes: far below fp16's grid)
                 ss = __builtin_fmaf(x, x, ss);
                 h[j] = (_Float16)x;
+                // what the rounding took: x - fp16(x) is exact in fp32 (the low bits of x). An image component in fp16's
+                // subnormal range counts with the larger of that and |x|: the bound then holds whether or not the matrix
+                // unit flushes such an input (a unit row has one such component in ten rows, 2^-14 against a residual of 2e-3)
+                const float back = (float)h[j];
+                float dl = x - back;
+                if (fabsf(back) < 6.103515625e-05f) dl = fmaxf(fabsf(dl), fabsf(x));
+                rs = __builtin_fmaf(dl, dl, rs);
             }
             *reinterpret_cast<half4 *>(d + i) = h;   // one 8-byte store per lane
         }
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
+    for (int off = 32; off >= 1; off >>= 1) { ss += __shfl_xor(ss, off); rs += __shfl_xor(rs, off); }
     if (lane == 0) {
         float nrm = sqrtf(ss) * 1.000001f;  // round up: it multiplies an error bound
         if (!(nrm == nrm)) nrm = INFINITY;
+        float rn = sqrtf(rs) * 1.000002f;   // (16 fmaf + 6 additions of positive terms, the root, the product: under 2^-19 in all)
+        if (!(rn == rn)) rn = INFINITY;
+        if (a.res) a.res[row] = rn;
+        if (a.resmax_bits && !anybad) atomicMax(a.resmax_bits, __float_as_uint(rn));
         if (a.norm) a.norm[row] = nrm;
         if (a.scale_exp) a.scale_exp[row] = e;
         if (a.bad) a.bad[row] = anybad ? 1 : 0;

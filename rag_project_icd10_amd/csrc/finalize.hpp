@@ -8,6 +8,7 @@
 //   services/milvus_service.py:550-558  level weights {1:1.2, 2:1.0, 3:0.8}, default 1.0
 //   services/milvus_service.py:314      stable sort by adjusted score, descending
 #pragma once
+#include "cert_bound.hpp"
 #include "exact_kernel.hpp"
 #include "topk_select.hpp"
 
@@ -63,7 +64,10 @@ struct FinArgs {
     const float *qnorm;          // [query] norm of the query's SCALED fp16 image (coarse_common.hpp)
     const int *qexp;             // [query] its power-of-two scale exponent
     const unsigned char *qbad;   // [query] 1 = fp16 image unusable (non-finite input)
-    float rmax, eps_rel;         // rmax: largest norm of the scaled corpus rows (of the CENTRED rows when the index centres its image)
+    const float *qres;           // [query] | scaled query - its fp16 image |, rounded up (coarse_common.hpp)
+    float cmax16, dcmax;         // the same of the corpus, measured at icd_index_create: an upper bound of every row's norm (fp16 image and scaled
+    float acc_rel;               // fp32 row alike; of the CENTRED rows when the index centres its image), the largest | row - its image |, and the
+                                 // weight of the summation terms (cert_bound.hpp)
     float rmax_unc, eps_f32;     // centred image only (else 0): largest norm of the uncentred rows in the image's scale, and the fp32
                                  // chain's relative error bound on them (coarse_common.hpp, "centred")
     int cexp;                    // the corpus's scale exponent
@@ -195,8 +199,8 @@ __device__ __forceinline__ int perm_row(int p, long long mul, int n, double inv)
 }
 
 // the certification bound of one query (derivation: step 3 of finalize_kernel)
-__device__ __forceinline__ float fin_eps(const FinArgs &a, float qn, int qexp) {
-    return a.eps_rel * qn * a.rmax + a.eps_f32 * qn * a.rmax_unc + ldexpf((float)a.dim, qexp + a.cexp - 148);
+__device__ __forceinline__ float fin_eps(const FinArgs &a, float qn, float qres, int qexp) {
+    return (cert_eps_round(qn, qres, a.cmax16, a.dcmax, a.acc_rel) + a.eps_f32 * qn * a.rmax_unc + ldexpf((float)a.dim, qexp + a.cexp - 148)) * CERT_ROUND_UP;
 }
 
 // Canonical score of one corpus row, four lanes per row (the quad walk of step 4 of finalize_kernel): lane 4 g + qi loads
@@ -427,11 +431,12 @@ __global__ __launch_bounds__(256, EWM == 1 ? ICD_FIN_OCC : 1) void finalize_kern
     float *qvec = reinterpret_cast<float *>(adjbuf + fin_adj_slots(EWM));
     // issued first, consumed last: the query (rescoring operand) and its norm / usability flag travel while the
     // candidates are merged (a wave's life is a chain of dependent round trips; these need not be part of it)
-    float qn_early = 0.0f;
+    float qn_early = 0.0f, qres_early = 0.0f;
     int qexp_early = 0;
     unsigned char qbad_early = 0;
     if (RESCORE) {
         qn_early = a.qnorm[qidx];
+        qres_early = a.qres[qidx];
         qexp_early = a.qexp[qidx];
         qbad_early = a.qbad[qidx];
         const float *qsrc0 = a.queries + (size_t)qidx * a.dim;
@@ -465,7 +470,7 @@ __global__ __launch_bounds__(256, EWM == 1 ? ICD_FIN_OCC : 1) void finalize_kern
     bool merged = false;
     if constexpr (RESCORE && EWM >= 4) {
         if (T > 64) {   // (wave-uniform) a wide window: only what can be within 2 eps of the k-th best is ranked
-            const float two_eps = 2.0f * fin_eps(a, qn_early, qexp_early);
+            const float two_eps = 2.0f * fin_eps(a, qn_early, qres_early, qexp_early);
             nres = ncand <= 128 ? fin_merge_window<2>(a, pbase, ncand, T, k, two_eps, keys, sorted, lane, tau)
                                 : fin_merge_window<FIN_EF>(a, pbase, ncand, T, k, two_eps, keys, sorted, lane, tau);
             merged = true;
@@ -494,18 +499,19 @@ __global__ __launch_bounds__(256, EWM == 1 ? ICD_FIN_OCC : 1) void finalize_kern
             mine[e] = (e < EW && idx < nres) ? sorted[idx] : 0ull;
             coarse[e] = mine[e] != 0ull ? key_score(mine[e]) : -INFINITY;
         }
-        // |coarse - canonical| <= eps for every row, in the coarse pass's scaled units 2^(qexp + cexp):
-        //   relative part: fp16 rounding of both operands (their images sit in fp16's normal range by construction; the
-        //   components that still underflow add at most 2^-25 sqrt(dim) (|q| + |c|), which both norms >= 1 turn into a
-        //   relative 3.3e-6: inside EPS_REL's margin) + fp32 accumulation of both chains;
+        // |coarse - canonical| <= eps for every row, in the coarse pass's scaled units 2^(qexp + cexp) (cert_bound.hpp):
+        //   rounding: q16.c16 - q'.c' = dq.c16 + q'.dc, so at most |dq| cmax16 + |q'| dcmax with the MEASURED residual norms of
+        //   the query (this call's prep) and of the corpus (icd_index_create) - about 2.1e-4 of the norm each on unit rows,
+        //   where the format's worst case is 4.9e-4;
+        //   summation: the MFMA chain of the coarse score and the canonical fmaf chain, acc_rel (|q'| + |dq|) cmax16;
         //   absolute part: the canonical chain runs on the UNSCALED fp32 data, where a result in fp32's subnormal range
         //   rounds to a multiple of 2^-149: <= dim * 2^-150 over the chain (2^-148 here), times the scale. For data
         //   anywhere near unit norm this term is 0; for data scaled by ~1e-38 it takes over and nothing is certified.
-        //   centred image (coarse = q.(c - mu) in scaled units): the rounding terms above are relative to the CENTRED rows
-        //   (rmax); the canonical chain still runs on the uncentred rows, and its own accumulation error - relative to THEIR
-        //   norm - is the second term (eps_f32 = 2 dim 2^-24 >= the chain's gamma_dim). q.mu is one constant per query: it
+        //   centred image (coarse = q.(c - mu) in scaled units): the terms above are relative to the CENTRED rows; the
+        //   canonical chain still runs on the uncentred rows, and its own accumulation error - relative to THEIR
+        //   norm - is the extra term (eps_f32 = 2 dim 2^-24 >= the chain's gamma_dim). q.mu is one constant per query: it
         //   shifts every coarse score of the query alike and never enters a comparison.
-        const float eps = fin_eps(a, qn_early, qexp_early);
+        const float eps = fin_eps(a, qn_early, qres_early, qexp_early);
         bool certified;
         float L;
         if (nres >= k) {

@@ -103,7 +103,6 @@ namespace {
         }                                                                                                                  \
     } while (0)
 
-constexpr float EPS_REL = 1.2e-3f;
 constexpr size_t PACE_WORDS = (size_t)1 << 18;   // arrival counters of a paced coarse sweep: classes x epochs (1 MB)
 constexpr size_t COARSE_CACHED_IMAGE_BYTES = (size_t)96 << 20;   // fp16 images up to this size take CF_CACHED_VAR (both corpus copies then fit the 256 MiB Infinity Cache)
 constexpr int FAST_MAX_K = 100;      // the rescoring window holds up to 256 candidates (four per lane): k + the rows inside 2 eps of the k-th
@@ -167,6 +166,7 @@ struct icd_index {
     bool fast = false;
     float rmax = 0.f;        // largest row norm (unscaled; reported by icd_index_stats)
     float rmax_scaled = 0.f; // largest norm of the scaled fp16 rows
+    float dcmax_scaled = 0.f;   // largest | scaled row - its fp16 image | (the certificate's measured rounding error, cert_bound.hpp)
     int cexp = 0;            // fp16 corpus = fp32 corpus * 2^cexp
     float *cmean = nullptr;  // [dim] column mean subtracted from the fp16 image (nullptr: not centred; coarse_common.hpp)
     float rmax_unc_scaled = 0.f;   // centred image: largest norm of the UNcentred rows, in the image's scale
@@ -180,6 +180,7 @@ struct icd_index {
     float *qdev = nullptr;  // staging for host queries
     _Float16 *q16 = nullptr;
     float *qnorm = nullptr;
+    float *qres = nullptr;   // [query] | scaled query - its fp16 image |
     int *qexp = nullptr;
     unsigned char *qbad = nullptr;
     float *thr0 = nullptr;   // [query] threshold an uncertified query hands to its exact re-search (finalize.hpp)
@@ -194,7 +195,7 @@ struct icd_index {
     int *h_nflag = nullptr;                          // pinned (mapped) host copy of nflag[4], written by the last kernel of every search
     int *h_nflag_dev = nullptr;                      // its device-side address
     hipEvent_t ev_nflag = nullptr;                   // recorded behind that copy: icd_index_stats waits for it and nothing else
-    unsigned int *scratch_u32 = nullptr;  // [0]=rmax bits, [1]=any_bad
+    unsigned int *scratch_u32 = nullptr;  // [0]=rmax bits, [1]=any_bad, [2]=largest component, [3]=largest uncentred norm, [4]=largest residual norm
     int *order = nullptr, *order_key = nullptr; unsigned int *order_hist = nullptr;   // wide-window finalize in family order (finalize.hpp, order_*_kernel)
     // output staging (used when the caller's buffers are host memory)
     float *o_scores = nullptr; long long *o_ids = nullptr;
@@ -266,7 +267,7 @@ namespace {
 void free_all(icd_index *x) {
     if (!x) return;
     hipFree(x->corpus); hipFree(x->c16); hipFree(x->levels); hipFree(x->qdev); hipFree(x->q16);
-    hipFree(x->qnorm); hipFree(x->qexp); hipFree(x->qbad); hipFree(x->thr0); hipFree(x->shared_thr); hipFree(x->partc_s); hipFree(x->partc_r); hipFree(x->partc_b); hipFree(x->partx_s);
+    hipFree(x->qnorm); hipFree(x->qres); hipFree(x->qexp); hipFree(x->qbad); hipFree(x->thr0); hipFree(x->shared_thr); hipFree(x->partc_s); hipFree(x->partc_r); hipFree(x->partc_b); hipFree(x->partx_s);
     hipFree(x->part2_s); hipFree(x->part2_r); hipFree(x->part2_b);
     hipFree(x->partx_r); hipFree(x->lists_s); hipFree(x->lists_r); hipFree(x->nflag); hipFree(x->flagged); hipFree(x->scratch_u32);
     hipFree(x->order); hipFree(x->order_key); hipFree(x->order_hist); hipFree(x->cmean);
@@ -609,7 +610,8 @@ SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use
     c.row_tiles = (int)((x->n + 127) / 128);
     FinArgs &f = c.f;
     f.k = k; f.queries = dq; f.corpus = x->corpus; f.dim = x->dim; f.qnorm = x->qnorm; f.qbad = x->qbad;
-    f.qexp = x->qexp; f.rmax = x->rmax_scaled; f.cexp = x->cexp; f.eps_rel = EPS_REL; f.nflag = x->nflag; f.flagged = x->flagged;
+    f.qexp = x->qexp; f.qres = x->qres; f.cexp = x->cexp; f.nflag = x->nflag; f.flagged = x->flagged;
+    f.cmax16 = cert_cmax16(x->rmax_scaled, x->dcmax_scaled); f.dcmax = x->dcmax_scaled; f.acc_rel = cert_acc_rel(x->dim);
     if (use_fast) f.thr0 = x->thr0;
     if (x->cmean) { f.rmax_unc = x->rmax_unc_scaled; f.eps_f32 = 2.0f * (float)x->dim * 5.9604645e-8f; }
     f.levels = x->levels; f.id_base = x->id_base; f.row_map = x->row_map;
@@ -899,7 +901,7 @@ int auto_prep(const SearchCtx &c, int nq_pad) {
     icd_index *x = c.x;
     ConvertArgs cv{};
     cv.src = c.dq; cv.dst = x->q16; cv.rows = c.nq; cv.rows_pad = nq_pad; cv.dim = x->dim; cv.mode = 0;
-    cv.norm = x->qnorm; cv.scale_exp = x->qexp; cv.bad = x->qbad; cv.zero_u32 = x->shared_thr; cv.zero_i32 = x->nflag;
+    cv.norm = x->qnorm; cv.res = x->qres; cv.scale_exp = x->qexp; cv.bad = x->qbad; cv.zero_u32 = x->shared_thr; cv.zero_i32 = x->nflag;
     cv.zero_u32b = x->shared_thr + x->max_nq_pad;
     hipLaunchKernelGGL(convert_rows_kernel, dim3((nq_pad + 3) / 4), dim3(256), 0, c.s, cv);
     HIP_TRY(hipGetLastError());
@@ -1254,8 +1256,8 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
         if (levels)
             CR_TRY(hipMemcpy(x->levels, levels, (size_t)n * sizeof(int), corpus_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     }
-    CR_TRY(dmalloc(&x->scratch_u32, 4));
-    CR_TRY(hipMemset(x->scratch_u32, 0, 4 * sizeof(unsigned)));
+    CR_TRY(dmalloc(&x->scratch_u32, 8));
+    CR_TRY(hipMemset(x->scratch_u32, 0, 8 * sizeof(unsigned)));
     size_t ws = 0;
     auto wsalloc = [&](auto **p, size_t count) -> hipError_t {
         hipError_t e = dmalloc(p, count);
@@ -1300,19 +1302,20 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
         cv.amax_bits = x->scratch_u32 + 2; cv.any_bad = x->scratch_u32 + 1; cv.mode = 2;
         hipLaunchKernelGGL(convert_rows_kernel, dim3((x->n_pad + 3) / 4), dim3(256), 0, 0, cv);
         CR_TRY(hipGetLastError());
-        unsigned hv[4] = {0, 0, 0, 0};
+        unsigned hv[5] = {0, 0, 0, 0, 0};
         CR_TRY(hipMemcpy(hv, x->scratch_u32, sizeof hv, hipMemcpyDeviceToHost));
         float amax = 0.f;
         memcpy(&amax, &hv[2], 4);
         x->cexp = scale_exp_for(amax);
         cv.mode = 1; cv.fixed_exp = x->cexp; cv.amax_bits = nullptr;
-        cv.rmax_bits = x->scratch_u32;
+        cv.rmax_bits = x->scratch_u32; cv.resmax_bits = x->scratch_u32 + 4;
         if (x->cmean) cv.norm_raw_max = reinterpret_cast<float *>(x->scratch_u32 + 3);
         cv.perm_mul = x->perm_mul; cv.perm_mod = x->perm_mod;
         hipLaunchKernelGGL(convert_rows_kernel, dim3((x->n_pad + 3) / 4), dim3(256), 0, 0, cv);
         CR_TRY(hipGetLastError());
         CR_TRY(hipMemcpy(hv, x->scratch_u32, sizeof hv, hipMemcpyDeviceToHost));
         memcpy(&x->rmax_scaled, &hv[0], 4);
+        memcpy(&x->dcmax_scaled, &hv[4], 4);
         x->rmax = ldexpf(x->rmax_scaled, -x->cexp);
         if (x->cmean) {   // (rmax as reported stays the largest UNcentred norm; the certificate uses both)
             float raw = 0.f;
@@ -1338,6 +1341,7 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
         CR_TRY(wsalloc(&x->part2_b, x->part2_cap / CO_KP));
     }
     CR_TRY(wsalloc(&x->qnorm, (size_t)x->max_nq_pad));
+    CR_TRY(wsalloc(&x->qres, (size_t)x->max_nq_pad));
     CR_TRY(wsalloc(&x->qexp, (size_t)x->max_nq_pad));
     CR_TRY(wsalloc(&x->qbad, (size_t)x->max_nq_pad));
     CR_TRY(wsalloc(&x->thr0, (size_t)x->max_nq_pad));
@@ -1761,6 +1765,24 @@ int icd_index_stats(icd_index *idx, icd_stats *out) {
     out->sparse_fallback_armed = idx->pol.sparse_disarmed ? 0 : 1;
     out->centered = idx->cmean ? 1 : 0; out->mean_share = idx->mean_share;
     out->last_chunks = idx->last_chunks; out->last_mode = idx->last_mode;
+    return ICD_OK;
+}
+
+int icd_index_cert_terms(icd_index *idx, float *cmax, float *dcmax, int32_t *cexp, float *qnorm, float *qres, int64_t count) {
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    std::lock_guard<std::mutex> guard(idx->mu);
+    if (!idx->fast) return fail(ICD_ERR_INVALID, "the index has no fp16 image");
+    if (count < 0 || count > idx->max_nq_pad || ((qnorm || qres) && count > idx->last_nq))
+        return fail(ICD_ERR_INVALID, "count=%lld exceeds the last search's batch", (long long)count);
+    if (cmax) *cmax = idx->rmax_scaled;
+    if (dcmax) *dcmax = idx->dcmax_scaled;
+    if (cexp) *cexp = idx->cexp;
+    if (count > 0 && (qnorm || qres)) {
+        HIP_TRY(hipSetDevice(idx->device));
+        HIP_TRY(hipDeviceSynchronize());
+        if (qnorm) HIP_TRY(hipMemcpy(qnorm, idx->qnorm, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+        if (qres) HIP_TRY(hipMemcpy(qres, idx->qres, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    }
     return ICD_OK;
 }
 
