@@ -307,6 +307,20 @@ __device__ __forceinline__ void compact_all_parallel(char *smem, Sel2 &st, uint3
 //   33554432  diagnostic: every wave stamps s_memtime / s_memrealtime once at its start and once at its end and leaves the two
 //        differences in CoarseFlatArgs::dbg: the in-kernel clock the chip holds under this kernel (MI355X_MICROARCH.md,
 //        DVFS give-back item 6); nothing inside the loops changes
+//   134217728  LOOK-AHEAD quad tests. The quad select pays one VALU -> SGPR -> SALU -> branch round trip per quad (four v_cmp,
+//        three s_or_b64, s_cbranch: ~50 cycles with nothing to hide them at one wave per SIMD), sixteen in a row per tile.
+//        With this bit a tile's quads go in blocks of 4 (+ 268435456: of 8): the compares of ALL the block's quads are
+//        issued back to back (asm volatile: the compiler would sink them to their uses), then the block is walked with
+//        scalar code only - OR of the quad's four masks, branch, the exec-masked appends from the masks already in SGPRs.
+//        Only the first quad of a block waits for its compares. The masks of a block are made against the threshold at
+//        the block's start: a compaction inside the block (the overflow guard stays behind every second quad) may raise
+//        the threshold under them, and the later quads of the block then append some entries at or below it. That is
+//        legal (see filter_block) and costs a few appends.
+//   536870912  (with 134217728) the test of a quad is ONE compare of its lane maximum (v_max3 + v_max + v_cmp) instead of four
+//        compares and three ORs; the four per-register compares run only inside a quad that passes
+//   1073741824  (with 134217728) the overflow guard behind every second quad tests "appended more than the quota" with one
+//        v_sad_u32 (|aw - aw0|) and one compare instead of two subtractions, a select and the compare: the guard is the other
+//        VALU -> SALU round trip of the select (eight per tile) and its whole VALU chain is in front of the branch
 //   TIMING ONLY (the results are not the scores; they size the parts of the kernel, profiles/r02_coarse_loop_decomposition.log):
 //   256 no s_barrier   512 no wait for the LDS-DMA pieces   4096 thresholds at +inf (nothing passes)
 //   8192 no select at all   16384 no LDS-DMA inside the tile loop   65536 (with 32768) no lane swaps
@@ -319,7 +333,11 @@ constexpr int CF_PRODUCT_VAR = 1 + 2 + 8 + 128 + 16 + 2048 + 32768;   // measure
 // (profiles/r04_ab_coarse_variants.log): 10 000 x 37 000 -0.9 ... -2.6 %, the family corpus in wide mode (a third of a
 // list's tiles are bootstrap tiles) -3 %; on a 1.25 M-row shard streamed from HBM the later issue of half the pieces costs
 // +6 % (less run-ahead for a longer latency), so shards keep CF_PRODUCT_VAR (icd_search.hip picks by the image's size).
-constexpr int CF_CACHED_VAR = CF_PRODUCT_VAR + 2097152 + 4194304;
+// + the look-ahead quad tests in blocks of 8 with the one-compare overflow guard (profiles/coarse_lookahead_ab.log: blocks of 8
+// take 2.4 % off the kernel, blocks of 4 1.7 %; the one-compare test of the quad maximum wins on blocks of 4 and nothing on
+// blocks of 8; the guard takes another 0.6 % off the step). Measured on this kernel only: the HBM-streamed and wide-list
+// instantiations keep the quad-by-quad select.
+constexpr int CF_CACHED_VAR = CF_PRODUCT_VAR + 2097152 + 4194304 + 134217728 + 268435456 + 1073741824;
 // images streamed from HBM (row shards): the classes are paced (VAR list, 67108864)
 constexpr int CF_PACED_VAR = CF_PRODUCT_VAR + 67108864;
 __host__ __device__ constexpr int cf_ring_stages(int var) { return (var & 1048576) ? 6 : CO_S; }
@@ -361,6 +379,13 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
     constexpr bool PACE = (VAR & 67108864) != 0;
     static_assert(!PACE || (EARLY_THR && EXCH == 1 && !PERSIST), "the pace poll rides on the early threshold load of every tile");
     static_assert(!(CLOCKS && STAMPS), "one use of the debug buffer at a time");
+    constexpr bool LOOKAHEAD = (VAR & 134217728) != 0;
+    constexpr int LA_B = (VAR & 268435456) ? 8 : 4;      // quads per look-ahead block
+    constexpr bool LA_MAX = (VAR & 536870912) != 0;
+    static_assert(!LOOKAHEAD || (QUAD && X16 && !SPARSE_PRE), "the look-ahead tests are built on the quad select of the 16x16x32 form");
+    constexpr bool LA_GUARDX = (VAR & 1073741824) != 0;
+    static_assert(LOOKAHEAD || (VAR & (268435456 | 536870912 | 1073741824)) == 0, "sub-flags of the look-ahead bit");
+    static_assert(!LA_GUARDX || !DIRTY_GUARD, "one form of the overflow guard");
     constexpr int S = cf_ring_stages(VAR);            // ring slots
     constexpr int VM_MID = NOVM ? 63 : (PAIRBAR ? 4 : 4 * (S - 3));   // LDS-DMA pieces that may stay in flight at the mid-stage wait
     constexpr int PRO = PAIRBAR ? 4 : S - 1;          // stages issued by a list's prologue
@@ -430,6 +455,7 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
     const uint32_t wave_scratch = RING_BYTES + (uint32_t)CO_BM * Ops::QBYTES + (uint32_t)wave * 256u;
     unsigned long long st_vm = 0, st_bar = 0, st_body = 0, st_sel = 0, st_tiles = 0, st_prev = 0;   // (STAMPS)
     unsigned long long st_comp[2] = {0, 0}, st_thr = 0, st_boot = 0;                              // compactions, their cycles
+    [[maybe_unused]] unsigned long long st_app = 0;                                                 // appended entries (all lanes)
     const int last_tile = a.ctiles - 1;
 
     half8 qf[NF];
@@ -547,6 +573,54 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
             }
         };
 
+        // LOOKAHEAD (filter_block below): the four appends of a quad under its four masks and the overflow guard, the same
+        // instructions as in filter_quad (whose text stays as it is, so that the kernels without the bit compile as before)
+        [[maybe_unused]] auto append_quad = [&](unsigned long long m0, unsigned long long m1, unsigned long long m2, unsigned long long m3,
+                               float v0, float v1, float v2, float v3, uint32_t rowq) {
+            uint32_t r1, r2, r3, aw = st.aw;
+            const uint32_t inc = st.inc;
+            asm volatile("v_or_b32_e32 %1, 1, %12\n\t"
+                         "v_or_b32_e32 %2, 2, %12\n\t"
+                         "v_or_b32_e32 %3, 3, %12\n\t"
+                         "s_mov_b64 exec, %4\n\t"
+                         "ds_write2st64_b32 %0, %8, %12 offset1:1\n\t"
+                         "v_add_u32_e32 %0, %0, %13\n\t"
+                         "s_mov_b64 exec, %5\n\t"
+                         "ds_write2st64_b32 %0, %9, %1 offset1:1\n\t"
+                         "v_add_u32_e32 %0, %0, %13\n\t"
+                         "s_mov_b64 exec, %6\n\t"
+                         "ds_write2st64_b32 %0, %10, %2 offset1:1\n\t"
+                         "v_add_u32_e32 %0, %0, %13\n\t"
+                         "s_mov_b64 exec, %7\n\t"
+                         "ds_write2st64_b32 %0, %11, %3 offset1:1\n\t"
+                         "v_add_u32_e32 %0, %0, %13\n\t"
+                         "s_mov_b64 exec, -1"
+                         : "+v"(aw), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+                         : "s"(m0), "s"(m1), "s"(m2), "s"(m3), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(rowq), "v"(inc)
+                         : "memory");
+            st.aw = aw;
+            if constexpr (DIRTY_GUARD) dirty = 1;
+            if constexpr (STAMPS) st_app += (unsigned long long)(__builtin_popcountll(m0) + __builtin_popcountll(m1) + __builtin_popcountll(m2) + __builtin_popcountll(m3));
+        };
+        [[maybe_unused]] auto quad_guard = [&]() {
+            if constexpr (LA_GUARDX) {
+                // used > CO_QUOTA as |aw - aw0| > 4 CO_QUOTA: the low lane grows up from aw0, the high lane down, and v_sad_u32
+                // gives the distance of either in one instruction (Ops::used: two subtractions and a select by the half)
+                const uint32_t aw = st.aw, aw0 = st.aw0;
+                uint32_t dist;
+                asm("v_sad_u32 %0, %1, %2, 0" : "=v"(dist) : "v"(aw), "v"(aw0));
+                if (__builtin_amdgcn_ballot_w64(dist > 4u * (uint32_t)CO_QUOTA) != 0ull)
+                    Ops::template check<PAIRBAR>(st, lane, smem, wave_qbase, wave_scratch, false, CO_LIMIT, STAMPS ? st_comp : nullptr, CO_QUOTA);
+            } else
+            if constexpr (DIRTY_GUARD) {
+                if (dirty) {
+                    dirty = 0;
+                    if (__builtin_amdgcn_ballot_w64(Ops::used(st, h) > CO_QUOTA) != 0ull)
+                        Ops::template check<PAIRBAR>(st, lane, smem, wave_qbase, wave_scratch, false, CO_LIMIT, STAMPS ? st_comp : nullptr, CO_QUOTA);
+                }
+            } else if (__builtin_amdgcn_ballot_w64(Ops::used(st, h) > CO_QUOTA) != 0ull)
+                Ops::template check<PAIRBAR>(st, lane, smem, wave_qbase, wave_scratch, false, CO_LIMIT, STAMPS ? st_comp : nullptr, CO_QUOTA);
+        };
         auto filter_quad = [&](const f32x16 (&pa)[X16 ? 1 : 4], const f32x4 (&px)[X16 ? 16 : 1], auto Q, uint32_t rowbase, auto GUARD) {
             constexpr int q = decltype(Q)::value;
             constexpr int t = q >> 2, g = q & 3;
@@ -587,6 +661,7 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
                              : "s"(m0), "s"(m1), "s"(m2), "s"(m3), "v"(v0), "v"(v1), "v"(v2), "v"(v3), "v"(rowq), "v"(st.inc)
                              : "memory");
                 if constexpr (DIRTY_GUARD) dirty = 1;
+                if constexpr (STAMPS) st_app += (unsigned long long)(__builtin_popcountll(m0) + __builtin_popcountll(m1) + __builtin_popcountll(m2) + __builtin_popcountll(m3));
             }
             if constexpr (q % 2 == 1) {   // every 8 registers: the overflow guard of filter_reg
                 if constexpr (DIRTY_GUARD) {
@@ -614,6 +689,69 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
                 filter_quad(pa, px, std::integral_constant<int, 2 * g>{}, rowbase, GUARD);
                 filter_quad(pa, px, std::integral_constant<int, 2 * g + 1>{}, rowbase, GUARD);
             }
+        };
+        // LOOKAHEAD: quads Q0 .. Q0 + LA_B - 1. Test phase: the compares of the whole block, back to back, into SGPR masks
+        // (asm volatile keeps them here and in this order; as ballots the compiler sinks each to its branch). Walk phase:
+        // scalar code only up to a passing quad's appends, which run from the masks made above.
+        // STALE THRESHOLDS: a compaction inside the block (quad_guard, behind every second quad as before) may raise st.thr
+        // after the masks were made, so a later quad of the block can append entries at or below the new threshold. The
+        // buffer already holds such entries whenever a threshold is adopted (flush_emit_parallel: "candidates like any
+        // other"): the next compaction or the flush drops them with everything else at or below its cut, the list's bound
+        // is still the threshold it ends on and still bounds everything dropped. The appends happen in the same order with
+        // the same guards between them, at most 8 registers' worth per lane between two guards: the overflow quota holds.
+        // Rows past the corpus: the compares read the masked values, the appends the raw ones (a pad row's mask bit is 0).
+        auto filter_block = [&](const f32x4 (&px)[X16 ? 16 : 1], auto Q0, uint32_t rowbase, auto GUARD) {
+            constexpr int q0 = decltype(Q0)::value;
+            unsigned long long m[LA_B][LA_MAX ? 1 : 4];
+            auto masked = [&](auto Q, auto I) {   // register I of quad Q as the test sees it
+                constexpr int q = decltype(Q)::value, i = decltype(I)::value;
+                float v = px[X16 ? q : 0][i];
+                if constexpr (decltype(GUARD)::value) {
+                    if ((int)(rowbase + (uint32_t)(16 * (q >> 1) + 4 * (q & 1) + i)) >= a.n) v = -INFINITY;
+                }
+                return v;
+            };
+            using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+            using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+            auto cmp4 = [&](auto Q, unsigned long long &m0, unsigned long long &m1, unsigned long long &m2, unsigned long long &m3) {
+                // (operands are locals: an asm operand alone does not capture a variable of an enclosing lambda)
+                const float t0 = masked(Q, I0{}), t1 = masked(Q, I1{}), t2 = masked(Q, I2{}), t3 = masked(Q, I3{}), thr = st.thr;
+                asm volatile("v_cmp_gt_f32_e64 %0, %4, %8\n\t"
+                             "v_cmp_gt_f32_e64 %1, %5, %8\n\t"
+                             "v_cmp_gt_f32_e64 %2, %6, %8\n\t"
+                             "v_cmp_gt_f32_e64 %3, %7, %8"
+                             : "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3)
+                             : "v"(t0), "v"(t1), "v"(t2), "v"(t3), "v"(thr));
+            };
+            static_for<0, LA_B>([&](auto J) {
+                using Q = std::integral_constant<int, q0 + decltype(J)::value>;
+                constexpr int j = decltype(J)::value;
+                if constexpr (LA_MAX) {
+                    const float mx = raw_max_f32(raw_max3_f32(masked(Q{}, I0{}), masked(Q{}, I1{}), masked(Q{}, I2{})), masked(Q{}, I3{}));
+                    const float thr = st.thr;
+                    unsigned long long mq;
+                    asm volatile("v_cmp_gt_f32_e64 %0, %1, %2" : "=s"(mq) : "v"(mx), "v"(thr));
+                    m[j][0] = mq;
+                } else cmp4(Q{}, m[j][0], m[j][LA_MAX ? 0 : 1], m[j][LA_MAX ? 0 : 2], m[j][LA_MAX ? 0 : 3]);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<0, LA_B>([&](auto J) {
+                constexpr int j = decltype(J)::value, q = q0 + j;
+                using Q = std::integral_constant<int, q>;
+                const uint32_t rowq = rowbase + (uint32_t)(16 * (q >> 1) + 4 * (q & 1));
+                const f32x4 &x = px[X16 ? q : 0];
+                if constexpr (LA_MAX) {
+                    if (__builtin_expect(m[j][0] != 0ull, 0)) {   // (the four masks against the threshold as it is now)
+                        unsigned long long m0, m1, m2, m3;
+                        cmp4(Q{}, m0, m1, m2, m3);
+                        append_quad(m0, m1, m2, m3, x[0], x[1], x[2], x[3], rowq);
+                    }
+                } else {
+                    const unsigned long long m0 = m[j][0], m1 = m[j][LA_MAX ? 0 : 1], m2 = m[j][LA_MAX ? 0 : 2], m3 = m[j][LA_MAX ? 0 : 3];
+                    if (__builtin_expect(((m0 | m1) | (m2 | m3)) != 0ull, 0)) append_quad(m0, m1, m2, m3, x[0], x[1], x[2], x[3], rowq);
+                }
+                if constexpr (q % 2 == 1) quad_guard();
+            });
         };
 
         // prologue: stages 0..S-2 in flight, stage 0 published, its first fragments read
@@ -921,6 +1059,9 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) asm volatile("" ::"v"(acc[X16 ? 0 : t]));
                 }
+            } else if constexpr (LOOKAHEAD) {
+                if (tile_row0 + CO_BN > a.n) static_for<0, 16 / LA_B>([&](auto Bk) { filter_block(xs, std::integral_constant<int, LA_B * decltype(Bk)::value>{}, rowbase, std::true_type{}); });
+                else static_for<0, 16 / LA_B>([&](auto Bk) { filter_block(xs, std::integral_constant<int, LA_B * decltype(Bk)::value>{}, rowbase, std::false_type{}); });
             } else if constexpr (QUAD) {
                 if (tile_row0 + CO_BN > a.n) static_for<0, 16>([&](auto Q) { filter_quad(acc, xs, Q, rowbase, std::true_type{}); });
                 else if (SPARSE_PRE && tile >= a.sparse_from) static_for<0, 8>([&](auto G) { filter_group(acc, xs, G, rowbase, std::false_type{}); });
@@ -979,7 +1120,7 @@ __global__ __launch_bounds__(256, 1) void coarse_flat_kernel(CoarseFlatArgs a) {
     if constexpr (STAMPS) {
         if (lane == 0 && a.dbg) {
             unsigned long long *d = a.dbg + ((size_t)blockIdx.x * 4 + wave) * 8;
-            d[0] = st_vm; d[1] = st_bar; d[2] = st_body; d[3] = st_sel; d[4] = st_tiles; d[5] = st_comp[0]; d[6] = st_comp[1];
+            d[0] = st_vm; d[1] = st_bar; d[2] = st_body; d[3] = st_sel; d[4] = (st_app << 32) | (st_tiles & 0xffffffffull); d[5] = st_comp[0]; d[6] = st_comp[1];
             d[7] = (st_thr << 32) | (st_boot & 0xffffffffull);
         }
     }

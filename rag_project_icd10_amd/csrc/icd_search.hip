@@ -561,6 +561,9 @@ bool launch_coarse_variant(icd_index *x, const SearchOverrides &ov, const Coarse
     if (false) {}
 #define ICD_FV_CASE(V) else if (v == V) *rc = launch_coarse_flat<768, V>(x, a, nwg, s);
 #ifdef ICD_FV_LIST
+    // (the look-ahead select's A/B, profiles/coarse_lookahead_ab.log: 6326427 = CF_CACHED_VAR without it, + 134217728 blocks of
+    //  4, + 268435456 blocks of 8, + 536870912 the quad-maximum test; each also + 4096 for the compare path alone and + 1024 for
+    //  the stamps and the append count)
     ICD_FV_LIST
 #else
     ICD_FV_CASE(0) ICD_FV_CASE(139) ICD_FV_CASE(143) ICD_FV_CASE(155) ICD_FV_CASE(171) ICD_FV_CASE(187) ICD_FV_CASE(2187) ICD_FV_CASE(2203)
