@@ -512,6 +512,62 @@ int icd_sparse_match_rowmasks(icd_index *idx, icd_sparse *sp, const int64_t *q_o
 int icd_rowmask_read(icd_rowmask *m, uint32_t *out_words, int64_t out_count);
 
 /*
+ * Filter expressions on the device: the row masks of a batch of boolean filter programs, one per query, any shape of AND / OR / NOT
+ * over integer predicates on the rows' columns and keyword matches on the sparse index. DESIGN.md section 18.
+ *
+ * icd_columns: `ncols` int32 columns of the n rows of ONE index (not a view: ICD_ERR_UNSUPPORTED, as is n >= 2^31), uploaded once
+ * from the HOST array cols[ncols][n] (1 <= ncols <= ICD_FILTER_MAX_COLUMNS). The library knows only "int32 column c": what a value
+ * means (a level, a flag, the rank of a string among the sorted distinct strings) is the caller's. The handle keeps no pointer into
+ * its index - it is compared, never followed - and either may be destroyed first. icd_columns_stats: columns, rows, device bytes
+ * (any pointer may be NULL).
+ *
+ * A program is a postfix sequence of operations over a stack of row sets; query q's program is the uint32 words
+ * prog[prog_off[q] .. prog_off[q + 1]) (prog_off[0] = 0). The first word of an operation holds its kind in bits 0 .. 7:
+ *   ICD_FILTER_RANGE  { 1, col, lo, hi }                         push the rows with lo <= column[col][row] < hi; lo and hi are int32
+ *                                                                bit patterns, lo >= hi is the empty set
+ *   ICD_FILTER_SET    { 2 | count << 8, col, ids[count] }        push the rows whose value is one of ids (int32 bit patterns, strictly
+ *                                                                increasing as int32); count 0 .. 64, 0 is the empty set
+ *   ICD_FILTER_TEXT   { 3 | count << 8 | m << 16, terms[count] } push the rows that hold at least m of the terms, under
+ *                                                                icd_sparse_match_rowmasks' rules: terms strictly increasing and
+ *                                                                below the vocabulary, count 0 .. 64, m 1 .. 64; m > count is the
+ *                                                                empty set. Needs the sparse index.
+ *   ICD_FILTER_AND { 4 }, ICD_FILTER_OR { 5 }                    pop two sets, push their intersection / union
+ *   ICD_FILTER_NOT { 6 }                                         replace the top set by its complement within the index's n rows
+ * All other bits of a first word are 0. A program holds 1 .. 32 operations, at most 16 leaves (RANGE, SET, TEXT) of which at most
+ * 4 are TEXT, never more than 8 sets on the stack, never pops from an empty stack and ends with exactly ONE set: mask q.
+ *
+ * icd_filter_program_check (host only: no device, no handle): validates nq programs against `ncols` columns and a vocabulary of
+ * `vocab` terms (0: no sparse index - a TEXT leaf is refused): structure, stack discipline and every bound above. ICD_OK, or
+ * ICD_ERR_INVALID with the reason in msg (msg_len bytes, NUL-terminated; msg may be NULL) and in icd_last_error.
+ *
+ * icd_filter_rowmasks: creates nq masks of `idx` with ONE launch of filter_mask_kernel over (query, tile) on `stream`; mask q = the
+ * program's set AND (base_masks[q] != NULL) that base mask. sparse: the index's sparse index, or NULL when no program holds a TEXT
+ * leaf. Programs always come from HOST memory and are checked (icd_filter_program_check's rules) before any device call. The masks
+ * are ordinary icd_rowmask handles, exactly as icd_sparse_match_rowmasks makes them: every masked entry point accepts them,
+ * icd_rowmask_stats reports the row count the kernel counted, icd_rowmask_read their words, icd_rowmask_destroy frees them - each
+ * alone, in any order, before or after the index, the columns and the sparse index (the bitsets of one call share one allocation,
+ * released with the last of them). The call allocates and synchronises `stream` before it returns: not graph-capturable
+ * (ICD_ERR_INVALID while `stream` is capturing). On any error no mask is created and every out_masks[q] is NULL.
+ * ICD_ERR_INVALID: a program the checker refuses (a TEXT leaf with sparse = NULL among them), columns, a sparse index or a base
+ * mask created for another index, NULL arrays. ICD_ERR_STATE: a destroyed index, columns, sparse index or base mask.
+ * ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 creates nothing.
+ */
+typedef struct icd_columns icd_columns;
+#define ICD_FILTER_MAX_COLUMNS 256
+#define ICD_FILTER_RANGE 1
+#define ICD_FILTER_SET 2
+#define ICD_FILTER_TEXT 3
+#define ICD_FILTER_AND 4
+#define ICD_FILTER_OR 5
+#define ICD_FILTER_NOT 6
+int icd_columns_create(icd_index *idx, const int32_t *cols, int32_t ncols, icd_columns **out);
+int icd_columns_destroy(icd_columns *columns);
+int icd_columns_stats(icd_columns *columns, int32_t *out_ncols, int64_t *out_rows, int64_t *out_bytes);
+int icd_filter_program_check(const int64_t *prog_off, const uint32_t *prog, int64_t nq, int32_t ncols, int64_t vocab, char *msg, int64_t msg_len);
+int icd_filter_rowmasks(icd_index *idx, icd_columns *columns, icd_sparse *sparse, const int64_t *prog_off, const uint32_t *prog, int64_t nq,
+                        icd_rowmask *const *base_masks, icd_rowmask **out_masks, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

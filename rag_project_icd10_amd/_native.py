@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "icd_grouping_pair_sparse", "icd_sparse_search_grouped", "icd_index_search_hybrid_grouped", "icd_fusion_fuse_lists_grouped",
     "icd_sparse_search_range",
     "icd_sparse_match_rowmasks", "icd_rowmask_read",
+    "icd_columns_create", "icd_columns_destroy", "icd_columns_stats", "icd_filter_program_check", "icd_filter_rowmasks",
 )
 SPARSE_MAX_QUERY_TERMS = 64   # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
@@ -145,6 +146,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_grouping_pair_sparse.argtypes = [vp, vp, vp]
     lib.icd_sparse_match_rowmasks.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
     lib.icd_rowmask_read.argtypes = [vp, vp, i64]
+    lib.icd_columns_create.argtypes = [vp, vp, i32, C.POINTER(vp)]
+    lib.icd_columns_destroy.argtypes = [vp]
+    lib.icd_columns_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_filter_program_check.argtypes = [vp, vp, i64, i32, i64, vp, i64]
+    lib.icd_filter_rowmasks.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
@@ -825,6 +831,36 @@ class IcdIndex:
         _check(self._lib, rc)
         return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
 
+    def columns(self, cols) -> "IcdColumns":
+        """int32 columns of this index's rows on the device (icd_columns_*): cols [ncols, n]"""
+        return IcdColumns(self, cols)
+
+    def filter_masks(self, columns: "IcdColumns", sparse, prog_off, prog, base_masks=None) -> list:
+        """The row masks of a batch of filter programs (icd_filter_rowmasks), one IcdRowMask per query, built
+        on the device in one launch: query q's program is the uint32 words prog[prog_off[q] : prog_off[q + 1]] in
+        include/icd_search.h's layout (services/filter_expr.device_program writes them) over `columns` and - for TEXT leaves -
+        the sparse index `sparse` (None: no program holds one). base_masks: None, ONE IcdRowMask for every query, or nq of
+        IcdRowMask or None, ANDed in. Host arrays, checked by the library (ValueError). The masks are ordinary row masks of this
+        index: every masked search takes them; close() them (or drop them) when the search they were made for is done."""
+        if self.closed or columns is None or columns.closed or (sparse is not None and sparse.closed):
+            raise IcdError(-5, "index, columns or sparse index is closed")
+        off = np.ascontiguousarray(np.asarray(prog_off).reshape(-1), dtype=np.int64)
+        pr = np.ascontiguousarray(np.asarray(prog).reshape(-1), dtype=np.uint32)
+        nq = int(off.size) - 1
+        if nq < 0 or (nq > 0 and int(off[-1]) != pr.size):
+            raise ValueError("prog_off must hold nq + 1 offsets that end at the number of program words")
+        base_h = None if base_masks is None else _mask_table(base_masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
+        if nq == 0:
+            return []
+        out = (C.c_void_p * nq)()
+        rc = self._lib.icd_filter_rowmasks(self._h, columns._h, None if sparse is None else sparse._h, off.ctypes.data,
+                                           pr.ctypes.data if pr.size else off.ctypes.data, nq,
+                                           None if base_h is None else base_h.ctypes.data, C.cast(out, C.c_void_p), None)
+        if rc == -1:
+            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+        _check(self._lib, rc)
+        return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
+
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""
         import torch
@@ -1018,6 +1054,43 @@ class IcdSparse(_Handle):
         vv, nn, bb = C.c_int64(), C.c_int64(), C.c_int64()
         _check(self._lib, self._lib.icd_sparse_stats(self._h, C.byref(vv), C.byref(nn), C.byref(bb)))
         return {"vocab": vv.value, "nnz": nn.value, "bytes": bb.value}
+
+
+class IcdColumns(_Handle):
+    """int32 columns of the rows of one IcdIndex on the device (icd_columns_*): what the filter programs of IcdIndex.filter_masks
+    read. Independent of the index's lifetime: either may be closed first (a call with a closed partner raises)."""
+    _destroy = "icd_columns_destroy"
+
+    def __init__(self, index: "IcdIndex", cols):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        keep = np.ascontiguousarray(np.asarray(cols), dtype=np.int32)
+        if keep.ndim != 2 or keep.shape[0] < 1 or keep.shape[1] != index.n:
+            raise ValueError(f"cols of shape {keep.shape}: [ncols >= 1, n = {index.n}]")
+        self.n, self.ncols, self.device = index.n, int(keep.shape[0]), index.device
+        rc = self._lib.icd_columns_create(index._h, keep.ctypes.data, self.ncols, C.byref(self._h))
+        if rc == -1:
+            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+        _check(self._lib, rc)
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "columns are closed")
+        c, r, b = C.c_int32(), C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_columns_stats(self._h, C.byref(c), C.byref(r), C.byref(b)))
+        return {"ncols": c.value, "rows": r.value, "bytes": b.value}
+
+
+def filter_program_check(prog_off, prog, ncols: int, vocab: int = 0):
+    """icd_filter_program_check (host only): None when the nq programs are well-formed for `ncols` columns and a vocabulary of
+    `vocab` terms (0: no sparse index), else the library's reason"""
+    lib = load_library()
+    off = np.ascontiguousarray(np.asarray(prog_off).reshape(-1), dtype=np.int64)
+    pr = np.ascontiguousarray(np.asarray(prog).reshape(-1), dtype=np.uint32)
+    msg = C.create_string_buffer(256)
+    rc = lib.icd_filter_program_check(off.ctypes.data, pr.ctypes.data if pr.size else None, int(off.size) - 1, int(ncols), int(vocab),
+                                      C.cast(msg, C.c_void_p), len(msg))
+    return None if rc == 0 else msg.value.decode("utf-8", "replace")
 
 
 def rowmask_words(n: int) -> int:

@@ -364,6 +364,7 @@ class Columns:
         self._sel: "OrderedDict[str, np.ndarray]" = OrderedDict()
         self._groups: Dict[str, Any] = {}
         self._matchers: Dict[str, Any] = {}
+        self._device_cols = None   # (device_columns(),) once built
         self._lock = threading.Lock()
 
     @classmethod
@@ -399,6 +400,26 @@ class Columns:
         out[0].setflags(write=False)
         with self._lock:
             self._groups[field] = out
+        return out
+
+    def device_columns(self):
+        """int32 [len(DEVICE_COLUMNS), n], C-contiguous: what IcdColumns uploads. A string field goes in as
+        group_ids(field) - the rank of the row's value among the sorted distinct values -, level as it is, has_complication as
+        0 / 1. None when a level does not fit (INT32_MIN, INT32_MAX): such a store keeps the host route. Cached."""
+        with self._lock:
+            hit = self._device_cols
+        if hit is not None:
+            return hit[0]
+        level = self.arrays["level"]
+        if self.n and (int(level.min()) <= _I32_MIN or int(level.max()) >= _I32_MAX):
+            out = None
+        else:
+            out = np.empty((len(DEVICE_COLUMNS), self.n), np.int32)
+            for c, f in enumerate(DEVICE_COLUMNS):
+                out[c] = self.group_ids(f)[0] if f in STRING_FIELDS else self.arrays[f].astype(np.int32)
+            out.setflags(write=False)
+        with self._lock:
+            self._device_cols = (out,)
         return out
 
     def set_text_matcher(self, field: str, fn) -> None:
@@ -480,6 +501,144 @@ def select(expr: str, columns: Union[Columns, Dict[str, np.ndarray]]) -> np.ndar
     if missing:
         raise ValueError(f"filter expression needs column(s) {missing} that were not given")
     return np.flatnonzero(_eval(node, cols, n)).astype(np.int64)   # (a TEXT_MATCH needs a Columns with its matcher: ValueError here)
+
+
+# ---- filter programs for the device (the word layout is include/icd_search.h's) ---------------------------------
+DEVICE_COLUMNS = FIELDS   # column c of Columns.device_columns() is field DEVICE_COLUMNS[c]
+OP_RANGE, OP_SET, OP_TEXT, OP_AND, OP_OR, OP_NOT = 1, 2, 3, 4, 5, 6
+PROGRAM_MAX_OPS, PROGRAM_MAX_LEAVES, PROGRAM_MAX_STACK, PROGRAM_MAX_TEXT, PROGRAM_MAX_SET = 32, 16, 8, 4, 64
+_I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+class _NoProgram(Exception):
+    """the tree does not fit a device program: the host route evaluates it"""
+
+
+def _u32(v: int) -> int:
+    return int(v) & 0xFFFFFFFF
+
+
+def _clamp(v: int) -> int:
+    return min(max(int(v), _I32_MIN), _I32_MAX)
+
+
+def _prefix_range(values: np.ndarray, prefix: str) -> Tuple[int, int]:
+    """[lo, hi) of the sorted distinct `values` that start with `prefix`: contiguous in code-point order, found with two binary
+    searches and verified at the range's four borders (anything else: _NoProgram)"""
+    if prefix == "":
+        return 0, len(values)
+    lo = int(np.searchsorted(values, prefix, side="left"))
+    last = ord(prefix[-1])
+    if last >= 0x10FFFF:
+        raise _NoProgram
+    hi = int(np.searchsorted(values, prefix[:-1] + chr(last + 1), side="left"))
+    ok = lo <= hi and (hi == lo or (str(values[lo]).startswith(prefix) and str(values[hi - 1]).startswith(prefix)))
+    ok = ok and (lo == 0 or not str(values[lo - 1]).startswith(prefix)) and (hi == len(values) or not str(values[hi]).startswith(prefix))
+    if not ok:
+        raise _NoProgram
+    return lo, hi
+
+
+def _leaf(node, columns: "Columns", text_index) -> Tuple[List[int], bool]:
+    """(the leaf's words, whether a NOT follows it) of a predicate node"""
+    kind = node[0]
+    if kind == "text_match":
+        tx = (text_index or {}).get(node[1])
+        if tx is None:
+            raise _NoProgram
+        try:
+            known, _total = tx.match_terms(node[2])
+        except ValueError:
+            raise _NoProgram from None
+        return [OP_TEXT | len(known) << 8 | int(node[3]) << 16] + [int(t) for t in known], False
+    field = node[1]
+    col = DEVICE_COLUMNS.index(field)
+    if field in STRING_FIELDS:
+        values = columns.group_ids(field)[1]
+        if kind == "cmp":   # (== or !=: the parser admits nothing else on a string)
+            at = int(np.searchsorted(values, node[3], side="left")) if len(values) else 0
+            lo, hi = (at, at + 1) if at < len(values) and str(values[at]) == node[3] else (0, 0)
+            return [OP_RANGE, col, lo, hi], node[2] == "!="
+        if kind == "like" and (node[2] == "prefix" or node[3] == ""):   # (an empty suffix or infix is the empty prefix: every value)
+            lo, hi = _prefix_range(values, node[3])
+            return [OP_RANGE, col, lo, hi], False
+        if kind == "like":
+            if not len(values):
+                ids = np.zeros(0, np.int64)
+            else:
+                ids = np.flatnonzero(np.char.endswith(values, node[3]) if node[2] == "suffix" else np.char.find(values, node[3]) >= 0)
+        else:   # in / not in
+            ids = np.flatnonzero(np.isin(values, np.array(node[3], dtype=values.dtype))) if node[3] and len(values) else np.zeros(0, np.int64)
+        if len(ids) > PROGRAM_MAX_SET:
+            raise _NoProgram
+        return [OP_SET | len(ids) << 8, col] + [int(i) for i in ids], kind == "in" and node[2]
+    if kind == "cmp":
+        v, op = int(node[3]), node[2]   # (a bool literal is 0 / 1, as its column)
+        lo, hi = {"==": (v, v + 1), "!=": (v, v + 1), "<": (_I32_MIN, v), "<=": (_I32_MIN, v + 1), ">": (v + 1, _I32_MAX), ">=": (v, _I32_MAX)}[op]
+        # (device_columns() admits no value of INT32_MAX: hi = INT32_MAX is "no upper bound")
+        return [OP_RANGE, col, _u32(_clamp(lo)), _u32(_clamp(hi))], op == "!="
+    if kind == "in":
+        ids = sorted({int(v) for v in node[3] if _I32_MIN <= int(v) <= _I32_MAX})
+        if len(ids) > PROGRAM_MAX_SET:
+            raise _NoProgram
+        return [OP_SET | len(ids) << 8, col] + [_u32(i) for i in ids], bool(node[2])
+    raise AssertionError(kind)
+
+
+def device_program(expr: str, columns: "Columns", text_index=None):
+    """`expr` as a postfix program for IcdIndex.filter_masks: uint32 words over the columns of
+    `columns.device_columns()`, or None when the tree does not fit - more than 16 leaves or 32 operations, a set above 64 values,
+    more than 8 sets on the stack, more than 4 TEXT_MATCHes, a TEXT_MATCH on a field without an entry in `text_index` (a dict
+    field -> SparseTextIndex) or with more than 64 known terms, a prefix whose values are not contiguous among the sorted distinct
+    values, a column that does not fit int32. None means the host route (`select`). Operands are evaluated in the order written.
+    A string predicate becomes an integer predicate on the value's rank among the field's sorted distinct values: == and a prefix
+    `like` a rank range, `in` and suffix / infix `like` a rank set, != and `not in` the NOT of those."""
+    node = _parse(expr)[0]
+    if columns.device_columns() is None:
+        return None
+    words: List[int] = []
+    tally = {"ops": 0, "leaves": 0, "text": 0, "depth": 0}
+
+    def op(word):
+        words.append(word)
+        tally["ops"] += 1
+
+    def emit(t):
+        if t[0] in ("and", "or"):
+            emit(t[1][0])
+            for u in t[1][1:]:
+                emit(u)
+                op(OP_AND if t[0] == "and" else OP_OR)
+                tally["depth"] -= 1
+        elif t[0] == "not":
+            emit(t[1])
+            op(OP_NOT)
+        else:
+            leaf, negate = _leaf(t, columns, text_index)
+            words.extend(leaf)
+            tally["ops"] += 1
+            tally["leaves"] += 1
+            tally["text"] += t[0] == "text_match"
+            tally["depth"] += 1
+            if tally["depth"] > PROGRAM_MAX_STACK or tally["leaves"] > PROGRAM_MAX_LEAVES or tally["text"] > PROGRAM_MAX_TEXT:
+                raise _NoProgram
+            if negate:
+                op(OP_NOT)
+        if tally["ops"] > PROGRAM_MAX_OPS:
+            raise _NoProgram
+
+    try:
+        emit(node)
+    except _NoProgram:
+        return None
+    return np.asarray(words, dtype=np.uint32)
+
+
+def pack_programs(programs: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+    """(prog_off int64 [nq + 1], prog uint32) of a batch of device programs"""
+    off = np.zeros(len(programs) + 1, np.int64)
+    np.cumsum([len(p) for p in programs], out=off[1:])
+    return off, (np.concatenate(programs).astype(np.uint32) if len(programs) else np.zeros(0, np.uint32))
 
 
 def _fields_of(node) -> List[str]:

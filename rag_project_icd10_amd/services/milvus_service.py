@@ -69,7 +69,9 @@ class MilvusService:
         self._fusion = None
         # sparse search: (the index it belongs to, IcdSparse, SparseTextIndex, field, store generation); built lazily, one handle
         self._sparse = None
-        self._columns = None        # filter_expr.Columns of the store generation they were built from (rebuilt when it moves on)
+        # filter programs: (the index they belong to, IcdColumns, the filter_expr.Columns they were made from)
+        self._dev_columns = None
+        self._columns = None       # filter_expr.Columns of the store generation they were built from (rebuilt when it moves on)
         self._connect()
         self._setup_collection()
 
@@ -223,6 +225,7 @@ class MilvusService:
             self._views.clear()
             self._groupings.clear()
             self._masks.clear()
+            self._dev_columns = None
             self._fusion = None
             self._sparse = None
 
@@ -383,31 +386,102 @@ class MilvusService:
             if m_ is not None and getattr(m_, "transient", False):
                 m_.close()
 
+    # ---- filter programs (any boolean shape on the device) ---------------------------------------------------
+    FILTER_ON_DEVICE = True   # False: section 17's two shapes keep section 17's call, every other expression takes the host route (tests compare the routes' bits)
+
+    def _device_columns(self, index):
+        """(IcdColumns, filter_expr.Columns) of the store's index, uploaded on the first device-routed expression and dropped where
+        the masks are; (None, cols) for a store whose columns do not fit int32"""
+        cols = self._filter_columns()
+        with self._views_lock:
+            hit = self._dev_columns
+            if hit is not None and hit[0] is index and hit[2] is cols and not index.closed and not hit[1].closed:
+                return hit[1], cols
+        table = cols.device_columns()
+        if table is None:
+            return None, cols
+        dev = index.columns(table)
+        with self._views_lock:
+            self._dev_columns = (index, dev, cols)
+        return dev, cols
+
+    def _device_program(self, index, expr):
+        """the device program of `expr` (filter_expr.device_program), or None for the host route: the switch is off, the
+        expression holds a TEXT_MATCH while TEXT_MATCH_ON_DEVICE is off, or the tree does not fit"""
+        if not self.FILTER_ON_DEVICE:
+            return None
+        text = None
+        if filter_expr.has_text_match(expr):
+            if not self.TEXT_MATCH_ON_DEVICE:
+                return None
+            _sp, tx, field = self._text_index()
+            text = {field: tx}
+        dev, cols = self._device_columns(index)
+        return None if dev is None else filter_expr.device_program(expr, cols, text)
+
+    def _program_masks(self, index, exprs, programs):
+        """The masks of a batch of expressions with their device programs in ONE IcdIndex.filter_masks call. A scalar-only
+        expression's mask enters the mask cache under its normalised key, as a host-made one does; a mask of an expression that
+        holds a TEXT_MATCH belongs to the search it was made for (mask.transient, section 17's rule)."""
+        dev, _cols = self._device_columns(index)
+        text = [filter_expr.has_text_match(e) for e in exprs]
+        sp = self._text_index()[0] if any(text) else None
+        masks = index.filter_masks(dev, sp, *filter_expr.pack_programs(programs))
+        for i, (m_, t) in enumerate(zip(masks, text)):
+            if t:
+                m_.transient = True
+            elif m_.stats()["rows"] == index.n:   # (a selection of every row passes no mask and is not cached, as on the host route)
+                m_.close()
+                masks[i] = None
+        with self._views_lock:
+            for e, m_, t in zip(exprs, masks, text):
+                if m_ is not None and not t:
+                    self._masks[(filter_expr.compile(e), self.client.generation)] = (index, m_)
+            while len(self._masks) > self._max_masks:
+                self._masks.popitem(last=False)
+        return masks
+
+    def _cached_mask(self, index, key):
+        with self._views_lock:
+            hit = self._masks.get((key, self.client.generation))
+            if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
+                self._masks.move_to_end((key, self.client.generation))
+                return hit[1]
+        return None
+
     def _filter_mask(self, index, expr):
         """the row mask of `expr` on the store's index: None when the expression is None or selects every row, else the
-        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation). A
-        device-shaped TEXT_MATCH expression gets a mask of its own from the device, uncached."""
+        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation). An
+        expression with a device program (section 18) gets its mask from the device - one that holds a TEXT_MATCH a mask of its
+        own, uncached -, section 17's shapes fall back to section 17's call, and only what both refuse is evaluated on the host."""
         if expr is None:
             return None
         key = filter_expr.compile(expr)
+        own = self.TEXT_MATCH_ON_DEVICE and filter_expr.has_text_match(expr)   # (the device's mask is the search's own: the cache is not asked first)
+        hit = None if own else self._cached_mask(index, key)
+        if hit is not None:
+            return hit
+        program = self._device_program(index, expr)
+        if program is not None:
+            mask = self._program_masks(index, [expr], [program])[0]
+            if mask is not None:
+                mask.stats()   # (one mask: its row count is read now, for the callers that ask whether it is empty)
+            return mask
         if self.TEXT_MATCH_ON_DEVICE:
             shape = filter_expr.text_match_shape(expr)
             if shape is not None:
                 mask = self._match_masks(index, [shape])[0]
-                mask.stats()   # (one mask: its row count is read now, for the callers that ask whether it is empty)
+                mask.stats()   # (as above)
                 return mask
-        ck = (key, self.client.generation)
-        with self._views_lock:
-            hit = self._masks.get(ck)
-            if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
-                self._masks.move_to_end(ck)
-                return hit[1]
+        hit = self._cached_mask(index, key) if own else None
+        if hit is not None:
+            return hit
         rows = self.filter_rows(expr)
         if len(rows) == index.n:
             return None
         with self._views_lock:
             mask = index.rowmask(rows)
-            self._masks[ck] = (index, mask)
+            self._masks[(key, self.client.generation)] = (index, mask)
             while len(self._masks) > self._max_masks:
                 self._masks.popitem(last=False)
         return mask
@@ -417,16 +491,25 @@ class MilvusService:
         exprs = list(filter) if isinstance(filter, (list, tuple)) else [filter] * nq
         seen: Dict[Any, Any] = {}
         device: Dict[Any, Any] = {}   # expression -> its device shape: the text parts of ALL such queries are one match_masks call
+        programs: Dict[Any, Any] = {}   # expression -> its device program: ALL of them are one filter_masks call (section 18)
         for e in exprs:
-            if e is None or e in seen or e in device:
+            if e is None or e in seen or e in device or e in programs:
                 continue
-            shape = filter_expr.text_match_shape(e) if self.TEXT_MATCH_ON_DEVICE else None
+            own = self.TEXT_MATCH_ON_DEVICE and filter_expr.has_text_match(e)
+            hit = None if own else self._cached_mask(index, filter_expr.compile(e))
+            program = None if hit is not None else self._device_program(index, e)
+            if program is not None:
+                programs[e] = program
+                continue
+            shape = filter_expr.text_match_shape(e) if hit is None and self.TEXT_MATCH_ON_DEVICE else None
             if shape is not None:
                 device[e] = shape
             else:
-                seen[e] = self._filter_mask(index, e)
+                seen[e] = hit if hit is not None else self._filter_mask(index, e)
         if device:
             seen.update(zip(device, self._match_masks(index, list(device.values()))))
+        if programs:
+            seen.update(zip(programs, self._program_masks(index, list(programs), list(programs.values()))))
         return [None if e is None else seen[e] for e in exprs]
 
     def filter_masks(self) -> List[Dict[str, Any]]:
