@@ -805,6 +805,19 @@ class IcdIndex:
             _check(self._lib, rc)
         return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
 
+    def _produce_masks(self, nq, base_masks, call) -> list:
+        """what match_masks and filter_masks share: the base table, the handles' out array, call(base, out) -> rc with ICD_ERR_INVALID
+        as a ValueError, and the nq handles adopted as IcdRowMask"""
+        base_h = None if base_masks is None else _mask_table(base_masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
+        if nq == 0:
+            return []
+        out = (C.c_void_p * nq)()
+        rc = call(None if base_h is None else base_h.ctypes.data, C.cast(out, C.c_void_p))
+        if rc == -1:
+            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+        _check(self._lib, rc)
+        return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
+
     def match_masks(self, sp: "IcdSparse", q_off, q_terms, min_match, base_masks=None) -> list:
         """The row masks of a batch of keyword matches (icd_sparse_match_rowmasks), one IcdRowMask per query,
         built on the device from the sparse index's postings in one launch: row r is in mask q iff it holds at least
@@ -820,16 +833,8 @@ class IcdIndex:
         nq = int(off.size) - 1
         if nq < 0 or mm.size != nq or (nq > 0 and int(off[-1]) != tr.size):
             raise ValueError("q_off must hold nq + 1 offsets that end at the number of terms; min_match one entry per query")
-        base_h = None if base_masks is None else _mask_table(base_masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
-        if nq == 0:
-            return []
-        out = (C.c_void_p * nq)()
-        rc = self._lib.icd_sparse_match_rowmasks(self._h, sp._h, off.ctypes.data, tr.ctypes.data if tr.size else off.ctypes.data, mm.ctypes.data,
-                                                 nq, 0, None if base_h is None else base_h.ctypes.data, C.cast(out, C.c_void_p), None)
-        if rc == -1:
-            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-        _check(self._lib, rc)
-        return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
+        return self._produce_masks(nq, base_masks, lambda base, out: self._lib.icd_sparse_match_rowmasks(
+            self._h, sp._h, off.ctypes.data, tr.ctypes.data if tr.size else off.ctypes.data, mm.ctypes.data, nq, 0, base, out, None))
 
     def columns(self, cols) -> "IcdColumns":
         """int32 columns of this index's rows on the device (icd_columns_*): cols [ncols, n]"""
@@ -849,17 +854,9 @@ class IcdIndex:
         nq = int(off.size) - 1
         if nq < 0 or (nq > 0 and int(off[-1]) != pr.size):
             raise ValueError("prog_off must hold nq + 1 offsets that end at the number of program words")
-        base_h = None if base_masks is None else _mask_table(base_masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
-        if nq == 0:
-            return []
-        out = (C.c_void_p * nq)()
-        rc = self._lib.icd_filter_rowmasks(self._h, columns._h, None if sparse is None else sparse._h, off.ctypes.data,
-                                           pr.ctypes.data if pr.size else off.ctypes.data, nq,
-                                           None if base_h is None else base_h.ctypes.data, C.cast(out, C.c_void_p), None)
-        if rc == -1:
-            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-        _check(self._lib, rc)
-        return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
+        return self._produce_masks(nq, base_masks, lambda base, out: self._lib.icd_filter_rowmasks(
+            self._h, columns._h, None if sparse is None else sparse._h, off.ctypes.data, pr.ctypes.data if pr.size else off.ctypes.data, nq,
+            base, out, None))
 
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""

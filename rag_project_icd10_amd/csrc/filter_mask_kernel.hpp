@@ -11,13 +11,14 @@
 //                takes the ballot: its low half is mask word 64 w + 2 s, its high half word 64 w + 2 s + 1 - both owned by lanes of
 //                the SAME wave, so the two halves go to their owners with one select and nothing crosses waves. A SET's ids are
 //                staged in LDS behind INT32_MAX padding and searched with six halving steps.
-//   TEXT         section 17's byte counters in LDS: cleared, one LDS atomic add per posting of the tile (a wave per term), tested
-//                with count + 0x80 - m. The leaves of a program run one after another on the same counters, behind a barrier.
+//   TEXT         section 17's byte counters in LDS, through text_match_kernel.hpp's own device functions (tm_segment_search,
+//                tm_counter_walk, tm_threshold_word, unguarded: the checker vouches for terms and m): cleared here, filled and
+//                tested there. The leaves of a program run one after another on the same counters, behind a barrier.
 //   AND, OR, NOT on 32-bit words in registers: the stack is eight registers with its TOP at position 0 - a push moves every entry
 //                one position down, a pop one up, all at compile-time positions, so nothing is indexed at run time (no scratch).
-// NOT sets the bits of rows at or behind n as well; they are cleared ONCE, on the final word, which is then ANDed with the optional
-// base mask's word and written with an ordinary vector store. The words' popcounts are summed per wave and added to the mask's row
-// counter with one global (vector) atomic add per wave. Every word below rowmask_tile_words(n) is written for every query.
+// NOT sets the bits of rows at or behind n as well; they are cleared ONCE, on the final word, by text_match_kernel.hpp's
+// tm_store_word, which also ANDs the base mask's word, stores and counts the rows as it does for a keyword mask. Every word below
+// rowmask_tile_words(n) is written for every query.
 //
 // Programs come from the host and were checked there (filter_check_programs): the kernel trusts their structure.
 //
@@ -121,36 +122,11 @@ __global__ __launch_bounds__(SP_THREADS) void filter_mask_kernel(const FilterMas
             for (int i = tid; i < TM_COUNT_WORDS; i += SP_THREADS) cnt[i] = 0u;
             if (tid < count) ids[tid] = p[pc + 1 + tid];
             __syncthreads();
-            if (tid < 2 * count) {   // the tile's segment of every term's postings: lane 2 t finds its begin, lane 2 t + 1 its end
-                const uint32_t term = ids[tid >> 1];
-                const u64 target = (u64)tile0 + ((tid & 1) ? (u64)SP_TILE : 0ull);
-                long long lo = a.post_off[term], hi = a.post_off[term + 1];
-                while (lo < hi) {   // first posting whose row is at or behind target
-                    const long long mid = (lo + hi) >> 1;
-                    if ((u64)a.post_row[mid] < target) lo = mid + 1; else hi = mid;
-                }
-                seg[tid] = lo;
-            }
+            tm_segment_search<false>(a, ids, count, tile0, tid, seg);
             __syncthreads();
-            for (int t = wave; t < count; t += SP_THREADS / 64) {   // a wave per term, no barrier between terms (integer adds commute)
-                const long long lo = seg[2 * t], hi = seg[2 * t + 1];
-                for (long long i = lo + lane; i < hi; i += 64) {
-                    const uint32_t l = a.post_row[i] - tile0;
-                    if (l < (uint32_t)SP_TILE) atomicAdd(&cnt[l >> 2], 1u << (8 * (l & 3)));   // (always, for postings icd_sparse_pack built)
-                }
-            }
+            tm_counter_walk(a, seg, count, tile0, wave, lane, cnt);
             __syncthreads();
-            if (m <= count) {   // (m is 1 .. 64: the checker; m above count is the empty set)
-                const uint32_t bias = (uint32_t)(0x80 - m) * 0x01010101u;   // count + 0x80 - m sets a byte's top bit iff count >= m
-                const uint4 *c4 = reinterpret_cast<const uint4 *>(cnt) + 2 * tid;
-                const uint4 c0 = c4[0], c1 = c4[1];
-                const uint32_t w8[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const uint32_t top = ((w8[j] + bias) >> 7) & 0x01010101u;
-                    word |= ((top | (top >> 7) | (top >> 14) | (top >> 21)) & 0xFu) << (4 * j);
-                }
-            }
+            word = tm_threshold_word<false>(cnt, m, count, tid);
             pc += 1 + count;
         }
         // push
@@ -160,21 +136,7 @@ __global__ __launch_bounds__(SP_THREADS) void filter_mask_kernel(const FilterMas
     }
 
     // the final word: rows at or behind n cleared once (a NOT set them), the base mask, the store, the count
-    uint32_t word = st[0];
-    const long long gw = (long long)(tile0 >> 5) + tid;   // the word's index in the bitset
-    const long long row0 = gw * 32;
-    if (row0 + 32 > a.n) word &= row0 < a.n ? (1u << (int)(a.n - row0)) - 1u : 0u;
-    if (gw < a.mask_words) {
-        const uint32_t *base = a.base ? a.base[q] : nullptr;
-        if (base) word &= base[gw];
-        a.bits[(size_t)q * a.stride + gw] = word;
-    } else {
-        word = 0u;
-    }
-    int pc_rows = __popc(word);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) pc_rows += __shfl_down(pc_rows, off, 64);
-    if (lane == 0 && pc_rows) atomicAdd(a.count + q, pc_rows);
+    tm_store_word(a, st[0], q, tile0, tid, lane);
 }
 
 }  // namespace icd

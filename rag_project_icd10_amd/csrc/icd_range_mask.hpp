@@ -1,7 +1,9 @@
 // icd_range_mask.hpp - range and masked search (DESIGN.md sections 11 and 12): the callers' bounds and their packing, the row-mask
-// handle and its table, icd_index_search_range / icd_index_search_masked. Part of icd_search.hip's translation unit (fail(), HIP_TRY,
-// the owned-handle and request helpers, run_search); included there and nowhere else.
+// handle and its table, the block of a call's produced masks (ProducedMasks: sections 17.3 and 18.3), icd_index_search_range /
+// icd_index_search_masked. Part of icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle and request helpers,
+// run_search); included there and nowhere else.
 #pragma once
+#include "produced_mask_layout.hpp"
 
 // The bounds of a banded search as the caller gave them: packed into BandQ inside run_search, under the handle's mutex.
 struct RangeBounds {
@@ -103,8 +105,8 @@ struct icd_rowmask : OwnedHandle {
     static constexpr const char *NOUN = "row mask";
     int64_t rows = 0;           // -1: counted on the device (count_dev), read back by the first icd_rowmask_stats
     uint32_t *bits = nullptr;   // [rowmask_tile_words(n) + ROWMASK_TAIL_WORDS]
-    // a mask icd_sparse_match_rowmasks produced: bits and count_dev point into ONE allocation the masks of
-    // that call share; the last of them to be destroyed frees it
+    // a produced mask (ProducedMasks below; DESIGN.md sections 17 and 18): bits and count_dev point into ONE allocation the masks
+    // of that call share; the last of them to be destroyed frees it
     struct SharedBlock { void *dev = nullptr; std::atomic<int> refs{0}; };
     SharedBlock *block = nullptr;
     const int *count_dev = nullptr;
@@ -142,6 +144,105 @@ static int stage_masks(icd_index *x, icd_rowmask *const *masks, int nq, hipStrea
     }
     return ICD_OK;
 }
+
+// ---- produced masks: what icd_sparse_match_rowmasks and icd_filter_rowmasks share (DESIGN.md sections 17.3 and 18.3) ------------
+// Their common checks, in the two places they hold in both entries: the entry's own handle checks stand between them (handle-state
+// errors win over ownership errors). The base table follows check_masks' rules without its bound on the table's length.
+static int produced_check_index(icd_index *idx, int64_t nq, icd_rowmask **out_masks) {
+    if (!out_masks) return fail(ICD_ERR_INVALID, "out_masks is NULL");
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    for (int64_t q = 0; q < nq; ++q) out_masks[q] = nullptr;
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (idx->row_map) return fail(ICD_ERR_UNSUPPORTED, "row masks on a view are not supported: mask the parent");
+    return ICD_OK;
+}
+static int produced_check_batch(const icd_index *idx, int64_t nq, icd_rowmask *const *base_masks, int64_t *tiles, bool *any_base) {
+    *tiles = (idx->n + SP_TILE - 1) / SP_TILE;
+    if (nq * *tiles > 0x7FFFFFFFll) return fail(ICD_ERR_INVALID, "nq=%lld: %lld tiles of rows times nq exceed 2^31 - 1 work-groups", (long long)nq, (long long)*tiles);
+    *any_base = false;
+    for (int64_t q = 0; base_masks && q < nq; ++q) {
+        const icd_rowmask *m = base_masks[q];
+        if (!m) continue;
+        *any_base = true;
+        if (!valid_handle(m)) return fail(ICD_ERR_STATE, "base_masks[%lld]: invalid row mask handle", (long long)q);
+        if (const int rc = check_owner(m->at, idx, "base_masks", (long long)q)) return rc;
+    }
+    return ICD_OK;
+}
+
+// The block of a call's nq masks (produced_mask_layout.hpp): ONE allocation of bitsets, row counters, base pointers and whatever
+// the entry stages behind them. Every mask is an ordinary icd_rowmask that points into it; the block goes with the last of them
+// (icd_rowmask_destroy). begin() refuses a capturing stream in the entry's name, allocates, makes the handles, clears bitsets and
+// counters (the tails, the words of tiles the kernel leaves alone) and stages the base table; an entry then stages its regions
+// and launches under PM_TRY, and publish() hands the masks out. Until then undo() takes everything back.
+#define PM_TRY(pm, expr) HIP_TRY_OR((pm).undo(), expr)
+struct ProducedMasks {
+    hipStream_t s = nullptr;
+    int64_t nq = 0;
+    icd_rowmask **out = nullptr;
+    ProducedMaskLayout at{};
+    char *dev = nullptr;
+    icd_rowmask::SharedBlock *blk = nullptr;
+    std::vector<icd_rowmask *> made;
+    std::vector<const uint32_t *> h_base;   // (with a base mask; pageable: alive until the entry's synchronisation)
+
+    template <typename T>
+    T *region(size_t offset) const { return reinterpret_cast<T *>(dev + offset); }
+
+    // (the stream is drained first, a launch may be reading the block)
+    void undo() {
+        hipStreamSynchronize(s);
+        for (icd_rowmask *m : made) free_handle(m);
+        for (int64_t q = 0; q < nq; ++q) out[q] = nullptr;
+        hipFree(dev);
+        delete blk;
+    }
+
+    int begin(const char *entry, const icd_index *idx, int64_t nq_, icd_rowmask *const *base_masks, bool any_base, icd_rowmask **out_masks,
+              const size_t *staged_bytes, int n_staged, void *stream) {
+        s = reinterpret_cast<hipStream_t>(stream); nq = nq_; out = out_masks;
+        if (stream_capturing(s)) return fail(ICD_ERR_INVALID, "%s allocates: it cannot be captured into a graph", entry);
+        HIP_TRY(hipSetDevice(idx->device));
+        at = produced_mask_layout(nq, idx->n, any_base, staged_bytes, n_staged);
+        blk = new (std::nothrow) icd_rowmask::SharedBlock();
+        try {
+            made.reserve((size_t)nq);
+            if (any_base) h_base.resize((size_t)nq);
+        } catch (const std::bad_alloc &) {
+            delete blk;
+            blk = nullptr;
+        }
+        if (!blk) return fail(ICD_ERR_NOMEM, "host allocation failed");
+        PM_TRY(*this, hipMalloc(reinterpret_cast<void **>(&dev), at.total));
+        blk->dev = dev;
+        for (int64_t q = 0; q < nq; ++q) {
+            icd_rowmask *m = new_handle<icd_rowmask>(idx);
+            if (!m) { undo(); return fail(ICD_ERR_NOMEM, "host allocation failed"); }
+            m->rows = -1; m->bytes = at.words * sizeof(uint32_t) + sizeof(int);
+            m->bits = region<uint32_t>(at.bits) + (size_t)q * at.words; m->count_dev = region<int>(at.counters) + q; m->block = blk;
+            made.push_back(m);
+        }
+        PM_TRY(*this, hipMemsetAsync(dev, 0, at.zeroed, s));
+        if (any_base) {
+            for (int64_t q = 0; q < nq; ++q) h_base[(size_t)q] = base_masks[q] ? base_masks[q]->bits : nullptr;
+            PM_TRY(*this, hipMemcpyAsync(region<void>(at.base), h_base.data(), (size_t)nq * 8, hipMemcpyHostToDevice, s));
+        }
+        return ICD_OK;
+    }
+
+    // the fields TextMatchArgs and FilterMaskArgs name alike
+    template <typename Args>
+    void fill(Args *a, const icd_index *idx, int64_t tiles) const {
+        a->base = h_base.empty() ? nullptr : region<const uint32_t *>(at.base);
+        a->bits = region<uint32_t>(at.bits); a->stride = (long long)at.words; a->count = region<int>(at.counters);
+        a->n = idx->n; a->mask_words = rowmask_tile_words(idx->n); a->tiles = (int)tiles;
+    }
+
+    void publish() {
+        blk->refs.store((int)nq);
+        for (int64_t q = 0; q < nq; ++q) out[q] = made[(size_t)q];
+    }
+};
 
 // ---- row masks --------------------------------------------------------------------------------------------------------------
 // A row list that already sits on the device -> bitset: one memset in front, then one vector atomicOr per row. The list is

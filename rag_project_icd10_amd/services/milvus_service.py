@@ -449,67 +449,64 @@ class MilvusService:
                 return hit[1]
         return None
 
-    def _filter_mask(self, index, expr):
-        """the row mask of `expr` on the store's index: None when the expression is None or selects every row, else the
-        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation). An
-        expression with a device program (section 18) gets its mask from the device - one that holds a TEXT_MATCH a mask of its
-        own, uncached -, section 17's shapes fall back to section 17's call, and only what both refuse is evaluated on the host."""
-        if expr is None:
-            return None
+    def _mask_route(self, index, expr):
+        """where the mask of `expr` comes from - the ONE place that holds the order and the two switches: ("cached", mask),
+        ("program", its device program: section 18), ("text", its shape: section 17's call, for what section 18 refuses) or
+        ("host", None). An expression whose TEXT_MATCH runs on the device gets a mask of its own: the cache is asked only once the
+        device has refused it."""
         key = filter_expr.compile(expr)
-        own = self.TEXT_MATCH_ON_DEVICE and filter_expr.has_text_match(expr)   # (the device's mask is the search's own: the cache is not asked first)
+        own = self.TEXT_MATCH_ON_DEVICE and filter_expr.has_text_match(expr)
         hit = None if own else self._cached_mask(index, key)
         if hit is not None:
-            return hit
+            return "cached", hit
         program = self._device_program(index, expr)
         if program is not None:
-            mask = self._program_masks(index, [expr], [program])[0]
-            if mask is not None:
-                mask.stats()   # (one mask: its row count is read now, for the callers that ask whether it is empty)
-            return mask
-        if self.TEXT_MATCH_ON_DEVICE:
-            shape = filter_expr.text_match_shape(expr)
-            if shape is not None:
-                mask = self._match_masks(index, [shape])[0]
-                mask.stats()   # (as above)
-                return mask
+            return "program", program
+        shape = filter_expr.text_match_shape(expr) if self.TEXT_MATCH_ON_DEVICE else None
+        if shape is not None:
+            return "text", shape
         hit = self._cached_mask(index, key) if own else None
-        if hit is not None:
-            return hit
+        return ("host", None) if hit is None else ("cached", hit)
+
+    def _host_mask(self, index, expr):
+        """the host route: the selection's rows as a cached mask (None when every row is selected: not cached)"""
         rows = self.filter_rows(expr)
         if len(rows) == index.n:
             return None
         with self._views_lock:
             mask = index.rowmask(rows)
-            self._masks[(key, self.client.generation)] = (index, mask)
+            self._masks[(filter_expr.compile(expr), self.client.generation)] = (index, mask)
             while len(self._masks) > self._max_masks:
                 self._masks.popitem(last=False)
         return mask
 
+    def _filter_mask(self, index, expr):
+        """the row mask of `expr` on the store's index: None when the expression is None or selects every row, else the
+        selection's IcdRowMask (the empty mask when nothing is selected), cached per (normalised expression, generation) unless
+        it is the search's own (_mask_route). The one-expression case of _masks_for."""
+        mask = self._masks_for(index, expr, 1)[0]
+        if mask is not None:
+            mask.stats()   # (one mask: its row count is read now, for the callers that ask whether it is empty)
+        return mask
+
     def _masks_for(self, index, filter, nq: int):   # noqa: A002
-        """one entry per query: None (unfiltered) or the expression's mask; equal expressions share one mask"""
+        """one entry per query: None (unfiltered) or the expression's mask; equal expressions share one mask. ALL device programs
+        of the batch are one filter_masks call (section 18), the text parts of ALL section-17 shapes one match_masks call."""
         exprs = list(filter) if isinstance(filter, (list, tuple)) else [filter] * nq
         seen: Dict[Any, Any] = {}
-        device: Dict[Any, Any] = {}   # expression -> its device shape: the text parts of ALL such queries are one match_masks call
-        programs: Dict[Any, Any] = {}   # expression -> its device program: ALL of them are one filter_masks call (section 18)
+        batched: Dict[str, Dict[Any, Any]] = {"text": {}, "program": {}}   # route -> expression -> its shape / program
         for e in exprs:
-            if e is None or e in seen or e in device or e in programs:
+            if e is None or e in seen or e in batched["text"] or e in batched["program"]:
                 continue
-            own = self.TEXT_MATCH_ON_DEVICE and filter_expr.has_text_match(e)
-            hit = None if own else self._cached_mask(index, filter_expr.compile(e))
-            program = None if hit is not None else self._device_program(index, e)
-            if program is not None:
-                programs[e] = program
-                continue
-            shape = filter_expr.text_match_shape(e) if hit is None and self.TEXT_MATCH_ON_DEVICE else None
-            if shape is not None:
-                device[e] = shape
+            route, what = self._mask_route(index, e)
+            if route in batched:
+                batched[route][e] = what
             else:
-                seen[e] = hit if hit is not None else self._filter_mask(index, e)
-        if device:
-            seen.update(zip(device, self._match_masks(index, list(device.values()))))
-        if programs:
-            seen.update(zip(programs, self._program_masks(index, list(programs), list(programs.values()))))
+                seen[e] = what if route == "cached" else self._host_mask(index, e)
+        if batched["text"]:
+            seen.update(zip(batched["text"], self._match_masks(index, list(batched["text"].values()))))
+        if batched["program"]:
+            seen.update(zip(batched["program"], self._program_masks(index, list(batched["program"]), list(batched["program"].values()))))
         return [None if e is None else seen[e] for e in exprs]
 
     def filter_masks(self) -> List[Dict[str, Any]]:

@@ -185,3 +185,14 @@ def test_program_checker_under_the_host_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "filter program cases ok" in out.stdout
+
+
+def test_produced_mask_layout_under_the_host_sanitizers(tmp_path):
+    """tests/produced_mask_layout_check.cpp: the host-only header that lays out the block of a call's produced masks (sections 17.3
+    and 18.3), in a program of its own, with ASan and UBSan"""
+    exe = str(tmp_path / "produced_mask_layout_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I",
+                    os.path.join(ROOT, "rag_project_icd10_amd", "csrc"), os.path.join(ROOT, "tests", "produced_mask_layout_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "produced-mask layouts ok" in out.stdout

@@ -407,6 +407,39 @@ def test_service_routes_agree(services):
     assert answers[0][0] == ms.search(vecs[0], 5, filter=SCALAR[2])   # the default mode (a view) gives the same hits
 
 
+def test_a_batch_is_one_filter_masks_call(services):
+    """What _masks_for promises: the programs of ALL fresh expressions of a batch - scalar-only ones, ones that hold a TEXT_MATCH
+    anywhere, section 17's shapes with an S the device takes - are ONE filter_masks call and no match_masks call. The same batch
+    again finds the scalar-only masks in the cache and carries only the text-holding ones: their masks are the search's own."""
+    ms, es, recs = services["ms"], services["es"], services["recs"]
+    exprs = ['code like "A02%"', 'level == 2 and code like "A0%"',
+             'level == 2 or TEXT_MATCH(preferred_zh, "霍乱")', 'not TEXT_MATCH(preferred_zh, "结核")',
+             'TEXT_MATCH(preferred_zh, "伤寒")', 'level >= 2 and TEXT_MATCH(preferred_zh, "感染")']
+    text = [fe.has_text_match(e) for e in exprs]
+    assert text == [False, False, True, True, True, True]
+    assert [fe.text_match_shape(e) is not None for e in exprs] == [False, False, False, False, True, True]
+    assert len({fe.compile(e) for e in exprs}) == len(exprs) and ms.FILTER_ON_DEVICE and ms.TEXT_MATCH_ON_DEVICE
+    titles = [r["preferred_zh"] for r in recs]
+    vecs = np.asarray(es.encode_query_batch([titles[(5 * i) % len(titles)] for i in range(len(exprs))]), dtype=np.float32)
+    index = ms._ready_index()
+    ms._clear_views()   # (nothing cached)
+    assert ms.filter_masks() == []
+    calls = {"match_masks": [], "filter_masks": []}
+    real_match, real_filter = index.match_masks, index.filter_masks
+    index.match_masks = lambda *a, **k: (calls["match_masks"].append(len(a[3])), real_match(*a, **k))[1]
+    index.filter_masks = lambda *a, **k: (calls["filter_masks"].append(len(a[2]) - 1), real_filter(*a, **k))[1]
+    try:
+        first = ms.search_batch(vecs, 10, filter=exprs, filter_mode="mask")
+        assert calls == {"match_masks": [], "filter_masks": [len(exprs)]}
+        second = ms.search_batch(vecs, 10, filter=exprs, filter_mode="mask")
+    finally:
+        del index.match_masks, index.filter_masks
+    own = sum(text)   # (has_text_match with TEXT_MATCH_ON_DEVICE on: the `own` rule - never read from the cache, never entered)
+    assert calls == {"match_masks": [], "filter_masks": [len(exprs), own]}
+    assert {f["expression"] for f in ms.filter_masks()} == {fe.compile(e) for e, t in zip(exprs, text) if not t}
+    assert _bits(first) == _bits(second)
+
+
 def test_endpoints_take_device_filters(services):
     # (last of the module: the app's lifespan disconnects the installed services when the client closes)
     from fastapi.testclient import TestClient

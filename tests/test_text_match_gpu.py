@@ -367,6 +367,44 @@ def _bits_rows(outs):
     return [(o.cpu().numpy() if hasattr(o, "cpu") else np.asarray(o)) for o in outs]
 
 
+def test_a_refused_program_falls_back_to_one_match_masks_call(services):
+    """FILTER_ON_DEVICE on, but S has 17 leaves and device_program refuses it: `S and TEXT_MATCH(...)` keeps section 17's call - the
+    text parts of the whole batch in ONE match_masks call over S's host-made mask, no filter_masks call - and the masks are the
+    host route's, word for word and in row count."""
+    ms = services["ms"]
+    index = ms._ready_index()
+    S = " or ".join(f"level == {i}" for i in range(2, 19))
+    exprs = [f'({S}) and TEXT_MATCH(preferred_zh, "{w}")' for w in ("结核", "伤寒", "霍乱 感染", "zzzz")]
+    dev, cols = ms._device_columns(index)
+    _sp, tx, field = ms._text_index()
+    assert ms.FILTER_ON_DEVICE and ms.TEXT_MATCH_ON_DEVICE and dev is not None
+    assert filter_expr.device_program(S, cols) is None
+    assert all(filter_expr.device_program(e, cols, {field: tx}) is None and filter_expr.text_match_shape(e) is not None for e in exprs)
+    assert 0 < len(ms.filter_rows(S)) < index.n   # (S does select: the text masks are built over a base mask)
+    calls = {"match_masks": [], "filter_masks": []}
+    real_match, real_filter = index.match_masks, index.filter_masks
+    index.match_masks = lambda *a, **k: (calls["match_masks"].append(len(a[3])), real_match(*a, **k))[1]
+    index.filter_masks = lambda *a, **k: (calls["filter_masks"].append(len(a[2]) - 1), real_filter(*a, **k))[1]
+    try:
+        made = ms._masks_for(index, exprs, len(exprs))
+    finally:
+        del index.match_masks, index.filter_masks
+    assert calls == {"match_masks": [len(exprs)], "filter_masks": []}
+    device = [(m.words(), m.stats()["rows"]) for m in made]
+    assert all(getattr(m, "transient", False) for m in made)
+    ms._release_masks(made)
+    ms.TEXT_MATCH_ON_DEVICE = False
+    try:
+        host = [(m.words(), m.stats()["rows"]) for m in ms._masks_for(index, exprs, len(exprs))]
+        rows = [ms.filter_rows(e) for e in exprs]
+    finally:
+        ms.TEXT_MATCH_ON_DEVICE = True
+    for e, (dw, dr), (hw, hr), r in zip(exprs, device, host, rows):
+        assert np.array_equal(dw, hw) and dr == hr == len(r), e
+        assert np.array_equal(dw, _native.pack_rowmask(r, index.n)), e
+    assert len(rows[0]) > 0 and len(rows[3]) == 0
+
+
 def test_endpoints_take_a_text_match_filter(services):
     # (last of the module: the app's lifespan disconnects the installed services when the client closes)
     from fastapi.testclient import TestClient
