@@ -568,6 +568,30 @@ int icd_filter_rowmasks(icd_index *idx, icd_columns *columns, icd_sparse *sparse
                         icd_rowmask *const *base_masks, icd_rowmask **out_masks, void *stream);
 
 /*
+ * The ordered select over a batch of row masks: what a Milvus query / count(*) / query_iterator asks of a filter once no vector is
+ * involved. For every query q of the batch:
+ *
+ *   out_total[q]            the rows set in masks[q] (a NULL entry: every row of the index, n)
+ *   out_taken[q]            clamp(out_total[q] - offsets[q], 0, limit)
+ *   out_ids[q][0 .. limit)  the rows of ranks offsets[q] .. offsets[q] + out_taken[q] of the mask in ascending row order, then -1.
+ *                           Rows as icd_rowmask_create takes them: 0 .. n - 1 (a hit's id is the row plus the index's id_base).
+ *
+ * icd_rowmask_select: two launches on `stream` whatever nq and the masks hold (mask_count_kernel, mask_select_kernel over
+ * (query, segment of 16 384 rows)); no atomic touches the outputs: the same bytes on every run. masks: icd_index_search_masked's
+ * rules - a HOST array of nq entries, each NULL or a live mask of `idx`, staged through the index's pinned table (ICD_ERR_INVALID
+ * while `stream` is capturing). offsets: a HOST array of nq entries >= 0, or NULL for 0. limit: 1 .. ICD_SELECT_MAX_LIMIT.
+ * out_ids may be NULL: a count (out_taken may then be NULL too). out_on_device = 1: the outputs are device memory and the call only
+ * enqueues; 0: host memory, written when the call returns, and nq * limit is bounded by the staging the index allocated at create
+ * (max(64 * max_nq, 4 * ICD_SELECT_MAX_LIMIT) ids; ICD_ERR_INVALID above it: use device outputs). Nothing is allocated in a call.
+ * Every check comes before the first device call: ICD_ERR_INVALID for a limit or an offset out of range, nq above the index's
+ * max_nq, a mask of another index, NULL arrays; ICD_ERR_STATE for a destroyed index or mask; ICD_ERR_UNSUPPORTED for a view as
+ * `idx`. nq = 0 does nothing.
+ */
+#define ICD_SELECT_MAX_LIMIT 16384
+int icd_rowmask_select(icd_index *idx, icd_rowmask *const *masks, int64_t nq, const int64_t *offsets, int32_t limit, int64_t *out_ids,
+                       int64_t *out_total, int32_t *out_taken, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -44,8 +44,11 @@ EXPORTED_SYMBOLS = (
     "icd_sparse_search_range",
     "icd_sparse_match_rowmasks", "icd_rowmask_read",
     "icd_columns_create", "icd_columns_destroy", "icd_columns_stats", "icd_filter_program_check", "icd_filter_rowmasks",
+    "icd_rowmask_select",
 )
-SPARSE_MAX_QUERY_TERMS = 64   # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
+SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
+SELECT_SEGMENT_ROWS = 16384   # csrc/mask_select_plan.hpp MS_SEG_ROWS: rows of one work-group of the select's two passes
+SPARSE_MAX_QUERY_TERMS = 64  # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
 RANKER_RRF, RANKER_WEIGHTED = 0, 1
 NORMS = {"none": 0, "cosine": 1, "atan": 2}   # ICD_NORM_*
@@ -151,6 +154,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_columns_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_filter_program_check.argtypes = [vp, vp, i64, i32, i64, vp, i64]
     lib.icd_filter_rowmasks.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
+    lib.icd_rowmask_select.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, i32, vp]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
@@ -857,6 +861,59 @@ class IcdIndex:
         return self._produce_masks(nq, base_masks, lambda base, out: self._lib.icd_filter_rowmasks(
             self._h, columns._h, None if sparse is None else sparse._h, off.ctypes.data, pr.ctypes.data if pr.size else off.ctypes.data, nq,
             base, out, None))
+
+    def select_rows(self, masks, limit: int, offsets=None, *, on_device: bool = False):
+        """The ordered select over a batch of row masks (icd_rowmask_select), a Milvus query / count(*) /
+        query_iterator page per entry: masks is a sequence of IcdRowMask or None (None: every row of the index), offsets None (0),
+        one int for every query or one per query (>= 0), limit 1 .. SELECT_MAX_LIMIT. Returns (ids int64 [nq, limit], total int64
+        [nq], taken int32 [nq]): total[q] the rows of mask q, taken[q] = clamp(total - offset, 0, limit), ids[q] the rows of
+        ranks offset .. offset + taken of the mask in ascending order, then -1. numpy arrays; on_device=True: torch tensors on
+        the index's device, enqueued on torch's current stream, no synchronisation. Two launches whatever the batch holds; the same
+        bytes on every run. At most max_nq masks per call. Bad arguments raise ValueError."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        masks = list(masks)
+        nq, limit = len(masks), int(limit)
+        if not 1 <= limit <= SELECT_MAX_LIMIT:
+            raise ValueError(f"limit={limit}: 1 .. {SELECT_MAX_LIMIT}")
+        table = _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
+        off = None
+        if offsets is not None:
+            off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+            if off.size == 1:
+                off = np.full(nq, off[0], np.int64)
+            if off.size != nq:
+                raise ValueError(f"offsets holds {off.size} entries for {nq} queries")
+        # host outputs go through the staging the index allocated (ms_host_slots); a larger call writes device tensors and copies them
+        through = on_device or nq * limit > max(64 * self.max_nq, 4 * SELECT_MAX_LIMIT)
+        (ids,), ptr, stream, dev = _outputs(through, self.device, (nq, limit), (np.int64,))
+        (total,), _, _, _ = _outputs(through, self.device, (nq,), (np.int64,))
+        (taken,), _, _, _ = _outputs(through, self.device, (nq,), (np.int32,))
+        if nq:
+            rc = self._lib.icd_rowmask_select(self._h, table.ctypes.data, nq, None if off is None else off.ctypes.data, limit, ptr(ids),
+                                              ptr(total), ptr(taken), dev, stream)
+            if rc == -1:
+                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+            _check(self._lib, rc)
+        if through and not on_device:
+            return ids.cpu().numpy(), total.cpu().numpy(), taken.cpu().numpy()
+        return ids, total, taken
+
+    def count_rows(self, masks, *, on_device: bool = False):
+        """total of select_rows alone (int64 [nq]; numpy, or a torch tensor on the index's device when on_device): the count pass
+        and the totals, no row is written"""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        masks = list(masks)
+        nq = len(masks)
+        table = _mask_table(masks, nq, f"{nq} queries", "query")
+        (total,), ptr, stream, dev = _outputs(on_device, self.device, (nq,), (np.int64,))
+        if nq:
+            rc = self._lib.icd_rowmask_select(self._h, table.ctypes.data, nq, None, 1, None, ptr(total), None, dev, stream)
+            if rc == -1:
+                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+            _check(self._lib, rc)
+        return total
 
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""

@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /codes/query, GET /codes/{code}, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -18,7 +18,7 @@ from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
 from .icd_models import (DiagnosisMatch, EmbeddingRequest, EmbeddingResponse, HealthCheckResponse,
-                         HybridQueryRequest, QueryRequest, QueryResponse, convert_numpy_types)
+                         HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
 
@@ -222,6 +222,44 @@ async def hybrid_query(request: HybridQueryRequest):
         raise
     except Exception as exc:
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+
+
+@app.post("/codes/query", response_model=ScalarQueryResponse)
+async def codes_query(request: ScalarQueryRequest):
+    """MilvusClient.query over the scalar fields (MilvusService.query_batch / count): the rows a filter
+    selects, in ascending id, and their number. `total` is always filled - the device counts the selection in the call that pages
+    it. count=true returns the total alone. Bad arguments are a 400."""
+    if not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        if not 1 <= request.limit <= 1000:
+            raise ValueError(f"limit={request.limit}: 1 .. 1000")
+        if request.count:
+            return ScalarQueryResponse(total=milvus_service.count(request.filter), rows=[])
+        lists, totals = milvus_service.query_batch([request.filter], request.limit, request.offset, request.output_fields, with_totals=True)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    return ScalarQueryResponse(total=totals[0], rows=convert_numpy_types(lists[0]))
+
+
+@app.get("/codes/{code}")
+async def codes_get(code: str):
+    """The stored record of one ICD code (`code == "..."` through MilvusService.query); 404 when the collection holds none"""
+    if not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    if '"' in code or "\\" in code:
+        raise HTTPException(status_code=400, detail="code: no quotes or backslashes")
+    try:
+        rows = milvus_service.query(f'code == "{code}"', limit=10)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    if not rows:
+        raise HTTPException(status_code=404, detail=f"no record with code {code}")
+    return convert_numpy_types(rows[0])
 
 
 @app.post("/embed", response_model=EmbeddingResponse)

@@ -258,3 +258,18 @@ class HealthCheckResponse(BaseModel):
     milvus_connected: bool
     embedding_model_loaded: bool
     total_records: int
+
+
+class ScalarQueryRequest(BaseModel):
+    """POST /codes/query: MilvusClient.query over the scalar fields - no text, no vector (MilvusService.query / count). The ranges
+    are checked by the route (a 400 with the reason), not by the model (which would answer 422)."""
+    filter: str = Field(default="", description="Milvus filter expression over the scalar fields; empty: every row")
+    limit: int = Field(default=100, description="rows returned (1 .. 1000)")
+    offset: int = Field(default=0, description="rows of the selection skipped first (offset + limit <= 16384)")
+    output_fields: Optional[List[str]] = Field(default=None, description="fields of every row (default: the stored fields and id)")
+    count: bool = Field(default=False, description="only the total: no rows are returned")
+
+
+class ScalarQueryResponse(BaseModel):
+    total: int = Field(..., description="rows the filter selects (the device's count, whatever limit and offset say)")
+    rows: List[Dict[str, Any]] = Field(default_factory=list, description="the selection's rows offset .. offset + limit in ascending id")

@@ -372,6 +372,71 @@ int icd_rowmask_read(icd_rowmask *m, uint32_t *out_words, int64_t out_count) {
     return ICD_OK;
 }
 
+// ---- the ordered select over a batch of masks (mask_select_kernel.hpp) ---------------------------------------
+// Its mask table keeps the NULL entries (the kernels count and walk "every row" without a bitset) and travels with the offsets:
+// both through pinned blocks behind stage_masks' event, under the handle's mutex.
+static int stage_select(icd_index *x, icd_rowmask *const *masks, const int64_t *offsets, int nq, hipStream_t s) {
+    if (x->mask_copy_pending) { HIP_TRY(hipEventSynchronize(x->ev_mask)); x->mask_copy_pending = false; }
+    for (int q = 0; q < nq; ++q) {
+        x->h_mask[q] = masks[q] ? masks[q]->bits : nullptr;
+        x->h_sel_off[q] = offsets ? (long long)offsets[q] : 0ll;
+    }
+    const hipError_t em = hipMemcpyAsync(x->mask_dev, x->h_mask, (size_t)nq * sizeof(uint32_t *), hipMemcpyHostToDevice, s);
+    const hipError_t eo = hipMemcpyAsync(x->sel_off, x->h_sel_off, (size_t)nq * sizeof(long long), hipMemcpyHostToDevice, s);
+    const hipError_t ee = hipEventRecord(x->ev_mask, s);   // (also behind a copy that failed to enqueue, as in stage_masks)
+    x->mask_copy_pending = ee == hipSuccess;
+    if (em != hipSuccess || eo != hipSuccess || ee != hipSuccess) {
+        hipStreamSynchronize(s);
+        x->mask_copy_pending = false;
+        return fail(ICD_ERR_HIP, "select table: %s", hipGetErrorString(em != hipSuccess ? em : eo != hipSuccess ? eo : ee));
+    }
+    return ICD_OK;
+}
+
+int icd_rowmask_select(icd_index *idx, icd_rowmask *const *masks, int64_t nq, const int64_t *offsets, int32_t limit, int64_t *out_ids,
+                       int64_t *out_total, int32_t *out_taken, int32_t out_on_device, void *stream) {
+    static_assert(ICD_SELECT_MAX_LIMIT == MS_MAX_LIMIT, "include/icd_search.h and mask_select_plan.hpp disagree");
+    if (limit < 1 || limit > ICD_SELECT_MAX_LIMIT) return fail(ICD_ERR_INVALID, "limit=%d: a select returns 1 .. %d rows per query", limit, ICD_SELECT_MAX_LIMIT);
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    if (!out_total) return fail(ICD_ERR_INVALID, "out_total is NULL");
+    if (out_ids && !out_taken) return fail(ICD_ERR_INVALID, "out_taken is NULL (out_ids without it cannot be read)");
+    if (nq > 0 && !masks) return fail(ICD_ERR_INVALID, "masks is NULL");
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    bool any = false;
+    if (const int rc = check_masks(idx, masks, nq, "row select", &any)) return rc;
+    for (int64_t q = 0; offsets && q < nq; ++q)
+        if (offsets[q] < 0) return fail(ICD_ERR_INVALID, "offsets[%lld]=%lld is negative", (long long)q, (long long)offsets[q]);
+    const long long segments = ms_segments(idx->n);
+    if (nq * segments > 0x7FFFFFFFll) return fail(ICD_ERR_INVALID, "nq=%lld: %lld segments of rows times nq exceed 2^31 - 1 work-groups", (long long)nq, segments);
+    const size_t slots = (size_t)nq * (size_t)limit;
+    if (!out_on_device && out_ids && slots > idx->sel_out_cap)
+        return fail(ICD_ERR_INVALID, "nq=%lld x limit=%d: host outputs hold up to %lld ids per call (device outputs have no such bound)", (long long)nq, limit, (long long)idx->sel_out_cap);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (stream_capturing(s)) return fail(ICD_ERR_INVALID, "a row select stages its mask table on the host at call time: it cannot be captured into a graph");
+    if (nq == 0) return ICD_OK;
+    std::lock_guard<std::mutex> guard(idx->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    if (const int rc = stage_select(idx, masks, offsets, (int)nq, s)) return rc;
+    const bool host = !out_on_device;
+    MaskSelectArgs a{};
+    a.masks = idx->mask_dev; a.offsets = idx->sel_off; a.counts = idx->sel_counts;
+    a.ids = reinterpret_cast<long long *>(out_ids && host ? reinterpret_cast<int64_t *>(idx->sel_ids) : out_ids);
+    a.total = host ? idx->sel_total : reinterpret_cast<long long *>(out_total);
+    a.taken = out_taken && host ? idx->sel_taken : out_taken;
+    a.n = idx->n; a.mask_words = rowmask_tile_words(idx->n); a.segments = (int)segments; a.limit = limit;
+    const dim3 grid((unsigned)(nq * segments));
+    hipLaunchKernelGGL(mask_count_kernel, grid, dim3(MS_THREADS), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mask_select_kernel, grid, dim3(MS_THREADS), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    if (!host) return ICD_OK;
+    if (out_ids) HIP_TRY(hipMemcpyAsync(out_ids, idx->sel_ids, slots * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_total, idx->sel_total, (size_t)nq * sizeof(long long), hipMemcpyDeviceToHost, s));
+    if (out_taken) HIP_TRY(hipMemcpyAsync(out_taken, idx->sel_taken, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ICD_OK;
+}
+
 // A NULL table or an all-NULL table is the range search (which the all-NULL table equals bit for bit), under its name.
 int icd_index_search_masked(icd_index *idx, icd_rowmask *const *masks, const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
                             const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,

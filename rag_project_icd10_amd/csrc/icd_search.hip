@@ -25,6 +25,7 @@
 #include "sparse_kernel.hpp"
 #include "text_match_kernel.hpp"
 #include "filter_mask_kernel.hpp"
+#include "mask_select_kernel.hpp"
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
@@ -247,6 +248,13 @@ struct icd_index {
     uint32_t *mask_ones = nullptr;
     hipEvent_t ev_mask = nullptr;       // recorded behind the table's copy: the next masked call waits for it before it refills the
     bool mask_copy_pending = false;     // pinned table - whatever became of the call in between (an error return included)
+    // ordered select over row masks (icd_rowmask_select): the per-(query, segment) counts of a call, its
+    // offsets (pinned h_sel_off -> sel_off, behind the mask table's event), and the staging of a call with host outputs
+    int *sel_counts = nullptr;          // [max_nq][ms_segments(n)]
+    long long *sel_off = nullptr, *h_sel_off = nullptr;   // [max_nq] each
+    long long *sel_ids = nullptr, *sel_total = nullptr;   // [sel_out_cap], [max_nq]
+    int *sel_taken = nullptr;           // [max_nq]
+    size_t sel_out_cap = 0;             // id slots of a call with host outputs (ms_host_slots)
     unsigned long long uid = 0;         // identity of this index among all ever created in the process (a row mask remembers it)
     unsigned long long *dbg = nullptr;  // diagnostic cycle counters [8192][4][4]
     unsigned int *pace = nullptr;       // [PACE_WORDS] arrival counters of the paced coarse sweep (coarse_flat_kernel.hpp, 67108864)
@@ -281,6 +289,8 @@ void free_all(icd_index *x) {
     if (x->h_band) hipHostFree(x->h_band);
     hipFree(x->mask_dev); hipFree(x->mask_ones);
     if (x->h_mask) hipHostFree(x->h_mask);
+    hipFree(x->sel_counts); hipFree(x->sel_off); hipFree(x->sel_ids); hipFree(x->sel_total); hipFree(x->sel_taken);
+    if (x->h_sel_off) hipHostFree(x->h_sel_off);
     if (x->ev_mask) hipEventDestroy(x->ev_mask);
     if (x->h_nflag) hipHostFree(x->h_nflag);
     if (x->h_pin) hipHostFree(x->h_pin);
@@ -1380,6 +1390,14 @@ static int create_index(const float *corpus, int64_t n, int32_t dim, const int32
         for (int64_t r = 0; r < n; r += 32) ones[(size_t)(r >> 5)] = n - r >= 32 ? ~0u : ((1u << (n - r)) - 1u);
         CR_TRY(wsalloc(&x->mask_ones, mw));
         CR_TRY(hipMemcpy(x->mask_ones, ones.data(), mw * sizeof(uint32_t), hipMemcpyHostToDevice));
+        // the ordered select's scratch and staging (icd_rowmask_select allocates nothing)
+        CR_TRY(wsalloc(&x->sel_counts, (size_t)ms_scratch_counts(n, max_nq)));
+        CR_TRY(wsalloc(&x->sel_off, (size_t)max_nq));
+        CR_TRY(hipHostMalloc(reinterpret_cast<void **>(&x->h_sel_off), (size_t)max_nq * sizeof(long long), hipHostMallocDefault));
+        x->sel_out_cap = (size_t)ms_host_slots(max_nq);
+        CR_TRY(wsalloc(&x->sel_ids, x->sel_out_cap));
+        CR_TRY(wsalloc(&x->sel_total, (size_t)max_nq));
+        CR_TRY(wsalloc(&x->sel_taken, (size_t)max_nq));
     }
     CR_TRY(wsalloc(&x->pace, PACE_WORDS));
     CR_TRY(wsalloc(&x->dbg, (size_t)8192 * 16));

@@ -39,6 +39,46 @@ _OUTPUT_FIELDS = ("code", "preferred_zh", "has_complication", "main_code", "seco
                   "parent_code", "category_path", "semantic_text")
 
 
+class QueryIterator:
+    """pymilvus's query_iterator surface (MilvusService.query_iterator): next() -> the following rows of a
+    filter's selection in ascending id as `query`-shaped dicts ([] when exhausted or after `limit` rows), close(). The cursor is a
+    rank offset into ONE row mask held for the iterator's life (None: every row): a page is one select_rows call, whatever its
+    depth. The iterator pins the index and the store generation it started on: after a mutation of the store next() raises
+    RuntimeError instead of paging through two different corpora."""
+
+    def __init__(self, service, index, mask, batch_size: int, limit: int, fields, start: int, generation_of):
+        self._service, self._index, self._mask = service, index, mask
+        self._batch, self._left = batch_size, (None if limit == -1 else limit)
+        self._fields, self._cursor = fields, start
+        self._generation_of = generation_of
+        self._generation = generation_of()
+        self._done = index is None
+
+    def next(self) -> List[Dict[str, Any]]:   # noqa: A003 (pymilvus's name)
+        if self._done or (self._left is not None and self._left <= 0):
+            self._done = True
+            return []
+        if self._generation_of() != self._generation or self._index.closed or (self._mask is not None and self._mask.closed):
+            raise RuntimeError("the collection changed under the iterator: start a new query_iterator")
+        want = self._batch if self._left is None else min(self._batch, self._left)
+        ids, total, taken = self._index.select_rows([self._mask], want, self._cursor)
+        got = int(taken[0])
+        self._cursor += got
+        if got < want or self._cursor >= int(total[0]):
+            self._done = True
+        if got == 0:
+            return []
+        if self._left is not None:
+            self._left -= got
+        return self._service._rows_to_dicts(ids[0, :got], self._fields)
+
+    def close(self):
+        self._done = True
+        if self._mask is not None:
+            self._service._release_masks([self._mask])   # (a TEXT_MATCH mask is the iterator's own; a cached one stays)
+        self._index = self._mask = None
+
+
 class MilvusService:
     def __init__(self, embedding_service=None):
         self.config = self._load_config()
@@ -520,6 +560,188 @@ class MilvusService:
             st = mask.stats()
             out.append({"expression": key, "rows": int(st["rows"]), "generation": gen, "bytes": int(st["bytes"])})
         return out
+
+    # ---- scalar query (Milvus query / count(*) / get / query_iterator) ----------------------------------------
+    # The calls of MilvusClient that carry no vector. The primary key is the store's row id - the `id` a search hit carries (the
+    # reference's collection is auto-id); results come in ascending id. The filter goes through _mask_route like a masked search's;
+    # what is left is an ordered select over the masks' bits, on the device (_native.IcdIndex.select_rows). These methods are
+    # additive: the reference's "never raise out of search" rule is not extended to them - a bad argument raises ValueError.
+    QUERY_WINDOW = 16384   # Milvus's offset + limit bound; _native.SELECT_MAX_LIMIT
+    COUNT_FIELD = "count(*)"
+
+    @staticmethod
+    def _query_fields(output_fields):
+        """the checked field list of a query: the nine stored fields and `id` by default; `vector` on request"""
+        if output_fields is None:
+            return list(_OUTPUT_FIELDS) + ["id"]
+        if isinstance(output_fields, str) or not isinstance(output_fields, (list, tuple)):
+            raise ValueError("output_fields: a list of field names")
+        fields = list(output_fields)
+        for f in fields:
+            if f not in _OUTPUT_FIELDS and f not in ("id", "vector"):
+                raise ValueError(f"output_fields: unknown field {f!r}")
+        if "id" not in fields:
+            fields.append("id")   # (Milvus always returns the primary key)
+        return fields
+
+    @staticmethod
+    def _query_expr(filter):   # noqa: A002
+        """a query's filter as _masks_for takes it: None for no filter (also "" and blanks), else the checked expression"""
+        if filter is None:
+            return None
+        if not isinstance(filter, str):
+            raise ValueError("filter: a Milvus filter expression (a string)")
+        if not filter.strip():
+            return None
+        filter_expr.compile(filter)   # (ValueError on a bad one, before anything is loaded)
+        return filter
+
+    @classmethod
+    def _query_window(cls, limit, offset):
+        for name, v, least in (("limit", limit, 1), ("offset", offset, 0)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+                raise ValueError(f"{name}={v!r}: an int >= {least}")
+        if int(offset) + int(limit) > cls.QUERY_WINDOW:
+            raise ValueError(f"offset + limit = {int(offset) + int(limit)} exceeds {cls.QUERY_WINDOW}")
+        return int(limit), int(offset)
+
+    def _rows_to_dicts(self, ids, fields) -> List[Dict[str, Any]]:
+        recs = self.client.records
+        mat = self.client.matrix() if "vector" in fields else None
+        out = []
+        for i in ids:
+            i = int(i)
+            rec = recs[i]
+            row = {}
+            for f in fields:
+                row[f] = i if f == "id" else (mat[i].tolist() if f == "vector" else rec.get(f))
+            out.append(row)
+        return out
+
+    def _select_rows(self, index, masks, limit: int, offsets):
+        """IcdIndex.select_rows over a batch of any length: max_nq masks per call"""
+        nq, step = len(masks), index.max_nq
+        if nq <= step:
+            return index.select_rows(masks, limit, offsets)
+        parts = [index.select_rows(masks[s:s + step], limit, offsets[s:s + step]) for s in range(0, nq, step)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+
+    def query_batch(self, filters, limit: int, offset=0, output_fields=None, with_totals: bool = False):
+        """One `query` per entry of `filters` (an expression, "" or None each) with a shared limit and one offset for all or one per
+        entry: a list of row lists. All masks come from ONE _masks_for call (one filter_masks launch for every device program of the
+        batch, equal expressions share a mask), all rows from ONE select_rows call. with_totals: (lists, totals) - the number of
+        rows every filter selects, counted by the same call."""
+        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
+            raise ValueError("filters: a list of filter expressions")
+        exprs = [self._query_expr(e) for e in filters]
+        nq = len(exprs)
+        fields = self._query_fields(output_fields)
+        offs = list(offset) if isinstance(offset, (list, tuple, np.ndarray)) else [offset] * nq
+        if len(offs) != nq:
+            raise ValueError(f"offset holds {len(offs)} entries for {nq} filters")
+        offs = [self._query_window(limit, o)[1] for o in offs] if nq else []
+        limit = self._query_window(limit, 0)[0]
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None or nq == 0:
+            return ([[] for _ in exprs], [0] * nq) if with_totals else [[] for _ in exprs]
+        masks = self._masks_for(index, exprs, nq)
+        try:
+            ids, total, taken = self._select_rows(index, masks, limit, np.asarray(offs, np.int64))
+        finally:
+            self._release_masks(masks)
+        lists = [self._rows_to_dicts(ids[q, :int(taken[q])], fields) for q in range(nq)]
+        return (lists, [int(t) for t in total]) if with_totals else lists
+
+    def count_batch(self, filters) -> List[int]:
+        """the number of rows every filter of the list selects: one _masks_for call, one count pass over the masks"""
+        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
+            raise ValueError("filters: a list of filter expressions")
+        exprs = [self._query_expr(e) for e in filters]
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None or not exprs:
+            return [0] * len(exprs)
+        masks = self._masks_for(index, exprs, len(exprs))
+        try:
+            step = index.max_nq
+            total = np.concatenate([index.count_rows(masks[s:s + step]) for s in range(0, len(masks), step)])
+        finally:
+            self._release_masks(masks)
+        return [int(t) for t in total]
+
+    def count(self, filter: str = "") -> int:   # noqa: A002
+        """Milvus's query(filter, output_fields=["count(*)"]) as a number"""
+        return self.count_batch([filter])[0]
+
+    def get(self, ids, output_fields=None) -> List[Dict[str, Any]]:
+        """MilvusClient.get: the rows with these ids, in the order asked for; unknown ids are left out. Host only."""
+        fields = self._query_fields(output_fields)
+        if isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+            ids = [ids]
+        if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple, np.ndarray)):
+            raise ValueError("ids: an int or a list of ints")
+        for i in ids:
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+                raise ValueError(f"ids: {i!r} is not an int")
+        if self.client is None or not self.client.exists():
+            return []
+        n = self.client.count
+        return self._rows_to_dicts([int(i) for i in ids if 0 <= int(i) < n], fields)
+
+    def query(self, filter: str = "", output_fields=None, limit: Optional[int] = None, offset: int = 0, ids=None) -> List[Dict[str, Any]]:   # noqa: A002
+        """MilvusClient.query: the rows the filter selects, in ascending id, as dicts of output_fields (default: the nine stored
+        fields and `id`; `vector` on request). output_fields=["count(*)"] gives [{"count(*)": total}] and takes neither limit nor
+        offset, as in Milvus. limit=None: every matching row (walked in windows of 16384); else offset + limit <= 16384. ids=[...]
+        without a filter is `get`. An empty or unloaded collection answers [] (a count of 0). Bad arguments raise ValueError."""
+        expr = self._query_expr(filter)
+        if ids is not None:
+            if expr is not None:
+                raise ValueError("query takes ids or a filter, not both")
+            if limit is not None or offset != 0:
+                raise ValueError("query by ids takes no limit and no offset")
+            return self.get(ids, output_fields)
+        if output_fields is not None and not isinstance(output_fields, str) and self.COUNT_FIELD in list(output_fields):
+            if list(output_fields) != [self.COUNT_FIELD]:
+                raise ValueError("count(*) cannot be combined with other output fields")
+            if limit is not None or offset != 0:
+                raise ValueError("count(*) takes no limit and no offset")
+            return [{self.COUNT_FIELD: self.count(filter)}]
+        if limit is not None:
+            return self.query_batch([expr], limit, offset, output_fields)[0]
+        fields = self._query_fields(output_fields)
+        start = self._query_offset(offset)
+        out: List[Dict[str, Any]] = []
+        it = self.query_iterator(batch_size=self.QUERY_WINDOW, filter=filter, output_fields=fields, _start=start)
+        try:
+            while True:
+                page = it.next()
+                if not page:
+                    return out
+                out.extend(page)
+        finally:
+            it.close()
+
+    @staticmethod
+    def _query_offset(offset) -> int:
+        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
+            raise ValueError(f"offset={offset!r}: an int >= 0")
+        return int(offset)
+
+    def query_iterator(self, batch_size: int = 1000, limit: int = -1, filter: str = "", output_fields=None, _start: int = 0) -> "QueryIterator":   # noqa: A002
+        """pymilvus's query_iterator: an object whose next() returns the following batch_size rows of the filter's selection in
+        ascending id ([] when exhausted or after `limit` rows), and close(). The cursor is a rank offset into ONE mask the iterator
+        holds for its life; next() raises RuntimeError after the store changed, as search_iterator's does.
+        batch_size <= 16384. Bad arguments raise ValueError."""
+        expr = self._query_expr(filter)
+        fields = self._query_fields(output_fields)
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 1 <= batch_size <= self.QUERY_WINDOW:
+            raise ValueError(f"batch_size={batch_size!r}: an int in 1 .. {self.QUERY_WINDOW}")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or (limit < 0 and limit != -1):
+            raise ValueError("limit must be -1 (no limit) or a non-negative integer")
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        mask = None if index is None or expr is None else self._masks_for(index, [expr], 1)[0]
+        client = self.client
+        return QueryIterator(self, index, mask, int(batch_size), int(limit), fields, int(_start),
+                             lambda: (id(self.client), None if client is None else (client.generation, client.count)))
 
     @staticmethod
     def _check_band(top_k, group_by_field, radius, range_filter, offset, search_params):
