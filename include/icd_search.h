@@ -592,6 +592,29 @@ int icd_rowmask_select(icd_index *idx, icd_rowmask *const *masks, int64_t nq, co
                        int64_t *out_total, int32_t *out_taken, int32_t out_on_device, void *stream);
 
 /*
+ * Facet counts: how the rows of every mask of a batch spread over the groups of a grouping - the terms aggregation of a search
+ * front end, the count that goes with group_by_field. For every query q and every group j of `grouping`:
+ *
+ *   out_counts[q][j]        the rows r with bit r set in masks[q] (a NULL entry: every row of the index) whose group is the j-th
+ *                           smallest distinct id of the grouping's group_of - the dense number icd_grouping_create assigns.
+ *                           int32 [nq][G], G from icd_grouping_stats; a row of it sums to the mask's icd_rowmask_select total.
+ *
+ * One memset and ONE launch on `stream` (facet_count_kernel over (query, segment of 16 384 rows)) whatever nq and the masks hold.
+ * The counts are summed with integer atomic adds, in LDS up to 8 192 groups and in the output above it: integer addition commutes,
+ * the result is the same bytes on every run. The call zeroes the output itself: nothing of an earlier call shows. masks:
+ * icd_rowmask_select's rules - a HOST array of nq entries, each NULL or a live mask of `idx`, staged through the index's pinned table
+ * (ICD_ERR_INVALID while `stream` is capturing). out_on_device = 1: out_counts is device memory and the call only enqueues; 0: host
+ * memory, written when the call returns - the counts go through the grouping's per-group key block (idle outside a grouped search,
+ * taken under the grouping's lock; twice its query block of queries per launch, a longer batch runs in passes). Nothing is
+ * allocated in a call. Every check comes before the first device call: ICD_ERR_INVALID for nq above the index's max_nq, a mask or a
+ * grouping of another index, NULL arrays; ICD_ERR_STATE for a destroyed index, grouping or mask; ICD_ERR_UNSUPPORTED for a view as
+ * `idx` and for a grouping that was created on a view (group and mask the parent). nq = 0 does nothing. A refused call leaves the
+ * index and the grouping usable. The row-sharded path (icd_group_*) has no facet call: count on every shard and add the rows.
+ */
+int icd_rowmask_group_counts(icd_index *idx, icd_grouping *grouping, icd_rowmask *const *masks, int64_t nq,
+                             int32_t *out_counts /* [nq][G] */, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

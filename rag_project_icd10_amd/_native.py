@@ -44,10 +44,11 @@ EXPORTED_SYMBOLS = (
     "icd_sparse_search_range",
     "icd_sparse_match_rowmasks", "icd_rowmask_read",
     "icd_columns_create", "icd_columns_destroy", "icd_columns_stats", "icd_filter_program_check", "icd_filter_rowmasks",
-    "icd_rowmask_select",
+    "icd_rowmask_select", "icd_rowmask_group_counts",
 )
 SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
 SELECT_SEGMENT_ROWS = 16384   # csrc/mask_select_plan.hpp MS_SEG_ROWS: rows of one work-group of the select's two passes
+FACET_LDS_GROUPS = 8192   # csrc/facet_count_plan.hpp FC_LDS_GROUPS: groups up to which a facet count sums in LDS (above it: global adds)
 SPARSE_MAX_QUERY_TERMS = 64  # include/icd_search.h ICD_SPARSE_MAX_QUERY_TERMS
 MAX_REQUESTS = 8   # include/icd_search.h ICD_MAX_REQUESTS: requests per query of a hybrid search
 RANKER_RRF, RANKER_WEIGHTED = 0, 1
@@ -155,6 +156,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_filter_program_check.argtypes = [vp, vp, i64, i32, i64, vp, i64]
     lib.icd_filter_rowmasks.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
     lib.icd_rowmask_select.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, i32, vp]
+    lib.icd_rowmask_group_counts.argtypes = [vp, vp, vp, i64, vp, i32, vp]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
@@ -915,6 +917,25 @@ class IcdIndex:
             _check(self._lib, rc)
         return total
 
+    def group_counts(self, masks, grouping: "IcdGrouping", *, on_device: bool = False):
+        """Facet counts (icd_rowmask_group_counts): int32 [nq, G], counts[q][j] = the rows of masks[q] whose
+        group is grouping.group_ids[j]. masks is a sequence of IcdRowMask or None (None: every row of the index, so the row of
+        counts is the group sizes). A numpy array; on_device=True: a torch tensor on the index's device, enqueued on torch's
+        current stream, no synchronisation. One launch whatever the batch holds; exact integers, the same bytes on every run; a
+        row sums to count_rows of its mask. At most max_nq masks per call. Bad arguments raise ValueError."""
+        if self.closed or grouping is None or grouping.closed:
+            raise IcdError(-5, "index or grouping is closed")
+        masks = list(masks)
+        nq = len(masks)
+        table = _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the call)
+        (counts,), ptr, stream, dev = _outputs(on_device, self.device, (nq, grouping.groups), (np.int32,))
+        if nq:
+            rc = self._lib.icd_rowmask_group_counts(self._h, grouping._h, table.ctypes.data, nq, ptr(counts), dev, stream)
+            if rc == -1:
+                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
+            _check(self._lib, rc)
+        return counts
+
     def lookup_levels(self, ids):
         """Levels of hit ids (torch CUDA int64 tensor) -> int32 tensor; ids < 0 give 0."""
         import torch
@@ -991,6 +1012,20 @@ class IcdGrouping(_Handle):
         self.n, self.max_nq, self.device = n, int(max_nq), index.device
         _check(self._lib, self._lib.icd_grouping_create(index._h, ptr, n, on_dev, self.max_nq, C.byref(self._h)))
         self._paired = False
+        self._group_of, self._group_ids = keep, None   # (kept until group_ids is first asked for)
+        self.groups = int(self.stats()["groups"])
+
+    @property
+    def group_ids(self) -> np.ndarray:
+        """the sorted distinct ids of group_of (int32 [groups]): entry j is the group of column j of IcdIndex.group_counts, the
+        dense number icd_grouping_create assigns"""
+        if self._group_ids is None:
+            ids = self._group_of
+            ids = ids.cpu().numpy() if _is_torch_tensor(ids) else ids
+            self._group_ids = np.unique(ids).astype(np.int32)
+            self._group_ids.setflags(write=False)
+            self._group_of = None
+        return self._group_ids
 
     def pair_sparse(self, index: "IcdIndex", sp: "IcdSparse"):
         """The one-time pairing with a sparse index of the same IcdIndex (icd_grouping_pair_sparse): the grouping's row ->

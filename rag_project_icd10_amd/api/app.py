@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /codes/query, GET /codes/{code}, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -17,7 +17,7 @@ from contextlib import asynccontextmanager
 from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
-from .icd_models import (DiagnosisMatch, EmbeddingRequest, EmbeddingResponse, HealthCheckResponse,
+from .icd_models import (DiagnosisMatch, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
                          HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
@@ -242,6 +242,21 @@ async def codes_query(request: ScalarQueryRequest):
     except Exception as exc:
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
     return ScalarQueryResponse(total=totals[0], rows=convert_numpy_types(lists[0]))
+
+
+@app.post("/codes/facets", response_model=FacetResponse)
+async def codes_facets(request: FacetRequest):
+    """The terms aggregation of a code browser (MilvusService.facet_batch): the rows a filter selects counted
+    per value of `field`, most frequent first, and their number. Bad arguments are a 400."""
+    if not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        lists, totals = milvus_service.facet_batch(request.field, [request.filter], request.limit, request.min_count, with_totals=True)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    return FacetResponse(field=request.field, total=totals[0], facets=convert_numpy_types(lists[0]))
 
 
 @app.get("/codes/{code}")

@@ -273,3 +273,18 @@ class ScalarQueryRequest(BaseModel):
 class ScalarQueryResponse(BaseModel):
     total: int = Field(..., description="rows the filter selects (the device's count, whatever limit and offset say)")
     rows: List[Dict[str, Any]] = Field(default_factory=list, description="the selection's rows offset .. offset + limit in ascending id")
+
+
+class FacetRequest(BaseModel):
+    """POST /codes/facets: how the rows a filter selects spread over the values of one field (MilvusService.facet_batch). The
+    ranges are checked by the route (a 400 with the reason), not by the model."""
+    field: str = Field(..., description="the field counted: level, code, parent_code, has_complication, ... or category")
+    filter: str = Field(default="", description="Milvus filter expression over the scalar fields; empty: every row")
+    limit: Optional[int] = Field(default=None, description="values returned, most frequent first (default: every value)")
+    min_count: int = Field(default=1, description="values with fewer rows are left out")
+
+
+class FacetResponse(BaseModel):
+    field: str
+    total: int = Field(..., description="rows the filter selects (every row carries exactly one value of the field)")
+    facets: List[Dict[str, Any]] = Field(default_factory=list, description='{"value", "count"}: count descending, then value ascending')

@@ -10,6 +10,7 @@ struct icd_grouping : OwnedHandle {
     static constexpr uint32_t MAGIC = 0x1CD96B0Fu;
     static constexpr const char *NOUN = "grouping";
     int G = 0, largest = 0, max_nq = 0, qb = 0;
+    bool on_view = false;   // created for a view: its rows are the view's, not the parent's (no mask addresses them)
     long long ldS = 0;
     int *group_of = nullptr, *dense_of = nullptr, *order = nullptr, *gpos = nullptr, *seg = nullptr;
     int *pos_of = nullptr;   // [n] the inverse of `order`; built by icd_grouping_pair_sparse, absent before
@@ -112,7 +113,7 @@ int icd_grouping_create(icd_index *idx, const int32_t *group_of, int64_t n, int3
 
     icd_grouping *g = new_handle<icd_grouping>(idx);
     if (!g) return fail(ICD_ERR_NOMEM, "host allocation failed");
-    g->G = G; g->largest = largest; g->max_nq = max_nq;
+    g->G = G; g->largest = largest; g->max_nq = max_nq; g->on_view = idx->row_map != nullptr;
     g->qb = std::min(GROUP_QUERY_BLOCK, (max_nq + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE);
     g->ldS = ((long long)n + GROUP_TILE - 1) / GROUP_TILE * GROUP_TILE;
     const size_t no = (size_t)max_nq * ICD_MAX_K;

@@ -672,6 +672,52 @@ class MilvusService:
         """Milvus's query(filter, output_fields=["count(*)"]) as a number"""
         return self.count_batch([filter])[0]
 
+    # ---- facet counts (the terms aggregation over a filter's rows; DESIGN.md section 20) ---------------------------------------------
+    # How the rows a filter selects spread over the values of a field: the masks of _masks_for and the whole-store grouping of
+    # _grouping, read together on the device (_native.IcdIndex.group_counts). Additive like the scalar query: bad arguments raise.
+    @staticmethod
+    def _facet_args(field, limit, min_count):
+        if not isinstance(field, str) or field not in filter_expr.GROUP_FIELDS:
+            raise ValueError(f"field={field!r}: not one of {', '.join(filter_expr.GROUP_FIELDS)}")
+        if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1):
+            raise ValueError(f"limit={limit!r}: None or an int >= 1")
+        if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or min_count < 0:
+            raise ValueError(f"min_count={min_count!r}: an int >= 0")
+        return None if limit is None else int(limit), int(min_count)
+
+    def facet_batch(self, field: str, filters, limit: Optional[int] = None, min_count: int = 1, with_totals: bool = False):
+        """One facet list per entry of `filters` (an expression, "" or None each): [{"value": v, "count": c}, ...] - the number of
+        rows the filter selects under every value of `field` (one of filter_expr.GROUP_FIELDS), count descending, equal counts in
+        the values' ascending order; values below min_count are left out, the list is cut at `limit` when one is given. All masks
+        come from ONE _masks_for call (equal expressions share a mask, no filter is a NULL entry), all counts from one group_counts
+        call per max_nq masks. with_totals: (lists, totals) - the rows every filter selects, the sum of its counts before the cut.
+        An empty or unloaded collection answers []. Bad arguments raise ValueError."""
+        limit, min_count = self._facet_args(field, limit, min_count)
+        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
+            raise ValueError("filters: a list of filter expressions")
+        exprs = [self._query_expr(e) for e in filters]
+        nq = len(exprs)
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None or nq == 0:
+            return ([[] for _ in exprs], [0] * nq) if with_totals else [[] for _ in exprs]
+        grouping, values = self._grouping(field, index, None, None)
+        masks = self._masks_for(index, exprs, nq)
+        try:
+            step = index.max_nq
+            counts = np.concatenate([index.group_counts(masks[s:s + step], grouping) for s in range(0, nq, step)])
+        finally:
+            self._release_masks(masks)
+        lists = []
+        for row in counts:
+            order = np.argsort(-row.astype(np.int64), kind="stable")   # (stable: equal counts keep the values' order)
+            order = order[row[order] >= min_count][:limit]
+            lists.append([{"value": values[j].item() if hasattr(values[j], "item") else values[j], "count": int(row[j])} for j in order])
+        return (lists, [int(t) for t in counts.sum(axis=1, dtype=np.int64)]) if with_totals else lists
+
+    def facet(self, field: str, filter: str = "", limit: Optional[int] = None, min_count: int = 1) -> List[Dict[str, Any]]:   # noqa: A002
+        """the facet list of ONE filter (facet_batch)"""
+        return self.facet_batch(field, [filter], limit, min_count)[0]
+
     def get(self, ids, output_fields=None) -> List[Dict[str, Any]]:
         """MilvusClient.get: the rows with these ids, in the order asked for; unknown ids are left out. Host only."""
         fields = self._query_fields(output_fields)
