@@ -615,6 +615,55 @@ int icd_rowmask_group_counts(icd_index *idx, icd_grouping *grouping, icd_rowmask
                              int32_t *out_counts /* [nq][G] */, int32_t out_on_device, void *stream);
 
 /*
+ * MMR search: the k best rows that are not copies of each other - maximal marginal relevance over the exact candidate list, what
+ * LangChain's Milvus vector store does on the host in max_marginal_relevance_search(query, k, fetch_k, lambda_mult) (DESIGN.md
+ * section 21). Per query q, with 1 <= k <= fetch_k <= ICD_MAX_K, fetch_k <= the index's max_k and lambda a double in [0, 1]:
+ *   candidates        what icd_index_search_masked returns for the query at k = fetch_k, reweighted = 0, with the call's masks /
+ *                     radius / range_filter (no cursor); with no mask and no bound what icd_index_search_range returns, the
+ *                     ICD_MODE_EXACT list. Candidate i has row r_i, raw score rel_i (the canonical score) and a level; C is the
+ *                     number of real hits, padding slots are not candidates.
+ *   sim(i, j)         the canonical score of row r_j with row r_i as the query: the strict d-ascending fmaf chain from +0.0f over
+ *                     the fp32 rows the index holds (oracle/icd_oracle.c chain_score); symmetric in its two rows.
+ *   picks             pick 0 is candidate 0. For t >= 1 every unpicked i has pen_i, the float maximum of sim(i, s) over the picked
+ *                     s: it starts at sim(i, pick 0) and is updated with plain `s > pen ? s : pen`. value_i = lambda * (double)rel_i
+ *                     - (1 - lambda) * (double)pen_i: the two products and the difference each rounded once, in double, no
+ *                     contraction; 1 - lambda is computed once on the host. The pick is the unpicked candidate of the greatest
+ *                     value under plain `>`, ties to the lower candidate index (the better (score desc, id asc) rank). A NaN value
+ *                     never wins; when no unpicked candidate has a comparable value the lowest unpicked index is taken. Picking
+ *                     stops after min(k, C) picks.
+ *   reweighted = 0    pick order: out_raw, out_ids, out_levels, out_mmr [nq][k]; out_mmr is a double, the value the pick won with
+ *                     (pick 0 carries lambda * rel_0). out_adj is not written.
+ *   reweighted = 1    the picked hits through icd_index_search_reweighted's step: adj = (double)raw * w[level], ONE stable descending
+ *                     re-sort; raw, id, level and mmr value travel with the hit.
+ *   unused slots      score -inf, id -1, level 0, mmr -inf, adj -inf. out_levels and out_mmr may be NULL.
+ * lambda = 1 returns icd_index_search_masked at k bit for bit (reweighted = 1: that call's reweighted form); k = fetch_k returns a
+ * permutation of the candidate list.
+ *
+ * icd_mmr_create: the workspace of the MMR searches of `idx` for up to max_nq queries per call: the staging of the candidate
+ * lists ([max_nq][ICD_MAX_K] raw scores, ids, levels) and of a host caller's outputs. Nothing is allocated in a search. The handle
+ * keeps no pointer into its index: it is compared, never followed, and either may be destroyed first. It serves one stream at a
+ * time, like the index it belongs to. A view has no MMR search (ICD_ERR_UNSUPPORTED: mask the parent), nor has the row-sharded
+ * path (icd_group_*).
+ *
+ * icd_index_search_mmr: ONE sub-search at fetch_k into the staging, then one launch of mmr_select_kernel (one work-group per
+ * query; no atomics: the same call twice gives the same bytes). masks: a HOST array of nq handles (NULL entries: unfiltered) or
+ * NULL; radius / range_filter: nq floats each or NULL, host or (bounds_on_device = 1) device. Masks, bounds, synchronisation and
+ * the capture rule are icd_index_search_masked's. Every check comes before the first device call. ICD_ERR_INVALID: k or fetch_k
+ * out of range, k > fetch_k, fetch_k above the index's max_k, nq above the handle's or the index's max_nq, lambda outside [0, 1]
+ * or NaN, host bounds holding NaN or radius >= range_filter, a handle or a mask of another index. ICD_ERR_STATE: a destroyed
+ * handle or mask. ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 does nothing. A refused call leaves outputs and handles as they were.
+ */
+typedef struct icd_mmr icd_mmr;
+int icd_mmr_create(icd_index *idx, int64_t max_nq, icd_mmr **out);
+int icd_mmr_destroy(icd_mmr *mmr);
+/* queries per call, device bytes held (either pointer may be NULL) */
+int icd_mmr_stats(icd_mmr *mmr, int64_t *out_max_nq, int64_t *out_bytes);
+int icd_index_search_mmr(icd_index *idx, icd_mmr *mmr, icd_rowmask *const *masks, const float *queries, int64_t nq, int32_t k,
+                         int32_t fetch_k, double lambda, int32_t queries_on_device, const float *radius, const float *range_filter,
+                         int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                         int32_t *out_levels, double *out_mmr, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

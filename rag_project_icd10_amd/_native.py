@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "icd_sparse_match_rowmasks", "icd_rowmask_read",
     "icd_columns_create", "icd_columns_destroy", "icd_columns_stats", "icd_filter_program_check", "icd_filter_rowmasks",
     "icd_rowmask_select", "icd_rowmask_group_counts",
+    "icd_mmr_create", "icd_mmr_destroy", "icd_mmr_stats", "icd_index_search_mmr",
 )
 SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
 SELECT_SEGMENT_ROWS = 16384   # csrc/mask_select_plan.hpp MS_SEG_ROWS: rows of one work-group of the select's two passes
@@ -157,6 +158,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_filter_rowmasks.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
     lib.icd_rowmask_select.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, i32, vp]
     lib.icd_rowmask_group_counts.argtypes = [vp, vp, vp, i64, vp, i32, vp]
+    lib.icd_mmr_create.argtypes = [vp, i64, C.POINTER(vp)]
+    lib.icd_mmr_destroy.argtypes = [vp]
+    lib.icd_mmr_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_search_mmr.argtypes = [vp, vp, vp, vp, i64, i32, i32, C.c_double, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
@@ -584,6 +589,54 @@ class IcdIndex:
                     _check(self._lib, self._lib.icd_index_search_masked(self._h, mask_h.ctypes.data + 8 * s0, *tail))
             return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
         return _chunked(q, self.max_nq, on_dev, call)
+
+    # -- MMR search (a diverse top-k: LangChain's max_marginal_relevance_search on the device) -------------
+    def mmr(self, max_nq: Optional[int] = None) -> "IcdMmr":
+        """The workspace of this index's MMR searches (icd_mmr_create) for calls of up to max_nq queries (default: the index's)."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdMmr(self, int(max_nq if max_nq is not None else self.max_nq))
+
+    def search_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float, *, mmr: "IcdMmr", masks=None, radius=None, range_filter=None,
+                   reweighted: bool = True, on_device: bool = False):
+        """The k hits of every query picked greedily out of its fetch_k exact candidates by maximal marginal relevance
+        (icd_index_search_mmr): value = lambda_mult * score - (1 - lambda_mult) * max similarity to a hit already picked, the
+        similarity being the canonical inner product of the two stored rows. 1 <= k <= fetch_k <= 128 (and the index's max_k),
+        lambda_mult in [0, 1]; masks, radius and range_filter as in search_masked (they shape the candidate list). Returns
+        (adj f64, raw f32, ids i64, levels i32, mmr_values f64), each [nq, k]: reweighted=True in search_reweighted's order (level
+        weight, one stable re-sort of the picked hits), False in pick order with adj None. Padding: -inf, id -1, level 0, mmr -inf.
+        lambda_mult = 1 is search_masked at k, bit for bit. CUDA queries or on_device=True: device tensors out on torch's current
+        stream. A batch longer than the workspace's max_nq runs in chunks."""
+        if self.closed or mmr is None or mmr.closed:
+            raise IcdError(-5, "index or mmr workspace is closed")
+        q, q_dev = self._prep_queries(queries)
+        if q.shape[-1] != self.dim:
+            raise ValueError(f"query dim {q.shape[-1]} != index dim {self.dim}")
+        k, fetch_k, lam = int(k), int(fetch_k), float(lambda_mult)
+        if not (1 <= k <= fetch_k <= min(MAX_K, self.max_k)):
+            raise ValueError(f"k={k}, fetch_k={fetch_k}: need 1 <= k <= fetch_k <= {min(MAX_K, self.max_k)}")
+        if not (0.0 <= lam <= 1.0):
+            raise ValueError(f"lambda_mult={lambda_mult}: the relevance weight lies in [0, 1]")
+        out_dev = bool(on_device) or q_dev
+        nq = int(q.shape[0])
+        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the calls below)
+        bounds = [None if v is None else _bound(v, np.float32, (nq,), q_dev, self.device) for v in (radius, range_filter)]
+
+        def call(qs, s0):
+            m = qs.shape[0]
+            (adj, raw, ids, lv, mv), ptr, stream, dev = _outputs(out_dev, self.device, (m, k), (np.float64, np.float32, np.int64, np.int32, np.float64))
+            if m:
+                if q_dev and stream is None:
+                    stream = _current_stream_ptr(self.device)
+                part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
+                qptr = _dev_ptr if q_dev else _host_ptr
+                _check(self._lib, self._lib.icd_index_search_mmr(
+                    self._h, mmr._h, None if mask_h is None else mask_h.ctypes.data + 8 * s0, qptr(qs), m, k, fetch_k, lam, 1 if q_dev else 0,
+                    *[None if b is None else qptr(b) for b in part], 1 if q_dev else 0, 1 if reweighted else 0,
+                    ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(mv), dev, stream))
+            return (adj, raw, ids, lv, mv) if reweighted else (raw, ids, lv, mv)
+        outs = _chunked(q, min(self.max_nq, mmr.max_nq), out_dev, call)
+        return outs if reweighted else (None,) + tuple(outs)
 
     # -- hybrid search (Milvus hybrid_search over dense requests) -----------------------------------------
     def fusion(self, max_total: int) -> "IcdFusion":
@@ -1062,6 +1115,25 @@ class IcdFusion(_Handle):
         t, b = C.c_int64(), C.c_int64()
         _check(self._lib, self._lib.icd_fusion_stats(self._h, C.byref(t), C.byref(b)))
         return {"max_total": t.value, "bytes": b.value}
+
+
+class IcdMmr(_Handle):
+    """The workspace of one IcdIndex's MMR searches (icd_mmr_*): the staging of max_nq candidate lists of 128 hits and of a host
+    caller's outputs."""
+    _destroy = "icd_mmr_destroy"
+
+    def __init__(self, index: "IcdIndex", max_nq: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        self.max_nq = int(max_nq)
+        _check(self._lib, self._lib.icd_mmr_create(index._h, self.max_nq, C.byref(self._h)))
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "mmr workspace is closed")
+        t, b = C.c_int64(0), C.c_int64(0)
+        _check(self._lib, self._lib.icd_mmr_stats(self._h, C.byref(t), C.byref(b)))
+        return {"max_nq": t.value, "bytes": b.value}
 
 
 def sparse_tile_rows() -> int:

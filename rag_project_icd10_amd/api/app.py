@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /diverse_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -17,7 +17,7 @@ from contextlib import asynccontextmanager
 from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
-from .icd_models import (DiagnosisMatch, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
+from .icd_models import (DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
                          HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
@@ -217,6 +217,50 @@ async def hybrid_query(request: HybridQueryRequest):
                                 original_score=float(h["fused_score"]), similarity_factors={"matched_requests": h["matched_requests"]})
                       for h in hits]
         response = QueryResponse(candidates=candidates, is_multi_diagnosis=False, extracted_diagnoses=[request.texts[0]])
+        return QueryResponse(**convert_numpy_types(response.model_dump()))
+    except HTTPException:
+        raise
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+
+
+@app.post("/diverse_query", response_model=QueryResponse)
+async def diverse_query(request: DiverseQueryRequest):
+    """One text, the top_k hits that are not copies of each other (MilvusService.search_mmr): the text is
+    encoded like /query's, its fetch_k best rows are the candidates, and the device picks top_k of them by maximal marginal
+    relevance. The response has /hybrid_query's hit shape: `score` the adjusted score, `original_score` the raw inner product,
+    `similarity_factors.mmr_score` the value the hit was picked with. Bad arguments are a 400."""
+    try:
+        if not isinstance(request.text, str) or not request.text.strip():
+            raise ValueError("text: a non-empty string")
+        if not 1 <= request.top_k <= 50:
+            raise ValueError(f"top_k={request.top_k}: 1 .. 50")
+        if request.fetch_k is not None and not request.top_k <= request.fetch_k <= 128:
+            raise ValueError(f"fetch_k={request.fetch_k}: top_k={request.top_k} .. 128")
+        if not 0.0 <= request.lambda_mult <= 1.0:
+            raise ValueError(f"lambda_mult={request.lambda_mult}: 0 .. 1")
+        from ..services import filter_expr, range_search
+        if request.filter is not None:
+            filter_expr.compile(request.filter)
+        range_search.check_bounds(request.radius, request.range_filter)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    if not embedding_service or not milvus_service:
+        raise HTTPException(status_code=500, detail="查询失败: 服务未就绪")   # (as /query: the 503 surfaces as a 500)
+    try:
+        import numpy as np
+        vec = np.asarray(embedding_service.encode_query(request.text), dtype=np.float32).reshape(-1)
+        try:
+            hits = milvus_service.search_mmr(vec, request.top_k, request.fetch_k, request.lambda_mult, filter=request.filter,
+                                             radius=request.radius, range_filter=request.range_filter)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+        from .icd_models import Candidate
+        candidates = [Candidate(code=h["code"], title=h["title"] or "", score=max(float(h["score"]), 0.0), enhanced_score=float(h["score"]),
+                                level=h["metadata"].get("level", 1), parent_code=h["metadata"].get("parent_code", ""),
+                                original_score=float(h["original_score"]), similarity_factors={"mmr_score": float(h["mmr_score"])})
+                      for h in hits]
+        response = QueryResponse(candidates=candidates, is_multi_diagnosis=False, extracted_diagnoses=[request.text])
         return QueryResponse(**convert_numpy_types(response.model_dump()))
     except HTTPException:
         raise

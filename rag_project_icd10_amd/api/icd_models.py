@@ -236,6 +236,18 @@ class HybridQueryRequest(BaseModel):
     group_size: int = Field(default=1, description="rows returned per group (top_k * group_size and req_limit * group_size <= 128)")
 
 
+class DiverseQueryRequest(BaseModel):
+    """POST /diverse_query: the top_k hits of one text that are not copies of each other (MilvusService.search_mmr: maximal
+    marginal relevance over the fetch_k best rows). The ranges are checked by the route (a 400 with the reason), not by the model."""
+    text: str = Field(..., description="the diagnosis text")
+    top_k: int = Field(default=5, description="hits returned (1 .. 50)")
+    fetch_k: Optional[int] = Field(default=None, description="candidates the hits are picked from (top_k .. 128; default max(20, 4 * top_k))")
+    lambda_mult: float = Field(default=0.5, description="0 .. 1: 1 ranks by relevance alone, 0 by diversity alone")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression: only the rows it selects are candidates")
+    radius: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is above this are candidates")
+    range_filter: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is at or below this are candidates")
+
+
 class QueryResponse(BaseModel):
     model_config = ConfigDict(arbitrary_types_allowed=True)
     candidates: List[Candidate] = Field(..., description="候选结果列表")

@@ -27,6 +27,7 @@
 #include "filter_mask_kernel.hpp"
 #include "mask_select_kernel.hpp"
 #include "facet_count_kernel.hpp"
+#include "mmr_select_kernel.hpp"
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
@@ -1932,5 +1933,6 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
 #include "icd_text_match.hpp" // keyword match filters: row masks from the sparse index's postings
 #include "icd_filter.hpp"     // filter programs: row masks from int32 columns and the postings, any boolean shape
 #include "icd_facet.hpp"      // facet counts: rows per group of a grouping under a batch of row masks
+#include "icd_mmr.hpp"        // MMR search: a diverse top-k out of the exact candidate list
 // the small-input sentence encoder (icd_encoder_*): its own file, this translation unit (fail(), HIP_TRY, packed_attention_kernel)
 #include "icd_encoder.hpp"

@@ -107,6 +107,8 @@ class MilvusService:
         # hybrid search: (the index it belongs to, IcdFusion, store generation); one handle, regrown when a call needs more
         # sub-lists, dropped where the views and masks are
         self._fusion = None
+        # MMR search: (the index it belongs to, IcdMmr, store generation); one handle, regrown like the fusion, dropped with it
+        self._mmr = None
         # sparse search: (the index it belongs to, IcdSparse, SparseTextIndex, field, store generation); built lazily, one handle
         self._sparse = None
         # filter programs: (the index they belong to, IcdColumns, the filter_expr.Columns they were made from)
@@ -267,6 +269,7 @@ class MilvusService:
             self._masks.clear()
             self._dev_columns = None
             self._fusion = None
+            self._mmr = None
             self._sparse = None
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
@@ -990,6 +993,102 @@ class MilvusService:
         if hasattr(adj, "cpu"):
             adj, raw, ids = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy()
         return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
+
+    # ---- MMR search (a diverse top-k) ---------------------------------------------------------------------------
+    MMR_MAX_FETCH = 128   # candidates per query (the hit list's slots)
+
+    def _mmr_for(self, index, nq: int):
+        """the cached IcdMmr of the store's index with room for `nq` queries (per store generation; regrown when short)"""
+        gen = self.client.generation
+        with self._views_lock:
+            hit = self._mmr
+            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_nq >= nq:
+                return hit[1]
+            mmr = index.mmr(min(index.max_nq, max(int(nq), 64)))
+            self._mmr = (index, mmr, gen)
+        return mmr
+
+    def _mmr_args(self, top_k, fetch_k, lambda_mult, radius, range_filter, search_params):
+        """(top_k, fetch_k or None, lambda, radius, range_filter) checked without a store: ValueError on a bad one"""
+        def whole(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name}={v!r}: an int")
+            return int(v)
+        top_k = whole("top_k", top_k)
+        if not 1 <= top_k <= self.MMR_MAX_FETCH:
+            raise ValueError(f"top_k={top_k}: 1 .. {self.MMR_MAX_FETCH}")
+        if fetch_k is not None:
+            fetch_k = whole("fetch_k", fetch_k)
+            if not top_k <= fetch_k <= self.MMR_MAX_FETCH:
+                raise ValueError(f"fetch_k={fetch_k}: top_k={top_k} .. {self.MMR_MAX_FETCH}")
+        if isinstance(lambda_mult, bool) or not isinstance(lambda_mult, (int, float, np.integer, np.floating)):
+            raise ValueError(f"lambda_mult={lambda_mult!r}: a number in [0, 1]")
+        lam = float(lambda_mult)
+        if not 0.0 <= lam <= 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"lambda_mult={lambda_mult!r}: a number in [0, 1]")
+        radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
+        return top_k, fetch_k, lam, radius, range_filter
+
+    def search_mmr_batch(self, query_vectors, top_k: int = 10, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
+                         filter=None, as_dicts: bool = False, radius: Optional[float] = None,   # noqa: A002
+                         range_filter: Optional[float] = None, search_params: Optional[Dict[str, Any]] = None):
+        """Additive: the top_k hits of every query that are not copies of each other - maximal marginal relevance over the query's
+        fetch_k exact candidates, picked on the device (LangChain's max_marginal_relevance_search(query, k, fetch_k, lambda_mult);
+        DESIGN.md section 21). lambda_mult in [0, 1]: 1 is plain relevance (`search` with filter_mode="mask"), 0 is diversity
+        alone. fetch_k=None: min(128, the store's max k, max(20, 4 * top_k)). filter: one expression for the whole batch or a list
+        with one entry (or None) per query, always as row masks of the index itself; radius / range_filter / search_params shape
+        the candidate list as in `search`. Returns (adjusted f64, raw f32, ids i64, levels i32, mmr f64), each [nq, top_k], in
+        adjusted-score order (level weight, one stable re-sort of the picked hits), padding id -1, -inf, level 0; with
+        as_dicts=True a list of `search`-shaped hit lists whose hits carry "mmr_score", the value the hit was picked with.
+        An empty or unloaded collection answers [] per query ([] hits each). Bad arguments raise ValueError."""
+        top_k, fetch_k, lam, radius, range_filter = self._mmr_args(top_k, fetch_k, lambda_mult, radius, range_filter, search_params)
+        shape = np.shape(query_vectors)
+        if len(shape) not in (1, 2):
+            raise ValueError("query_vectors: [nq, dim] (or one vector)")
+        nq = 1 if len(shape) == 1 else int(shape[0])
+        self._check_filter_args(filter, "mask", None, nq)   # (a bad expression raises before anything is loaded)
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None:
+            return [[] for _ in range(nq)]
+        if shape[-1] != index.dim:
+            raise ValueError(f"query dim {shape[-1]} != index dim {index.dim}")
+        cap = min(self.MMR_MAX_FETCH, index.max_k)
+        if fetch_k is None:
+            fetch_k = min(cap, max(20, 4 * top_k))
+        if fetch_k > cap or top_k > fetch_k:
+            raise ValueError(f"top_k={top_k}, fetch_k={fetch_k}: need top_k <= fetch_k <= {cap} (the store's max k)")
+        masks = None if filter is None else self._masks_for(index, filter, nq)
+        try:
+            adj, raw, ids, levels, mmr = index.search_mmr(query_vectors, top_k, fetch_k, lam, mmr=self._mmr_for(index, nq), masks=masks,
+                                                          radius=radius, range_filter=range_filter, reweighted=True)
+            if masks is not None and hasattr(adj, "cpu"):
+                import torch
+                torch.cuda.synchronize(index.device)   # (transient masks are closed below: the search has to have run)
+        finally:
+            self._release_masks(masks)
+        if not as_dicts:
+            return adj, raw, ids, levels, mmr
+        if hasattr(adj, "cpu"):
+            adj, raw, ids, mmr = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy(), mmr.cpu().numpy()
+        out = []
+        for q in range(len(ids)):
+            hits = self._hits_to_dicts(adj[q], raw[q], ids[q])
+            for hit, v in zip(hits, mmr[q]):   # (padding sits behind the hits: the first len(hits) slots are theirs)
+                hit["mmr_score"] = float(v)
+            out.append(hits)
+        return out
+
+    def search_mmr(self, query_vector, top_k: int = 10, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
+                   filter: Optional[str] = None, radius: Optional[float] = None, range_filter: Optional[float] = None,   # noqa: A002
+                   search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
+        """the diverse hit list of ONE query (search_mmr_batch): `search`'s dicts in adjusted-score order, "mmr_score" added"""
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_mmr_batch")
+        q = np.asarray(query_vector, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError("query_vector: one vector")
+        return self.search_mmr_batch(q.reshape(1, -1), top_k, fetch_k, lambda_mult, filter=filter, as_dicts=True, radius=radius,
+                                     range_filter=range_filter, search_params=search_params)[0]
 
     # ---- hybrid search (Milvus hybrid_search over dense requests; DESIGN.md section 13) ------------------------------------------
     def _fusion_for(self, index, total: int):
