@@ -212,6 +212,13 @@ def _check(lib, rc: int):
         raise IcdError(rc, (lib.icd_last_error() or b"").decode("utf-8", "replace"))
 
 
+def _check_inv(lib, rc: int):
+    """_check, with ICD_ERR_INVALID (a bad argument) as a ValueError"""
+    if rc == -1:
+        raise ValueError(lib.icd_last_error().decode("utf-8", "replace"))
+    _check(lib, rc)
+
+
 def device_count() -> int:
     lib = load_library()
     n = lib.icd_device_count()
@@ -298,6 +305,30 @@ def _check_group_args(grouping, k, group_size) -> int:
     if int(k) < 1 or group_size < 1 or int(k) * group_size > MAX_K:
         raise ValueError(f"k={k}, group_size={group_size}: need k >= 1, group_size >= 1 and k * group_size <= {MAX_K}")
     return group_size
+
+
+_SPARSE_OUTS = (np.float64, np.float32, np.int64, np.int32)   # search_sparse: adj, raw, ids, levels; grouped: the hits' groups behind them
+_SPARSE_OUTS_GROUPED = _SPARSE_OUTS + (np.int32,)
+
+
+def _fuse_params(limits, R: int, ranker: str, rrf_c, weights, norm: str):
+    """What search_hybrid and fuse_lists hand the fuse: limits as R contiguous int32 (one int is broadcast), weights as R contiguous
+    float64 (None unless the ranker is "weighted"), and the C ABI's (ranker, rrf_c, weights pointer, norm). ValueError on a bad one."""
+    lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.int32).reshape(-1), (R,)) if np.size(limits) == 1
+                               else np.asarray(limits, dtype=np.int32).reshape(-1))
+    if lim.size != R:
+        raise ValueError(f"limits holds {lim.size} entries for {R} requests")
+    if ranker not in ("rrf", "weighted"):
+        raise ValueError(f"ranker={ranker!r}: 'rrf' or 'weighted'")
+    if norm not in NORMS:
+        raise ValueError(f"norm={norm!r}: one of {sorted(NORMS)}")
+    wts = None
+    if ranker == "weighted":
+        wts = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if wts.size != R:
+            raise ValueError(f"weights holds {wts.size} entries for {R} requests")
+    fuse = (RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm])
+    return lim, wts, fuse
 
 
 def _mask_table(masks, count: int, what: str, per: str) -> np.ndarray:
@@ -669,19 +700,7 @@ class IcdIndex:
         if q.ndim != 3 or q.shape[-1] != self.dim:
             raise ValueError(f"queries must be [nq, R, {self.dim}], got {tuple(q.shape)}")
         nq, R = int(q.shape[0]), int(q.shape[1])
-        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.int32).reshape(-1), (R,)) if np.size(limits) == 1
-                                   else np.asarray(limits, dtype=np.int32).reshape(-1))
-        if lim.size != R:
-            raise ValueError(f"limits holds {lim.size} entries for {R} requests")
-        if ranker not in ("rrf", "weighted"):
-            raise ValueError(f"ranker={ranker!r}: 'rrf' or 'weighted'")
-        if norm not in NORMS:
-            raise ValueError(f"norm={norm!r}: one of {sorted(NORMS)}")
-        wts = None
-        if ranker == "weighted":
-            wts = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-            if wts.size != R:
-                raise ValueError(f"weights holds {wts.size} entries for {R} requests")
+        lim, wts, fuse = _fuse_params(limits, R, ranker, rrf_c, weights, norm)   # (lim and wts kept alive over the call)
         k = int(k)
         mask_h = None
         if masks is not None:
@@ -696,11 +715,8 @@ class IcdIndex:
                 on_dev, self.device, (nq, k * group_size), (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32, np.int32))
             rc = self._lib.icd_index_search_hybrid_grouped(
                 self._h, fusion._h, grouping._h, ptr(q) if nq else None, nq, R, dev, lim.ctypes.data, None, None, None,
-                RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
-                group_size, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), ptr(grp), dev, stream)
-            if rc == -1:
-                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-            _check(self._lib, rc)
+                *fuse, k, group_size, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), ptr(grp), dev, stream)
+            _check_inv(self._lib, rc)
             return (adj, fused, ids, lv, bits, grp) if reweighted else (fused, ids, lv, bits, grp)
         lo, hi = (_bound(v, np.float32, (nq, R), on_dev, self.device) for v in (radius, range_filter))
         (adj, fused, ids, lv, bits), ptr, stream, dev = _outputs(
@@ -708,8 +724,7 @@ class IcdIndex:
         rc = self._lib.icd_index_search_hybrid(
             self._h, fusion._h, ptr(q) if nq else None, nq, R, dev, lim.ctypes.data,
             None if mask_h is None else mask_h.ctypes.data, None if lo is None else ptr(lo), None if hi is None else ptr(hi),
-            dev, int(mode), RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c),
-            None if wts is None else wts.ctypes.data, NORMS[norm], k, 1 if reweighted else 0,
+            dev, int(mode), *fuse, k, 1 if reweighted else 0,
             ptr(adj) if reweighted else None, ptr(fused), ptr(ids), ptr(lv), ptr(bits), dev, stream)
         _check(self._lib, rc)
         return (adj, fused, ids, lv, bits) if reweighted else (fused, ids, lv, bits)
@@ -732,19 +747,7 @@ class IcdIndex:
         if sc.ndim != 3 or tuple(idt.shape) != tuple(sc.shape):
             raise ValueError(f"scores and ids must both be [nq, R, lmax], got {tuple(sc.shape)} and {tuple(idt.shape)}")
         nq, R, lmax = (int(v) for v in sc.shape)
-        lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limits, dtype=np.int32).reshape(-1), (R,)) if np.size(limits) == 1
-                                   else np.asarray(limits, dtype=np.int32).reshape(-1))
-        if lim.size != R:
-            raise ValueError(f"limits holds {lim.size} entries for {R} requests")
-        if ranker not in ("rrf", "weighted"):
-            raise ValueError(f"ranker={ranker!r}: 'rrf' or 'weighted'")
-        if norm not in NORMS:
-            raise ValueError(f"norm={norm!r}: one of {sorted(NORMS)}")
-        wts = None
-        if ranker == "weighted":
-            wts = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-            if wts.size != R:
-                raise ValueError(f"weights holds {wts.size} entries for {R} requests")
+        lim, wts, fuse = _fuse_params(limits, R, ranker, rrf_c, weights, norm)   # (lim and wts kept alive over the call)
         k = int(k)
         on_dev = not to_host
         dtypes = (np.float64, np.float64, np.int64, np.int32, np.int32 if on_dev else np.uint32) + ((np.int32,) if grouping is not None else ())
@@ -756,17 +759,13 @@ class IcdIndex:
             grp = outs[5]
             rc = self._lib.icd_fusion_fuse_lists_grouped(
                 self._h, fusion._h, grouping._h, sc.data_ptr() if nq else None, idt.data_ptr() if nq else None, nq, R, lmax, lim.ctypes.data,
-                RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
-                group_size, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(out_ids), ptr(lv), ptr(bits), ptr(grp),
+                *fuse, k, group_size, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(out_ids), ptr(lv), ptr(bits), ptr(grp),
                 dev, stream)
-            if rc == -1:
-                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-            _check(self._lib, rc)
+            _check_inv(self._lib, rc)
             return (adj, fused, out_ids, lv, bits, grp) if reweighted else (fused, out_ids, lv, bits, grp)
         rc = self._lib.icd_fusion_fuse_lists(
             self._h, fusion._h, sc.data_ptr() if nq else None, idt.data_ptr() if nq else None, nq, R, lmax, lim.ctypes.data,
-            RANKER_RRF if ranker == "rrf" else RANKER_WEIGHTED, float(rrf_c), None if wts is None else wts.ctypes.data, NORMS[norm], k,
-            1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(out_ids), ptr(lv), ptr(bits), dev, stream)
+            *fuse, k, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(fused), ptr(out_ids), ptr(lv), ptr(bits), dev, stream)
         _check(self._lib, rc)
         return (adj, fused, out_ids, lv, bits) if reweighted else (fused, out_ids, lv, bits)
 
@@ -831,38 +830,26 @@ class IcdIndex:
         mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")
         if grouping is not None:
             grouping.pair_sparse(self, sp)   # (behind every argument check of this layer: a refused call leaves the grouping as it was)
-            (adj, raw, ids, lv, grp), ptr, stream, dev = _outputs(on_dev, self.device, (nq, k * group_size),
-                                                                  (np.float64, np.float32, np.int64, np.int32, np.int32))
-            if nq:
-                rc = self._lib.icd_sparse_search_grouped(
-                    self._h, sp._h, grouping._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k, group_size,
-                    dev, None if mask_h is None else mask_h.ctypes.data, 1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw),
-                    ptr(ids), ptr(lv), ptr(grp), dev, stream)
-                if rc == -1:
-                    raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-                _check(self._lib, rc)
-            return (adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp)
-        (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (nq, k), (np.float64, np.float32, np.int64, np.int32))
+        outs, ptr, stream, dev = _outputs(on_dev, self.device, (nq, k * group_size), _SPARSE_OUTS if grouping is None else _SPARSE_OUTS_GROUPED)
+        bounds = ()
         if banded:
             bounds = [None if v is None else _bound(v, dt, (nq,), on_dev, self.device)   # (kept alive over the call)
                       for v, dt in ((radius, np.float32), (range_filter, np.float32), (a_sc, np.float32), (a_id, np.int64))]
-            if nq:
-                rc = self._lib.icd_sparse_search_range(
-                    self._h, sp._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k, dev,
-                    None if mask_h is None else mask_h.ctypes.data, *[None if b is None else ptr(b) for b in bounds], dev,
-                    1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
-                if rc == -1:
-                    raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-                _check(self._lib, rc)
-            return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
-        if nq:
-            rc = self._lib.icd_sparse_search(self._h, sp._h, ptr(off), ptr(tr) if n_terms else ptr(off), ptr(vl) if n_terms else ptr(off), nq, k,
-                                             dev, None if mask_h is None else mask_h.ctypes.data, 1 if reweighted else 0,
-                                             ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
-            if rc == -1:
-                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-            _check(self._lib, rc)
-        return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
+        if nq:   # what the three entry points share, once: the queries, the mask table, the outputs (no tuples: this is the nq = 1 path too)
+            p_off = ptr(off)
+            p_tr, p_vl = (ptr(tr), ptr(vl)) if n_terms else (p_off, p_off)
+            p_mask, rw = None if mask_h is None else mask_h.ctypes.data, 1 if reweighted else 0
+            p_adj, p_raw, p_ids, p_lv = ptr(outs[0]) if reweighted else None, ptr(outs[1]), ptr(outs[2]), ptr(outs[3])
+            if grouping is not None:
+                rc = self._lib.icd_sparse_search_grouped(self._h, sp._h, grouping._h, p_off, p_tr, p_vl, nq, k, group_size, dev, p_mask,
+                                                         rw, p_adj, p_raw, p_ids, p_lv, ptr(outs[4]), dev, stream)
+            elif banded:
+                rc = self._lib.icd_sparse_search_range(self._h, sp._h, p_off, p_tr, p_vl, nq, k, dev, p_mask,
+                                                       *[None if b is None else ptr(b) for b in bounds], dev, rw, p_adj, p_raw, p_ids, p_lv, dev, stream)
+            else:
+                rc = self._lib.icd_sparse_search(self._h, sp._h, p_off, p_tr, p_vl, nq, k, dev, p_mask, rw, p_adj, p_raw, p_ids, p_lv, dev, stream)
+            _check_inv(self._lib, rc)
+        return tuple(outs) if reweighted else tuple(outs[1:])
 
     def _produce_masks(self, nq, base_masks, call) -> list:
         """what match_masks and filter_masks share: the base table, the handles' out array, call(base, out) -> rc with ICD_ERR_INVALID
@@ -872,9 +859,7 @@ class IcdIndex:
             return []
         out = (C.c_void_p * nq)()
         rc = call(None if base_h is None else base_h.ctypes.data, C.cast(out, C.c_void_p))
-        if rc == -1:
-            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-        _check(self._lib, rc)
+        _check_inv(self._lib, rc)
         return [IcdRowMask._adopt(self, out[q]) for q in range(nq)]
 
     def match_masks(self, sp: "IcdSparse", q_off, q_terms, min_match, base_masks=None) -> list:
@@ -947,9 +932,7 @@ class IcdIndex:
         if nq:
             rc = self._lib.icd_rowmask_select(self._h, table.ctypes.data, nq, None if off is None else off.ctypes.data, limit, ptr(ids),
                                               ptr(total), ptr(taken), dev, stream)
-            if rc == -1:
-                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-            _check(self._lib, rc)
+            _check_inv(self._lib, rc)
         if through and not on_device:
             return ids.cpu().numpy(), total.cpu().numpy(), taken.cpu().numpy()
         return ids, total, taken
@@ -965,9 +948,7 @@ class IcdIndex:
         (total,), ptr, stream, dev = _outputs(on_device, self.device, (nq,), (np.int64,))
         if nq:
             rc = self._lib.icd_rowmask_select(self._h, table.ctypes.data, nq, None, 1, None, ptr(total), None, dev, stream)
-            if rc == -1:
-                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-            _check(self._lib, rc)
+            _check_inv(self._lib, rc)
         return total
 
     def group_counts(self, masks, grouping: "IcdGrouping", *, on_device: bool = False):
@@ -984,9 +965,7 @@ class IcdIndex:
         (counts,), ptr, stream, dev = _outputs(on_device, self.device, (nq, grouping.groups), (np.int32,))
         if nq:
             rc = self._lib.icd_rowmask_group_counts(self._h, grouping._h, table.ctypes.data, nq, ptr(counts), dev, stream)
-            if rc == -1:
-                raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-            _check(self._lib, rc)
+            _check_inv(self._lib, rc)
         return counts
 
     def lookup_levels(self, ids):
@@ -1181,9 +1160,7 @@ def sparse_pack(row_off, terms, vals, n: int, vocab: int):
     post_val = np.empty(max(t.size, 1), np.float32)
     rc = lib.icd_sparse_pack(off.ctypes.data, t.ctypes.data if t.size else None, v.ctypes.data if t.size else None, int(n), int(vocab),
                              post_off.ctypes.data, post_row.ctypes.data, post_val.ctypes.data)
-    if rc == -1:
-        raise ValueError(lib.icd_last_error().decode("utf-8", "replace"))
-    _check(lib, rc)
+    _check_inv(lib, rc)
     return post_off, post_row[:t.size], post_val[:t.size]
 
 
@@ -1205,9 +1182,7 @@ class IcdSparse(_Handle):
         self.n, self.vocab, self.max_nq, self.max_k, self.device = index.n, int(vocab), int(max_nq), int(max_k), index.device
         rc = self._lib.icd_sparse_create(index._h, off.ctypes.data, t.ctypes.data if t.size else None, v.ctypes.data if t.size else None,
                                          self.vocab, self.max_nq, self.max_k, C.byref(self._h))
-        if rc == -1:
-            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-        _check(self._lib, rc)
+        _check_inv(self._lib, rc)
 
     def stats(self) -> dict:
         if self.closed:
@@ -1230,9 +1205,7 @@ class IcdColumns(_Handle):
             raise ValueError(f"cols of shape {keep.shape}: [ncols >= 1, n = {index.n}]")
         self.n, self.ncols, self.device = index.n, int(keep.shape[0]), index.device
         rc = self._lib.icd_columns_create(index._h, keep.ctypes.data, self.ncols, C.byref(self._h))
-        if rc == -1:
-            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-        _check(self._lib, rc)
+        _check_inv(self._lib, rc)
 
     def stats(self) -> dict:
         if self.closed:
@@ -1266,9 +1239,7 @@ def pack_rowmask(rows, n: int) -> np.ndarray:
     r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
     out = np.empty(rowmask_words(n), dtype=np.uint32)
     rc = lib.icd_rowmask_pack(r.ctypes.data if r.size else None, int(r.size), int(n), out.ctypes.data, int(out.size))
-    if rc == -1:
-        raise ValueError(lib.icd_last_error().decode("utf-8", "replace"))
-    _check(lib, rc)
+    _check_inv(lib, rc)
     return out
 
 
@@ -1294,9 +1265,7 @@ class IcdRowMask(_Handle):
             ptr, on_dev, m = keep.ctypes.data, 0, int(keep.size)
         self.n, self.rows, self.device = index.n, m, index.device
         rc = self._lib.icd_rowmask_create(index._h, ptr if m else None, m, on_dev, C.byref(self._h))
-        if rc == -1:
-            raise ValueError(self._lib.icd_last_error().decode("utf-8", "replace"))
-        _check(self._lib, rc)
+        _check_inv(self._lib, rc)
 
     @classmethod
     def _adopt(cls, index: "IcdIndex", handle: int) -> "IcdRowMask":

@@ -1,5 +1,6 @@
-// icd_hybrid.hpp - the hybrid search (icd_fusion_*, icd_index_search_hybrid). Part of icd_search.hip's translation unit (fail(),
-// HIP_TRY, the owned-handle, request and host-call helpers, run_search); included there and nowhere else.
+// icd_hybrid.hpp - the hybrid search (icd_fusion_*, icd_index_search_hybrid), the fuse of caller-provided lists (icd_fusion_fuse_lists)
+// and their grouped forms. Part of icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle, request and host-call
+// helpers, run_search, the grouping); included there and nowhere else.
 #pragma once
 
 // ---- hybrid search (hybrid_fuse.hpp) -----------------------------------------------------------------
@@ -75,6 +76,29 @@ static int fuse_lists_step(icd_index *idx, icd_fusion *f, const float *st_scores
     return ICD_OK;
 }
 
+// The ranker's rules, the same for every fuse entry point: rrf_c in (0, 16384); R weights in [0, 1] and one of the three norms.
+static int check_fuse_ranker(int32_t R, int32_t ranker, double rrf_c, const double *weights, int32_t norm) {
+    if (ranker == ICD_RANKER_RRF) {
+        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
+    } else if (ranker == ICD_RANKER_WEIGHTED) {
+        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
+        for (int r = 0; r < R; ++r)
+            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
+        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
+    } else {
+        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
+    }
+    return ICD_OK;
+}
+
+// limits and weights of the current call into the fusion, where fuse_lists_step reads them (under the fusion's mutex)
+static void stage_fuse_params(icd_fusion *f, int32_t R, const int32_t *limits, int32_t ranker, const double *weights) {
+    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
+        f->limits[r] = r < R ? limits[r] : 0;
+        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
+    }
+}
+
 extern "C" {
 
 int icd_fusion_create(icd_index *idx, int64_t max_total, icd_fusion **out) {
@@ -133,16 +157,7 @@ int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *que
     if (total > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)total, (long long)f->max_total);
     if (total > idx->max_nq) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the index's max_nq=%d", (long long)total, idx->max_nq);
     if (mode != ICD_MODE_AUTO && mode != ICD_MODE_EXACT) return fail(ICD_ERR_INVALID, "mode=%d", mode);
-    if (ranker == ICD_RANKER_RRF) {
-        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
-    } else if (ranker == ICD_RANKER_WEIGHTED) {
-        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
-        for (int r = 0; r < R; ++r)
-            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
-        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
-    } else {
-        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
-    }
+    if ((rc = check_fuse_ranker(R, ranker, rrf_c, weights, norm))) return rc;
     if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
     const bool banded = radius || range_filter;
     const RangeBounds rb{radius, range_filter, nullptr, nullptr, bounds_on_device != 0};
@@ -157,10 +172,7 @@ int icd_index_search_hybrid(icd_index *idx, icd_fusion *fusion, const float *que
     const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
     bool capturing;
     if ((rc = check_capture(s, !queries_on_device || !out_on_device, banded && !bounds_on_device, masks != nullptr, &capturing))) return rc;
-    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
-        f->limits[r] = r < R ? limits[r] : 0;
-        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
-    }
+    stage_fuse_params(f, R, limits, ranker, weights);
     const float *dq;
     if ((rc = hc.upload(queries, f->qdev, (size_t)total * idx->dim, &dq))) return rc;
     // step 1 (its capture checks are the ones made above): ONE sub-search over the nq * R vectors at k = the largest limit, into the staging: the plain search in the caller's
@@ -204,28 +216,46 @@ static int check_grouped_fuse(icd_index *idx, icd_fusion *f, icd_grouping *g, in
     if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
     if (nq * R > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)(nq * R), (long long)f->max_total);
     if (nq * R > g->max_nq) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the grouping's max_nq=%d", (long long)(nq * R), g->max_nq);
-    if (ranker == ICD_RANKER_RRF) {
-        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
-    } else if (ranker == ICD_RANKER_WEIGHTED) {
-        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
-        for (int r = 0; r < R; ++r)
-            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
-        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
-    } else {
-        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
-    }
+    if ((rc = check_fuse_ranker(R, ranker, rrf_c, weights, norm))) return rc;
     if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
     return ICD_OK;
 }
 
-static void stage_fuse_params(icd_fusion *f, int32_t R, const int32_t *limits, int32_t ranker, const double *weights) {
-    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
-        f->limits[r] = r < R ? limits[r] : 0;
-        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
-    }
-}
-
 extern "C" {
+
+int icd_fusion_fuse_lists(icd_index *idx, icd_fusion *fusion, const float *scores, const int64_t *ids, int64_t nq, int32_t R, int32_t lmax,
+                          const int32_t *limits, int32_t ranker, double rrf_c, const double *weights, int32_t norm, int32_t k,
+                          int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
+                          uint32_t *out_reqbits, int32_t out_on_device, void *stream) {
+    // the checks of icd_index_search_hybrid that concern its step 2, before the first device call
+    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
+    if (!valid_handle(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
+    icd_fusion *f = fusion;
+    int rc = check_owner(f->at, idx, "the fusion");
+    if (rc) return rc;
+    if (R < 1 || R > ICD_MAX_REQUESTS) return fail(ICD_ERR_INVALID, "R=%d: a hybrid search takes 1 .. %d requests per query", R, ICD_MAX_REQUESTS);
+    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a hybrid search returns 1 .. %d hits per query", k, ICD_MAX_K);
+    if (lmax < 1 || lmax > ICD_MAX_K) return fail(ICD_ERR_INVALID, "lmax=%d: a list holds 1 .. %d hits", lmax, ICD_MAX_K);
+    if (!limits) return fail(ICD_ERR_INVALID, "limits is NULL");
+    for (int r = 0; r < R; ++r)
+        if (limits[r] < 1 || limits[r] > lmax) return fail(ICD_ERR_INVALID, "limits[%d]=%d: a request returns 1 .. lmax=%d hits", r, limits[r], lmax);
+    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
+    if (nq * R > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)(nq * R), (long long)f->max_total);
+    if ((rc = check_fuse_ranker(R, ranker, rrf_c, weights, norm))) return rc;
+    if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
+    if (nq == 0) return ICD_OK;
+    if (!scores || !ids) return fail(ICD_ERR_INVALID, "scores / ids NULL");
+    std::lock_guard<std::mutex> guard(f->mu);
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const HostCall hc{s, true, out_on_device != 0};
+    if ((rc = check_capture(s, !out_on_device, false, false))) return rc;
+    stage_fuse_params(f, R, limits, ranker, weights);
+    if ((rc = fuse_lists_step(idx, f, scores, reinterpret_cast<const long long *>(ids), nq, R, lmax, ranker, rrf_c, norm, k, reweighted, out_adj,
+                              out_fused, out_ids, out_levels, out_reqbits, hc, s)))
+        return rc;
+    return hc.finish();
+}
 
 int icd_fusion_fuse_lists_grouped(icd_index *idx, icd_fusion *fusion, icd_grouping *grouping, const float *scores, const int64_t *ids, int64_t nq,
                                   int32_t R, int32_t lmax, const int32_t *limits, int32_t ranker, double rrf_c, const double *weights, int32_t norm,

@@ -1928,8 +1928,8 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
 // the other entry families, each its own file in this translation unit (launch_lds's per-kernel state and the kernel templates exist once)
 #include "icd_utility.hpp"   // the stateless utility entry points
 #include "icd_grouped.hpp"   // the grouping search
-#include "icd_hybrid.hpp"    // the hybrid search
-#include "icd_sparse.hpp"    // the sparse-vector search, the fuse of caller-provided lists
+#include "icd_hybrid.hpp"    // the hybrid search, the fuse of caller-provided lists
+#include "icd_sparse.hpp"    // the sparse-vector search
 #include "icd_text_match.hpp" // keyword match filters: row masks from the sparse index's postings
 #include "icd_filter.hpp"     // filter programs: row masks from int32 columns and the postings, any boolean shape
 #include "icd_facet.hpp"      // facet counts: rows per group of a grouping under a batch of row masks

@@ -1,7 +1,6 @@
-// icd_sparse.hpp - the sparse-vector search (icd_sparse_*), its grouped form (icd_grouping_pair_sparse, icd_sparse_search_grouped)
-// and the fuse of caller-provided lists (icd_fusion_fuse_lists). Part of
-// icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle, mask and host-call helpers, the grouping, the fusion); included there and
-// nowhere else.
+// icd_sparse.hpp - the sparse-vector search (icd_sparse_*) and its grouped form (icd_grouping_pair_sparse, icd_sparse_search_grouped).
+// Part of icd_search.hip's translation unit (fail(), HIP_TRY, the owned-handle, mask and host-call helpers, the grouping); included
+// there and nowhere else.
 #pragma once
 #include "sparse_pack.hpp"
 
@@ -95,6 +94,53 @@ int icd_sparse_stats(icd_sparse *sp, int64_t *out_vocab, int64_t *out_nnz, int64
 
 }  // extern "C"
 
+// A caller's queries (CSR; host or device memory) and what icd_sparse_search, icd_sparse_search_range and icd_sparse_search_grouped do
+// with them on either side of their locks.
+struct SparseQueries {
+    const int64_t *off; const uint32_t *terms; const float *vals;
+    int64_t nq; bool on_device;
+    int64_t nnz = 0;   // of a host caller's queries, measured by check()
+
+    // before the first device call: a host caller's CSR against the sparse index's vocabulary, a device caller's pointers against NULL
+    int check(const icd_sparse *sp) {
+        if (!off) return fail(ICD_ERR_INVALID, "q_off is NULL");
+        if (!on_device) {
+            char msg[200];
+            if (sparse_check_csr(off, terms, vals, nq, sp->vocab, SP_MAX_TERMS, "query", msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);
+            nnz = off[nq];
+        } else if (!terms || !vals) {
+            return fail(ICD_ERR_INVALID, "q_terms / q_vals NULL");
+        }
+        return ICD_OK;
+    }
+
+    // behind the caller's locks and check_capture: the postings, queries, masks and tiles of `a`. masks != nullptr (a table that holds a
+    // mask): the call reads section 12's table of the index, so `table` takes the index's mutex here and the caller keeps it to its last
+    // launch, as every masked dense search does (an unmasked call touches nothing of the index's workspace). A host caller's queries go
+    // into the sparse index's staging.
+    int stage(icd_index *idx, icd_sparse *sp, icd_rowmask *const *masks, std::unique_lock<std::mutex> &table, hipStream_t s, SparseArgs &a) {
+        int rc;
+        if (masks) {
+            table.lock();
+            if ((rc = stage_masks(idx, masks, (int)nq, s))) return rc;
+        }
+        a.post_off = sp->post_off; a.post_row = sp->post_row; a.post_val = sp->post_val; a.vocab = sp->vocab;
+        a.q_off = reinterpret_cast<const long long *>(off); a.q_terms = terms; a.q_vals = vals;
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(sp->q_off, off, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, s));
+            if (nnz) {
+                HIP_TRY(hipMemcpyAsync(sp->q_terms, terms, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(sp->q_vals, vals, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+            }
+            a.q_off = sp->q_off; a.q_terms = sp->q_terms; a.q_vals = sp->q_vals;
+        }
+        a.masks = masks ? idx->mask_dev : nullptr;
+        a.mask_words = rowmask_tile_words(idx->n);
+        a.tiles = sp->tiles;
+        return ICD_OK;
+    }
+};
+
 // icd_sparse_search and icd_sparse_search_range: rb = nullptr is the search without a band, through the BAND = false kernel.
 static int sparse_search_lists(icd_index *idx, icd_sparse *sp, const int64_t *q_off, const uint32_t *q_terms, const float *q_vals, int64_t nq,
                                int32_t k, int32_t queries_on_device, icd_rowmask *const *masks, const RangeBounds *rb, int32_t reweighted,
@@ -117,42 +163,18 @@ static int sparse_search_lists(icd_index *idx, icd_sparse *sp, const int64_t *q_
     bool any_mask = false;
     if (masks && (rc = check_masks(idx, masks, nq, "masked sparse search", &any_mask))) return rc;
     if (nq == 0) return ICD_OK;
-    if (!q_off) return fail(ICD_ERR_INVALID, "q_off is NULL");
-    int64_t q_nnz = 0;
-    if (!queries_on_device) {
-        char msg[200];
-        if (sparse_check_csr(q_off, q_terms, q_vals, nq, sp->vocab, SP_MAX_TERMS, "query", msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);
-        q_nnz = q_off[nq];
-    } else if (!q_terms || !q_vals) {
-        return fail(ICD_ERR_INVALID, "q_terms / q_vals NULL");
-    }
+    SparseQueries sq{q_off, q_terms, q_vals, nq, queries_on_device != 0};
+    if ((rc = sq.check(sp))) return rc;
     std::lock_guard<std::mutex> guard(sp->mu);
     HIP_TRY(hipSetDevice(idx->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
     const bool host_bands = rb && !rb->on_device;
     if ((rc = check_capture(s, !queries_on_device || !out_on_device, host_bands, any_mask))) return rc;
-    // a masked call reads section 12's table of the index: it holds the index's mutex from the table's fill to its last launch, as
-    // every masked dense search does (an unmasked call touches nothing of the index's workspace and takes only its own)
     std::unique_lock<std::mutex> table(idx->mu, std::defer_lock);
-    if (any_mask) {
-        table.lock();
-        if ((rc = stage_masks(idx, masks, (int)nq, s))) return rc;
-    }
     SparseArgs a{};
-    a.post_off = sp->post_off; a.post_row = sp->post_row; a.post_val = sp->post_val; a.vocab = sp->vocab;
-    a.q_off = reinterpret_cast<const long long *>(q_off); a.q_terms = q_terms; a.q_vals = q_vals;
-    if (!queries_on_device) {
-        HIP_TRY(hipMemcpyAsync(sp->q_off, q_off, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, s));
-        if (q_nnz) {
-            HIP_TRY(hipMemcpyAsync(sp->q_terms, q_terms, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(sp->q_vals, q_vals, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
-        }
-        a.q_off = sp->q_off; a.q_terms = sp->q_terms; a.q_vals = sp->q_vals;
-    }
-    a.masks = any_mask ? idx->mask_dev : nullptr;
-    a.mask_words = rowmask_tile_words(idx->n);
-    a.tiles = sp->tiles; a.nq = (int)nq; a.k = k; a.part = sp->part;
+    if ((rc = sq.stage(idx, sp, any_mask ? masks : nullptr, table, s, a))) return rc;
+    a.nq = (int)nq; a.k = k; a.part = sp->part;
     if (rb) {   // the bounds -> BandQ (a sparse index has no views: row_map = nullptr), then the BAND = true form
         if (rb->on_device) {
             hipLaunchKernelGGL(band_pack_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, rb->radius, rb->range_filter, rb->after_scores,
@@ -259,15 +281,8 @@ int icd_sparse_search_grouped(icd_index *idx, icd_sparse *sp, icd_grouping *grou
     bool any_mask = false;
     if (masks && (rc = check_masks(idx, masks, nq, "masked sparse search", &any_mask))) return rc;
     if (nq == 0) return ICD_OK;
-    if (!q_off) return fail(ICD_ERR_INVALID, "q_off is NULL");
-    int64_t q_nnz = 0;
-    if (!queries_on_device) {
-        char msg[200];
-        if (sparse_check_csr(q_off, q_terms, q_vals, nq, sp->vocab, SP_MAX_TERMS, "query", msg, sizeof msg)) return fail(ICD_ERR_INVALID, "%s", msg);
-        q_nnz = q_off[nq];
-    } else if (!q_terms || !q_vals) {
-        return fail(ICD_ERR_INVALID, "q_terms / q_vals NULL");
-    }
+    SparseQueries sq{q_off, q_terms, q_vals, nq, queries_on_device != 0};
+    if ((rc = sq.check(sp))) return rc;
     // lock order: sparse index, grouping, index
     std::lock_guard<std::mutex> guard_sp(sp->mu);
     std::lock_guard<std::mutex> guard_g(g->mu);
@@ -276,25 +291,9 @@ int icd_sparse_search_grouped(icd_index *idx, icd_sparse *sp, icd_grouping *grou
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const HostCall hc{s, queries_on_device != 0, out_on_device != 0};
     if ((rc = check_capture(s, !queries_on_device || !out_on_device, false, any_mask))) return rc;
-    std::unique_lock<std::mutex> table(idx->mu, std::defer_lock);   // (a masked call reads the index's mask table: icd_sparse_search)
-    if (any_mask) {
-        table.lock();
-        if ((rc = stage_masks(idx, masks, (int)nq, s))) return rc;
-    }
+    std::unique_lock<std::mutex> table(idx->mu, std::defer_lock);
     SparseStoreArgs a{};
-    a.sp.post_off = sp->post_off; a.sp.post_row = sp->post_row; a.sp.post_val = sp->post_val; a.sp.vocab = sp->vocab;
-    a.sp.q_off = reinterpret_cast<const long long *>(q_off); a.sp.q_terms = q_terms; a.sp.q_vals = q_vals;
-    if (!queries_on_device) {
-        HIP_TRY(hipMemcpyAsync(sp->q_off, q_off, ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, s));
-        if (q_nnz) {
-            HIP_TRY(hipMemcpyAsync(sp->q_terms, q_terms, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(sp->q_vals, q_vals, (size_t)q_nnz * 4, hipMemcpyHostToDevice, s));
-        }
-        a.sp.q_off = sp->q_off; a.sp.q_terms = sp->q_terms; a.sp.q_vals = sp->q_vals;
-    }
-    a.sp.masks = any_mask ? idx->mask_dev : nullptr;
-    a.sp.mask_words = rowmask_tile_words(idx->n);
-    a.sp.tiles = sp->tiles;
+    if ((rc = sq.stage(idx, sp, any_mask ? masks : nullptr, table, s, a.sp))) return rc;
     a.n = (int)idx->n; a.pos_of = g->pos_of; a.S = g->S; a.ldS = g->ldS;
     const GroupedOuts o{hc.target(out_adj, g->o_adj), hc.target(out_raw, g->o_raw), hc.target(reinterpret_cast<long long *>(out_ids), g->o_ids),
                         hc.target(out_levels, g->o_lv), hc.target(out_groups, g->o_grp)};
@@ -307,52 +306,6 @@ int icd_sparse_search_grouped(icd_index *idx, icd_sparse *sp, icd_grouping *grou
     }
     if ((rc = hc.copy_back({{reweighted ? out_adj : nullptr, o.d_adj, 8}, {out_raw, o.d_raw, 4}, {out_ids, o.d_ids, 8}, {out_levels, o.d_lv, 4},
                             {out_groups, o.d_grp, 4}}, (size_t)nq * k * group_size)))
-        return rc;
-    return hc.finish();
-}
-
-int icd_fusion_fuse_lists(icd_index *idx, icd_fusion *fusion, const float *scores, const int64_t *ids, int64_t nq, int32_t R, int32_t lmax,
-                          const int32_t *limits, int32_t ranker, double rrf_c, const double *weights, int32_t norm, int32_t k,
-                          int32_t reweighted, double *out_adj, double *out_fused, int64_t *out_ids, int32_t *out_levels,
-                          uint32_t *out_reqbits, int32_t out_on_device, void *stream) {
-    // the checks of icd_index_search_hybrid that concern its step 2, before the first device call
-    if (!valid(idx)) return fail(ICD_ERR_STATE, "invalid handle");
-    if (!valid_handle(fusion)) return fail(ICD_ERR_STATE, "invalid fusion handle");
-    icd_fusion *f = fusion;
-    int rc = check_owner(f->at, idx, "the fusion");
-    if (rc) return rc;
-    if (R < 1 || R > ICD_MAX_REQUESTS) return fail(ICD_ERR_INVALID, "R=%d: a hybrid search takes 1 .. %d requests per query", R, ICD_MAX_REQUESTS);
-    if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a hybrid search returns 1 .. %d hits per query", k, ICD_MAX_K);
-    if (lmax < 1 || lmax > ICD_MAX_K) return fail(ICD_ERR_INVALID, "lmax=%d: a list holds 1 .. %d hits", lmax, ICD_MAX_K);
-    if (!limits) return fail(ICD_ERR_INVALID, "limits is NULL");
-    for (int r = 0; r < R; ++r)
-        if (limits[r] < 1 || limits[r] > lmax) return fail(ICD_ERR_INVALID, "limits[%d]=%d: a request returns 1 .. lmax=%d hits", r, limits[r], lmax);
-    if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
-    if (nq * R > f->max_total) return fail(ICD_ERR_INVALID, "nq * R = %lld exceeds the fusion's max_total=%lld", (long long)(nq * R), (long long)f->max_total);
-    if (ranker == ICD_RANKER_RRF) {
-        if (!(rrf_c > 0.0 && rrf_c < 16384.0)) return fail(ICD_ERR_INVALID, "rrf_c=%g: need 0 < c < 16384", rrf_c);
-    } else if (ranker == ICD_RANKER_WEIGHTED) {
-        if (!weights) return fail(ICD_ERR_INVALID, "weights is NULL");
-        for (int r = 0; r < R; ++r)
-            if (!(weights[r] >= 0.0 && weights[r] <= 1.0)) return fail(ICD_ERR_INVALID, "weights[%d]=%g: a weight lies in [0, 1]", r, weights[r]);
-        if (norm != ICD_NORM_NONE && norm != ICD_NORM_COSINE && norm != ICD_NORM_ATAN) return fail(ICD_ERR_INVALID, "norm=%d", norm);
-    } else {
-        return fail(ICD_ERR_INVALID, "ranker=%d", ranker);
-    }
-    if (!out_fused || !out_ids || (reweighted && !out_adj)) return fail(ICD_ERR_INVALID, "output pointer is NULL");
-    if (nq == 0) return ICD_OK;
-    if (!scores || !ids) return fail(ICD_ERR_INVALID, "scores / ids NULL");
-    std::lock_guard<std::mutex> guard(f->mu);
-    HIP_TRY(hipSetDevice(idx->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const HostCall hc{s, true, out_on_device != 0};
-    if ((rc = check_capture(s, !out_on_device, false, false))) return rc;
-    for (int r = 0; r < ICD_MAX_REQUESTS; ++r) {
-        f->limits[r] = r < R ? limits[r] : 0;
-        f->weights[r] = (r < R && ranker == ICD_RANKER_WEIGHTED) ? weights[r] : 0.0;
-    }
-    if ((rc = fuse_lists_step(idx, f, scores, reinterpret_cast<const long long *>(ids), nq, R, lmax, ranker, rrf_c, norm, k, reweighted, out_adj,
-                              out_fused, out_ids, out_levels, out_reqbits, hc, s)))
         return rc;
     return hc.finish();
 }

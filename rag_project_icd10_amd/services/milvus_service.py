@@ -397,6 +397,10 @@ class MilvusService:
     # ---- keyword match filters (TEXT_MATCH) ------------------------------------------------------------------
     TEXT_MATCH_ON_DEVICE = True   # False: every TEXT_MATCH expression takes the host route (tests compare the two routes' bits)
 
+    def _sparse_index(self):
+        """(IcdSparse, SparseTextIndex) over the store's sparse field: the cached index's field, "preferred_zh" before one is built"""
+        return self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+
     def _text_index(self):
         """(IcdSparse, SparseTextIndex, field) of the store's sparse index, built on the first TEXT_MATCH as search_text builds it"""
         field = self._sparse[3] if self._sparse is not None else "preferred_zh"
@@ -867,6 +871,22 @@ class MilvusService:
             logger.error("搜索失败: %s", exc)
             return []
 
+    def _hit_lists(self, adj, raw, ids, group=None, extra=None) -> List[List[Dict[str, Any]]]:
+        """as_dicts of a batch: [nq, k] arrays (device tensors are moved to the host) -> one _hits_to_dicts list per query. group:
+        None, or (field, the hits' group ids [nq, k], the field's values); extra: None, or (key, a float per hit [nq, k])"""
+        host = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else t   # noqa: E731
+        adj, raw, ids = host(adj), host(raw), host(ids)
+        if group is None:
+            out = [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
+        else:
+            groups = host(group[1])
+            out = [self._hits_to_dicts(adj[q], raw[q], ids[q], (group[0], groups[q], group[2])) for q in range(len(ids))]
+        if extra is not None:
+            for hits, vals in zip(out, host(extra[1])):   # (padding sits behind the hits: the first len(hits) slots are theirs)
+                for hit, v in zip(hits, vals):
+                    hit[extra[0]] = float(v)
+        return out
+
     def _hits_to_dicts(self, adj, raw, ids, group=None) -> List[Dict[str, Any]]:
         """group: None, or (field, the hits' group ids, the field's sorted distinct values) of a grouping search"""
         out = []
@@ -964,9 +984,7 @@ class MilvusService:
                 self._release_masks(pair[1])   # (closing synchronises the device: the search has run)
             if not as_dicts:
                 return adj, raw, ids, levels
-            if hasattr(adj, "cpu"):
-                adj, raw, ids = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy()
-            return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
+            return self._hit_lists(adj, raw, ids)
         if filter is not None:
             index, rows = self._filtered_index(filter)
             if index is None:   # nothing selected: no device call
@@ -978,9 +996,7 @@ class MilvusService:
             adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, query_vectors, top_k, group_by_field, group_size)
             if not as_dicts:
                 return adj, raw, ids, levels, groups
-            if hasattr(adj, "cpu"):
-                adj, raw, ids, groups = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy(), groups.cpu().numpy()
-            return [self._hits_to_dicts(adj[q], raw[q], ids[q], (group_by_field, groups[q], values)) for q in range(len(ids))]
+            return self._hit_lists(adj, raw, ids, (group_by_field, groups, values))
         # (large batches on a corpus of tight families of near-identical rows - ICD sibling codes - are handled inside the
         #  library: a second coarse pass over the queries the first could not certify, and from the next large batch on the
         #  wider partition right away; include/icd_search.h icd_stats.last_second_pass / wide_mode)
@@ -990,9 +1006,7 @@ class MilvusService:
             adj, raw, ids, levels = index.search_reweighted(query_vectors, int(top_k))
         if not as_dicts:
             return adj, raw, ids, levels
-        if hasattr(adj, "cpu"):
-            adj, raw, ids = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy()
-        return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(len(ids))]
+        return self._hit_lists(adj, raw, ids)
 
     # ---- MMR search (a diverse top-k) ---------------------------------------------------------------------------
     MMR_MAX_FETCH = 128   # candidates per query (the hit list's slots)
@@ -1068,15 +1082,7 @@ class MilvusService:
             self._release_masks(masks)
         if not as_dicts:
             return adj, raw, ids, levels, mmr
-        if hasattr(adj, "cpu"):
-            adj, raw, ids, mmr = adj.cpu().numpy(), raw.cpu().numpy(), ids.cpu().numpy(), mmr.cpu().numpy()
-        out = []
-        for q in range(len(ids)):
-            hits = self._hits_to_dicts(adj[q], raw[q], ids[q])
-            for hit, v in zip(hits, mmr[q]):   # (padding sits behind the hits: the first len(hits) slots are theirs)
-                hit["mmr_score"] = float(v)
-            out.append(hits)
-        return out
+        return self._hit_lists(adj, raw, ids, extra=("mmr_score", mmr))
 
     def search_mmr(self, query_vector, top_k: int = 10, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
                    filter: Optional[str] = None, radius: Optional[float] = None, range_filter: Optional[float] = None,   # noqa: A002
@@ -1193,7 +1199,7 @@ class MilvusService:
         for e in (filter if isinstance(filter, (list, tuple)) else [filter]):
             if e is not None:
                 filter_expr.compile(e)
-        sp, _tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        sp, _tx = self._sparse_index()
         index = self._index
         if int(top_k) > index.max_k:
             raise ValueError(f"top_k={top_k} exceeds the index's max_k={index.max_k} (ICD_GPU_MAX_K)")
@@ -1208,7 +1214,7 @@ class MilvusService:
             adj, raw, ids, levels, groups = self._sparse_lists(index, sp, q_off, q_terms, q_vals, int(top_k), masks, True, grouping, int(group_size))
             if not as_dicts:
                 return adj, raw, ids, levels, groups
-            return [self._hits_to_dicts(adj[q], raw[q], ids[q], (group_by_field, groups[q], values)) for q in range(nq)]
+            return self._hit_lists(adj, raw, ids, (group_by_field, groups, values))
         if banded and nq > 0:
             band = range_search.SparseBandIndex(index, sp, masks)
             adj, raw, ids, levels = range_search.search_band(band, (np.asarray(q_off, np.int64).reshape(-1), q_terms, q_vals), int(top_k),
@@ -1217,7 +1223,7 @@ class MilvusService:
             adj, raw, ids, levels = self._sparse_lists(index, sp, q_off, q_terms, q_vals, int(top_k), masks, True)
         if not as_dicts:
             return adj, raw, ids, levels
-        return [self._hits_to_dicts(adj[q], raw[q], ids[q]) for q in range(nq)]
+        return self._hit_lists(adj, raw, ids)
 
     def search_text(self, text: str, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002
                     group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
@@ -1239,7 +1245,7 @@ class MilvusService:
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 128:
             raise ValueError(f"top_k={top_k!r}: an int in 1 .. 128")
         radius, range_filter, offset, _banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
-        _sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        _sp, tx = self._sparse_index()
         return self.search_sparse_batch(*tx.encode_queries([text]), top_k, filter=filter, as_dicts=True,
                                         group_by_field=group_by_field, group_size=group_size, radius=radius, range_filter=range_filter,
                                         offset=offset)[0]
@@ -1261,7 +1267,7 @@ class MilvusService:
             filter_expr.compile(filter)
         band, query = None, None
         if self.client is not None and self.client.exists() and self._ready_index() is not None:
-            sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+            sp, tx = self._sparse_index()
             index = self._index
             query = tx.encode_queries([text])
             mask = self._filter_mask(index, filter)
@@ -1275,11 +1281,10 @@ class MilvusService:
         """hybrid_search_batch with at least one sparse request: the dense requests as ONE search_batch-style sub-search, the
         sparse ones as ONE search_sparse_batch-style call, their raw lists interleaved into [nq, R, lmax] on the device, fused by
         fuse_lists. Returns device tensors."""
-        import torch
         index = self._ready_index()
         if index is None:
             raise RuntimeError(f"collection {self.collection_name} is empty or missing")
-        sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
+        sp, tx = self._sparse_index()
         dense = [r for r in reqs if r.anns_field == "vector"]
         sparse = [r for r in reqs if r.anns_field == "sparse"]
         sq = [hybrid.sparse_queries(r) for r in sparse]
@@ -1296,11 +1301,7 @@ class MilvusService:
             raise ValueError(f"a request's limit exceeds the index's max_k={index.max_k} (ICD_GPU_MAX_K)")
         if nq * R > index.max_nq:
             raise ValueError(f"{nq} queries x {R} requests exceed the index's batch of {index.max_nq} (ICD_GPU_MAX_BATCH)")
-        where = torch.device("cuda", index.device)
-        scores = torch.full((nq, R, lmax), float("-inf"), dtype=torch.float32, device=where)
-        ids = torch.full((nq, R, lmax), -1, dtype=torch.int64, device=where)
-        dense_at = [i for i, r in enumerate(reqs) if r.anns_field == "vector"]
-        sparse_at = [i for i, r in enumerate(reqs) if r.anns_field == "sparse"]
+        scores, ids, put = self._interleave_lists(index, reqs, nq, lmax)
         if dense:   # ONE banded / masked / plain sub-search over the nq * Rd vectors, as search_hybrid's step 1
             Rd, ld = len(dense), max(r.limit for r in dense)
             flat = qd.reshape(nq * Rd, -1) if hasattr(qd, "is_cuda") else np.ascontiguousarray(qd.reshape(nq * Rd, -1))
@@ -1312,26 +1313,41 @@ class MilvusService:
                 d_raw, d_ids, _lv = index.search_masked(flat, ld, per * nq, radius=bound(lo, -np.inf), range_filter=bound(hi, np.inf), reweighted=False)
             else:
                 d_raw, d_ids = index.search(flat, ld)   # (AUTO: the same hits as EXACT, as search_hybrid's plain step 1)
-            d_raw = torch.as_tensor(d_raw).to(where).reshape(nq, Rd, ld)
-            d_ids = torch.as_tensor(d_ids).to(where).reshape(nq, Rd, ld)
-            for j, at in enumerate(dense_at):
-                scores[:, at, :ld], ids[:, at, :ld] = d_raw[:, j], d_ids[:, j]
-        if sparse:  # ONE sparse call over the nq * Rs queries
-            Rs, ls = len(sparse), max(r.limit for r in sparse)
-            pairs = []
-            for q in range(nq):
-                for x in sq:
-                    pairs.append(tx.encode_query(x[q]) if isinstance(x[q], str) else sparse_text.query_from_dict(x[q], tx.vocab_size))
-            per = [self._filter_mask(index, r.expr) for r in sparse]
-            masks = per * nq if any(m is not None for m in per) else None
-            s_raw, s_ids, _lv = self._sparse_lists(index, sp, *sparse_text.csr_from_pairs(pairs), ls, masks, False)
-            s_raw = torch.from_numpy(s_raw).to(where).reshape(nq, Rs, ls)
-            s_ids = torch.from_numpy(s_ids).to(where).reshape(nq, Rs, ls)
-            for j, at in enumerate(sparse_at):
-                scores[:, at, :ls], ids[:, at, :ls] = s_raw[:, j], s_ids[:, j]
-        kw = ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
-              else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
-        return index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, **kw), nq, R
+            put("vector", d_raw, d_ids, ld)
+        ls = max(r.limit for r in sparse)   # ONE sparse call over the nq * Rs queries (a caller sends at least one sparse request)
+        csr = self._sparse_request_csr(tx, sq, nq)
+        per = [self._filter_mask(index, r.expr) for r in sparse]
+        s_raw, s_ids, _lv = self._sparse_lists(index, sp, *csr, ls, per * nq if any(m is not None for m in per) else None, False)
+        put("sparse", s_raw, s_ids, ls)
+        return index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, **self._ranker_kw(ranker)), nq, R
+
+    @staticmethod
+    def _ranker_kw(ranker):
+        """search_hybrid's / fuse_lists' ranker keywords of an RRFRanker or a WeightedRanker"""
+        return ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
+                else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
+
+    @staticmethod
+    def _sparse_request_csr(tx, sq, nq: int):
+        """the nq * Rs sparse queries of a hybrid call as CSR, query-major: sq[r][q] is request r's text or {term id: weight} for query q"""
+        return sparse_text.csr_from_pairs([tx.encode_query(x[q]) if isinstance(x[q], str) else sparse_text.query_from_dict(x[q], tx.vocab_size)
+                                           for q in range(nq) for x in sq])
+
+    @staticmethod
+    def _interleave_lists(index, reqs, nq: int, width: int):
+        """fuse_lists' input on the index's device: scores float32 (-inf) / ids int64 (-1) [nq, R, width], filled here, and
+        put(field, scores, ids, w), which copies one side's raw lists ([nq * R_side, w], request order) into that side's columns"""
+        import torch
+        where = torch.device("cuda", index.device)
+        scores = torch.full((nq, len(reqs), width), float("-inf"), dtype=torch.float32, device=where)
+        ids = torch.full((nq, len(reqs), width), -1, dtype=torch.int64, device=where)
+
+        def put(field, raw, lid, w):
+            at = [i for i, r in enumerate(reqs) if r.anns_field == field]
+            raw, lid = (torch.as_tensor(x).to(where).reshape(nq, len(at), w) for x in (raw, lid))
+            for j, a in enumerate(at):
+                scores[:, a, :w], ids[:, a, :w] = raw[:, j], lid[:, j]
+        return scores, ids, put
 
     @staticmethod
     def _check_hybrid_grouping(reqs, limit, field, group_size):
@@ -1363,8 +1379,6 @@ class MilvusService:
         dense = [r for r in reqs if r.anns_field == "vector"]
         sparse = [r for r in reqs if r.anns_field == "sparse"]
         R = len(reqs)
-        kw = ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
-              else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
         qd = hybrid.stack_requests(dense) if dense else None
         sq = [hybrid.sparse_queries(r) for r in sparse]
         counts = {len(x) for x in sq} | ({int(qd.shape[0])} if dense else set())
@@ -1385,35 +1399,21 @@ class MilvusService:
                      np.zeros((nq, kk), np.uint32), np.full((nq, kk), -1, np.int32)), nq, R, values)
         g_target = g_parent if target is index else self._grouping(field, target, rows, fkey)[0]
         if not sparse:
-            out = target.search_hybrid(qd, [r.limit for r in reqs], limit, self._fusion_for(target, nq * R), grouping=g_target, group_size=s, **kw)
+            out = target.search_hybrid(qd, [r.limit for r in reqs], limit, self._fusion_for(target, nq * R), grouping=g_target, group_size=s, **self._ranker_kw(ranker))
             return out, nq, R, values
-        import torch
-        sp, tx = self.build_sparse_index(self._sparse[3] if self._sparse is not None else "preferred_zh")
-        lmax = max(r.limit for r in reqs) * s
-        where = torch.device("cuda", index.device)
-        scores = torch.full((nq, R, lmax), float("-inf"), dtype=torch.float32, device=where)
-        ids = torch.full((nq, R, lmax), -1, dtype=torch.int64, device=where)
+        sp, tx = self._sparse_index()
+        scores, ids, put = self._interleave_lists(index, reqs, nq, max(r.limit for r in reqs) * s)
         if dense:   # ONE grouped search over the nq * Rd vectors, on the view with the view's grouping (global ids come back)
             Rd, ld = len(dense), max(r.limit for r in dense)
             flat = qd.reshape(nq * Rd, -1) if hasattr(qd, "is_cuda") else np.ascontiguousarray(qd.reshape(nq * Rd, -1))
             d_raw, d_ids, _lv, _g = target.search_grouped(flat, ld, s, g_target, reweighted=False)
-            d_raw = torch.as_tensor(d_raw).to(where).reshape(nq, Rd, ld * s)
-            d_ids = torch.as_tensor(d_ids).to(where).reshape(nq, Rd, ld * s)
-            for j, at in enumerate(i for i, r in enumerate(reqs) if r.anns_field == "vector"):
-                scores[:, at, :ld * s], ids[:, at, :ld * s] = d_raw[:, j], d_ids[:, j]
+            put("vector", d_raw, d_ids, ld * s)
         Rs, ls = len(sparse), max(r.limit for r in sparse)   # ONE grouped sparse call over the nq * Rs queries, on the parent with the mask
-        pairs = []
-        for q in range(nq):
-            for x in sq:
-                pairs.append(tx.encode_query(x[q]) if isinstance(x[q], str) else sparse_text.query_from_dict(x[q], tx.vocab_size))
+        csr = self._sparse_request_csr(tx, sq, nq)
         mask = self._filter_mask(index, expr)
-        s_raw, s_ids, _lv, _g = self._sparse_lists(index, sp, *sparse_text.csr_from_pairs(pairs), ls, None if mask is None else [mask] * (nq * Rs),
-                                                   False, g_parent, s)
-        s_raw = torch.from_numpy(s_raw).to(where).reshape(nq, Rs, ls * s)
-        s_ids = torch.from_numpy(s_ids).to(where).reshape(nq, Rs, ls * s)
-        for j, at in enumerate(i for i, r in enumerate(reqs) if r.anns_field == "sparse"):
-            scores[:, at, :ls * s], ids[:, at, :ls * s] = s_raw[:, j], s_ids[:, j]
-        out = index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, grouping=g_parent, group_size=s, **kw)
+        s_raw, s_ids, _lv, _g = self._sparse_lists(index, sp, *csr, ls, None if mask is None else [mask] * (nq * Rs), False, g_parent, s)
+        put("sparse", s_raw, s_ids, ls * s)
+        out = index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, grouping=g_parent, group_size=s, **self._ranker_kw(ranker))
         return out, nq, R, values
 
     def hybrid_search_batch(self, reqs, ranker, limit: int = 10, as_dicts: bool = False, group_by_field: Optional[str] = None,
@@ -1455,21 +1455,17 @@ class MilvusService:
             lo = np.array([-np.inf if r.radius is None else r.radius for r in reqs], np.float32)
         if any(r.range_filter is not None for r in reqs):
             hi = np.array([np.inf if r.range_filter is None else r.range_filter for r in reqs], np.float32)
-        kw = ({"ranker": "rrf", "rrf_c": ranker.k} if isinstance(ranker, hybrid.RRFRanker)
-              else {"ranker": "weighted", "weights": ranker.weights, "norm": ranker.norm_score})
         out = index.search_hybrid(q, [r.limit for r in reqs], limit, self._fusion_for(index, nq * R), masks=masks, radius=lo,
-                                  range_filter=hi, **kw)
+                                  range_filter=hi, **self._ranker_kw(ranker))
         if not as_dicts:
             return out
         return self._hybrid_dicts(out, nq, R, limit)
 
     def _hybrid_dicts(self, out, nq: int, R: int, limit: int, group=None):
         """group: None, or (field, the field's sorted distinct values) of a grouped hybrid search (a sixth array holds the group ids)"""
-        adj, fused, ids, _levels, bits = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in out[:5]]
-        groups = None if group is None else (out[5].cpu().numpy() if hasattr(out[5], "cpu") else out[5])
+        ids, bits = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in (out[2], out[4])]
         res = []
-        for qi in range(nq):
-            hits = self._hits_to_dicts(adj[qi], fused[qi], ids[qi], None if group is None else (group[0], groups[qi], group[1]))
+        for qi, hits in enumerate(self._hit_lists(out[0], out[1], ids, None if group is None else (group[0], out[5], group[1]))):
             valid = [j for j in range(ids.shape[1]) if ids[qi][j] >= 0]
             for hit, j in zip(hits, valid):
                 hit["fused_score"] = hit.pop("original_score")

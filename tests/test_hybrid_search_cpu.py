@@ -284,3 +284,21 @@ def test_a_ranking_shifted_by_id_base_gives_the_same_outputs_with_the_ids_shifte
     got = fuse_query(moved, levels, 10, ranker, id_base=id_base, **kw2)
     for g, w in zip(got[0] + got[1], want[0] + want[1]):
         assert g.tobytes() == (shift(w) if w.dtype == np.int64 else w).tobytes()
+
+
+def test_fuse_params_normalises_limits_ranker_norm_and_weights_without_a_library():
+    """_native._fuse_params, what search_hybrid and fuse_lists share in front of the C call: search_hybrid's messages, no library"""
+    lim, wts, fuse = _native._fuse_params(7, 3, "rrf", 60, [0.5, "not read"], "atan")   # (weights is ignored for "rrf")
+    assert lim.dtype == np.int32 and lim.flags.c_contiguous and lim.tolist() == [7, 7, 7] and wts is None
+    assert fuse == (_native.RANKER_RRF, 60.0, None, _native.NORMS["atan"]) and isinstance(fuse[1], float)
+    lim, wts, fuse = _native._fuse_params([3, 1], 2, "weighted", 60.0, (0.25, 1), "cosine")
+    assert lim.tolist() == [3, 1] and wts.dtype == np.float64 and wts.flags.c_contiguous and wts.tolist() == [0.25, 1.0]
+    assert fuse == (_native.RANKER_WEIGHTED, 60.0, wts.ctypes.data, _native.NORMS["cosine"])
+    for args, text in ((([3, 1], 3, "rrf", 60.0, None, "none"), "limits holds 2 entries for 3 requests"),
+                       ((4, 2, "max", 60.0, None, "none"), "ranker='max': 'rrf' or 'weighted'"),
+                       ((4, 2, "rrf", 60.0, None, "l2"), f"norm='l2': one of {sorted(_native.NORMS)}"),
+                       ((4, 2, "weighted", 60.0, [0.5], "none"), "weights holds 1 entries for 2 requests"),
+                       (([3, 1], 3, "max", 60.0, None, "l2"), "limits holds 2 entries for 3 requests")):   # (limits first, then the ranker)
+        with pytest.raises(ValueError) as err:
+            _native._fuse_params(*args)
+        assert str(err.value) == text
