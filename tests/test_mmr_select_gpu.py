@@ -1,7 +1,8 @@
 """icd_index_search_mmr on the device against tests/mmr_oracle.py, byte for byte: no tolerance anywhere.
-Corpus sizes sit around the 128 candidates of a list (fewer rows than fetch_k, one row, one more than a list), dims at the chain's
-two trip widths (32: pairs only; 768 and 4096: eight blocks a trip), corpora that make values tie (exact duplicates, every row
-equal, rows of zeros), subnormal scores and NaN rows; every (k, fetch_k) of the issue's list at every lambda; batches of 1, 3 and
+Corpus sizes sit around the 128 candidates of a list (fewer rows than fetch_k, one row, one more than a list), dims at every gear
+of the chain's walk (32 and 64: pairs only; 768, 1024 and 4096: trips of eight blocks only; 160, 224 and 800: trips, then one or
+three pairs - the hand-over of b0 from the trip loop to the pair loop), corpora that make values tie (exact duplicates, every row
+equal, rows of zeros; duplicates and subnormals at 160 too), subnormal scores and NaN rows; every (k, fetch_k) of the issue's list at every lambda; batches of 1, 3 and
 300 queries with per-query masks and bands; device against host outputs; every refusal of the C entry point."""
 import ctypes
 
@@ -102,7 +103,10 @@ def sweep(case):
 
 @pytest.mark.parametrize("n,dim,id_base", [(1, 32, 0), (2, 32, 0), (9, 32, 0), (127, 32, 0), (128, 32, 0), (129, 32, 5_000_000_000), (257, 32, 0),
                                            (1, 768, 0), (2, 768, 0), (9, 768, 0), (127, 768, 0), (128, 768, 0), (129, 768, 0), (257, 768, 7),
-                                           (129, 4096, 0)])
+                                           (129, 4096, 0),
+                                           # the walk changes gear (16 floats a block, 8 blocks a trip, then pairs): two pairs and no trip;
+                                           # one trip + one pair; one trip + three pairs; six trips + one pair; eight trips and no pair
+                                           (129, 64, 0), (129, 160, 0), (129, 224, 0), (129, 800, 0), (129, 1024, 0), (257, 160, 7)])
 def test_corpus_shapes(oracle, n, dim, id_base):
     case = Case(oracle, "random", n, dim, 100 + n + dim, id_base=id_base)
     try:
@@ -111,9 +115,10 @@ def test_corpus_shapes(oracle, n, dim, id_base):
         case.close()
 
 
-@pytest.mark.parametrize("kind", ["duplicates", "equal", "zeros", "subnormal", "nan"])
-def test_corpora_that_tie(oracle, kind):
-    case = Case(oracle, kind, 129, 32, 7, qscale=1e-21 if kind == "subnormal" else 1.0)
+@pytest.mark.parametrize("kind,dim", [pytest.param(kind, 32, id=kind) for kind in ("duplicates", "equal", "zeros", "subnormal", "nan")]
+                         + [pytest.param("duplicates", 160, id="duplicates-160"), pytest.param("subnormal", 160, id="subnormal-160")])
+def test_corpora_that_tie(oracle, kind, dim):
+    case = Case(oracle, kind, 129, dim, 7, qscale=1e-21 if kind == "subnormal" else 1.0)
     try:
         if kind == "subnormal":
             s = case.fs[np.isfinite(case.fs)]
