@@ -664,6 +664,52 @@ int icd_index_search_mmr(icd_index *idx, icd_mmr *mmr, icd_rowmask *const *masks
                          int32_t *out_levels, double *out_mmr, int32_t out_on_device, void *stream);
 
 /*
+ * Boosted search: Milvus 2.6's boost ranker ({"reranker": "boost", "filter", "weight"}) - "rows that match this filter count
+ * `weight` times as much" - applied BEFORE the top-k is chosen, exact over every row. A query carries up to
+ * ICD_MAX_BOOSTS boosts (M_j, w_j): M_j a row mask of the index, w_j an fp32 weight. Per query q and row r:
+ *   boosted(q, r)     starts as the canonical fp32 score of the row (oracle/icd_oracle.c chain_score); for j = 0, 1, 2, 3 in that
+ *                     order, if slot j is in use and r is in M_j: s = s * w_j - ONE IEEE fp32 multiply, rounded once, subnormals
+ *                     kept, fused with nothing. The slot order is part of the contract: rounding does not commute.
+ *   ranking           (boosted desc, id asc). The query's filter mask (masks[q]), radius, range_filter and the cursor
+ *                     (after_scores / after_ids) apply to the BOOSTED score and ranking exactly as icd_index_search_masked applies
+ *                     them to the raw one: a cursor pages through the boosted ranking. A row whose boosted score is NaN or -inf is
+ *                     not a hit; +inf is an ordinary score and ranks first.
+ *   outputs           icd_index_search_masked's: out_raw carries the boosted score, reweighted = 1 runs the level reweight on it
+ *                     (adj = (double)boosted * w[level], one stable re-sort); padding as there (-inf, id -1, level 0).
+ * With every slot unused the outputs are icd_index_search_masked's bit for bit; a boost of weight exactly 1.0f changes nothing.
+ *
+ * icd_boost_create: the workspace of the boosted searches of `idx` for up to max_nq queries per call: the pinned block the call's
+ * boost table is filled in, its device copy, the event that guards the block. Nothing is allocated in a search. The handle keeps
+ * no pointer into its index: it is compared, never followed, and either may be destroyed first. It serves one stream at a time,
+ * like the index it belongs to. A view has no boosted search (ICD_ERR_UNSUPPORTED: mask the parent), nor has the row-sharded path
+ * (icd_group_*): boost on every shard and merge.
+ *
+ * icd_index_search_boosted: icd_index_search_masked's dispatch and launches, on the kernel instantiations that carry the multiply
+ * (up to four queries at k <= 16 one launch, up to 64 the streaming kernel, more the fp32-MFMA kernel). masks: a HOST array of nq
+ * handles (NULL entries: unfiltered) or NULL. boost_masks: a HOST array [nq][ICD_MAX_BOOSTS] of handles, NULL = slot unused (holes
+ * are allowed: the used slots still apply in slot order), or NULL = no boost at all. boost_weights: HOST floats
+ * [nq][ICD_MAX_BOOSTS], read where the mask is not NULL. Bounds, cursor, outputs and synchronisation are
+ * icd_index_search_masked's. The boost table is filled on the host at call time, so the call cannot be captured into a graph:
+ * ICD_ERR_INVALID on a capturing stream. Every check comes before the first device call. ICD_ERR_INVALID: a weight of a used
+ * slot that is NaN, infinite, <= 0 or subnormal, a boost mask, a mask or a workspace of another index, nq above the workspace's
+ * or the index's max_nq, and whatever icd_index_search_masked refuses. ICD_ERR_STATE: a destroyed mask, workspace or index.
+ * ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 does nothing. A refused call leaves outputs and handles as they were.
+ */
+#define ICD_MAX_BOOSTS 4
+typedef struct icd_boost icd_boost;
+int icd_boost_create(icd_index *idx, int64_t max_nq, icd_boost **out);
+int icd_boost_destroy(icd_boost *b);
+/* queries per call, bytes held (either pointer may be NULL) */
+int icd_boost_stats(icd_boost *b, int64_t *out_max_nq, int64_t *out_bytes);
+int icd_index_search_boosted(icd_index *idx, icd_boost *ws, icd_rowmask *const *masks,
+                             icd_rowmask *const *boost_masks /* host [nq][ICD_MAX_BOOSTS], NULL = slot unused */,
+                             const float *boost_weights      /* host [nq][ICD_MAX_BOOSTS], read where the mask is not NULL */,
+                             const float *queries, int64_t nq, int32_t k, int32_t queries_on_device,
+                             const float *radius, const float *range_filter, const float *after_scores, const int64_t *after_ids,
+                             int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                             int32_t *out_levels, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

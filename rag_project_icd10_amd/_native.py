@@ -46,7 +46,9 @@ EXPORTED_SYMBOLS = (
     "icd_columns_create", "icd_columns_destroy", "icd_columns_stats", "icd_filter_program_check", "icd_filter_rowmasks",
     "icd_rowmask_select", "icd_rowmask_group_counts",
     "icd_mmr_create", "icd_mmr_destroy", "icd_mmr_stats", "icd_index_search_mmr",
+    "icd_boost_create", "icd_boost_destroy", "icd_boost_stats", "icd_index_search_boosted",
 )
+MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
 SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
 SELECT_SEGMENT_ROWS = 16384   # csrc/mask_select_plan.hpp MS_SEG_ROWS: rows of one work-group of the select's two passes
 FACET_LDS_GROUPS = 8192   # csrc/facet_count_plan.hpp FC_LDS_GROUPS: groups up to which a facet count sums in LDS (above it: global adds)
@@ -162,6 +164,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_mmr_destroy.argtypes = [vp]
     lib.icd_mmr_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_mmr.argtypes = [vp, vp, vp, vp, i64, i32, i32, C.c_double, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_boost_create.argtypes = [vp, i64, C.POINTER(vp)]
+    lib.icd_boost_destroy.argtypes = [vp]
+    lib.icd_boost_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_search_boosted.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_index_search_hybrid_grouped.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, C.c_double, vp, i32, i32, i32, i32,
                                                     vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_fusion_fuse_lists_grouped.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp, i32, C.c_double, vp, i32, i32, i32, i32,
@@ -354,6 +360,48 @@ def _mask_table(masks, count: int, what: str, per: str) -> np.ndarray:
             raise IcdError(-5, "a row mask is closed")
         vals[j] = m_._h.value
     return np.ascontiguousarray(vals[inverse.reshape(-1)]) if count else np.zeros(1, np.uint64)
+
+
+def _boost_tables(boosts, nq: int):
+    """[nq][MAX_BOOSTS] row-mask handles (uint64, 0: slot unused) and weights (float32) of a boosted search, from one list of
+    (IcdRowMask, weight) pairs - or None - per query"""
+    boosts = list(boosts)
+    if len(boosts) != nq:
+        raise ValueError(f"boosts holds {len(boosts)} entries for {nq} queries")
+    handles = np.zeros((max(nq, 1), MAX_BOOSTS), np.uint64)
+    weights = np.ones((max(nq, 1), MAX_BOOSTS), np.float32)
+    done = {}
+    for q, per in enumerate(boosts):
+        key = id(per)
+        if key in done:   # (the same list object on many queries: filled once)
+            handles[q], weights[q] = handles[done[key]], weights[done[key]]
+            continue
+        done[key] = q
+        per = [] if per is None else list(per)
+        if len(per) > MAX_BOOSTS:
+            raise ValueError(f"boosts[{q}] holds {len(per)} pairs: a query carries up to {MAX_BOOSTS}")
+        for j, pair in enumerate(per):
+            if pair is None:
+                continue
+            m_, w = pair
+            if not isinstance(m_, IcdRowMask):
+                raise TypeError("boosts: (IcdRowMask, weight) pairs")
+            if m_.closed:
+                raise IcdError(-5, "a row mask is closed")
+            handles[q, j] = m_._h.value
+            weights[q, j] = np.float32(w)
+    return handles, weights
+
+
+class BoostTable:
+    """The boosts of a batch in the form the C ABI takes, built once: search_boosted accepts it in place of the per-query lists,
+    which it would otherwise walk in Python on every call (a millisecond per thousand queries, in front of a launch of that
+    length). Keeps the masks alive."""
+
+    def __init__(self, boosts, nq: int):
+        self._keep = boosts
+        self.nq = int(nq)
+        self.handles, self.weights = _boost_tables(boosts, self.nq)
 
 
 class _Handle:
@@ -596,10 +644,17 @@ class IcdIndex:
         current stream, enqueued only; the call is not graph-capturable (the mask table is staged on the host at call time)."""
         return self._search_band(queries, k, radius, range_filter, after, reweighted, masks)
 
-    def _search_band(self, queries, k, radius, range_filter, after, reweighted, masks):
+    def _search_band(self, queries, k, radius, range_filter, after, reweighted, masks, boost=None):
         q, on_dev = self._prep_queries(queries)
         self._validate(q, k)
         nq = int(q.shape[0])
+        step = self.max_nq
+        if boost is not None:   # (workspace, boosts): the [nq][MAX_BOOSTS] tables of the call, kept alive over the calls below
+            step = min(step, boost[0].max_nq)
+            table = boost[1] if isinstance(boost[1], BoostTable) else BoostTable(boost[1], nq)   # (kept alive over the calls below)
+            if table.nq != nq:
+                raise ValueError(f"the boost table holds {table.nq} entries for {nq} queries")
+            boost_h, boost_w = table.handles, table.weights
         mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the calls below)
         a_sc, a_id = (None, None) if after is None else after
         if (a_sc is None) != (a_id is None):
@@ -614,12 +669,36 @@ class IcdIndex:
                 part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
                 tail = (ptr(qs), m, k, dev, *[None if b is None else ptr(b) for b in part], dev, 1 if reweighted else 0,
                         ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
-                if mask_h is None:
+                if boost is not None:
+                    _check(self._lib, self._lib.icd_index_search_boosted(
+                        self._h, boost[0]._h, None if mask_h is None else mask_h.ctypes.data + 8 * s0,
+                        boost_h.ctypes.data + 8 * MAX_BOOSTS * s0, boost_w.ctypes.data + 4 * MAX_BOOSTS * s0, *tail))
+                elif mask_h is None:
                     _check(self._lib, self._lib.icd_index_search_range(self._h, *tail))
                 else:
                     _check(self._lib, self._lib.icd_index_search_masked(self._h, mask_h.ctypes.data + 8 * s0, *tail))
             return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
-        return _chunked(q, self.max_nq, on_dev, call)
+        return _chunked(q, step, on_dev, call)
+
+    # -- boosted search (Milvus 2.6's boost ranker: rows inside a mask count `weight` times as much, before the top-k is chosen) --
+    def boost_workspace(self, max_nq: Optional[int] = None) -> "IcdBoost":
+        """The workspace of this index's boosted searches (icd_boost_create) for calls of up to max_nq queries (default: the index's)."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdBoost(self, int(max_nq if max_nq is not None else self.max_nq))
+
+    def search_boosted(self, queries, k: int, boosts, masks=None, *, workspace: "IcdBoost", reweighted: bool = True, radius=None,
+                       range_filter=None, after=None):
+        """search_masked over the BOOSTED ranking (icd_index_search_boosted): boosts holds, per query, a list of up to MAX_BOOSTS
+        (IcdRowMask, weight) pairs - None in a pair's place for an unused slot, None or [] for a query without boosts - or a
+        BoostTable made of such lists once, for a batch that is searched again and again; the score
+        of a row inside a pair's mask is multiplied by its weight (one fp32 multiply per pair, in list order) before anything is
+        selected. masks, radius, range_filter and after=(scores, ids) are search_masked's and act on the boosted score; the raw
+        output carries it. Weights are positive normal floats (IcdError -1 otherwise). Outputs as search_masked; with no pair at
+        all they are search_masked's bit for bit. Not graph-capturable."""
+        if self.closed or workspace is None or workspace.closed:
+            raise IcdError(-5, "index or boost workspace is closed")
+        return self._search_band(queries, k, radius, range_filter, after, reweighted, masks, (workspace, boosts))
 
     # -- MMR search (a diverse top-k: LangChain's max_marginal_relevance_search on the device) -------------
     def mmr(self, max_nq: Optional[int] = None) -> "IcdMmr":
@@ -1112,6 +1191,25 @@ class IcdMmr(_Handle):
             raise IcdError(-5, "mmr workspace is closed")
         t, b = C.c_int64(0), C.c_int64(0)
         _check(self._lib, self._lib.icd_mmr_stats(self._h, C.byref(t), C.byref(b)))
+        return {"max_nq": t.value, "bytes": b.value}
+
+
+class IcdBoost(_Handle):
+    """The workspace of one IcdIndex's boosted searches (icd_boost_*): the staging of a call's per-query boost table. The owning
+    index must outlive its use; close() (or garbage collection) frees it."""
+    _destroy = "icd_boost_destroy"
+
+    def __init__(self, index: "IcdIndex", max_nq: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        self.max_nq = int(max_nq)
+        _check(self._lib, self._lib.icd_boost_create(index._h, self.max_nq, C.byref(self._h)))
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "boost workspace is closed")
+        t, b = C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_boost_stats(self._h, C.byref(t), C.byref(b)))
         return {"max_nq": t.value, "bytes": b.value}
 
 

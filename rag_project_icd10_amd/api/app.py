@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /diverse_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -17,7 +17,7 @@ from contextlib import asynccontextmanager
 from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
-from .icd_models import (DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
+from .icd_models import (BoostedQueryRequest, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
                          HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
@@ -261,6 +261,51 @@ async def diverse_query(request: DiverseQueryRequest):
                                 original_score=float(h["original_score"]), similarity_factors={"mmr_score": float(h["mmr_score"])})
                       for h in hits]
         response = QueryResponse(candidates=candidates, is_multi_diagnosis=False, extracted_diagnoses=[request.text])
+        return QueryResponse(**convert_numpy_types(response.model_dump()))
+    except HTTPException:
+        raise
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+
+
+@app.post("/boosted_query", response_model=QueryResponse)
+async def boosted_query(request: BoostedQueryRequest):
+    """Every text's top_k hits over the boosted ranking (MilvusService.search_boosted_batch): the texts are
+    encoded like /query's, the score of every row a boost's filter selects is multiplied by its weight on the device BEFORE the
+    top-k is chosen, and `filter` drops rows as everywhere. The response has /diverse_query's hit shape - `score` the adjusted
+    score, `original_score` the boosted inner product: `candidates` are the first text's hits, `diagnosis_matches` holds one
+    entry per text. Bad arguments are a 400."""
+    try:
+        if not request.texts or len(request.texts) > 16 or any(not isinstance(t, str) or not t.strip() for t in request.texts):
+            raise ValueError("texts: 1 .. 16 non-empty strings")
+        if not 1 <= request.top_k <= 50:
+            raise ValueError(f"top_k={request.top_k}: 1 .. 50")
+        from ..services import boost_ranker, filter_expr
+        if len(request.boosts) > boost_ranker.MAX_BOOSTS:
+            raise ValueError(f"{len(request.boosts)} boosts: up to {boost_ranker.MAX_BOOSTS}")
+        rankers = [boost_ranker.BoostRanker(b.filter, b.weight) for b in request.boosts]
+        if request.filter is not None:
+            filter_expr.compile(request.filter)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    if not embedding_service or not milvus_service:
+        raise HTTPException(status_code=500, detail="查询失败: 服务未就绪")   # (as /query: the 503 surfaces as a 500)
+    try:
+        import numpy as np
+        vecs = np.stack([np.asarray(embedding_service.encode_query(t), dtype=np.float32).reshape(-1) for t in request.texts])
+        try:
+            lists = milvus_service.search_boosted_batch(vecs, request.top_k, rankers, as_dicts=True, filter=request.filter)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+        from .icd_models import Candidate
+        per_text = [[Candidate(code=h["code"], title=h["title"] or "", score=max(float(h["score"]), 0.0), enhanced_score=float(h["score"]),
+                               level=h["metadata"].get("level", 1), parent_code=h["metadata"].get("parent_code", ""),
+                               original_score=float(h["original_score"]))
+                     for h in hits] for hits in lists]
+        matches = [DiagnosisMatch(diagnosis_text=t, candidates=c, match_confidence=min(max(c[0].score, 0.0), 1.0) if c else 0.0)
+                   for t, c in zip(request.texts, per_text)]
+        response = QueryResponse(candidates=per_text[0], is_multi_diagnosis=len(request.texts) > 1, extracted_diagnoses=list(request.texts),
+                                 diagnosis_matches=matches)
         return QueryResponse(**convert_numpy_types(response.model_dump()))
     except HTTPException:
         raise

@@ -248,6 +248,22 @@ class DiverseQueryRequest(BaseModel):
     range_filter: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is at or below this are candidates")
 
 
+class BoostSpec(BaseModel):
+    """one boost of POST /boosted_query: Milvus 2.6's boost ranker parameters"""
+    filter: str = Field(..., description="Milvus filter expression: the rows whose score is multiplied")
+    weight: float = Field(..., description="the factor (a positive number): above 1 lifts the rows, below 1 demotes them")
+
+
+class BoostedQueryRequest(BaseModel):
+    """POST /boosted_query: the top_k hits of every text over the BOOSTED ranking (MilvusService.search_boosted_batch: the score
+    of a row a boost's filter selects is multiplied by its weight before the top-k is chosen). The ranges are checked by the route
+    (a 400 with the reason), not by the model."""
+    texts: List[str] = Field(..., description="diagnosis texts (1 .. 16): each is one query")
+    top_k: int = Field(default=5, description="hits returned per text (1 .. 50)")
+    boosts: List[BoostSpec] = Field(default_factory=list, description="up to 4 boosts, applied in order to every text")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression: only the rows it selects are ranked")
+
+
 class QueryResponse(BaseModel):
     model_config = ConfigDict(arbitrary_types_allowed=True)
     candidates: List[Candidate] = Field(..., description="候选结果列表")

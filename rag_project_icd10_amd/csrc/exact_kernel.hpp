@@ -42,6 +42,8 @@ struct ExactArgs {
     int *part_rows;        // [slot][P][KP]
     const BandQ *band;     // BAND = true only: [query] the band every hit of the query lies in (topk_select.hpp)
     RowMasks mask;         // MASK = true only: [query] the bitset of the rows that may be hits (topk_select.hpp)
+    const BoostQ *boost;   // BOOST = true only: [query] the boosts of the query (topk_select.hpp)
+    const uint32_t *boost_zeros;   // BOOST = true only: an all-zero bitset of the index's size, read in an unused slot's place
 };
 
 // chunk count of the adaptive layout (device: exact_topk_kernel; the same call in finalize.hpp)
@@ -83,7 +85,14 @@ __host__ __device__ inline int exact_adaptive_chunks(int nq_active, int bmq, int
 // behind the MFMA loop: nothing is held across it) and uses the 16 bits 4 h + (r & 3) + 8 (r >> 2) of word t. Masked-out
 // rows are -inf in front of the bootstrap like rows outside the band, so its count is a count of masked-in rows.
 // MASK = false compiles to what it compiled to before the parameter existed.
-template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false, bool MASK = false>
+// BOOST (with BAND and MASK): the query's boosts multiply the scores of the rows inside their masks, slot 0
+// first, IN FRONT of the band test and the mask overwrite - the band, the cursor, the bootstrap and the floor-seeded threshold
+// all see boosted scores and need no change. The lane keeps its query's four bitset pointers and weights (12 registers, loaded
+// once where the band is: the instantiations have the room); a slot no query of the wave uses is skipped
+// (wave-uniform), a lane whose query leaves a slot unused that another lane's uses reads the all-zero bitset. Per tile and used
+// slot: the tile's four words, one aligned 16-byte load behind the MFMA loop like the row mask's.
+// BOOST = false compiles to what it compiled to before the parameter existed.
+template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false, bool MASK = false, bool BOOST = false>
 __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
     constexpr int BMQ = NW * 32, BN = 128, LDT = BK + 1, NT = NW * 64;
     constexpr int CAP = CAPV, LIMIT = CAP - GROUP;
@@ -91,6 +100,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
     static_assert(CAP <= 64 * E && LIMIT >= KP && CAP % 2 == 0, "candidate buffer: KP kept + GROUP appended per check, E keys per lane");
     static_assert(BK == 16 || BK == 32, "stage depth");
     static_assert(BAND || !MASK, "a row mask rides on the band's overwrite");
+    static_assert((BAND && MASK) || !BOOST, "boosts are instantiated on top of the masked search only");
     constexpr int C4 = BK / 4;             // float4 per corpus row and stage
     constexpr int CL = (BN * C4) / NT;     // corpus float4 loads per thread per stage
     constexpr int QH = BK / 2;             // floats of a query a lane holds per stage = k-step pairs per stage
@@ -151,6 +161,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
     float band_hi = INFINITY;
     u64 band_below = ~0ull;
     const uint32_t *mask_words = nullptr;
+    [[maybe_unused]] const uint32_t *boost_words[BOOST_SLOTS];
+    [[maybe_unused]] float boost_w[BOOST_SLOTS];
+    [[maybe_unused]] uint32_t boost_used = 0u;   // bit j: a query of this wave uses slot j (wave-uniform)
     {
         const int sq = min(my_slot, nq - 1);
         const int gq = a.qlist ? a.qlist[sq] : sq;
@@ -165,6 +178,16 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
             if (my_valid && b.lo > st.thr) st.thr = b.lo;   // (thr_row stays 0: a row AT the floor is out)
         }
         if constexpr (MASK) mask_words = a.mask[gq];
+        if constexpr (BOOST) {
+            const BoostQ b = a.boost[gq];
+#pragma unroll
+            for (int j = 0; j < BOOST_SLOTS; ++j) {
+                const bool used = my_valid && b.m[j] != nullptr;
+                boost_words[j] = used ? b.m[j] : a.boost_zeros;
+                boost_w[j] = used ? b.w[j] : 1.0f;
+                if (__any(used)) boost_used |= 1u << j;
+            }
+        }
     }
     float bq[QH];   // the stage's k-step pairs of the query operand: bq[s] = (k = 2 s | 2 s + 1)
     auto q_pairs = [&](const float4 (&qreg)[Q4]) {
@@ -259,6 +282,22 @@ __global__ __launch_bounds__(NW * 64, OCC) void exact_topk_kernel(ExactArgs a) {
             if constexpr (MASK) {
                 const uint4 m4 = *reinterpret_cast<const uint4 *>(mask_words + (tile_row0 >> 5));   // (tile_row0 is a multiple of 128)
                 mw[0] = m4.x >> (4 * h); mw[1] = m4.y >> (4 * h); mw[2] = m4.z >> (4 * h); mw[3] = m4.w >> (4 * h);
+            }
+            if constexpr (BOOST) {
+#pragma unroll
+                for (int j = 0; j < BOOST_SLOTS; ++j) {
+                    if (!((boost_used >> j) & 1u)) continue;   // (wave-uniform)
+                    const uint4 b4 = *reinterpret_cast<const uint4 *>(boost_words[j] + (tile_row0 >> 5));
+                    const uint32_t bw[4] = {b4.x >> (4 * h), b4.y >> (4 * h), b4.z >> (4 * h), b4.w >> (4 * h)};
+                    const float w = boost_w[j];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const bool hit = ((bw[t] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0u;
+                            acc[t][r] = hit ? boost_mul(acc[t][r], w) : acc[t][r];
+                        }
+                }
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t)

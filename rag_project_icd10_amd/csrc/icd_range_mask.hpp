@@ -133,7 +133,7 @@ static int check_masks(const icd_index *idx, icd_rowmask *const *masks, int64_t 
 // that is being rewritten. (A view has no table: check_masks refused the call.)
 static int stage_masks(icd_index *x, icd_rowmask *const *masks, int nq, hipStream_t s) {
     if (x->mask_copy_pending) { HIP_TRY(hipEventSynchronize(x->ev_mask)); x->mask_copy_pending = false; }
-    for (int q = 0; q < nq; ++q) x->h_mask[q] = masks[q] ? masks[q]->bits : x->mask_ones;
+    for (int q = 0; q < nq; ++q) x->h_mask[q] = (masks && masks[q]) ? masks[q]->bits : x->mask_ones;   // (masks == nullptr: a boosted search without a table)
     const hipError_t ec = hipMemcpyAsync(x->mask_dev, x->h_mask, (size_t)nq * sizeof(uint32_t *), hipMemcpyHostToDevice, s);
     const hipError_t ee = hipEventRecord(x->ev_mask, s);   // (also behind a copy that failed to enqueue: whatever did get queued is covered)
     x->mask_copy_pending = ee == hipSuccess;
@@ -258,11 +258,12 @@ __global__ void rowmask_build_kernel(const long long *rows, long long n_rows, lo
 }  // extern "C"
 
 
-// The two banded entry points behind their own checks: masks = nullptr is the range search, `noun` names the caller in messages.
+// The banded entry points behind their own checks: masks = nullptr is the range search, `noun` names the caller in messages;
+// boost (icd_boost.hpp): the boosted search's table, its entries already checked.
 // (The checks that need neither the handle nor the device come first.)
 static int search_banded(icd_index *idx, icd_rowmask *const *masks, const char *noun, const float *queries, int64_t nq, int32_t k,
                          int32_t queries_on_device, const RangeBounds &rb, int32_t reweighted, double *out_adj, float *out_raw,
-                         int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream) {
+                         int64_t *out_ids, int32_t *out_levels, int32_t out_on_device, void *stream, const BoostRequest *boost = nullptr) {
     if (k < 1 || k > ICD_MAX_K) return fail(ICD_ERR_INVALID, "k=%d: a %s search returns 1 .. %d hits per query", k, noun, ICD_MAX_K);
     if ((rb.after_scores == nullptr) != (rb.after_ids == nullptr)) return fail(ICD_ERR_INVALID, "after_scores and after_ids: both or neither (a cursor is a hit's score AND id)");
     if (nq < 0) return fail(ICD_ERR_INVALID, "nq=%lld", (long long)nq);
@@ -270,7 +271,7 @@ static int search_banded(icd_index *idx, icd_rowmask *const *masks, const char *
     if (const int rc = check_bands(rb, nq, "query")) return rc;
     return run_search(idx, SearchRequest{queries, nq, k, queries_on_device != 0, out_on_device != 0, ICD_MODE_EXACT,
                                          outs_for(reweighted != 0, out_adj, out_raw, out_ids, out_levels), &rb, masks,
-                                         reinterpret_cast<hipStream_t>(stream)});
+                                         reinterpret_cast<hipStream_t>(stream), nullptr, boost});
 }
 
 extern "C" {

@@ -339,9 +339,9 @@ int pick_chunks(int mtiles, int row_tiles, int pmax, int slots) {
     return std::max(1, p);
 }
 
-template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false, bool MASK = false>
+template <int KP, int E, int NW, int CAPV = 64 * E, int BK = 32, int OCC = 1, int GROUP = 32, bool BAND = false, bool MASK = false, bool BOOST = false>
 int launch_exact(icd_index *x, const ExactArgs &a, int mtiles, hipStream_t s) {
-    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP, BAND, MASK>;
+    constexpr auto kern = exact_topk_kernel<KP, E, NW, CAPV, BK, OCC, GROUP, BAND, MASK, BOOST>;
     const size_t lds = exact_lds_bytes<KP, E, NW, CAPV, BK>();
     HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(mtiles * a.P), dim3(NW * 64), lds, s, a));
     return ICD_OK;
@@ -368,9 +368,10 @@ inline bool stream_fits(int kp, int qb, int dim) {
     return (size_t)qb * dim * 4 + (size_t)4 * 2 * ST_STAGE_BYTES + (size_t)4 * qb * 64 * e * 8 <= (size_t)LDS_LIMIT;
 }
 
-template <int KP, int E, int QB, bool BAND = false, bool MASK = false>
+template <int KP, int E, int QB, bool BAND = false, bool MASK = false, bool BOOST = false>
 int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq_ptr, int nq, int max_active,
-                  int p_out, int *p_used, hipStream_t s, const float *thr0 = nullptr, const BandQ *band = nullptr, RowMasks mask = nullptr) {
+                  int p_out, int *p_used, hipStream_t s, const float *thr0 = nullptr, const BandQ *band = nullptr, RowMasks mask = nullptr,
+                  const BoostQ *boost = nullptr) {
     const int n = (int)x->n;
     const int per_max = FIN_MAX_CAND / KP;                       // lists one reduce wave can merge
     const int p_cap = FIN_MAX_CAND / KP;                         // lists finalize<false> can merge
@@ -385,7 +386,7 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
     StreamArgs a{};
     a.corpus = x->corpus; a.queries = dq; a.qlist = qlist; a.nq_ptr = nq_ptr; a.nq = std::min(nq, max_active);
     a.max_active = max_active; a.n = n; a.dim = x->dim; a.rows_per_wg = rows_per_wg; a.nwg = nwg;
-    a.list_scores = x->lists_s; a.list_rows = x->lists_r; a.thr0 = thr0; a.band.q = band; a.mask = mask;
+    a.list_scores = x->lists_s; a.list_rows = x->lists_r; a.thr0 = thr0; a.band.q = band; a.mask = mask; a.boost = boost;
     // wave-private LDS ring: as many 8-KB stages per wave as fit next to the queries and candidate buffers
     int stages = 4;
     while (stages > 2 && stream_lds_bytes<KP, E, QB>(x->dim, stages) > (size_t)LDS_LIMIT) --stages;
@@ -395,7 +396,7 @@ int launch_stream(icd_index *x, const float *dq, const int *qlist, const int *nq
         const size_t cap = (l % 2 == 0) ? x->partx_cap + (size_t)128 * FIN_MAX_CAND_X : x->lists_cap;
         if ((size_t)a.nq * plan[l] * KP > cap) return fail(ICD_ERR_INVALID, "stream workspace too small for reduction level %d", l);
     }
-    constexpr auto kern = stream_topk_kernel<KP, E, QB, false, BAND, MASK>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, false, BAND, MASK, BOOST>;
     const size_t lds = stream_lds_bytes<KP, E, QB>(x->dim, stages);
     if (lds > (size_t)LDS_LIMIT) return fail(ICD_ERR_INVALID, "stream kernel: dim=%d does not fit LDS with %d queries per pass", x->dim, QB);
     HIP_TRY(launch_lds<kern>(x->device, (size_t)((int)lds), dim3(nwg), dim3(256), lds, s, a));
@@ -429,9 +430,9 @@ inline bool plan_stream_one(int n, int dim, int num_cu, int qb, int cap_entries,
     return p->nwg >= 1 && p->nwg <= 256 && p->stages >= 2;
 }
 
-template <int KP, int E, int QB, bool BAND = false, bool MASK = false>
+template <int KP, int E, int QB, bool BAND = false, bool MASK = false, bool BOOST = false>
 int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, hipStream_t s, const float *host_q = nullptr, bool poll_done = false,
-                      const BandArgs *band = nullptr, RowMasks mask = nullptr) {
+                      const BandArgs *band = nullptr, RowMasks mask = nullptr, const BoostQ *boost = nullptr) {
     StreamOnePlan pl;
     if (!plan_stream_one((int)x->n, x->dim, x->num_cu, QB, 64 * E, &pl)) return fail(ICD_ERR_INVALID, "single-launch stream kernel: no plan for n=%lld dim=%d", (long long)x->n, x->dim);
     if ((size_t)nq * pl.nwg * KP * 2 > x->lists_cap) return fail(ICD_ERR_INVALID, "stream workspace too small");
@@ -444,7 +445,7 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
     a.fin = f;
     a.fin.counters = x->nflag; a.fin.host_counters = x->h_nflag_dev;
     if (band) a.band = *band;
-    a.mask = mask;
+    a.mask = mask; a.boost = boost;
     if (poll_done) {
         a.done = reinterpret_cast<u64 *>(x->h_pin_dev + PIN_Q_BYTES + PIN_OUT_BYTES);
         a.done_value = ++x->done_seq;
@@ -453,10 +454,10 @@ int launch_stream_one(icd_index *x, const float *dq, int nq, const FinArgs &f, h
     // (at least 84 KB: ONE work-group per CU whatever the corpus size - the fence-free sc1 hand-off of the kernel's tail is the
     //  form measured for one work-group per CU, MI355X_MICROARCH.md visibility table)
     const size_t lds = std::max<size_t>(stream_one_lds_bytes<KP, E, QB>(x->dim, pl.stages, pl.rps), (size_t)84 * 1024);
-    constexpr auto kern = stream_topk_kernel<KP, E, QB, true, BAND, MASK>;
+    constexpr auto kern = stream_topk_kernel<KP, E, QB, true, BAND, MASK, BOOST>;
     if constexpr (QB == 1) {
         if (host_q) {   // the vector in the kernel arguments: no copy command in front of the launch
-            constexpr auto kern_in = stream_one_inline_kernel<KP, E, BAND, MASK>;
+            constexpr auto kern_in = stream_one_inline_kernel<KP, E, BAND, MASK, BOOST>;
             StreamInlineQuery iq;
             memcpy(iq.v, host_q, (size_t)x->dim * sizeof(float));
             a.queries = nullptr;
@@ -594,6 +595,12 @@ inline bool launch_coarse_variant(icd_index *, const SearchOverrides &, const Co
 #endif
 
 // ---- the search paths --------------------------------------------------------------------------------------------------------
+// The boost table of a boosted search as the kernels get it (icd_boost.hpp stages it): [query] -> BoostQ, and the all-zero bitset.
+struct BoostDev {
+    const BoostQ *q;
+    const uint32_t *zeros;
+};
+
 // What the four paths of a search share, computed once by search_device.
 struct SearchCtx {
     icd_index *x;
@@ -617,11 +624,13 @@ struct SearchCtx {
     bool stream_ok;      // small batches (the reference's one-query-per-call shape): stream the corpus once, exact, no coarse pass
     const BandArgs *band;   // range search: the queries' bands (nullptr: none, and no band kernel runs)
     RowMasks mask;          // masked search (with band): [query] -> bitset in device memory (nullptr: none, and no mask kernel runs)
+    const BoostDev *boost;  // boosted search (with band and mask): [query] -> boosts in device memory (nullptr: none, and no boost kernel runs)
 };
 
-SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s, const BandArgs *band, RowMasks mask) {
+SearchCtx make_search_ctx(icd_index *x, const float *dq, int nq, int k, bool use_fast, const Outs &o, hipStream_t s, const BandArgs *band, RowMasks mask,
+                          const BoostDev *boost) {
     SearchCtx c{};
-    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast; c.band = band; c.mask = mask;
+    c.x = x; c.dq = dq; c.nq = nq; c.k = k; c.s = s; c.use_fast = use_fast; c.band = band; c.mask = mask; c.boost = boost;
     c.ov = search_overrides();
     c.row_tiles = (int)((x->n + 127) / 128);
     FinArgs &f = c.f;
@@ -659,12 +668,19 @@ int run_stream(const SearchCtx &c, const int *qlist, const int *nq_ptr, int nqs,
     int qb = nq_ptr ? 8 : (nqs <= 1 ? 1 : (nqs <= 2 ? 2 : (nqs <= 4 ? 4 : 8)));
     const int max_act = nq_ptr ? c.sparse_max : std::max(c.sparse_max, nqs);   // (a direct call - up to ST_MAX_ACTIVE queries - is not gated)
     while (qb > 1 && !stream_fits(c.kpx, qb, x->dim)) qb >>= 1;
-#define ICD_ST_M(KPV, EV, BANDV, BQ, MASKV, MQ) \
-    (qb == 1 ? launch_stream<KPV, EV, 1, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ) : \
-     qb == 2 ? launch_stream<KPV, EV, 2, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ) : \
-     qb == 4 ? launch_stream<KPV, EV, 4, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ) : \
-               launch_stream<KPV, EV, 8, BANDV, MASKV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ))
+#define ICD_ST_B(KPV, EV, BANDV, BQ, MASKV, MQ, BOOSTV, OQ) \
+    (qb == 1 ? launch_stream<KPV, EV, 1, BANDV, MASKV, BOOSTV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ, OQ) : \
+     qb == 2 ? launch_stream<KPV, EV, 2, BANDV, MASKV, BOOSTV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ, OQ) : \
+     qb == 4 ? launch_stream<KPV, EV, 4, BANDV, MASKV, BOOSTV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ, OQ) : \
+               launch_stream<KPV, EV, 8, BANDV, MASKV, BOOSTV>(x, c.dq, qlist, nq_ptr, nqs, max_act, p_out, p_used, c.s, thr0, BQ, MQ, OQ))
+#define ICD_ST_M(KPV, EV, BANDV, BQ, MASKV, MQ) ICD_ST_B(KPV, EV, BANDV, BQ, MASKV, MQ, false, nullptr)
 #define ICD_ST(KPV, EV, BANDV, BQ) ICD_ST_M(KPV, EV, BANDV, BQ, false, nullptr)
+    if (c.band && c.mask && c.boost) {   // (boosted search: the masked instantiations with the boost multiply)
+        if (c.kpx == 16) return ICD_ST_B(16, 2, true, c.band->q, true, c.mask, true, c.boost->q);
+        if (c.kpx == 32) return ICD_ST_B(32, 2, true, c.band->q, true, c.mask, true, c.boost->q);
+        if (c.kpx == 64) return ICD_ST_B(64, 3, true, c.band->q, true, c.mask, true, c.boost->q);
+        return ICD_ST_B(128, 4, true, c.band->q, true, c.mask, true, c.boost->q);
+    }
     if (c.band && c.mask) {   // (masked search: the band instantiations with the row-mask term)
         if (c.kpx == 16) return ICD_ST_M(16, 2, true, c.band->q, true, c.mask);
         if (c.kpx == 32) return ICD_ST_M(32, 2, true, c.band->q, true, c.mask);
@@ -683,6 +699,7 @@ int run_stream(const SearchCtx &c, const int *qlist, const int *nq_ptr, int nqs,
     return ICD_ST(128, 4, false, nullptr);
 #undef ICD_ST
 #undef ICD_ST_M
+#undef ICD_ST_B
 }
 
 // A chunk count the exact kernel's list workspace holds for EVERY query of the batch (all of them may be flagged: all-zero
@@ -737,7 +754,14 @@ int run_exact(const SearchCtx &c, const int *qlist, const int *nq_ptr, int px, b
         // (LDS: k <= 16 two work-groups per CU - 17 KB of stage + 60-entry buffers; k <= 64 one of four waves - 34 KB +
         //  112-entry buffers; larger k two waves. Eight waves on 64-entry buffers at k <= 32 - two per SIMD - were built and
         //  are slower, 9.2 against 7.2 ms per 10 000 queries: a 64-entry buffer with 32 kept is compacted after every append)
-        if (c.band && c.mask) {   // (masked search: the band instantiations with the row-mask term)
+        if (c.band && c.mask && c.boost) {   // (boosted search: the masked instantiations with the boost multiply)
+            a.band = c.band->q; a.mask = c.mask; a.boost = c.boost->q; a.boost_zeros = c.boost->zeros;
+            if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2, 32, true, true, true>(x, a, c.mtx, s);
+            else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16, true, true, true>(x, a, c.mtx, s);
+            else if (kpx == 64) rc = launch_exact<64, 2, 4, 112, 32, 1, 32, true, true, true>(x, a, c.mtx, s);
+            else rc = launch_exact<128, 3, 2, 192, 32, 1, 32, true, true, true>(x, a, c.mtx, s);
+        }
+        else if (c.band && c.mask) {   // (masked search: the band instantiations with the row-mask term)
             a.band = c.band->q; a.mask = c.mask;
             if (kpx == 16) rc = launch_exact<16, 1, 4, 60, 16, 2, 32, true, true>(x, a, c.mtx, s);
             else if (kpx == 32) rc = launch_exact<32, 1, 4, 62, 16, 2, 16, true, true>(x, a, c.mtx, s);
@@ -817,6 +841,14 @@ int search_tiny(const SearchCtx &c) {
         if (c.band) {   // a page of a range search: still ONE launch (host-packed bands travel in the arguments)
             BandArgs b = *c.band;
             if (x->band_pending > 0) { b.q = nullptr; x->band_pending = 0; }
+            if (c.mask && c.boost) {   // (the boost table is in device memory already, like the pointer table: run_search copied both)
+                const int rco = qb1 == 1 ? launch_stream_one<16, 2, 1, true, true, true>(x, c.dq, 1, c.f, s, hq, poll, &b, c.mask, c.boost->q)
+                              : qb1 == 2 ? launch_stream_one<16, 2, 2, true, true, true>(x, c.dq, 2, c.f, s, nullptr, false, &b, c.mask, c.boost->q)
+                                         : launch_stream_one<16, 2, 4, true, true, true>(x, c.dq, (int)nq, c.f, s, nullptr, false, &b, c.mask, c.boost->q);
+                rec(x, 4, s);
+                rec(x, 5, s);
+                return rco;
+            }
             if (c.mask) {   // (the pointer table is in device memory already: run_search copied it)
                 const int rcm = qb1 == 1 ? launch_stream_one<16, 2, 1, true, true>(x, c.dq, 1, c.f, s, hq, poll, &b, c.mask)
                               : qb1 == 2 ? launch_stream_one<16, 2, 2, true, true>(x, c.dq, 2, c.f, s, nullptr, false, &b, c.mask)
@@ -1180,7 +1212,9 @@ int search_auto(const SearchCtx &c) {
 // band: a range search (icd_index_search_range; mode EXACT) - the streaming forms up to ST_MAX_ACTIVE queries, plain lists of
 // KP >= k on the MFMA kernel above; nullptr for every other caller, and no band kernel runs.
 // mask (with band): a masked search (icd_index_search_masked) - the same dispatch, the instantiations with the row-mask term.
-int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s, const BandArgs *band = nullptr, RowMasks mask = nullptr) {
+// boost (with band and mask): a boosted search (icd_index_search_boosted) - the same dispatch again, the instantiations with the multiply.
+int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const Outs &o, hipStream_t s, const BandArgs *band = nullptr, RowMasks mask = nullptr,
+                  const BoostDev *boost = nullptr) {
     const bool use_fast = !band && (mode == ICD_MODE_AUTO) && x->fast && k <= FAST_MAX_K && (x->dim == 768 || x->dim == 1024);
     x->prof_now = !x->capturing && x->profiling && (x->prof_tick++ % x->prof_every == 0);
     if (x->prof_now) {
@@ -1195,7 +1229,7 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
     x->last_p2 = 0;
     x->last_mode = use_fast ? ICD_MODE_AUTO : ICD_MODE_EXACT;
     rec(x, 0, s);
-    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s, band, mask);
+    const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s, band, mask, boost);
     // (k > 16 needs the 64-entry lists of the streaming kernel, ~0.9 ms per 16 queries: the coarse pass is faster there)
     if (c.stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE)) return search_tiny(c);
     { const int rcq = stage_host_query(c); if (rcq) return rcq; }
@@ -1511,12 +1545,13 @@ static bool stream_capturing(hipStream_t s) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
 }
-static int check_capture(hipStream_t s, bool host_buffers, bool host_bounds, bool mask_table, bool *capturing = nullptr) {
+static int check_capture(hipStream_t s, bool host_buffers, bool host_bounds, bool mask_table, bool *capturing = nullptr, bool boost_table = false) {
     const bool on = stream_capturing(s);
     if (capturing) *capturing = on;
     if (!on) return ICD_OK;
     if (host_buffers) return fail(ICD_ERR_INVALID, "a search with host buffers synchronises: it cannot be captured into a graph");
     if (host_bounds) return fail(ICD_ERR_INVALID, "a range search with host bounds synchronises: it cannot be captured into a graph");
+    if (boost_table) return fail(ICD_ERR_INVALID, "a boosted search stages its boost table on the host at call time: it cannot be captured into a graph");
     if (mask_table) return fail(ICD_ERR_INVALID, "a masked search stages its mask table on the host at call time: it cannot be captured into a graph");
     return ICD_OK;
 }
@@ -1549,6 +1584,7 @@ struct HostCall {
 };
 
 struct RangeBounds;
+struct BoostRequest;
 // ONE dense search as every entry point hands it to run_search, its own arguments already checked.
 struct SearchRequest {
     const float *queries;
@@ -1561,6 +1597,7 @@ struct SearchRequest {
     icd_rowmask *const *masks;      // nullptr: no mask table (never an all-NULL table: that is the range search)
     hipStream_t stream;
     const bool *capture_checked = nullptr;   // the stream's capture state when the caller has run check_capture for this very request (hybrid)
+    const BoostRequest *boost = nullptr;     // a boosted search (icd_boost.hpp; with a band, never an all-unused table: that is the masked search)
 };
 static int run_search(icd_index *x, const SearchRequest &r);
 
@@ -1577,6 +1614,8 @@ static Outs outs_for(bool reweighted, double *adj, float *raw, int64_t *ids, int
 
 // range and masked search: the bounds, the row masks, their two entry points
 #include "icd_range_mask.hpp"
+// boosted search: the workspace, the boost table and its staging, the entry point
+#include "icd_boost.hpp"
 
 extern "C" {
 
@@ -1660,8 +1699,10 @@ static int run_search(icd_index *x, const SearchRequest &r) {
     const bool host_bands = r.range && !r.range->on_device;
     int rc = ICD_OK;
     if (r.capture_checked) x->capturing = *r.capture_checked;
-    else if ((rc = check_capture(s, !r.q_on_device || !r.out_on_device, host_bands, r.masks != nullptr, &x->capturing))) return rc;
-    if (r.masks && (rc = stage_masks(x, r.masks, (int)nq, s))) return rc;
+    else if ((rc = check_capture(s, !r.q_on_device || !r.out_on_device, host_bands, r.masks != nullptr, &x->capturing, r.boost != nullptr))) return rc;
+    if ((r.masks || r.boost) && (rc = stage_masks(x, r.masks, (int)nq, s))) return rc;   // (a boosted search without a mask table: every query unfiltered)
+    BoostDev boost{};
+    if (r.boost && (rc = stage_boosts(*r.boost, (int)nq, s, &boost))) return rc;
     BandArgs band{};
     x->band_pending = 0;
     if (r.range && (rc = pack_bands(x, *r.range, (int)nq, s, &band))) return rc;
@@ -1695,7 +1736,7 @@ static int run_search(icd_index *x, const SearchRequest &r) {
     }
     x->done_armed = false;
     x->host_one_call = !r.q_on_device && nq == 1 && pinned_out && !x->capturing;
-    rc = search_device(x, dq, (int)nq, k, r.mode, dev, s, r.range ? &band : nullptr, r.masks ? x->mask_dev : nullptr);
+    rc = search_device(x, dq, (int)nq, k, r.mode, dev, s, r.range ? &band : nullptr, (r.masks || r.boost) ? x->mask_dev : nullptr, r.boost ? &boost : nullptr);
     x->band_pending = 0;
     x->host_q = nullptr;
     x->host_one_call = false;

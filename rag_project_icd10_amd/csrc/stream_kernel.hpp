@@ -73,6 +73,8 @@ struct StreamArgs {
     BandArgs band;
     // MASK = true only: [query index] the bitset of the rows that may be hits
     RowMasks mask;
+    // BOOST = true only: [query index] the boosts of the query
+    const BoostQ *boost;
 };
 
 // ONE query handed over IN the kernel arguments (a host caller's call: no H2D copy command in front of the launch). The
@@ -154,11 +156,19 @@ __device__ __forceinline__ void wait_vmcnt_uniform(int n) {
 // MASK (with BAND): the bitset pointers of a pass's queries are wave-uniform like the band; the 64 bits of
 // a step's rows are read per query at the head of the step (scalar loads: the vmcnt accounting of the LDS-DMA ring sees none
 // of them) and a row's bit is one more term of `pass`.
-template <int KP, int E, int QB, bool ONE, bool BAND = false, bool MASK = false>
+// BOOST (with BAND and MASK): a row's score is multiplied by the weights of the boosts whose masks hold it,
+// slot 0 first, in front of every test of the select - threshold, band, cursor and key all see the boosted score. The scalar
+// registers are full (the MASK instantiations already spill some into lanes), so the pass's up to QB x 4 (bitset pointer, weight)
+// pairs live one per LANE - lane 4 qi + j holds slot j of query qi, three registers - and a v_readlane makes the wave-uniform
+// value where it is needed; which pairs are in use is one scalar word. Per step the bits of the wave's 64 rows are read per used
+// pair as the row mask's are (scalar loads at the head of the step) and folded into ONE register per lane: bit 4 qi + j = this
+// lane's row is inside that mask. An unused slot costs nothing.
+template <int KP, int E, int QB, bool ONE, bool BAND = false, bool MASK = false, bool BOOST = false>
 __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const float *qsrc) {
     constexpr int CAP = 64 * E;
     static_assert(!ONE || (QB <= 4 && KP <= 16), "the single-launch form serves up to four queries at k <= 16");
     static_assert(BAND || !MASK, "a row mask rides on the band's test");
+    static_assert((BAND && MASK) || !BOOST, "boosts are instantiated on top of the masked search only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (the gate looks at the device's count itself: a.nq is already clamped to max_active by the host, and a list longer
     //  than that belongs to the MFMA kernel alone - round 3: the clamped count used to pass the gate and cost 24 sweeps)
@@ -235,6 +245,18 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
                                                                     (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)p));
             }
         }
+        [[maybe_unused]] u64 boost_ptr = 0ull;      // lane 4 qi + j: the bitset of slot j of query qi (0: unused) ...
+        [[maybe_unused]] float boost_wt = 1.0f;     // ... and its weight
+        [[maybe_unused]] uint32_t boost_used = 0u;  // bit 4 qi + j: that pair is in use (wave-uniform)
+        if constexpr (BOOST) {
+            if (lane < 4 * QB) {
+                const int slot = q0 + min(lane >> 2, nqp - 1);
+                const BoostQ *b = a.boost + (a.qlist ? a.qlist[slot] : slot);
+                boost_ptr = (u64)b->m[lane & 3];
+                boost_wt = b->w[lane & 3];
+            }
+            boost_used = (uint32_t)__ballot(boost_ptr != 0ull);
+        }
 
         // stage cursor of the DMA stream: (step, slice) -> ring slot; runs D - 1 stages ahead of the reader.
         // Past the last stage it re-reads the last step (valid memory, never consumed).
@@ -263,6 +285,17 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
             if constexpr (MASK) {
 #pragma unroll
                 for (int qi = 0; qi < QB; ++qi) mask_bits[qi] = rowmask_bits64(mask_words[qi], r0, mask_tile_words);
+            }
+            [[maybe_unused]] uint32_t boost_bits = 0u;   // bit 4 qi + j: this lane's row is inside slot j's mask of query qi
+            if constexpr (BOOST) {
+#pragma unroll
+                for (int i = 0; i < 4 * QB; ++i) {
+                    if (!((boost_used >> i) & 1u)) continue;   // (wave-uniform)
+                    const u64 p = ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(boost_ptr >> 32), i) << 32) |
+                                  (u64)(uint32_t)__builtin_amdgcn_readlane((int)boost_ptr, i);
+                    const u64 bits = rowmask_bits64(reinterpret_cast<const uint32_t *>(p), r0, mask_tile_words);
+                    boost_bits |= (uint32_t)((bits >> lane) & 1ull) << i;
+                }
             }
             for (int s = 0; s < nsl; ++s) {
                 // stage (t, s) has landed when at most D - 2 younger stages are outstanding
@@ -303,7 +336,15 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
             const bool rvalid = (int)row < row_end && (!ONE || lane < RPS);
 #pragma unroll
             for (int qi = 0; qi < QB; ++qi) {
-                const float v = acc[qi];
+                float v = acc[qi];
+                if constexpr (BOOST) {
+#pragma unroll
+                    for (int j = 0; j < BOOST_SLOTS; ++j) {
+                        if (!((boost_used >> (4 * qi + j)) & 1u)) continue;   // (wave-uniform)
+                        const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(boost_wt), 4 * qi + j));
+                        v = ((boost_bits >> (4 * qi + j)) & 1u) ? boost_mul(v, w) : v;
+                    }
+                }
                 bool pass = rvalid && (v > thr[qi] || (v == thr[qi] && row < thr_row[qi])) && v != -INFINITY;
                 if constexpr (BAND) pass = pass & band_under(v, row, band_hi[qi], band_below[qi]);
                 if constexpr (MASK) pass = pass & (((mask_bits[qi] >> lane) & 1ull) != 0ull);
@@ -534,14 +575,14 @@ __device__ __forceinline__ void stream_topk_body(const StreamArgs &a, const floa
     }
 }
 
-template <int KP, int E, int QB, bool ONE = false, bool BAND = false, bool MASK = false>
+template <int KP, int E, int QB, bool ONE = false, bool BAND = false, bool MASK = false, bool BOOST = false>
 __global__ __launch_bounds__(256) void stream_topk_kernel(StreamArgs a) {
-    stream_topk_body<KP, E, QB, ONE, BAND, MASK>(a, a.queries);
+    stream_topk_body<KP, E, QB, ONE, BAND, MASK, BOOST>(a, a.queries);
 }
 // the single-launch form of ONE query whose vector arrives in the kernel arguments (StreamInlineQuery)
-template <int KP, int E, bool BAND = false, bool MASK = false>
+template <int KP, int E, bool BAND = false, bool MASK = false, bool BOOST = false>
 __global__ __launch_bounds__(256) void stream_one_inline_kernel(StreamArgs a, StreamInlineQuery q) {
-    stream_topk_body<KP, E, 1, true, BAND, MASK>(a, q.v);
+    stream_topk_body<KP, E, 1, true, BAND, MASK, BOOST>(a, q.v);
 }
 
 // One wave per (slot, output list g): merge lists g, g + P_out, g + 2 P_out, ... of the slot's nlists

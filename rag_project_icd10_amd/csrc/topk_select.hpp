@@ -80,6 +80,21 @@ __device__ __forceinline__ u64 rowmask_bits64(const uint32_t *mask, int r0, int 
     return (lo >> sh) | ((hi << (31 - sh)) << 1);   // (two steps: sh = 0 shifts the third word out altogether)
 }
 
+// ---- boosts of one query (boosted search: DESIGN.md section 22) ---------------------------------------------------------------
+// Up to BOOST_SLOTS (row mask, weight) pairs: the score of a row inside mask j is multiplied by weight j, slot 0 first. A launch
+// gets [query index] -> BoostQ. An unused slot holds nullptr and 1.0f; the kernels never multiply for it.
+constexpr int BOOST_SLOTS = 4;
+struct BoostQ {
+    const uint32_t *m[BOOST_SLOTS];
+    float w[BOOST_SLOTS];
+};
+// ONE IEEE fp32 multiply, rounded once (the slot order is part of the contract: rounding does not commute). Nothing follows it
+// that it could be contracted with, and the pragma says so to the compiler.
+__device__ __forceinline__ float boost_mul(float s, float w) {
+#pragma clang fp contract(off)
+    return s * w;
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 template <typename T>

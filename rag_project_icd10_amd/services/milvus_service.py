@@ -31,7 +31,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..corpus_store import CorpusStore
-from . import filter_expr, hybrid_search as hybrid, range_search, sparse_text
+from . import boost_ranker, filter_expr, hybrid_search as hybrid, range_search, sparse_text
 
 logger = logging.getLogger(__name__)
 
@@ -109,6 +109,8 @@ class MilvusService:
         self._fusion = None
         # MMR search: (the index it belongs to, IcdMmr, store generation); one handle, regrown like the fusion, dropped with it
         self._mmr = None
+        # boosted search: (the index it belongs to, IcdBoost, store generation); one handle, regrown and dropped like the MMR's
+        self._boost = None
         # sparse search: (the index it belongs to, IcdSparse, SparseTextIndex, field, store generation); built lazily, one handle
         self._sparse = None
         # filter programs: (the index they belong to, IcdColumns, the filter_expr.Columns they were made from)
@@ -270,6 +272,7 @@ class MilvusService:
             self._dev_columns = None
             self._fusion = None
             self._mmr = None
+            self._boost = None
             self._sparse = None
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
@@ -1095,6 +1098,114 @@ class MilvusService:
             raise ValueError("query_vector: one vector")
         return self.search_mmr_batch(q.reshape(1, -1), top_k, fetch_k, lambda_mult, filter=filter, as_dicts=True, radius=radius,
                                      range_filter=range_filter, search_params=search_params)[0]
+
+    # ---- boosted search (Milvus 2.6's boost ranker) ----------------------------------------------------------
+    def _boost_for(self, index, nq: int):
+        """the cached IcdBoost of the store's index with room for `nq` queries (per store generation; regrown when short)"""
+        gen = self.client.generation
+        with self._views_lock:
+            hit = self._boost
+            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_nq >= nq:
+                return hit[1]
+            ws = index.boost_workspace(min(index.max_nq, max(int(nq), 64)))
+            self._boost = (index, ws, gen)
+        return ws
+
+    def _boosted_index(self, index, rankers, filter, nq: int):   # noqa: A002
+        """(the BoostedIndex of a batch, every mask it uses): the boost filters and the queries' own filters take ONE _masks_for
+        call - device filter programs, TEXT_MATCH masks and the mask cache; equal expressions share a mask. A boost filter that
+        selects every row still needs a mask (it rescales the whole ranking): the all-rows mask, made for this search."""
+        boost_exprs = [r.filter for per in rankers for r in per]
+        own = [] if filter is None else (list(filter) if isinstance(filter, (list, tuple)) else [filter] * nq)
+        exprs = boost_exprs + own
+        made = self._masks_for(index, exprs, len(exprs)) if exprs else []
+        every = None
+        pairs, at = [], 0
+        for per in rankers:
+            row = []
+            for r in per:
+                m_ = made[at]
+                at += 1
+                if m_ is None:
+                    if every is None:
+                        every = index.rowmask(np.arange(index.n, dtype=np.int64))
+                        every.transient = True
+                        made.append(every)
+                    m_ = every
+                row.append((m_, r.weight))
+            pairs.append(row)
+        masks = made[at:at + len(own)] if own else None
+        return boost_ranker.BoostedIndex(index, self._boost_for(index, nq), pairs, masks), made
+
+    def search_boosted_batch(self, query_vectors, top_k: int = 10, boosts=None, as_dicts: bool = False, filter=None,   # noqa: A002
+                             radius: Optional[float] = None, range_filter: Optional[float] = None, offset: int = 0,
+                             search_params: Optional[Dict[str, Any]] = None):
+        """Additive: `search_batch` over the BOOSTED ranking - Milvus 2.6's boost ranker. boosts: ONE list of up to 4
+        boost_ranker.BoostRanker (or {"filter", "weight"} dicts) for every query, or a list with one such list (or None) per
+        query. The score of a row a ranker's filter selects is multiplied by its weight, in list order, BEFORE the top-k is chosen,
+        exact over every row; `original_score` / the raw array carry the boosted score and the level reweight runs on it. filter:
+        one expression for the batch or one (or None) per query, as row masks; it drops rows where a boost only re-ranks them.
+        radius / range_filter / offset / search_params as in `search`, on the boosted score and ranking. Returns (adjusted f64,
+        raw f32, ids i64, levels i32), each [nq, top_k], or with as_dicts=True `search`-shaped hit lists. An empty or unloaded
+        collection answers [] per query. Bad arguments raise ValueError before anything is loaded."""
+        shape = np.shape(query_vectors)
+        if len(shape) not in (1, 2):
+            raise ValueError("query_vectors: [nq, dim] (or one vector)")
+        nq = 1 if len(shape) == 1 else int(shape[0])
+        rankers = boost_ranker.rankers_per_query(boosts, nq)
+        radius, range_filter, offset, _ = self._check_band(top_k, None, radius, range_filter, offset, search_params)
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= range_search.PAGE:
+            raise ValueError(f"top_k={top_k!r}: 1 .. {range_search.PAGE}")
+        self._check_filter_args(filter, "mask", None, nq)
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None:
+            return [[] for _ in range(nq)]
+        if shape[-1] != index.dim:
+            raise ValueError(f"query dim {shape[-1]} != index dim {index.dim}")
+        bi, made = self._boosted_index(index, rankers, filter, nq)
+        try:
+            adj, raw, ids, levels = range_search.search_band(bi, query_vectors, int(top_k), radius, range_filter, offset)
+            if hasattr(adj, "cpu"):
+                import torch
+                torch.cuda.synchronize(index.device)   # (transient masks are closed below: the search has to have run)
+        finally:
+            self._release_masks(made)
+        if not as_dicts:
+            return adj, raw, ids, levels
+        return self._hit_lists(adj, raw, ids)
+
+    def search_boosted(self, query_vector, top_k: int = 10, boosts=None, filter: Optional[str] = None,   # noqa: A002
+                       radius: Optional[float] = None, range_filter: Optional[float] = None, offset: int = 0,
+                       search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
+        """the boosted hit list of ONE query (search_boosted_batch): `search`'s dicts, `original_score` the boosted score"""
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_boosted_batch")
+        q = np.asarray(query_vector, dtype=np.float32)
+        if q.ndim != 1:
+            raise ValueError("query_vector: one vector")
+        if boosts is not None and any(b is None or isinstance(b, (list, tuple)) for b in (boosts if isinstance(boosts, (list, tuple)) else ())):
+            raise ValueError("boosts: one list of BoostRanker for the one query")
+        return self.search_boosted_batch(q.reshape(1, -1), top_k, boosts, as_dicts=True, filter=filter, radius=radius,
+                                         range_filter=range_filter, offset=offset, search_params=search_params)[0]
+
+    def search_boosted_iterator(self, query_vector, boosts=None, batch_size: int = 10, limit: int = -1, filter: Optional[str] = None,   # noqa: A002
+                                radius: Optional[float] = None, range_filter: Optional[float] = None,
+                                search_params: Optional[Dict[str, Any]] = None) -> "range_search.SearchIterator":
+        """`search_iterator` over the boosted ranking of one query: next() returns the following batch_size hits of it (inside the
+        band, on the filter's selection), pages disjoint and exact at any depth - the cursor is a boosted score and an id. The
+        iterator keeps its masks and the store generation it started on."""
+        radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("search_boosted_iterator takes one filter expression")
+        rankers = boost_ranker.rankers_per_query(boosts, 1)
+        self._check_filter_args(filter, "mask", None, 1)
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        range_search.SearchIterator(None if index is None else index, query_vector, batch_size, limit, radius, range_filter, None,
+                                    lambda: None).close()   # (its argument checks, before a mask is made)
+        bi = None if index is None else self._boosted_index(index, rankers, filter, 1)[0]
+        client = self.client
+        return range_search.SearchIterator(bi, query_vector, batch_size, limit, radius, range_filter, self._hits_to_dicts,
+                                           lambda: (id(self.client), None if client is None else (client.generation, client.count)))
 
     # ---- hybrid search (Milvus hybrid_search over dense requests; DESIGN.md section 13) ------------------------------------------
     def _fusion_for(self, index, total: int):
