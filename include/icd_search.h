@@ -710,6 +710,49 @@ int icd_index_search_boosted(icd_index *idx, icd_boost *ws, icd_rowmask *const *
                              int32_t *out_levels, int32_t out_on_device, void *stream);
 
 /*
+ * Search by stored rows: Milvus 2.6's search by primary key - the stored vector of an entity is the query - for "which rows are
+ * closest to this one?", a related-rows table (every row's neighbours) and a near-duplicate sweep. DESIGN.md section 23. Query q
+ * names a row of the index by its global id, ids[q] in [id_base, id_base + n).
+ *   answer            icd_index_search_masked's answer (masks[q], radius[q], range_filter[q], no cursor) for the row's stored
+ *                     fp32 values as the query vector, ranked over every row EXCEPT row ids[q] itself: the min(k, such rows in the
+ *                     mask and band) best by (score desc, id asc), then padding (score -inf, id -1, level 0). The raw form is
+ *                     icd_index_search_masked's list at k + 1 with the entry of id ids[q] removed and the gap closed, or, where
+ *                     that id is not in it (the row is outside its own mask or band, or holds a NaN), without its last entry.
+ *                     Bit-identical rows tie with the row itself and the smaller ids come first: the self hit is not always rank 0.
+ *   reweighted = 1    icd_index_search_reweighted's step on those k: out_adj = (double)raw * w[level], ONE stable descending
+ *                     re-sort. Where the row is outside its own mask or band this IS icd_index_search_masked at k.
+ *   include_self = 1  skips the removal: icd_index_search_masked at k, bit for bit.
+ *   k                 1 .. ICD_MAX_K - 1 (include_self = 1: ICD_MAX_K); the sub-search runs at k + 1, which the index's max_k bounds.
+ * The same id may appear any number of times in a batch. An index of one row yields padding.
+ *
+ * icd_byrows_create: the workspace of the searches by rows of `idx` for up to max_nq queries per call: the query block the rows
+ * are gathered into, the (k + 1)-wide lists, a host caller's ids and outputs. Nothing is allocated in a search. The handle keeps
+ * no pointer into its index: it is compared, never followed, and either may be destroyed first. It serves one stream at a time,
+ * like the index it belongs to. A view has no search by rows (ICD_ERR_UNSUPPORTED: mask the parent), nor has the row-sharded path.
+ *
+ * icd_index_search_by_rows: three steps on `stream`: byrows_gather_kernel (the rows -> the query block, on the device: no vector
+ * crosses the bus), icd_index_search_masked's request at k + 1 with device queries and device outputs (the same dispatch: up to
+ * four queries at k <= 16 one launch, up to 64 the streaming kernel, more the fp32-MFMA kernel), byrows_drop_self_kernel. ids:
+ * int64 [nq], host or (ids_on_device = 1) device; masks, radius, range_filter, bounds_on_device, outputs and synchronisation are
+ * icd_index_search_masked's, and so is the capture rule: with device ids, outputs and bounds and no masks the call only enqueues
+ * (graph-capturable), otherwise ICD_ERR_INVALID while `stream` is capturing. Device ids are not read on the host: one outside the
+ * index searches with a zero vector, never forms an address, and its outputs are padding; the other queries are not affected.
+ * Every check comes before the first device call. ICD_ERR_INVALID: a host id outside the index, k out of range (k = ICD_MAX_K with
+ * include_self = 0 among them) or k + 1 above the index's max_k, nq above the workspace's or the index's max_nq, a workspace or
+ * a mask of another index, and whatever icd_index_search_masked refuses. ICD_ERR_STATE: a destroyed index, workspace or mask.
+ * ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 does nothing. A refused call leaves outputs as they were.
+ */
+typedef struct icd_byrows icd_byrows;
+int icd_byrows_create(icd_index *idx, int64_t max_nq, icd_byrows **out);
+int icd_byrows_destroy(icd_byrows *ws);
+/* queries per call, device bytes held (either pointer may be NULL) */
+int icd_byrows_stats(icd_byrows *ws, int64_t *out_max_nq, int64_t *out_bytes);
+int icd_index_search_by_rows(icd_index *idx, icd_byrows *ws, icd_rowmask *const *masks, const int64_t *ids, int64_t nq, int32_t k,
+                             int32_t ids_on_device, int32_t include_self, const float *radius, const float *range_filter,
+                             int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                             int32_t *out_levels, int32_t out_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "icd_rowmask_select", "icd_rowmask_group_counts",
     "icd_mmr_create", "icd_mmr_destroy", "icd_mmr_stats", "icd_index_search_mmr",
     "icd_boost_create", "icd_boost_destroy", "icd_boost_stats", "icd_index_search_boosted",
+    "icd_byrows_create", "icd_byrows_destroy", "icd_byrows_stats", "icd_index_search_by_rows",
 )
 MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
 SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
@@ -164,6 +165,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_mmr_destroy.argtypes = [vp]
     lib.icd_mmr_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_mmr.argtypes = [vp, vp, vp, vp, i64, i32, i32, C.c_double, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_byrows_create.argtypes = [vp, i64, C.POINTER(vp)]
+    lib.icd_byrows_destroy.argtypes = [vp]
+    lib.icd_byrows_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_search_by_rows.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_boost_create.argtypes = [vp, i64, C.POINTER(vp)]
     lib.icd_boost_destroy.argtypes = [vp]
     lib.icd_boost_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -748,6 +753,58 @@ class IcdIndex:
         outs = _chunked(q, min(self.max_nq, mmr.max_nq), out_dev, call)
         return outs if reweighted else (None,) + tuple(outs)
 
+    # -- search by stored rows (Milvus's search by primary key: a stored row is the query) ----------------
+    def byrows(self, max_nq: Optional[int] = None) -> "IcdByRows":
+        """The workspace of this index's searches by rows (icd_byrows_create) for calls of up to max_nq ids (default: the index's)."""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return IcdByRows(self, int(max_nq if max_nq is not None else self.max_nq))
+
+    def search_by_rows(self, ids, k: int, *, workspace: "IcdByRows", masks=None, radius=None, range_filter=None, include_self: bool = False,
+                       reweighted: bool = True, on_device: bool = False):
+        """search_masked with, for query q, the stored fp32 row of global id ids[q] as the query vector, ranked over every row but
+        that row itself (icd_index_search_by_rows): the row is gathered on the device, the masked search runs at k + 1 and the
+        row's own hit is cut out there - no vector crosses the bus. ids: int64 [nq], a numpy array / sequence (checked: IcdError -1
+        for an id outside the index) or a torch CUDA tensor (not read on the host: an id outside the index yields padding); the
+        same id may repeat. 1 <= k <= 127 and k + 1 <= the index's max_k; include_self=True is search_masked at k, bit for bit
+        (k <= 128). masks, radius and range_filter as in search_masked. Returns (adj f64, raw f32, ids i64, levels i32), each
+        [nq, k], in search_reweighted's order, or (raw, ids, levels) in raw order with reweighted=False. Padding: -inf, id -1,
+        level 0. CUDA ids or on_device=True: device tensors out on torch's current stream. A batch longer than the workspace's
+        max_nq runs in chunks."""
+        if self.closed or workspace is None or workspace.closed:
+            raise IcdError(-5, "index or by-rows workspace is closed")
+        ids_dev = _is_torch_tensor(ids) and ids.is_cuda
+        if ids_dev:
+            import torch
+            rows = ids.to(dtype=torch.int64).contiguous().reshape(-1)
+        else:
+            if _is_torch_tensor(ids):
+                ids = ids.detach().cpu().numpy()
+            rows = np.ascontiguousarray(np.asarray(ids, np.int64).reshape(-1))
+        k = int(k)
+        top = min(MAX_K, self.max_k) - (0 if include_self else 1)
+        if not (1 <= k <= top):
+            raise ValueError(f"k={k}: need 1 <= k <= {top} (the search runs at k + 1 unless include_self)")
+        out_dev = bool(on_device) or ids_dev
+        nq = int(rows.shape[0])
+        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} ids", "id")   # (kept alive over the calls below)
+        bounds = [None if v is None else _bound(v, np.float32, (nq,), ids_dev, self.device) for v in (radius, range_filter)]
+
+        def call(rs, s0):
+            m = rs.shape[0]
+            (adj, raw, oid, lv), ptr, stream, dev = _outputs(out_dev, self.device, (m, k), (np.float64, np.float32, np.int64, np.int32))
+            if m:
+                if ids_dev and stream is None:
+                    stream = _current_stream_ptr(self.device)
+                part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
+                iptr = _dev_ptr if ids_dev else _host_ptr
+                _check(self._lib, self._lib.icd_index_search_by_rows(
+                    self._h, workspace._h, None if mask_h is None else mask_h.ctypes.data + 8 * s0, iptr(rs), m, k, 1 if ids_dev else 0,
+                    1 if include_self else 0, *[None if b is None else iptr(b) for b in part], 1 if ids_dev else 0,
+                    1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(oid), ptr(lv), dev, stream))
+            return (adj, raw, oid, lv) if reweighted else (raw, oid, lv)
+        return _chunked(rows, min(self.max_nq, workspace.max_nq), out_dev, call)
+
     # -- hybrid search (Milvus hybrid_search over dense requests) -----------------------------------------
     def fusion(self, max_total: int) -> "IcdFusion":
         """The workspace of this index's hybrid searches (icd_fusion_create) for calls of up to max_total = nq * R sub-lists."""
@@ -1191,6 +1248,26 @@ class IcdMmr(_Handle):
             raise IcdError(-5, "mmr workspace is closed")
         t, b = C.c_int64(0), C.c_int64(0)
         _check(self._lib, self._lib.icd_mmr_stats(self._h, C.byref(t), C.byref(b)))
+        return {"max_nq": t.value, "bytes": b.value}
+
+
+class IcdByRows(_Handle):
+    """The workspace of one IcdIndex's searches by rows (icd_byrows_*): the query block the rows are gathered into, the
+    (k + 1)-wide lists of max_nq queries and a host caller's ids and outputs. Independent of the index's lifetime: either may be
+    closed first (a search with a closed partner raises)."""
+    _destroy = "icd_byrows_destroy"
+
+    def __init__(self, index: "IcdIndex", max_nq: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        self.max_nq = int(max_nq)
+        _check(self._lib, self._lib.icd_byrows_create(index._h, self.max_nq, C.byref(self._h)))
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "by-rows workspace is closed")
+        t, b = C.c_int64(0), C.c_int64(0)
+        _check(self._lib, self._lib.icd_byrows_stats(self._h, C.byref(t), C.byref(b)))
         return {"max_nq": t.value, "bytes": b.value}
 
 

@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -13,12 +13,13 @@ from __future__ import annotations
 import logging
 import os
 from contextlib import asynccontextmanager
+from typing import Optional
 
 from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
 from .icd_models import (BoostedQueryRequest, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
-                         HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, convert_numpy_types)
+                         HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, SimilarCodesResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
 
@@ -346,6 +347,33 @@ async def codes_facets(request: FacetRequest):
     except Exception as exc:
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
     return FacetResponse(field=request.field, total=totals[0], facets=convert_numpy_types(lists[0]))
+
+
+@app.get("/codes/{code}/similar", response_model=SimilarCodesResponse)
+async def codes_similar(code: str, top_k: int = 10, filter: Optional[str] = None):   # noqa: A002
+    """The top_k codes closest to one stored code (MilvusService.similar_codes): the code's stored vector is
+    the query, on the device, and the code itself is left out. Hits have /diverse_query's shape - `score` the adjusted score,
+    `original_score` the raw inner product. An unknown code is a 404, bad arguments are a 400."""
+    if not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        if '"' in code or "\\" in code:
+            raise ValueError("code: no quotes or backslashes")
+        if not 1 <= top_k <= 50:
+            raise ValueError(f"top_k={top_k}: 1 .. 50")
+        hits = milvus_service.similar_codes(code, top_k, filter=filter or None)
+    except KeyError:
+        raise HTTPException(status_code=404, detail=f"no record with code {code}")
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    from .icd_models import Candidate
+    candidates = [Candidate(code=h["code"], title=h["title"] or "", score=max(float(h["score"]), 0.0), enhanced_score=float(h["score"]),
+                            level=h["metadata"].get("level", 1), parent_code=h["metadata"].get("parent_code", ""),
+                            original_score=float(h["original_score"]))
+                  for h in hits]
+    return SimilarCodesResponse(**convert_numpy_types(SimilarCodesResponse(code=code, candidates=candidates).model_dump()))
 
 
 @app.get("/codes/{code}")

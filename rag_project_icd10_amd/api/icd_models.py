@@ -316,3 +316,9 @@ class FacetResponse(BaseModel):
     field: str
     total: int = Field(..., description="rows the filter selects (every row carries exactly one value of the field)")
     facets: List[Dict[str, Any]] = Field(default_factory=list, description='{"value", "count"}: count descending, then value ascending')
+
+
+class SimilarCodesResponse(BaseModel):
+    """GET /codes/{code}/similar: the codes closest to one stored code (MilvusService.similar_codes); hits shaped like /query's"""
+    code: str
+    candidates: List[Candidate] = Field(default_factory=list, description="the top_k closest codes, the code itself left out: adjusted-score order")

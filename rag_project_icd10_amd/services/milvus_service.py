@@ -111,6 +111,9 @@ class MilvusService:
         self._mmr = None
         # boosted search: (the index it belongs to, IcdBoost, store generation); one handle, regrown and dropped like the MMR's
         self._boost = None
+        # search by stored ids: (the index it belongs to, IcdByRows, store generation); one handle, regrown and dropped like the MMR's
+        self._byrows = None
+        self._code_rows = None     # ((store, generation, rows), code -> first row): similar_codes' lookup, rebuilt when the store moves on
         # sparse search: (the index it belongs to, IcdSparse, SparseTextIndex, field, store generation); built lazily, one handle
         self._sparse = None
         # filter programs: (the index they belong to, IcdColumns, the filter_expr.Columns they were made from)
@@ -273,6 +276,7 @@ class MilvusService:
             self._fusion = None
             self._mmr = None
             self._boost = None
+            self._byrows = None
             self._sparse = None
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
@@ -1098,6 +1102,143 @@ class MilvusService:
             raise ValueError("query_vector: one vector")
         return self.search_mmr_batch(q.reshape(1, -1), top_k, fetch_k, lambda_mult, filter=filter, as_dicts=True, radius=radius,
                                      range_filter=range_filter, search_params=search_params)[0]
+
+    # ---- search by stored ids (Milvus 2.6's search by primary key) -------------------------------------------
+    BY_IDS_MAX_K = 127   # the search runs at top_k + 1: the row's own hit takes a slot of the 128
+
+    def _byrows_for(self, index, nq: int):
+        """the cached IcdByRows of the store's index with room for `nq` ids (per store generation; regrown when short)"""
+        gen = self.client.generation
+        with self._views_lock:
+            hit = self._byrows
+            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_nq >= nq:
+                return hit[1]
+            ws = index.byrows(min(index.max_nq, max(int(nq), 64)))
+            self._byrows = (index, ws, gen)
+        return ws
+
+    def _by_ids_args(self, top_k, include_self, radius, range_filter):
+        """(top_k, radius, range_filter) checked without a store: ValueError on a bad one"""
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)):
+            raise ValueError(f"top_k={top_k!r}: an int")
+        top = self.BY_IDS_MAX_K + (1 if include_self else 0)
+        if not 1 <= int(top_k) <= top:
+            raise ValueError(f"top_k={top_k}: 1 .. {top}")
+        radius, range_filter = range_search.check_bounds(radius, range_filter, None)
+        return int(top_k), radius, range_filter
+
+    @staticmethod
+    def _id_list(ids) -> np.ndarray:
+        if isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+            ids = [ids]
+        if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple, np.ndarray)):
+            raise ValueError("ids: an int or a list of ints")
+        arr = np.asarray(ids)
+        if arr.ndim != 1 or (arr.size and (arr.dtype == bool or not np.issubdtype(arr.dtype, np.integer))):
+            raise ValueError("ids: a flat list of ints")
+        return np.ascontiguousarray(arr, np.int64)
+
+    def _search_by_rows(self, index, rows, top_k, filter, nq, radius, range_filter, include_self):   # noqa: A002
+        """one library call (chunked by the workspace) with the filter's masks taken and released around it"""
+        masks = None if filter is None else self._masks_for(index, filter, nq)
+        try:
+            out = index.search_by_rows(rows, top_k, workspace=self._byrows_for(index, nq), masks=masks, radius=radius,
+                                       range_filter=range_filter, include_self=include_self, reweighted=True)
+            if masks is not None and hasattr(out[0], "cpu"):
+                import torch
+                torch.cuda.synchronize(index.device)   # (transient masks are closed below: the search has to have run)
+        finally:
+            self._release_masks(masks)
+        return out
+
+    def search_by_ids(self, ids, top_k: int = 10, filter=None, radius: Optional[float] = None,   # noqa: A002
+                      range_filter: Optional[float] = None, include_self: bool = False, as_dicts: bool = False):
+        """Additive: Milvus 2.6's search by primary key - for every id the top_k rows closest to THAT STORED ROW, the row itself
+        left out. The vectors never leave the device: the rows are gathered there, searched exactly at
+        top_k + 1 and the row's own hit - which is not always the first: bit-identical rows tie and the smaller id leads - is cut
+        out there. ids: an int or a list of row ids (the same id may repeat); an id the collection does not hold raises
+        ValueError. filter: one expression for the whole batch or a list with one entry (or None) per id, always as row masks of
+        the index itself; radius / range_filter as in `search`. include_self=True keeps the row's own hit (`search_batch` of the
+        stored vectors with filter_mode="mask"). top_k: 1 .. 127 (128 with include_self), within the store's max k. Returns
+        (adjusted f64, raw f32, ids i64, levels i32), each [len(ids), top_k], in the order `search` returns hits, padding id -1,
+        -inf, level 0; with as_dicts=True a list of `search`-shaped hit lists. An empty or unloaded collection answers [] per
+        id. Bad arguments raise ValueError."""
+        top_k, radius, range_filter = self._by_ids_args(top_k, include_self, radius, range_filter)
+        rows = self._id_list(ids)
+        nq = int(rows.size)
+        self._check_filter_args(filter, "mask", None, nq)   # (a bad expression raises before anything is loaded)
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None:
+            return [[] for _ in range(nq)]
+        bad = rows[(rows < 0) | (rows >= index.n)]
+        if bad.size:
+            raise ValueError(f"ids: {int(bad[0])} is no row of the collection (0 .. {index.n - 1})")
+        if top_k + (0 if include_self else 1) > index.max_k:
+            raise ValueError(f"top_k={top_k}: the search runs at {top_k + (0 if include_self else 1)}, above the store's max k {index.max_k}")
+        adj, raw, hit_ids, levels = self._search_by_rows(index, rows, top_k, filter, nq, radius, range_filter, include_self)
+        if not as_dicts:
+            return adj, raw, hit_ids, levels
+        return self._hit_lists(adj, raw, hit_ids)
+
+    def similar_codes(self, code: str, top_k: int = 10, filter: Optional[str] = None) -> List[Dict[str, Any]]:   # noqa: A002
+        """the top_k codes closest to the stored record of `code` (search_by_ids of its row; of several records with the code, the
+        first): `search`'s dicts, the record itself left out. KeyError when the collection holds no such code."""
+        if not isinstance(code, str) or not code or '"' in code or "\\" in code:
+            raise ValueError("code: a non-empty string without quotes or backslashes")
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("similar_codes takes one filter expression")
+        top_k, _, _ = self._by_ids_args(top_k, False, None, None)
+        self._check_filter_args(filter, "mask", None, 1)
+        row = self._row_of_code(code)
+        if row is None:
+            raise KeyError(code)
+        return self.search_by_ids([row], top_k, filter=filter, as_dicts=True)[0]
+
+    def _row_of_code(self, code: str) -> Optional[int]:
+        """the first row that carries `code`, from a dict built once per store generation (host only); None: no such code"""
+        if self.client is None or not self.client.exists():
+            return None
+        gen = (id(self.client), self.client.generation, self.client.count)
+        with self._views_lock:
+            if self._code_rows is None or self._code_rows[0] != gen:
+                table: Dict[str, int] = {}
+                for i, rec in enumerate(self.client.records):
+                    table.setdefault(rec.get("code"), i)
+                self._code_rows = (gen, table)
+            return self._code_rows[1].get(code)
+
+    def knn_graph(self, top_k: int = 10, filter: Optional[str] = None, reweighted: bool = True):   # noqa: A002
+        """Every row's top_k nearest other rows - a related-codes table, or the input of a near-duplicate sweep: (ids int64
+        [n, top_k], scores float64 [n, top_k]) on the host, row r of both for the row of id r, padding id -1 and -inf. The ids
+        are made on the device and walked in chunks of the workspace's max_nq; the host never holds a vector, only the two
+        results come back. filter: ONE expression - every row's neighbours are taken among the rows it selects (a row outside it
+        still gets neighbours). reweighted=True: `search`'s adjusted scores and order; False: the raw inner products, best
+        first. An empty or unloaded collection answers two [0, top_k] arrays."""
+        top_k, _, _ = self._by_ids_args(top_k, False, None, None)
+        if isinstance(filter, (list, tuple)):
+            raise ValueError("knn_graph takes one filter expression")
+        self._check_filter_args(filter, "mask", None, 1)
+        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        if index is None:
+            return np.zeros((0, top_k), np.int64), np.zeros((0, top_k), np.float64)
+        if top_k + 1 > index.max_k:
+            raise ValueError(f"top_k={top_k}: the search runs at {top_k + 1}, above the store's max k {index.max_k}")
+        import torch
+        n = int(index.n)
+        ws = self._byrows_for(index, min(n, index.max_nq))
+        step = min(ws.max_nq, index.max_nq)
+        out_ids, out_scores = np.empty((n, top_k), np.int64), np.empty((n, top_k), np.float64)
+        mask = None if filter is None else self._masks_for(index, filter, 1)[0]
+        try:
+            for r0 in range(0, n, step):
+                rows = torch.arange(r0, min(n, r0 + step), dtype=torch.int64, device=torch.device("cuda", index.device))
+                out = index.search_by_rows(rows, top_k, workspace=ws, masks=mask, reweighted=reweighted)
+                scores, hit_ids = (out[0], out[2]) if reweighted else (out[0], out[1])
+                out_ids[r0:r0 + len(rows)] = hit_ids.cpu().numpy()     # (the copy waits for the chunk: a mask is closed behind the loop)
+                out_scores[r0:r0 + len(rows)] = scores.cpu().numpy()
+        finally:
+            self._release_masks([mask])
+        return out_ids, out_scores
 
     # ---- boosted search (Milvus 2.6's boost ranker; DESIGN.md section 22) ----------------------------------------------------------
     def _boost_for(self, index, nq: int):
