@@ -195,6 +195,50 @@ int icd_index_search_grouped(icd_index *idx, icd_grouping *grouping, const float
                              int32_t queries_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
                              int32_t *out_levels, int32_t *out_groups, int32_t out_on_device, void *stream);
 
+/*
+ * Group scorers: Milvus's group scorer max / sum / avg of its grouping search. A group ranks by the sum, or
+ * the mean, of its group_size best rows instead of by its single best row - nearest-neighbour voting per group, exact over every
+ * row. The sum-ranked best groups are not among the max-ranked ones in general, so no step behind icd_index_search_grouped can
+ * answer this: every group of every query is reduced by its own top-group_size selection.
+ *
+ * For a query, a grouping, k, s = group_size and a scorer:
+ *   1. Scores, keys and "a NaN score is no hit" are icd_index_search_grouped's. A group's members rank by (score desc, row asc);
+ *      x_1 ... x_m are the scores of its m = min(s, hits in the group) best members, best first.
+ *   2. ICD_GROUP_SCORER_MAX: a = x_1. ICD_GROUP_SCORER_SUM: a = x_1, then a = a + x_i for i = 2 ... m IN THAT ORDER, each ONE IEEE
+ *      fp32 add (nothing contracted, nothing reassociated: the order is part of the contract, the worst-first sum differs in the
+ *      last bit for a third of all triples). ICD_GROUP_SCORER_AVG: the SUM value, then ONE IEEE fp32 divide by (float)m.
+ *   3. A group with no hit, or whose aggregate is NaN (+inf + -inf), is no hit. Every other aggregate ranks the way a row's score
+ *      does, +inf and -inf included: -inf is an ordinary lowest score, as a best row at -inf is in icd_index_search_grouped.
+ *   4. Groups rank by (aggregate desc, row of the group's best member asc). The answer is the min(k, groups that are hits) best
+ *      groups, of each its m best rows; layout, padding and the reweighted = 1 step are icd_index_search_grouped's. out_raw holds
+ *      the hit's own canonical score: the aggregate never replaces it and never enters the level reweight.
+ *   5. out_group_scores f32 [nq][k] (the aggregate; padding -inf) and out_group_ids i32 [nq][k] (the caller's group id; padding -1)
+ *      are in group-rank order in BOTH output modes (behind the reweight's re-sort the hits no longer say which group was first).
+ *      Either may be NULL.
+ *   6. MAX through this entry point is icd_index_search_grouped byte for byte (the same launches); SUM and AVG at s = 1 are MAX; one
+ *      group of all rows at s = m returns icd_index_search's rows at k = m; views and id_base as in icd_index_search_grouped.
+ *
+ * icd_grouping_prepare_scorers: once per grouping, outside any search and outside any stream capture (it allocates and copies
+ * synchronously, as icd_grouping_create does): builds the plan that cuts the grouping's positions into per-wave work along group
+ * boundaries, and a host caller's staging of the two group outputs. Idempotent. Its bytes are counted in icd_grouping_stats from
+ * then on. A search with scorer SUM or AVG, or with either group output, on a grouping that was never prepared is ICD_ERR_STATE;
+ * nothing is allocated in a search, so device-in / device-out scored searches stay graph-capturable.
+ *
+ * icd_index_search_grouped_scored: icd_index_search_grouped's arguments, checks and limits (k * group_size <= ICD_MAX_K), plus the
+ * scorer and the two group outputs. ICD_ERR_INVALID before any device call, with no output byte written: an unknown scorer, and
+ * whatever icd_index_search_grouped refuses (a grouping of another index among it). One scorer per call.
+ * Not offered: sparse grouped and hybrid grouped search with a scorer, the row-sharded path (icd_group_*), per-query scorers in
+ * one batch, k * group_size > 128, a sum weighted by rank.
+ */
+#define ICD_GROUP_SCORER_MAX 0
+#define ICD_GROUP_SCORER_SUM 1
+#define ICD_GROUP_SCORER_AVG 2
+int icd_grouping_prepare_scorers(icd_index *idx, icd_grouping *grouping);
+int icd_index_search_grouped_scored(icd_index *idx, icd_grouping *grouping, const float *queries, int64_t nq, int32_t k, int32_t group_size,
+                                    int32_t queries_on_device, int32_t reweighted, int32_t scorer, double *out_adj, float *out_raw,
+                                    int64_t *out_ids, int32_t *out_levels, int32_t *out_groups, float *out_group_scores,
+                                    int32_t *out_group_ids, int32_t out_on_device, void *stream);
+
 /* Raw top-k by inner product. out_scores float[nq][k], out_ids int64[nq][k]. */
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k,
                      int32_t queries_on_device, int32_t mode,

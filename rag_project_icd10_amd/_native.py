@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import sys
 from typing import Optional
 
 import numpy as np
@@ -48,7 +49,9 @@ EXPORTED_SYMBOLS = (
     "icd_mmr_create", "icd_mmr_destroy", "icd_mmr_stats", "icd_index_search_mmr",
     "icd_boost_create", "icd_boost_destroy", "icd_boost_stats", "icd_index_search_boosted",
     "icd_byrows_create", "icd_byrows_destroy", "icd_byrows_stats", "icd_index_search_by_rows",
+    "icd_grouping_prepare_scorers", "icd_index_search_grouped_scored",
 )
+GROUP_SCORERS = {"max": 0, "sum": 1, "avg": 2}   # include/icd_search.h ICD_GROUP_SCORER_*: what a group of a grouped search ranks by
 MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
 SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
 SELECT_SEGMENT_ROWS = 16384   # csrc/mask_select_plan.hpp MS_SEG_ROWS: rows of one work-group of the select's two passes
@@ -132,6 +135,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_grouping_destroy.argtypes = [vp]
     lib.icd_grouping_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_grouped.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_grouping_prepare_scorers.argtypes = [vp, vp]
+    lib.icd_index_search_grouped_scored.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_index_search_range.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_rowmask_create.argtypes = [vp, vp, i64, i32, C.POINTER(vp)]
     lib.icd_rowmask_destroy.argtypes = [vp]
@@ -598,11 +603,17 @@ class IcdIndex:
             raise IcdError(-5, "index is closed")
         return IcdGrouping(self, group_of, int(max_nq if max_nq is not None else self.max_nq))
 
-    def search_grouped(self, queries, k: int, group_size: int, grouping: "IcdGrouping", reweighted: bool = True):
+    def search_grouped(self, queries, k: int, group_size: int, grouping: "IcdGrouping", reweighted: bool = True, *, scorer: str = "max",
+                       group_scores: bool = False):
         """The k best groups of every query and the group_size best rows of each, exact (icd_index_search_grouped). Outputs are
         [nq, k * group_size]. reweighted=True: (adj f64, raw f32, ids i64, levels i32, groups i32) in search_reweighted's order
         (level weight, one stable re-sort of the query's hits); False: (raw, ids, levels, groups) group by group, best group
-        first. Padding: -inf, id -1, level 0, group -1. Device tensors in -> device tensors out on torch's current stream."""
+        first. Padding: -inf, id -1, level 0, group -1. Device tensors in -> device tensors out on torch's current stream.
+
+        scorer "max" | "sum" | "avg" (icd_index_search_grouped_scored): what a group ranks by - its best row, or the fp32 sum /
+        mean, best first, of its group_size best rows; the hits keep their own scores. group_scores=True appends two arrays
+        [nq, k] in group-rank order: that score (f32, padding -inf) and the group's id (i32, padding -1). The defaults are the
+        call above with its return tuple. The first scored call prepares the grouping (IcdGrouping.prepare_scorers)."""
         q, on_dev = self._prep_queries(queries)
         if self.closed or grouping is None or grouping.closed:
             raise IcdError(-5, "index or grouping is closed")
@@ -611,11 +622,24 @@ class IcdIndex:
         k, group_size = int(k), int(group_size)
         if k < 1 or group_size < 1 or k * group_size > MAX_K:
             raise ValueError(f"k={k}, group_size={group_size}: need k >= 1, group_size >= 1 and k * group_size <= {MAX_K}")
+        if scorer not in GROUP_SCORERS:
+            raise ValueError(f"scorer={scorer!r}: one of {sorted(GROUP_SCORERS)}")
+        scored = scorer != "max" or bool(group_scores)
+        if scored:
+            grouping.prepare_scorers(self)   # (behind every argument check of this layer: a refused call leaves the grouping as it was)
 
         def call(qs, s0):
             m = qs.shape[0]
             (adj, raw, ids, lv, grp), ptr, stream, dev = _outputs(on_dev, self.device, (m, k * group_size),
                                                                   (np.float64, np.float32, np.int64, np.int32, np.int32))
+            if scored:
+                (gsc, gid), _p, _s, _d = _outputs(on_dev, self.device, (m, k), (np.float32, np.int32))
+                if m:
+                    _check(self._lib, self._lib.icd_index_search_grouped_scored(
+                        self._h, grouping._h, ptr(qs), m, k, group_size, dev, 1 if reweighted else 0, GROUP_SCORERS[scorer],
+                        ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(grp),
+                        ptr(gsc) if group_scores else None, ptr(gid) if group_scores else None, dev, stream))
+                return ((adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp)) + ((gsc, gid) if group_scores else ())
             if m:
                 _check(self._lib, self._lib.icd_index_search_grouped(
                     self._h, grouping._h, ptr(qs), m, k, group_size, dev, 1 if reweighted else 0,
@@ -1180,6 +1204,7 @@ class IcdGrouping(_Handle):
         self.n, self.max_nq, self.device = n, int(max_nq), index.device
         _check(self._lib, self._lib.icd_grouping_create(index._h, ptr, n, on_dev, self.max_nq, C.byref(self._h)))
         self._paired = False
+        self._scorers = False
         self._group_of, self._group_ids = keep, None   # (kept until group_ids is first asked for)
         self.groups = int(self.stats()["groups"])
 
@@ -1204,6 +1229,21 @@ class IcdGrouping(_Handle):
             raise IcdError(-5, "index, grouping or sparse index is closed")
         _check(self._lib, self._lib.icd_grouping_pair_sparse(index._h, self._h, sp._h))
         self._paired = True
+
+    def prepare_scorers(self, index: "IcdIndex"):
+        """The one-time preparation for the group scorers (icd_grouping_prepare_scorers): the plan that cuts the grouping's rows
+        into per-wave work along group boundaries, counted in stats()["bytes"] from then on. search_grouped issues it at a
+        grouping's first scored call; later calls return at once. It allocates: refused while torch's current stream is being
+        captured into a graph - prepare first, then capture."""
+        if self._scorers:
+            return
+        if self.closed or index.closed:
+            raise IcdError(-5, "index or grouping is closed")
+        torch = sys.modules.get("torch")
+        if torch is not None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise IcdError(-1, "prepare_scorers allocates: it cannot run while a graph is being captured (prepare the grouping first)")
+        _check(self._lib, self._lib.icd_grouping_prepare_scorers(index._h, self._h))
+        self._scorers = True
 
     def stats(self) -> dict:
         if self.closed:

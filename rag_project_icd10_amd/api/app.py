@@ -120,6 +120,15 @@ async def query_similar(request: QueryRequest):
             filter_expr.check_grouping(request.group_by_field, request.top_k * 2, request.group_size)
         except ValueError as exc:
             raise HTTPException(status_code=400, detail=str(exc))
+    scorer = {}
+    if request.group_scorer is not None:
+        # (a name outside max / sum / avg, or one without group_by_field, is a 400 as well)
+        from ..services import filter_expr
+        try:
+            filter_expr.check_group_scorer(request.group_by_field, request.group_scorer)
+        except ValueError as exc:
+            raise HTTPException(status_code=400, detail=str(exc))
+        scorer = {"group_scorer": request.group_scorer}
     ranged = request.radius is not None or request.range_filter is not None
     if ranged:
         # (a bad band, or one next to grouping, is a 400 as well)
@@ -138,7 +147,7 @@ async def query_similar(request: QueryRequest):
                                                                       radius=radius, range_filter=range_filter, **mode)
         elif grouped:
             result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k, filter=request.filter,
-                                                                      group_by_field=request.group_by_field, group_size=request.group_size, **mode)
+                                                                      group_by_field=request.group_by_field, group_size=request.group_size, **mode, **scorer)
         elif request.filter is None:
             result = multi_diagnosis_service.match_multiple_diagnoses(text=request.text, top_k=request.top_k)
         else:

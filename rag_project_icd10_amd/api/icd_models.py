@@ -218,6 +218,7 @@ class QueryRequest(BaseModel):
     filter_mode: str = Field(default="view", description="how the filter is applied: 'view' (a cached view of the selected rows) or 'mask' (a row mask tested inside the scan: no second index)")
     group_by_field: Optional[str] = Field(default=None, description="Milvus grouping search: a scalar field, or 'category'; the search then ranks groups (2 * top_k * group_size <= 128)")
     group_size: int = Field(default=1, description="rows returned per group (with group_by_field)", ge=1, le=128)
+    group_scorer: Optional[str] = Field(default=None, description="Milvus group scorer (with group_by_field): 'max', 'sum' or 'avg' - a group ranks by its best row, or by the sum / mean of its group_size best rows")
     radius: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is ABOVE this are ranked")
     range_filter: Optional[float] = Field(default=None, description="Milvus range search: only rows whose inner product is at or below this are ranked (radius < range_filter)")
 

@@ -6,7 +6,8 @@
 //                           (exact_kernel.hpp: rows through LDS, queries from registers, v_mfma_f32_32x32x2_f32 = the d-ascending
 //                           fmaf chain) with a plain store epilogue. The rows are read THROUGH the grouping's `order`
 //                           (rows sorted by (group, row)), so a group's scores are one contiguous run of S.
-//   2. group_best_kernel    segmented maximum of the 64-bit key over those runs -> best[query][group]
+//   2. group_best_kernel    segmented maximum of the 64-bit key over those runs -> best[query][group] (the group scorers SUM /
+//                           AVG put group_aggregate_kernel.hpp's reduction here instead: DESIGN.md section 24)
 //   3. group_finish_kernel  one wave per query: the k best groups of best[query][.], of each its s best members (a second
 //                           pass over its run of S, only when s > 1), then emit_outputs (finalize.hpp): raw order, the level
 //                           reweight in double, the stable re-sort, row_map, with the group id travelling next to the level.
@@ -264,11 +265,15 @@ struct GroupFinishArgs {
     int nq, G, k, s;
     int q_base;           // first query of the block: the outputs are indexed by q_base + query
     FinArgs fin;          // k = k * s, levels, id_base, row_map, groups, the outputs (emit_outputs)
+    // GS instantiations only (the scored entry point), either may be null: the winning groups in rank order
+    float *out_group_scores;   // [query][k] the score the group ranked by; -inf in padding
+    int *out_group_ids;        // [query][k] the caller's id of the group; -1 in padding
 };
 
 constexpr int GROUP_FIN_WAVE_LDS = (256 + 128 + 128) * 8 + 128 * 8;   // select buffer | winning groups | hits | adjbuf
 
-template <int KP, int E>
+// GS = false is the kernel as it always was; GS = true also writes the winning groups' own scores and ids
+template <int KP, int E, bool GS = false>
 __global__ __launch_bounds__(256) void group_finish_kernel(GroupFinishArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[4 * GROUP_FIN_WAVE_LDS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -280,6 +285,13 @@ __global__ __launch_bounds__(256) void group_finish_kernel(GroupFinishArgs a) {
 
     const u64 *bq = a.best + (size_t)q * a.G;
     const int ng = min(a.k, wave_select<KP, E>([&](int i) { return bq[i]; }, a.G, buf, lane));
+    if constexpr (GS) {
+        const size_t o = (size_t)(a.q_base + q) * a.k;
+        for (int j = lane; j < a.k; j += 64) {
+            if (a.out_group_scores) a.out_group_scores[o + j] = j < ng ? key_score(buf[j]) : -INFINITY;
+            if (a.out_group_ids) a.out_group_ids[o + j] = j < ng ? a.fin.groups[key_row(buf[j])] : -1;
+        }
+    }
     const u64 *sorted = buf;
     int nres = ng;
     if (a.s > 1) {

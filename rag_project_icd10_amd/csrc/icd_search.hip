@@ -21,6 +21,7 @@
 #include "exact_kernel.hpp"
 #include "finalize.hpp"
 #include "group_topk.hpp"
+#include "group_aggregate_kernel.hpp"
 #include "hybrid_fuse.hpp"
 #include "sparse_kernel.hpp"
 #include "text_match_kernel.hpp"

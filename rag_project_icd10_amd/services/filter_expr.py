@@ -351,6 +351,20 @@ def check_grouping(field, top_k, group_size) -> None:
                          f"(top_k={top_k} groups of group_size={group_size})")
 
 
+GROUP_SCORERS = ("max", "sum", "avg")   # Milvus's group scorers: what a group of a grouping search ranks by
+
+
+def check_group_scorer(field, group_scorer) -> None:
+    """group_scorer of a call: None (not given: a group ranks by its best row, nothing new runs) or one of GROUP_SCORERS next to
+    group_by_field; anything else is a ValueError"""
+    if group_scorer is None:
+        return
+    if not isinstance(group_scorer, str) or group_scorer not in GROUP_SCORERS:
+        raise ValueError(f"group_scorer={group_scorer!r}: not one of {', '.join(GROUP_SCORERS)}")
+    if field is None:
+        raise ValueError("group_scorer needs group_by_field")
+
+
 class Columns:
     """The eight filter fields of a store's rows as column arrays, built once per generation of the store, with a bounded cache
     of selections keyed by the normalised expression. `generation` is the store's mutation counter when the columns were built."""

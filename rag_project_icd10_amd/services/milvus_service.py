@@ -311,12 +311,29 @@ class MilvusService:
                         "largest_group": int(st["largest_group"]), "bytes": int(st["bytes"])})
         return out
 
-    def _search_grouped(self, index, rows, filter, query_vectors, top_k: int, field: str, group_size: int):   # noqa: A002
-        """(adj, raw, ids, levels, group values' ids, values) of a grouped search on the store's index or a filter's view"""
+    _check_scorer = staticmethod(filter_expr.check_group_scorer)
+
+    def _search_grouped(self, index, rows, filter, query_vectors, top_k: int, field: str, group_size: int, group_scorer=None):   # noqa: A002
+        """(adj, raw, ids, levels, group values' ids, values) of a grouped search on the store's index or a filter's view; with a
+        group_scorer a seventh entry follows: (the winning groups' scores [nq, top_k], their ids)"""
         whole = filter is None or index is self._index
         grouping, values = self._grouping(field, index, rows, None if whole else filter_expr.compile(filter))
+        if group_scorer is not None:
+            adj, raw, ids, levels, groups, gsc, gid = index.search_grouped(query_vectors, int(top_k), int(group_size), grouping,
+                                                                            scorer=group_scorer, group_scores=True)
+            return adj, raw, ids, levels, groups, values, (gsc, gid)
         adj, raw, ids, levels, groups = index.search_grouped(query_vectors, int(top_k), int(group_size), grouping)
         return adj, raw, ids, levels, groups, values
+
+    @staticmethod
+    def _add_group_scores(hit_lists, field, values, gsc, gid):
+        """metadata["group_score"] of every hit of a scored grouped search: the score its group ranked by"""
+        host = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else t   # noqa: E731
+        for hits, sc, gi in zip(hit_lists, host(gsc), host(gid)):
+            by_value = {values[int(g)].item(): float(v) for v, g in zip(sc, gi) if g >= 0}
+            for hit in hits:
+                hit["metadata"]["group_score"] = by_value[hit["metadata"][field]]
+        return hit_lists
 
     def _filter_columns(self) -> "filter_expr.Columns":
         gen = self.client.generation
@@ -817,12 +834,15 @@ class MilvusService:
     def search(self, query_vector: np.ndarray, top_k: int = 10, filter: Optional[str] = None,   # noqa: A002 (Milvus's name)
                group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
                range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None,
-               filter_mode: str = "view") -> List[Dict[str, Any]]:
+               filter_mode: str = "view", group_scorer: Optional[str] = None) -> List[Dict[str, Any]]:
         """filter_mode: "view" (the default: the selection's cached view) or "mask" (the selection as a row mask of the index
         itself: no second index); the hits are the same. A bad value raises ValueError.
         group_by_field (one of filter_expr.GROUP_FIELDS) / group_size: Milvus's grouping search - the hits are the top_k best
         GROUPS' group_size best rows each (exact), re-sorted by adjusted score like any hit list; every hit's metadata then
         carries the group's value under the field's name. top_k * group_size <= 128. A bad grouping argument raises ValueError.
+        group_scorer ("max", "sum" or "avg", next to group_by_field; Milvus's group scorer): what a group
+        ranks by - its best row, or the sum / mean of its group_size best rows; every hit's metadata then also carries
+        "group_score", that value of its group. Not given (None): a group ranks by its best row and no key is added.
         radius / range_filter (also search_params={"params": {"radius": .., "range_filter": ..}}): Milvus's range search - only
         rows with radius < inner product <= range_filter are ranked (the band is on the RAW score, `original_score`). offset: the
         hits of ranks offset .. offset + top_k of that ranking (offset + top_k <= 16384), then re-sorted by adjusted score. Exact
@@ -831,6 +851,7 @@ class MilvusService:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
+        self._check_scorer(group_by_field, group_scorer)
         radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         if filter_mode not in self.FILTER_MODES:
             raise ValueError(f"filter_mode={filter_mode!r}: one of {self.FILTER_MODES}")
@@ -866,6 +887,11 @@ class MilvusService:
             #  an array's values arrive as float32 either way - converting through a Python list cost 35 us of a 130-us call)
             query_vector.tolist  # noqa: B018
             q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
+            if group_by_field is not None and group_scorer is not None:
+                adj, raw, ids, levels, groups, values, (gsc, gid) = self._search_grouped(index, rows, filter, q, top_k, group_by_field, group_size,
+                                                                                         group_scorer)
+                hits = self._hits_to_dicts(adj[0], raw[0], ids[0], (group_by_field, groups[0], values))
+                return self._add_group_scores([hits], group_by_field, values, gsc, gid)[0]
             if group_by_field is not None:
                 adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, q, top_k, group_by_field, group_size)
                 return self._hits_to_dicts(adj[0], raw[0], ids[0], (group_by_field, groups[0], values))
@@ -954,7 +980,7 @@ class MilvusService:
     def search_batch(self, query_vectors, top_k: int = 10, as_dicts: bool = False, filter: Optional[str] = None,   # noqa: A002
                      group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
                      range_filter: Optional[float] = None, offset: int = 0, search_params: Optional[Dict[str, Any]] = None,
-                     filter_mode: str = "view"):
+                     filter_mode: str = "view", group_scorer: Optional[str] = None):
         """Additive: many queries in one call. query_vectors: [nq, dim] numpy array or torch CUDA
         tensor. Returns (adjusted f64, raw f32, ids i64, levels i32), each [nq, top_k], in the order
         `search` returns hits; or, with as_dicts=True, a list of `search`-shaped hit lists.
@@ -967,12 +993,15 @@ class MilvusService:
         way, without a view; the default "view" is the cached view.
         group_by_field / group_size: as in `search`; the arrays are then [nq, top_k * group_size] and a fifth one follows, the
         hits' group ids (int32, -1 in padding: ranks of the field's sorted distinct values).
+        group_scorer: as in `search`; two more arrays [nq, top_k] then follow in group-rank order, the winning groups' scores
+        (float32, -inf in padding) and their ids (int32, -1 in padding); hit dicts carry metadata["group_score"].
         radius / range_filter / offset / search_params: as in `search`, the same band for every query of the batch; lists shorter
         than top_k are padded like a short filter selection's."""
         if group_by_field is not None:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
+        self._check_scorer(group_by_field, group_scorer)
         radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         nq = None
         if isinstance(filter, (list, tuple)) or filter_mode != "view":   # (only the mask path counts the queries: the default path takes whatever it took)
@@ -998,7 +1027,15 @@ class MilvusService:
                 empty = self._empty_hits(query_vectors, int(top_k) * int(group_size), as_dicts)
                 if group_by_field is None or as_dicts:
                     return empty
+                if group_scorer is not None:
+                    return empty + (empty[3] - 1, empty[1][:, :int(top_k)], (empty[3] - 1)[:, :int(top_k)])
                 return empty + (empty[3] - 1,)
+        if group_by_field is not None and group_scorer is not None:
+            adj, raw, ids, levels, groups, values, (gsc, gid) = self._search_grouped(index, rows, filter, query_vectors, top_k, group_by_field,
+                                                                                     group_size, group_scorer)
+            if not as_dicts:
+                return adj, raw, ids, levels, groups, gsc, gid
+            return self._add_group_scores(self._hit_lists(adj, raw, ids, (group_by_field, groups, values)), group_by_field, values, gsc, gid)
         if group_by_field is not None:
             adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, query_vectors, top_k, group_by_field, group_size)
             if not as_dicts:

@@ -56,7 +56,7 @@ class _gc_paused:
 CONFIDENCE_MODES = ("match", "multidimensional")
 
 
-def _search_options(filter, group_by_field, group_size, radius=None, range_filter=None, filter_mode="view") -> Dict[str, Any]:   # noqa: A002
+def _search_options(filter, group_by_field, group_size, radius=None, range_filter=None, filter_mode="view", group_scorer=None) -> Dict[str, Any]:   # noqa: A002
     """keyword arguments of MilvusService.search_batch for a request's filter / grouping / range: only the ones that were given"""
     opts: Dict[str, Any] = {}
     if filter_mode != "view":
@@ -69,6 +69,8 @@ def _search_options(filter, group_by_field, group_size, radius=None, range_filte
         opts["filter"] = filter
     if group_by_field is not None or group_size != 1:
         opts["group_by_field"], opts["group_size"] = group_by_field, group_size
+    if group_scorer is not None:
+        opts["group_scorer"] = group_scorer
     return opts
 
 
@@ -95,12 +97,18 @@ class MultiDiagnosisService:
 
     def match_multiple_diagnoses(self, text: str, top_k: int = 5, filter: Optional[str] = None,   # noqa: A002
                                  group_by_field: Optional[str] = None, group_size: int = 1, radius: Optional[float] = None,
-                                 range_filter: Optional[float] = None, filter_mode: str = "view") -> Dict[str, Any]:
-        """filter: a Milvus filter expression (services/filter_expr.py) - every diagnosis is searched among the rows it selects only
+                                 range_filter: Optional[float] = None, filter_mode: str = "view",
+                                 group_scorer: Optional[str] = None) -> Dict[str, Any]:
+        """group_scorer ("max", "sum", "avg", next to group_by_field): what a group of the grouped search ranks by
+        (MilvusService.search_batch); a value outside the three names, or one without group_by_field, is a ValueError.
+        filter: a Milvus filter expression (services/filter_expr.py) - every diagnosis is searched among the rows it selects only
         (the search of 2 top_k, on the device path and the host path alike); None ranks the whole corpus. filter_mode: "view" (the
         default) or "mask" - how MilvusService.search_batch applies it (a cached view, or a row mask of the index itself).
         radius / range_filter: Milvus's range search - only rows with radius < inner product <= range_filter are ranked
         (MilvusService.search_batch); a diagnosis with fewer than 2 top_k such rows is rescored on the shorter list."""
+        if group_scorer is not None:
+            from . import filter_expr
+            filter_expr.check_group_scorer(group_by_field, group_scorer)
         enhanced = self.text_processor.extract_diagnoses_enhanced(text)
         diagnoses = [d["text"] for d in enhanced]
         mode = self.text_processor.get_processing_mode()
@@ -117,6 +125,8 @@ class MultiDiagnosisService:
             grouped["range_filter"] = range_filter
         if filter_mode != "view":
             grouped["filter_mode"] = filter_mode
+        if group_scorer is not None:
+            grouped["group_scorer"] = group_scorer
         matches = None
         ner_job = vectors = None
         device = getattr(self.milvus_service, "supports_device_rescoring", lambda: False)()
@@ -154,7 +164,7 @@ class MultiDiagnosisService:
         if vectors is None:
             vectors = self._embed_diagnoses(diagnoses)
         try:
-            hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, **_search_options(filter, group_by_field, group_size, radius, range_filter, filter_mode))
+            hit_lists = self.milvus_service.search_batch(vectors, top_k * 2, as_dicts=True, **_search_options(filter, group_by_field, group_size, radius, range_filter, filter_mode, group_scorer))
         except Exception as exc:
             logger.error("batch search failed: %s", exc)
             hit_lists = [[] for _ in diagnoses]
@@ -226,7 +236,8 @@ class MultiDiagnosisService:
                               confidence_statistics: bool = False, entities=None, confidence: str = None,
                               filter: Optional[str] = None, group_by_field: Optional[str] = None,   # noqa: A002
                               group_size: int = 1, radius: Optional[float] = None,
-                              range_filter: Optional[float] = None, filter_mode: str = "view") -> List[DiagnosisMatch]:
+                              range_filter: Optional[float] = None, filter_mode: str = "view",
+                              group_scorer: Optional[str] = None) -> List[DiagnosisMatch]:
         """Additive (row N2): embed -> search(2 top_k) -> level reweight -> hierarchical rescoring for MANY diagnosis
         strings with everything between the tokenizer and the final top_k on the GPU: one encoder batch, one search_batch,
         one rescoring launch; only the top_k winners per string come back and become Candidate objects. Same results as
@@ -246,8 +257,12 @@ class MultiDiagnosisService:
         search (row masks), also with entities; filter_mode="mask" applies a single expression that way.
         group_by_field / group_size: Milvus's grouping search (MilvusService.search_batch): the search of 2 top_k then returns the
         group_size best rows of the 2 top_k best GROUPS, and the rescoring runs on those hits (2 top_k group_size <= 128).
+        group_scorer: what a group ranks by ("max", "sum", "avg"; MilvusService.search_batch); a bad value is a ValueError.
         radius / range_filter: Milvus's range search (MilvusService.search_batch): lists shorter than 2 top_k arrive padded, as a
         short filter selection's do."""
+        if group_scorer is not None:
+            from . import filter_expr
+            filter_expr.check_group_scorer(group_by_field, group_scorer)
         from .hierarchical_similarity_service import trusted_factors_row
         confidence = self.confidence if confidence is None else confidence
         if confidence not in CONFIDENCE_MODES:
@@ -262,7 +277,7 @@ class MultiDiagnosisService:
         hs = self.hierarchical_similarity
         if entities is None:
             qps = [hs.query_params(d) for d in diagnoses]   # ([1] is the context relevance the factors report)
-        adj, raw, ids = self.milvus_service.search_batch(vectors, top_k * 2, **_search_options(filter, group_by_field, group_size, radius, range_filter, filter_mode))[:3]
+        adj, raw, ids = self.milvus_service.search_batch(vectors, top_k * 2, **_search_options(filter, group_by_field, group_size, radius, range_filter, filter_mode, group_scorer))[:3]
         if entities is not None:
             if hasattr(entities, "result"):   # (the NER worker's Future: the classifier ran beside the embedding and the search)
                 entities = entities.result()
