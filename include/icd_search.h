@@ -239,6 +239,54 @@ int icd_index_search_grouped_scored(icd_index *idx, icd_grouping *grouping, cons
                                     int64_t *out_ids, int32_t *out_levels, int32_t *out_groups, float *out_group_scores,
                                     int32_t *out_group_ids, int32_t out_on_device, void *stream);
 
+/*
+ * Embedding-list search: Milvus's embedding lists under the MAX_SIM metric. A query is a LIST of vectors -
+ * the segments of one clinical text - and a group of rows scores the sum, over the list's vectors, of its best row's inner
+ * product: which category, parent code or code covers all segments best, and which row answers which segment. The group that is
+ * best in sum is in general not among any single vector's best groups, so no finished hit list can answer this: every row is
+ * scored for every vector and reduced per group (the two kernels of icd_index_search_grouped), then per list.
+ *
+ * A batch of nl lists: list_off is a HOST int64 array of nl + 1 entries, non-decreasing from 0; list L owns the vectors
+ * list_off[L] .. list_off[L + 1] (T_L of them) of queries[list_off[nl]][dim] (host, or device with queries_on_device = 1).
+ *   1. Scores, keys and "a NaN score is no hit" are icd_index_search_grouped's. For a vector t and a group g, b(t, g) is the key of
+ *      g's best row under t by (score desc, row asc), or none.
+ *   2. ICD_MAXSIM_SUM: over the vectors of L that have a hit in g, IN LIST ORDER, a = x_first, then a = a + x_t, each ONE IEEE fp32
+ *      add (nothing contracted, nothing reassociated: the order is part of the contract). ICD_MAXSIM_MEAN: that sum, then ONE IEEE
+ *      fp32 divide by (float)hits, the number of vectors that have a hit in g.
+ *   3. A group is no hit when no vector of L hits it or when its aggregate is NaN (+inf + -inf); +inf and -inf aggregates rank as
+ *      ordinary scores.
+ *   4. Groups rank by (aggregate desc, row of b(t1, g) asc), t1 the first vector of L that hits g. The answer is the
+ *      min(k, groups that are hits) best groups.
+ *   5. Outputs, host or (out_on_device = 1) device; any may be NULL except the first two:
+ *        out_group_scores f32 [nl][k]   the aggregate; padding -inf
+ *        out_group_ids    i32 [nl][k]   the caller's group id; padding -1
+ *        out_match_scores f32, out_match_ids i64, out_match_levels i32, each [list_off[nl]][k]: for vector t of list L, slot j
+ *        holds b(t, j-th group of L) - the canonical raw score, the id through row_map / id_base as everywhere, the level.
+ *        Padding -inf / -1 / 0, also where t has no hit in that group. No level reweight touches the aggregate.
+ *   6. Lists of one vector each give icd_index_search_grouped_scored(scorer MAX, group_size 1)'s group scores, group ids and hits
+ *      byte for byte; the list [v, v] gives the groups of [v] with aggregates x + x; MEAN at T = 1 is SUM; views and id_base as
+ *      in icd_index_search_grouped.
+ *   7. 1 <= T_L <= ICD_MAXSIM_MAX_T, 1 <= k <= ICD_MAX_K, nl <= max_lists and list_off[nl] <= max_vectors of the preparation.
+ *      A violation, an unknown scorer or a grouping of another index is ICD_ERR_INVALID before any device call, with no output
+ *      byte written; a grouping that was never prepared is ICD_ERR_STATE. nl = 0 does nothing.
+ *
+ * icd_grouping_prepare_maxsim: once per grouping, outside any search and outside any stream capture (it allocates): the block of
+ * the lists' aggregates and the staging of host callers for up to max_lists lists of max_vectors vectors in all. Idempotent: a
+ * repeated call within those sizes returns at once, a larger one is ICD_ERR_INVALID. Its bytes are counted in icd_grouping_stats.
+ * Nothing is allocated in a search (the list offsets travel in the launch arguments), so device-in / device-out calls are
+ * graph-capturable; with host buffers a capturing stream is ICD_ERR_INVALID.
+ * Not offered: per-list row masks (filter through a view, as for the grouping search), bands, per-vector weights, group_size > 1,
+ * sparse lists, the row-sharded path (icd_group_*).
+ */
+#define ICD_MAXSIM_SUM 1
+#define ICD_MAXSIM_MEAN 2
+#define ICD_MAXSIM_MAX_T 64
+int icd_grouping_prepare_maxsim(icd_index *idx, icd_grouping *grouping, int64_t max_lists, int64_t max_vectors);
+int icd_index_search_maxsim(icd_index *idx, icd_grouping *grouping, const float *queries, const int64_t *list_off, int64_t nl, int32_t k,
+                            int32_t scorer, int32_t queries_on_device, float *out_group_scores, int32_t *out_group_ids,
+                            float *out_match_scores, int64_t *out_match_ids, int32_t *out_match_levels, int32_t out_on_device,
+                            void *stream);
+
 /* Raw top-k by inner product. out_scores float[nq][k], out_ids int64[nq][k]. */
 int icd_index_search(icd_index *idx, const float *queries, int64_t nq, int32_t k,
                      int32_t queries_on_device, int32_t mode,

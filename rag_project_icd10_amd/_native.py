@@ -50,7 +50,10 @@ EXPORTED_SYMBOLS = (
     "icd_boost_create", "icd_boost_destroy", "icd_boost_stats", "icd_index_search_boosted",
     "icd_byrows_create", "icd_byrows_destroy", "icd_byrows_stats", "icd_index_search_by_rows",
     "icd_grouping_prepare_scorers", "icd_index_search_grouped_scored",
+    "icd_grouping_prepare_maxsim", "icd_index_search_maxsim",
 )
+MAXSIM_SCORERS = {"sum": 1, "mean": 2}   # include/icd_search.h ICD_MAXSIM_*: how an embedding list's per-vector maxima combine
+MAXSIM_MAX_T = 64                        # ICD_MAXSIM_MAX_T: vectors of one list
 GROUP_SCORERS = {"max": 0, "sum": 1, "avg": 2}   # include/icd_search.h ICD_GROUP_SCORER_*: what a group of a grouped search ranks by
 MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
 SELECT_MAX_LIMIT = 16384   # include/icd_search.h ICD_SELECT_MAX_LIMIT: rows per query of one select_rows call (Milvus's offset + limit window)
@@ -137,6 +140,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_index_search_grouped.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_grouping_prepare_scorers.argtypes = [vp, vp]
     lib.icd_index_search_grouped_scored.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_grouping_prepare_maxsim.argtypes = [vp, vp, i64, i64]
+    lib.icd_index_search_maxsim.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_index_search_range.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.icd_rowmask_create.argtypes = [vp, vp, i64, i32, C.POINTER(vp)]
     lib.icd_rowmask_destroy.argtypes = [vp]
@@ -282,6 +287,23 @@ def _chunked(q, step: int, on_dev: bool, call):
         import torch
         return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
     return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
+
+
+def check_list_offsets(list_off, vectors: int) -> np.ndarray:
+    """list_off of an embedding-list search as a contiguous int64 array: lists + 1 offsets from 0 to `vectors`, every list of
+    1 .. MAXSIM_MAX_T vectors; anything else is a ValueError"""
+    if _is_torch_tensor(list_off):
+        list_off = list_off.detach().cpu().numpy()
+    raw = np.asarray(list_off)
+    if raw.ndim != 1 or raw.size < 1 or raw.dtype.kind not in "iu":
+        raise ValueError("list_off: a one-dimensional integer array of lists + 1 offsets")
+    off = np.ascontiguousarray(raw, dtype=np.int64)
+    if off[0] != 0 or off[-1] != vectors:
+        raise ValueError(f"list_off runs from {int(off[0])} to {int(off[-1])}: need 0 to the number of vectors, {vectors}")
+    sizes = np.diff(off)
+    if sizes.size and (sizes.min() < 1 or sizes.max() > MAXSIM_MAX_T):
+        raise ValueError(f"list_off: every list holds 1 .. {MAXSIM_MAX_T} vectors (got {int(sizes.min())} .. {int(sizes.max())})")
+    return off
 
 
 def _bound(v, dtype, shape, on_dev: bool, device: int):
@@ -646,6 +668,55 @@ class IcdIndex:
                     ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(grp), dev, stream))
             return (adj, raw, ids, lv, grp) if reweighted else (raw, ids, lv, grp)
         return _chunked(q, grouping.max_nq, on_dev, call)
+
+    # -- embedding-list search (Milvus embedding lists, metric MAX_SIM) ---------------------------------
+    def search_lists(self, queries, list_off, k: int, grouping: "IcdGrouping", *, scorer: str = "sum", matches: bool = True):
+        """The k best groups of every LIST of query vectors, exact (icd_index_search_maxsim): list L owns the vectors
+        list_off[L] .. list_off[L + 1] of queries [vectors, dim] (1 .. 64 each; list_off a host array of lists + 1 offsets from
+        0), and a group scores the fp32 sum - scorer "mean": the mean over the vectors that hit it - in list order, of its best
+        row's inner product under every vector. Returns (group_scores f32 [lists, k], group_ids i32 [lists, k]) and, with
+        matches=True, (match_scores f32, match_ids i64, match_levels i32), each [vectors, k]: slot j of vector t is the best row
+        of its list's j-th group under t. Padding: -inf, group -1, id -1, level 0. Device tensors in -> device tensors out on
+        torch's current stream. The first call prepares the grouping for its max_nq (IcdGrouping.prepare_maxsim); a batch above
+        the preparation is split between lists into several calls."""
+        q, on_dev = self._prep_queries(queries)
+        if self.closed or grouping is None or grouping.closed:
+            raise IcdError(-5, "index or grouping is closed")
+        if q.ndim != 2 or q.shape[-1] != self.dim:
+            raise ValueError(f"queries of shape {tuple(q.shape)}: need [vectors, {self.dim}]")
+        off = check_list_offsets(list_off, q.shape[0])
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k={k} outside 1..{MAX_K}")
+        if scorer not in MAXSIM_SCORERS:
+            raise ValueError(f"scorer={scorer!r}: one of {sorted(MAXSIM_SCORERS)}")
+        if grouping.maxsim is None:   # (behind every argument check of this layer: a refused call leaves the grouping as it was)
+            grouping.prepare_maxsim(self, grouping.max_nq, max(grouping.max_nq, MAXSIM_MAX_T))
+        max_lists, max_vectors = grouping.maxsim
+        nl, nv = len(off) - 1, q.shape[0]
+        outs = []
+        l0 = 0
+        while l0 < nl:   # whole lists per call, within the preparation
+            l1 = min(nl, l0 + max_lists, int(np.searchsorted(off, off[l0] + max_vectors, side="right")) - 1)
+            v0, v1 = int(off[l0]), int(off[l1])
+            (gsc, gid), ptr, stream, dev = _outputs(on_dev, self.device, (l1 - l0, k), (np.float32, np.int32))
+            (msc, mid, mlv), _p, _s, _d = _outputs(on_dev, self.device, (v1 - v0, k) if matches else (0, k), (np.float32, np.int64, np.int32))
+            local = np.ascontiguousarray(off[l0:l1 + 1] - v0)
+            _check(self._lib, self._lib.icd_index_search_maxsim(
+                self._h, grouping._h, ptr(q[v0:v1]), local.ctypes.data, l1 - l0, k, MAXSIM_SCORERS[scorer], dev, ptr(gsc), ptr(gid),
+                ptr(msc) if matches else None, ptr(mid) if matches else None, ptr(mlv) if matches else None, dev, stream))
+            outs.append((gsc, gid, msc, mid, mlv) if matches else (gsc, gid))
+            l0 = l1
+        if len(outs) == 1:
+            return outs[0]
+        if not outs:
+            (gsc, gid), _p, _s, _d = _outputs(on_dev, self.device, (0, k), (np.float32, np.int32))
+            (msc, mid, mlv), _p, _s, _d = _outputs(on_dev, self.device, (0, k), (np.float32, np.int64, np.int32))
+            return (gsc, gid, msc, mid, mlv) if matches else (gsc, gid)
+        if on_dev:
+            import torch
+            return tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
+        return tuple(np.concatenate([o[i] for o in outs]) for i in range(len(outs[0])))
 
     # -- range search, offset, iterator pages (Milvus radius / range_filter, offset, search_iterator) ----
     def search_range(self, queries, k: int = 10, *, radius=None, range_filter=None, after=None, reweighted: bool = True):
@@ -1205,6 +1276,7 @@ class IcdGrouping(_Handle):
         _check(self._lib, self._lib.icd_grouping_create(index._h, ptr, n, on_dev, self.max_nq, C.byref(self._h)))
         self._paired = False
         self._scorers = False
+        self.maxsim = None   # (max_lists, max_vectors) once prepare_maxsim has run
         self._group_of, self._group_ids = keep, None   # (kept until group_ids is first asked for)
         self.groups = int(self.stats()["groups"])
 
@@ -1244,6 +1316,25 @@ class IcdGrouping(_Handle):
             raise IcdError(-1, "prepare_scorers allocates: it cannot run while a graph is being captured (prepare the grouping first)")
         _check(self._lib, self._lib.icd_grouping_prepare_scorers(index._h, self._h))
         self._scorers = True
+
+    def prepare_maxsim(self, index: "IcdIndex", max_lists: int, max_vectors: int):
+        """The one-time preparation for the embedding-list search (icd_grouping_prepare_maxsim): the block of the lists'
+        aggregates and a host caller's staging for calls of up to max_lists lists holding max_vectors vectors in all (at least 64:
+        one full list), counted in stats()["bytes"] from then on. search_lists issues it at a grouping's first call with the
+        grouping's max_nq for both; a repeated call within the prepared sizes returns at once. It allocates: refused while
+        torch's current stream is being captured into a graph - prepare first, then capture."""
+        max_lists, max_vectors = int(max_lists), int(max_vectors)
+        if max_lists < 1 or max_vectors < max(max_lists, MAXSIM_MAX_T):
+            raise ValueError(f"max_lists={max_lists}, max_vectors={max_vectors}: need max_lists >= 1 and max_vectors >= max(max_lists, {MAXSIM_MAX_T})")
+        if self.maxsim is not None and max_lists <= self.maxsim[0] and max_vectors <= self.maxsim[1]:
+            return
+        if self.closed or index.closed:
+            raise IcdError(-5, "index or grouping is closed")
+        torch = sys.modules.get("torch")
+        if torch is not None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise IcdError(-1, "prepare_maxsim allocates: it cannot run while a graph is being captured (prepare the grouping first)")
+        _check(self._lib, self._lib.icd_grouping_prepare_maxsim(index._h, self._h, max_lists, max_vectors))
+        self.maxsim = (max_lists, max_vectors)
 
     def stats(self) -> dict:
         if self.closed:

@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -19,7 +19,8 @@ from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
 from .icd_models import (BoostedQueryRequest, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
-                         HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, SimilarCodesResponse, convert_numpy_types)
+                         HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, SegmentsQueryRequest, SegmentsQueryResponse,
+                         SimilarCodesResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
 
@@ -321,6 +322,26 @@ async def boosted_query(request: BoostedQueryRequest):
         raise
     except Exception as exc:
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+
+
+@app.post("/segments_query", response_model=SegmentsQueryResponse)
+async def segments_query(request: SegmentsQueryRequest):
+    """The segments of one text as an embedding list under MAX_SIM (MilvusService.search_embedding_list): the
+    top_k groups - values of group_by_field, or single codes - whose best rows cover all segments best in sum, and per group the
+    row that answers each segment. Bad arguments are a 400."""
+    if not embedding_service or not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        if not 1 <= len(request.segments) <= milvus_service.LIST_MAX_VECTORS:
+            raise ValueError(f"segments: {len(request.segments)} texts, need 1 .. {milvus_service.LIST_MAX_VECTORS}")
+        import numpy as np
+        vecs = np.asarray(embedding_service.encode_query_batch(list(request.segments)), dtype=np.float32)
+        groups = milvus_service.search_embedding_list(vecs, request.top_k, request.group_by_field, request.filter or None, request.scorer)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    return SegmentsQueryResponse(**convert_numpy_types({"segments": len(request.segments), "groups": groups}))
 
 
 @app.post("/codes/query", response_model=ScalarQueryResponse)

@@ -323,3 +323,24 @@ class SimilarCodesResponse(BaseModel):
     """GET /codes/{code}/similar: the codes closest to one stored code (MilvusService.similar_codes); hits shaped like /query's"""
     code: str
     candidates: List[Candidate] = Field(default_factory=list, description="the top_k closest codes, the code itself left out: adjusted-score order")
+
+
+class SegmentsQueryRequest(BaseModel):
+    """POST /segments_query: the segments of ONE text as an embedding list (MilvusService.search_embedding_list; DESIGN.md section
+    25). The ranges are checked by the route (a 400 with the reason), not by the model."""
+    segments: List[str] = Field(..., description="1 .. 64 texts, one vector each: the segments of a clinical text")
+    top_k: int = Field(default=10, description="groups returned (1 .. 128)")
+    group_by_field: Optional[str] = Field(default=None, description="the field whose values are ranked (level, parent_code, category, ...); not given: every code by itself")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields: only those rows take part")
+    scorer: str = Field(default="sum", description="'sum' or 'mean' of the segments' best inner products in the group")
+
+
+class SegmentGroup(BaseModel):
+    group: Any = Field(..., description="the group's value of group_by_field; without one the code")
+    score: float = Field(..., description="the sum (mean) over the segments of the group's best row's inner product")
+    matches: List[Optional[Dict[str, Any]]] = Field(default_factory=list, description="per segment the group's best row (a hit with 'segment' = its index), or null")
+
+
+class SegmentsQueryResponse(BaseModel):
+    segments: int = Field(..., description="segments searched")
+    groups: List[SegmentGroup] = Field(default_factory=list, description="the top_k groups that cover the segments best, best first")

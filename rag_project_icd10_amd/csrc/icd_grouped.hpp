@@ -24,6 +24,13 @@ struct icd_grouping : OwnedHandle {
     int npacks = 0, nlong = 0;
     GaPack *packs = nullptr; int *long_groups = nullptr;
     float *o_gscore = nullptr; int *o_gid = nullptr;
+    // the embedding-list search (icd_grouping_prepare_maxsim; icd_maxsim.hpp), absent before: the lists' aggregates
+    // [min(ms_lists, qb)][G], and a host caller's vectors [ms_vectors][dim], group outputs [ms_lists][ICD_MAX_K] and match outputs
+    // [ms_vectors][ICD_MAX_K]
+    int64_t ms_lists = 0, ms_vectors = 0;
+    u64 *ms_agg = nullptr; float *ms_q = nullptr;
+    float *ms_gscore = nullptr; int *ms_gid = nullptr;
+    float *ms_mscore = nullptr; long long *ms_mid = nullptr; int *ms_mlv = nullptr;
     std::mutex mu;
 };
 
@@ -58,23 +65,38 @@ static int grouped_aggregate_pass(icd_grouping *g, int nb, int group_size, int s
     return ICD_OK;
 }
 
+// Step 1 for nb <= g->qb query vectors at dq: their scores of all rows -> g->S
+static int grouped_scores_pass(icd_index *idx, icd_grouping *g, const float *dq, int nb, hipStream_t s) {
+    GroupScoreArgs sa{};
+    sa.corpus = idx->corpus; sa.queries = dq; sa.order = g->order;
+    sa.nq = nb; sa.n = (int)g->at.n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
+    sa.S = g->S; sa.ldS = g->ldS;
+    hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)((int)(g->ldS / GROUP_TILE) * sa.mtiles)), dim3(256), 0, s, sa);
+    HIP_TRY(hipGetLastError());
+    return ICD_OK;
+}
+
+// Step 2 for the scorer MAX: g->best zeroed, then group_best_kernel over g->S
+static int grouped_best_pass(icd_grouping *g, int nb, hipStream_t s) {
+    const int n = (int)g->at.n;
+    HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
+    GroupBestArgs ba{};
+    ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
+    ba.nq = nb; ba.n = n; ba.G = g->G; ba.best = g->best;
+    ba.R = nb >= 64 ? 1024 : 128;
+    ba.nranges = (n + ba.R - 1) / ba.R;
+    constexpr int QW = 4;
+    const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
+    hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
+    HIP_TRY(hipGetLastError());
+    return ICD_OK;
+}
+
 static int grouped_reduce_pass(icd_index *idx, icd_grouping *g, int nb, int64_t q0, int k, int group_size, bool reweighted, const GroupedOuts &o,
                                hipStream_t s, int scorer = ICD_GROUP_SCORER_MAX) {
-    const int n = (int)g->at.n;
     if (scorer != ICD_GROUP_SCORER_MAX) {
         if (const int rc = grouped_aggregate_pass(g, nb, group_size, scorer, s)) return rc;
-    } else {
-        HIP_TRY(hipMemsetAsync(g->best, 0, (size_t)nb * g->G * sizeof(u64), s));
-        GroupBestArgs ba{};
-        ba.S = g->S; ba.ldS = g->ldS; ba.order = g->order; ba.gpos = g->gpos; ba.seg = g->seg;
-        ba.nq = nb; ba.n = n; ba.G = g->G; ba.best = g->best;
-        ba.R = nb >= 64 ? 1024 : 128;
-        ba.nranges = (n + ba.R - 1) / ba.R;
-        constexpr int QW = 4;
-        const long long waves = (long long)((nb + QW - 1) / QW) * ba.nranges;
-        hipLaunchKernelGGL(group_best_kernel<QW>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, ba);
-        HIP_TRY(hipGetLastError());
-    }
+    } else if (const int rc = grouped_best_pass(g, nb, s)) return rc;
 
     GroupFinishArgs fa{};
     fa.best = g->best; fa.S = g->S; fa.ldS = g->ldS; fa.order = g->order; fa.seg = g->seg; fa.dense_of = g->dense_of;
@@ -103,16 +125,9 @@ static int grouped_reduce_pass(icd_index *idx, icd_grouping *g, int nb, int64_t 
 // and the reduction. The hybrid grouped search runs it on the fusion's staged vectors. The caller holds the grouping's lock.
 static int grouped_search_device(icd_index *idx, icd_grouping *g, const float *dq, int64_t nq, int k, int group_size, bool reweighted,
                                  const GroupedOuts &o, hipStream_t s, int scorer = ICD_GROUP_SCORER_MAX) {
-    const int n = (int)g->at.n;
-    const int ntiles = (int)(g->ldS / GROUP_TILE);
     for (int64_t q0 = 0; q0 < nq; q0 += g->qb) {
         const int nb = (int)std::min<int64_t>(g->qb, nq - q0);
-        GroupScoreArgs sa{};
-        sa.corpus = idx->corpus; sa.queries = dq + (size_t)q0 * idx->dim; sa.order = g->order;
-        sa.nq = nb; sa.n = n; sa.dim = idx->dim; sa.mtiles = (nb + GROUP_TILE - 1) / GROUP_TILE;
-        sa.S = g->S; sa.ldS = g->ldS;
-        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)(ntiles * sa.mtiles)), dim3(256), 0, s, sa);
-        HIP_TRY(hipGetLastError());
+        if (const int rc = grouped_scores_pass(idx, g, dq + (size_t)q0 * idx->dim, nb, s)) return rc;
         if (const int rc = grouped_reduce_pass(idx, g, nb, q0, k, group_size, reweighted, o, s, scorer)) return rc;
     }
     return ICD_OK;

@@ -22,6 +22,7 @@
 #include "finalize.hpp"
 #include "group_topk.hpp"
 #include "group_aggregate_kernel.hpp"
+#include "maxsim_kernel.hpp"
 #include "hybrid_fuse.hpp"
 #include "sparse_kernel.hpp"
 #include "text_match_kernel.hpp"
@@ -1971,6 +1972,7 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
 // the other entry families, each its own file in this translation unit (launch_lds's per-kernel state and the kernel templates exist once)
 #include "icd_utility.hpp"   // the stateless utility entry points
 #include "icd_grouped.hpp"   // the grouping search
+#include "icd_maxsim.hpp"    // the embedding-list search: MAX_SIM over a list of vectors per query
 #include "icd_hybrid.hpp"    // the hybrid search, the fuse of caller-provided lists
 #include "icd_sparse.hpp"    // the sparse-vector search
 #include "icd_text_match.hpp" // keyword match filters: row masks from the sparse index's postings

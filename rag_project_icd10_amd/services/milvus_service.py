@@ -335,6 +335,101 @@ class MilvusService:
                 hit["metadata"]["group_score"] = by_value[hit["metadata"][field]]
         return hit_lists
 
+    # ---- embedding-list search (Milvus embedding lists, metric MAX_SIM) -----------------------------------
+    LIST_SCORERS = ("sum", "mean")
+    LIST_MAX_VECTORS = 64   # include/icd_search.h ICD_MAXSIM_MAX_T
+
+    @staticmethod
+    def _check_list_args(lists, top_k, group_by_field, filter, scorer):   # noqa: A002
+        """the checks of an embedding-list search that need no store and no device; returns the lists as float32 [T, dim] arrays"""
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= filter_expr.MAX_GROUPED_HITS:
+            raise ValueError(f"top_k={top_k!r}: must be an integer in 1 .. {filter_expr.MAX_GROUPED_HITS}")
+        if group_by_field is not None:
+            filter_expr.check_grouping(group_by_field, top_k, 1)
+        if not isinstance(scorer, str) or scorer not in MilvusService.LIST_SCORERS:
+            raise ValueError(f"scorer={scorer!r}: not one of {', '.join(MilvusService.LIST_SCORERS)}")
+        if filter is not None:
+            if not isinstance(filter, str):
+                raise ValueError("filter: one expression for all lists (a filter goes through a view)")
+            filter_expr.compile(filter)
+        out = []
+        for i, vectors in enumerate(lists):
+            v = np.asarray(vectors, dtype=np.float32)
+            if v.ndim != 2 or not 1 <= v.shape[0] <= MilvusService.LIST_MAX_VECTORS:
+                raise ValueError(f"list {i} of shape {v.shape}: need [1 .. {MilvusService.LIST_MAX_VECTORS} vectors, dim]")
+            if out and v.shape[1] != out[0].shape[1]:
+                raise ValueError(f"list {i} has dim {v.shape[1]}, list 0 dim {out[0].shape[1]}")
+            out.append(v)
+        return out
+
+    def _list_grouping(self, field, index, rows, filter_key):
+        """(IcdGrouping, values) for an embedding-list search: _grouping's for a field; for None every row is its own group, whose
+        id is the row's id in the store (values None). Cached and dropped where the groupings are."""
+        if field is not None:
+            return self._grouping(field, index, rows, filter_key)
+        ck = (None, self.client.generation, filter_key)
+        with self._views_lock:
+            hit = self._groupings.get(ck)
+            if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
+                self._groupings.move_to_end(ck)
+                return hit[1], None
+            grouping = index.grouping(np.arange(index.n, dtype=np.int32) if filter_key is None else np.asarray(rows, np.int32),
+                                      max_nq=min(index.max_nq, 2048))
+            self._groupings[ck] = (index, grouping)
+            while len(self._groupings) > self._max_groupings:
+                self._groupings.popitem(last=False)
+        return grouping, None
+
+    def search_embedding_lists_batch(self, lists, top_k: int = 10, group_by_field: Optional[str] = None,
+                                     filter: Optional[str] = None, scorer: str = "sum") -> List[List[Dict[str, Any]]]:   # noqa: A002
+        """Milvus's embedding-list search under MAX_SIM, exact: every entry of `lists` is ONE query of 1 .. 64 vectors [T, dim] -
+        the segments of a text - and a group of rows scores the sum (scorer "mean": the mean over the vectors that hit it) over
+        the list's vectors of its best row's inner product. group_by_field: one of filter_expr.GROUP_FIELDS, or None - every row
+        its own group: codes ranked by their summed similarity to all segments. filter: one expression for all lists (its view).
+        Per list the top_k best groups, best first: {"group": the group's value (None: the row's code), "score": the aggregate,
+        "matches": per vector of the list the group's best row under it - the usual hit dict with "segment" = the vector's
+        index - or None where the vector has no hit in the group}. A bad argument raises ValueError."""
+        vecs = self._check_list_args(lists, top_k, group_by_field, filter, scorer)
+        if not vecs:
+            return []
+        if self.client is None or not self.client.exists():
+            logger.error("集合 %s 不存在", self.collection_name)
+            return [[] for _ in vecs]
+        rows = None
+        if filter is not None:
+            index, rows = self._filtered_index(filter)
+        else:
+            index = self._ready_index()
+        if index is None:
+            return [[] for _ in vecs]
+        whole = filter is None or index is self._index
+        grouping, values = self._list_grouping(group_by_field, index, rows, None if whole else filter_expr.compile(filter))
+        list_off = np.concatenate([[0], np.cumsum([len(v) for v in vecs])]).astype(np.int64)
+        gsc, gid, msc, mid, mlv = index.search_lists(np.concatenate(vecs), list_off, int(top_k), grouping, scorer=scorer)
+        recs = self.client.records
+        out = []
+        for li in range(len(vecs)):
+            v0, v1 = int(list_off[li]), int(list_off[li + 1])
+            groups = []
+            for j in range(int(top_k)):
+                g = int(gid[li, j])
+                if g < 0:
+                    break
+                adj = [float(np.float64(msc[t, j]) * self._calculate_level_weight(int(mlv[t, j]))) for t in range(v0, v1)]
+                matches = []
+                for t in range(v0, v1):
+                    hit = self._hits_to_dicts(adj[t - v0:t - v0 + 1], msc[t, j:j + 1], mid[t, j:j + 1])
+                    matches.append(dict(hit[0], segment=t - v0) if hit else None)
+                groups.append({"group": recs[g].get("code") if values is None else values[g].item(), "score": float(gsc[li, j]),
+                               "matches": matches})
+            out.append(groups)
+        return out
+
+    def search_embedding_list(self, vectors, top_k: int = 10, group_by_field: Optional[str] = None, filter: Optional[str] = None,   # noqa: A002
+                              scorer: str = "sum") -> List[Dict[str, Any]]:
+        """search_embedding_lists_batch for ONE list of vectors [T, dim]"""
+        return self.search_embedding_lists_batch([vectors], top_k, group_by_field, filter, scorer)[0]
+
     def _filter_columns(self) -> "filter_expr.Columns":
         gen = self.client.generation
         cols = self._columns
