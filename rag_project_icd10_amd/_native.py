@@ -331,6 +331,25 @@ def _bound(v, dtype, shape, on_dev: bool, device: int):
     return t.contiguous().reshape(-1) if on_dev else np.ascontiguousarray(t).reshape(-1)
 
 
+class _Bands:
+    """The mask table and the bounds of ONE banded call, held over its chunks. The table is made first (a bad mask is the call's first
+    error), the bounds by `bound`; at(s0, m, ptr) -> (the mask-table pointer of the chunk of m queries from s0 on, or None; the
+    pointers of its bounds, None for an absent one). A chunk's slices are views of the call's arrays, which this object keeps alive."""
+
+    def __init__(self, masks, nq: int, what: str, per: str):
+        self.nq = nq
+        self.table = None if masks is None else _mask_table(masks, nq, what, per)
+        self.bounds = ()
+
+    def bound(self, values, on_dev: bool, device: int):
+        """values: (None or a scalar or one value per query, numpy dtype) per bound, in the C call's order"""
+        self.bounds = [None if v is None else _bound(v, dt, (self.nq,), on_dev, device) for v, dt in values]
+
+    def at(self, s0: int, m: int, ptr):
+        part = self.bounds if m == self.nq else [None if b is None else b[s0:s0 + m] for b in self.bounds]
+        return None if self.table is None else self.table.ctypes.data + 8 * s0, [None if b is None else ptr(b) for b in part]
+
+
 def _check_group_args(grouping, k, group_size) -> int:
     """group_size of a call that may carry a grouping, checked (ValueError / IcdError) before anything else happens"""
     group_size = int(group_size)
@@ -755,37 +774,40 @@ class IcdIndex:
             if table.nq != nq:
                 raise ValueError(f"the boost table holds {table.nq} entries for {nq} queries")
             boost_h, boost_w = table.handles, table.weights
-        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the calls below)
+        bands = _Bands(masks, nq, f"{nq} queries", "query")
         a_sc, a_id = (None, None) if after is None else after
         if (a_sc is None) != (a_id is None):
             raise ValueError("after = (scores, ids): both or neither")
-        bounds = [None if v is None else _bound(v, dt, (nq,), on_dev, self.device)
-                  for v, dt in ((radius, np.float32), (range_filter, np.float32), (a_sc, np.float32), (a_id, np.int64))]
+        bands.bound(((radius, np.float32), (range_filter, np.float32), (a_sc, np.float32), (a_id, np.int64)), on_dev, self.device)
 
         def call(qs, s0):
             m = qs.shape[0]
             (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, self.device, (m, k), (np.float64, np.float32, np.int64, np.int32))
             if m:
-                part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
-                tail = (ptr(qs), m, k, dev, *[None if b is None else ptr(b) for b in part], dev, 1 if reweighted else 0,
+                p_mask, p_bounds = bands.at(s0, m, ptr)
+                tail = (ptr(qs), m, k, dev, *p_bounds, dev, 1 if reweighted else 0,
                         ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), dev, stream)
                 if boost is not None:
                     _check(self._lib, self._lib.icd_index_search_boosted(
-                        self._h, boost[0]._h, None if mask_h is None else mask_h.ctypes.data + 8 * s0,
+                        self._h, boost[0]._h, p_mask,
                         boost_h.ctypes.data + 8 * MAX_BOOSTS * s0, boost_w.ctypes.data + 4 * MAX_BOOSTS * s0, *tail))
-                elif mask_h is None:
+                elif p_mask is None:
                     _check(self._lib, self._lib.icd_index_search_range(self._h, *tail))
                 else:
-                    _check(self._lib, self._lib.icd_index_search_masked(self._h, mask_h.ctypes.data + 8 * s0, *tail))
+                    _check(self._lib, self._lib.icd_index_search_masked(self._h, p_mask, *tail))
             return (adj, raw, ids, lv) if reweighted else (raw, ids, lv)
         return _chunked(q, step, on_dev, call)
+
+    def _workspace(self, cls, size):
+        """a sized workspace of this index (IcdBoost, IcdMmr, IcdByRows, IcdFusion)"""
+        if self.closed:
+            raise IcdError(-5, "index is closed")
+        return cls(self, int(size))
 
     # -- boosted search (Milvus 2.6's boost ranker: rows inside a mask count `weight` times as much, before the top-k is chosen) --
     def boost_workspace(self, max_nq: Optional[int] = None) -> "IcdBoost":
         """The workspace of this index's boosted searches (icd_boost_create) for calls of up to max_nq queries (default: the index's)."""
-        if self.closed:
-            raise IcdError(-5, "index is closed")
-        return IcdBoost(self, int(max_nq if max_nq is not None else self.max_nq))
+        return self._workspace(IcdBoost, max_nq if max_nq is not None else self.max_nq)
 
     def search_boosted(self, queries, k: int, boosts, masks=None, *, workspace: "IcdBoost", reweighted: bool = True, radius=None,
                        range_filter=None, after=None):
@@ -803,9 +825,7 @@ class IcdIndex:
     # -- MMR search (a diverse top-k: LangChain's max_marginal_relevance_search on the device) -------------
     def mmr(self, max_nq: Optional[int] = None) -> "IcdMmr":
         """The workspace of this index's MMR searches (icd_mmr_create) for calls of up to max_nq queries (default: the index's)."""
-        if self.closed:
-            raise IcdError(-5, "index is closed")
-        return IcdMmr(self, int(max_nq if max_nq is not None else self.max_nq))
+        return self._workspace(IcdMmr, max_nq if max_nq is not None else self.max_nq)
 
     def search_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float, *, mmr: "IcdMmr", masks=None, radius=None, range_filter=None,
                    reweighted: bool = True, on_device: bool = False):
@@ -829,8 +849,8 @@ class IcdIndex:
             raise ValueError(f"lambda_mult={lambda_mult}: the relevance weight lies in [0, 1]")
         out_dev = bool(on_device) or q_dev
         nq = int(q.shape[0])
-        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")   # (kept alive over the calls below)
-        bounds = [None if v is None else _bound(v, np.float32, (nq,), q_dev, self.device) for v in (radius, range_filter)]
+        bands = _Bands(masks, nq, f"{nq} queries", "query")
+        bands.bound(((radius, np.float32), (range_filter, np.float32)), q_dev, self.device)
 
         def call(qs, s0):
             m = qs.shape[0]
@@ -838,11 +858,11 @@ class IcdIndex:
             if m:
                 if q_dev and stream is None:
                     stream = _current_stream_ptr(self.device)
-                part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
                 qptr = _dev_ptr if q_dev else _host_ptr
+                p_mask, p_bounds = bands.at(s0, m, qptr)
                 _check(self._lib, self._lib.icd_index_search_mmr(
-                    self._h, mmr._h, None if mask_h is None else mask_h.ctypes.data + 8 * s0, qptr(qs), m, k, fetch_k, lam, 1 if q_dev else 0,
-                    *[None if b is None else qptr(b) for b in part], 1 if q_dev else 0, 1 if reweighted else 0,
+                    self._h, mmr._h, p_mask, qptr(qs), m, k, fetch_k, lam, 1 if q_dev else 0,
+                    *p_bounds, 1 if q_dev else 0, 1 if reweighted else 0,
                     ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(mv), dev, stream))
             return (adj, raw, ids, lv, mv) if reweighted else (raw, ids, lv, mv)
         outs = _chunked(q, min(self.max_nq, mmr.max_nq), out_dev, call)
@@ -851,9 +871,7 @@ class IcdIndex:
     # -- search by stored rows (Milvus's search by primary key: a stored row is the query) ----------------
     def byrows(self, max_nq: Optional[int] = None) -> "IcdByRows":
         """The workspace of this index's searches by rows (icd_byrows_create) for calls of up to max_nq ids (default: the index's)."""
-        if self.closed:
-            raise IcdError(-5, "index is closed")
-        return IcdByRows(self, int(max_nq if max_nq is not None else self.max_nq))
+        return self._workspace(IcdByRows, max_nq if max_nq is not None else self.max_nq)
 
     def search_by_rows(self, ids, k: int, *, workspace: "IcdByRows", masks=None, radius=None, range_filter=None, include_self: bool = False,
                        reweighted: bool = True, on_device: bool = False):
@@ -882,8 +900,8 @@ class IcdIndex:
             raise ValueError(f"k={k}: need 1 <= k <= {top} (the search runs at k + 1 unless include_self)")
         out_dev = bool(on_device) or ids_dev
         nq = int(rows.shape[0])
-        mask_h = None if masks is None else _mask_table(masks, nq, f"{nq} ids", "id")   # (kept alive over the calls below)
-        bounds = [None if v is None else _bound(v, np.float32, (nq,), ids_dev, self.device) for v in (radius, range_filter)]
+        bands = _Bands(masks, nq, f"{nq} ids", "id")
+        bands.bound(((radius, np.float32), (range_filter, np.float32)), ids_dev, self.device)
 
         def call(rs, s0):
             m = rs.shape[0]
@@ -891,11 +909,11 @@ class IcdIndex:
             if m:
                 if ids_dev and stream is None:
                     stream = _current_stream_ptr(self.device)
-                part = bounds if m == nq else [None if b is None else b[s0:s0 + m] for b in bounds]   # (kept alive over the call)
                 iptr = _dev_ptr if ids_dev else _host_ptr
+                p_mask, p_bounds = bands.at(s0, m, iptr)
                 _check(self._lib, self._lib.icd_index_search_by_rows(
-                    self._h, workspace._h, None if mask_h is None else mask_h.ctypes.data + 8 * s0, iptr(rs), m, k, 1 if ids_dev else 0,
-                    1 if include_self else 0, *[None if b is None else iptr(b) for b in part], 1 if ids_dev else 0,
+                    self._h, workspace._h, p_mask, iptr(rs), m, k, 1 if ids_dev else 0,
+                    1 if include_self else 0, *p_bounds, 1 if ids_dev else 0,
                     1 if reweighted else 0, ptr(adj) if reweighted else None, ptr(raw), ptr(oid), ptr(lv), dev, stream))
             return (adj, raw, oid, lv) if reweighted else (raw, oid, lv)
         return _chunked(rows, min(self.max_nq, workspace.max_nq), out_dev, call)
@@ -903,9 +921,7 @@ class IcdIndex:
     # -- hybrid search (Milvus hybrid_search over dense requests) -----------------------------------------
     def fusion(self, max_total: int) -> "IcdFusion":
         """The workspace of this index's hybrid searches (icd_fusion_create) for calls of up to max_total = nq * R sub-lists."""
-        if self.closed:
-            raise IcdError(-5, "index is closed")
-        return IcdFusion(self, int(max_total))
+        return self._workspace(IcdFusion, max_total)
 
     def search_hybrid(self, queries, limits, k: int, fusion: "IcdFusion", *, ranker: str = "rrf", rrf_c: float = 60.0, weights=None,
                       norm: str = "none", masks=None, radius=None, range_filter=None, mode: int = MODE_AUTO, reweighted: bool = True,
@@ -1344,81 +1360,52 @@ class IcdGrouping(_Handle):
         return {"groups": g.value, "largest_group": m.value, "bytes": b.value}
 
 
-class IcdFusion(_Handle):
+class _Workspace(_Handle):
+    """A sized workspace of one IcdIndex behind icd_<_prefix>_create / _stats / _destroy. A subclass names the prefix, the noun of
+    its closed message and the key its size goes by - in stats() and as the attribute that holds it (max_nq or max_total)."""
+    _prefix = _noun = _size_key = ""
+
+    def __init__(self, index: "IcdIndex", size: int):
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        setattr(self, self._size_key, int(size))
+        _check(self._lib, getattr(self._lib, f"icd_{self._prefix}_create")(index._h, int(size), C.byref(self._h)))
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, f"{self._noun} is closed")
+        t, b = C.c_int64(), C.c_int64()
+        _check(self._lib, getattr(self._lib, f"icd_{self._prefix}_stats")(self._h, C.byref(t), C.byref(b)))
+        return {self._size_key: t.value, "bytes": b.value}
+
+
+class IcdFusion(_Workspace):
     """The workspace of one IcdIndex's hybrid searches (icd_fusion_*): staging for max_total = nq * R sub-lists of 128 hits and
     for host callers. Independent of the index's lifetime: either may be closed first (a search with a closed partner raises)."""
-    _destroy = "icd_fusion_destroy"
+    _prefix, _noun, _size_key, _destroy = "fusion", "fusion", "max_total", "icd_fusion_destroy"
 
     def __init__(self, index: "IcdIndex", max_total: int):
-        self._lib = index._lib
-        self._h = C.c_void_p()
-        self.max_total, self.device = int(max_total), index.device
-        _check(self._lib, self._lib.icd_fusion_create(index._h, self.max_total, C.byref(self._h)))
-
-    def stats(self) -> dict:
-        if self.closed:
-            raise IcdError(-5, "fusion is closed")
-        t, b = C.c_int64(), C.c_int64()
-        _check(self._lib, self._lib.icd_fusion_stats(self._h, C.byref(t), C.byref(b)))
-        return {"max_total": t.value, "bytes": b.value}
+        super().__init__(index, max_total)
+        self.device = index.device
 
 
-class IcdMmr(_Handle):
+class IcdMmr(_Workspace):
     """The workspace of one IcdIndex's MMR searches (icd_mmr_*): the staging of max_nq candidate lists of 128 hits and of a host
     caller's outputs."""
-    _destroy = "icd_mmr_destroy"
-
-    def __init__(self, index: "IcdIndex", max_nq: int):
-        self._lib = index._lib
-        self._h = C.c_void_p()
-        self.max_nq = int(max_nq)
-        _check(self._lib, self._lib.icd_mmr_create(index._h, self.max_nq, C.byref(self._h)))
-
-    def stats(self) -> dict:
-        if self.closed:
-            raise IcdError(-5, "mmr workspace is closed")
-        t, b = C.c_int64(0), C.c_int64(0)
-        _check(self._lib, self._lib.icd_mmr_stats(self._h, C.byref(t), C.byref(b)))
-        return {"max_nq": t.value, "bytes": b.value}
+    _prefix, _noun, _size_key, _destroy = "mmr", "mmr workspace", "max_nq", "icd_mmr_destroy"
 
 
-class IcdByRows(_Handle):
+class IcdByRows(_Workspace):
     """The workspace of one IcdIndex's searches by rows (icd_byrows_*): the query block the rows are gathered into, the
     (k + 1)-wide lists of max_nq queries and a host caller's ids and outputs. Independent of the index's lifetime: either may be
     closed first (a search with a closed partner raises)."""
-    _destroy = "icd_byrows_destroy"
-
-    def __init__(self, index: "IcdIndex", max_nq: int):
-        self._lib = index._lib
-        self._h = C.c_void_p()
-        self.max_nq = int(max_nq)
-        _check(self._lib, self._lib.icd_byrows_create(index._h, self.max_nq, C.byref(self._h)))
-
-    def stats(self) -> dict:
-        if self.closed:
-            raise IcdError(-5, "by-rows workspace is closed")
-        t, b = C.c_int64(0), C.c_int64(0)
-        _check(self._lib, self._lib.icd_byrows_stats(self._h, C.byref(t), C.byref(b)))
-        return {"max_nq": t.value, "bytes": b.value}
+    _prefix, _noun, _size_key, _destroy = "byrows", "by-rows workspace", "max_nq", "icd_byrows_destroy"
 
 
-class IcdBoost(_Handle):
+class IcdBoost(_Workspace):
     """The workspace of one IcdIndex's boosted searches (icd_boost_*): the staging of a call's per-query boost table. The owning
     index must outlive its use; close() (or garbage collection) frees it."""
-    _destroy = "icd_boost_destroy"
-
-    def __init__(self, index: "IcdIndex", max_nq: int):
-        self._lib = index._lib
-        self._h = C.c_void_p()
-        self.max_nq = int(max_nq)
-        _check(self._lib, self._lib.icd_boost_create(index._h, self.max_nq, C.byref(self._h)))
-
-    def stats(self) -> dict:
-        if self.closed:
-            raise IcdError(-5, "boost workspace is closed")
-        t, b = C.c_int64(), C.c_int64()
-        _check(self._lib, self._lib.icd_boost_stats(self._h, C.byref(t), C.byref(b)))
-        return {"max_nq": t.value, "bytes": b.value}
+    _prefix, _noun, _size_key, _destroy = "boost", "boost workspace", "max_nq", "icd_boost_destroy"
 
 
 def sparse_tile_rows() -> int:

@@ -21,6 +21,7 @@ device), cached per (normalised expression, store generation) with LRU eviction 
 """
 from __future__ import annotations
 
+import contextlib
 import datetime
 import logging
 import os
@@ -104,15 +105,9 @@ class MilvusService:
         # grouping search: (field, store generation, normalised filter or None) -> (the index or view it belongs to, IcdGrouping)
         self._groupings: "OrderedDict[tuple, Any]" = OrderedDict()
         self._max_groupings = max(1, int(os.getenv("ICD_GROUPINGS", "16")))
-        # hybrid search: (the index it belongs to, IcdFusion, store generation); one handle, regrown when a call needs more
-        # sub-lists, dropped where the views and masks are
-        self._fusion = None
-        # MMR search: (the index it belongs to, IcdMmr, store generation); one handle, regrown like the fusion, dropped with it
-        self._mmr = None
-        # boosted search: (the index it belongs to, IcdBoost, store generation); one handle, regrown and dropped like the MMR's
-        self._boost = None
-        # search by stored ids: (the index it belongs to, IcdByRows, store generation); one handle, regrown and dropped like the MMR's
-        self._byrows = None
+        # hybrid, MMR, boosted and by-ids search: kind (_WORKSPACES) -> (the index it belongs to, its workspace handle, store
+        # generation); one handle per kind, regrown when a call needs more room, dropped where the views and masks are
+        self._workspaces: Dict[str, Any] = {}
         self._code_rows = None     # ((store, generation, rows), code -> first row): similar_codes' lookup, rebuilt when the store moves on
         # sparse search: (the index it belongs to, IcdSparse, SparseTextIndex, field, store generation); built lazily, one handle
         self._sparse = None
@@ -266,6 +261,10 @@ class MilvusService:
             self._load_collection_to_memory()
         return self._index
 
+    def _live_index(self):
+        """the store's ready index; None without a client or a collection"""
+        return self._ready_index() if self.client is not None and self.client.exists() else None
+
     # ---- filtered search ------------------------------------------------------------------------------------------------
     def _clear_views(self):
         with self._views_lock:
@@ -273,11 +272,24 @@ class MilvusService:
             self._groupings.clear()
             self._masks.clear()
             self._dev_columns = None
-            self._fusion = None
-            self._mmr = None
-            self._boost = None
-            self._byrows = None
+            self._workspaces.clear()
             self._sparse = None
+
+    # kind -> (the IcdIndex method that makes one, the attribute of the handle that holds its size)
+    _WORKSPACES = {"fusion": ("fusion", "max_total"), "mmr": ("mmr", "max_nq"), "boost": ("boost_workspace", "max_nq"), "byrows": ("byrows", "max_nq")}
+
+    def _workspace_for(self, kind: str, index, need: int):
+        """the cached workspace of `kind` of `index` (the store's, or a view) with room for `need` queries, ids or sub-lists: one per
+        kind, kept while the index, the store generation and the handle hold and it is large enough, else made anew"""
+        gen = self.client.generation
+        make, size = self._WORKSPACES[kind]
+        with self._views_lock:
+            hit = self._workspaces.get(kind)
+            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and getattr(hit[1], size) >= need:
+                return hit[1]
+            ws = getattr(index, make)(min(index.max_nq, max(int(need), 64)))
+            self._workspaces[kind] = (index, ws, gen)
+        return ws
 
     # ---- grouping search (Milvus group_by_field / group_size) -------------------------------------------------------------
     def _grouping(self, field: str, index, rows, filter_key):
@@ -285,17 +297,21 @@ class MilvusService:
         filter_key and whose rows are `rows` (the view then gets the parent's group ids restricted to them). Cached per
         (field, store generation, filter) and dropped where the views are."""
         ids, values = self._filter_columns().group_ids(field)
-        ck = (field, self.client.generation, filter_key)
+        return self._cached_grouping((field, self.client.generation, filter_key), index, lambda: ids if filter_key is None else ids[rows]), values
+
+    def _cached_grouping(self, key, index, make):
+        """the IcdGrouping of `index` cached under `key`, now the most recently used; a missing one - or one of another index, or a
+        closed one - is built from make() (the group id of every row of `index`) and the least recently used ones are evicted"""
         with self._views_lock:
-            hit = self._groupings.get(ck)
+            hit = self._groupings.get(key)
             if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
-                self._groupings.move_to_end(ck)
-                return hit[1], values
-            grouping = index.grouping(ids if filter_key is None else ids[rows], max_nq=min(index.max_nq, 2048))
-            self._groupings[ck] = (index, grouping)
+                self._groupings.move_to_end(key)
+                return hit[1]
+            grouping = index.grouping(make(), max_nq=min(index.max_nq, 2048))
+            self._groupings[key] = (index, grouping)
             while len(self._groupings) > self._max_groupings:
                 self._groupings.popitem(last=False)
-        return grouping, values
+        return grouping
 
     def groupings(self) -> List[Dict[str, Any]]:
         """the cached groupings, least recently used first: field, filter (normalised, None: the whole store), groups, rows of the
@@ -312,6 +328,32 @@ class MilvusService:
         return out
 
     _check_scorer = staticmethod(filter_expr.check_group_scorer)
+
+    # ---- argument checks the entry points share: none needs a store or a device ------------------------------------------------
+    @staticmethod
+    def _int_in(v, lo=None, hi=None) -> bool:
+        """True for an int or a numpy integer - never a bool - with lo <= v <= hi (a bound of None is open)"""
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and (lo is None or v >= lo) and (hi is None or v <= hi)
+
+    @staticmethod
+    def _one_filter(filter, message: str):   # noqa: A002
+        """ValueError(message) for a list of filters where an entry point takes one expression"""
+        if isinstance(filter, (list, tuple)):
+            raise ValueError(message)
+
+    def _filter_list(self, filters):
+        """the filters of a query / count / facet batch as _masks_for takes them (_query_expr each); ValueError when not a list"""
+        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
+            raise ValueError("filters: a list of filter expressions")
+        return [self._query_expr(e) for e in filters]
+
+    @staticmethod
+    def _batch_size(query_vectors):
+        """(shape, nq) of a batch [nq, dim] or of one vector; ValueError on any other rank"""
+        shape = np.shape(query_vectors)
+        if len(shape) not in (1, 2):
+            raise ValueError("query_vectors: [nq, dim] (or one vector)")
+        return shape, 1 if len(shape) == 1 else int(shape[0])
 
     def _search_grouped(self, index, rows, filter, query_vectors, top_k: int, field: str, group_size: int, group_scorer=None):   # noqa: A002
         """(adj, raw, ids, levels, group values' ids, values) of a grouped search on the store's index or a filter's view; with a
@@ -342,7 +384,7 @@ class MilvusService:
     @staticmethod
     def _check_list_args(lists, top_k, group_by_field, filter, scorer):   # noqa: A002
         """the checks of an embedding-list search that need no store and no device; returns the lists as float32 [T, dim] arrays"""
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= filter_expr.MAX_GROUPED_HITS:
+        if not MilvusService._int_in(top_k, 1, filter_expr.MAX_GROUPED_HITS):
             raise ValueError(f"top_k={top_k!r}: must be an integer in 1 .. {filter_expr.MAX_GROUPED_HITS}")
         if group_by_field is not None:
             filter_expr.check_grouping(group_by_field, top_k, 1)
@@ -367,18 +409,8 @@ class MilvusService:
         id is the row's id in the store (values None). Cached and dropped where the groupings are."""
         if field is not None:
             return self._grouping(field, index, rows, filter_key)
-        ck = (None, self.client.generation, filter_key)
-        with self._views_lock:
-            hit = self._groupings.get(ck)
-            if hit is not None and hit[0] is index and not index.closed and not hit[1].closed:
-                self._groupings.move_to_end(ck)
-                return hit[1], None
-            grouping = index.grouping(np.arange(index.n, dtype=np.int32) if filter_key is None else np.asarray(rows, np.int32),
-                                      max_nq=min(index.max_nq, 2048))
-            self._groupings[ck] = (index, grouping)
-            while len(self._groupings) > self._max_groupings:
-                self._groupings.popitem(last=False)
-        return grouping, None
+        own = lambda: np.arange(index.n, dtype=np.int32) if filter_key is None else np.asarray(rows, np.int32)   # noqa: E731
+        return self._cached_grouping((None, self.client.generation, filter_key), index, own), None
 
     def search_embedding_lists_batch(self, lists, top_k: int = 10, group_by_field: Optional[str] = None,
                                      filter: Optional[str] = None, scorer: str = "sum") -> List[List[Dict[str, Any]]]:   # noqa: A002
@@ -551,6 +583,26 @@ class MilvusService:
         for m_ in masks or ():
             if m_ is not None and getattr(m_, "transient", False):
                 m_.close()
+
+    @contextlib.contextmanager
+    def _released(self, masks):
+        """`masks` for the length of a block, released (_release_masks) when it ends, returned or raised. The list is read at
+        the end: a mask appended to it meanwhile is released with the others."""
+        try:
+            yield masks
+        finally:
+            self._release_masks(masks)
+
+    def _leased_masks(self, index, filter, nq: int):   # noqa: A002
+        """with ... as masks: the masks of a call's filter (_masks_for; None for no filter), released when the block ends"""
+        return self._released(None if filter is None else self._masks_for(index, filter, nq))
+
+    @staticmethod
+    def _sync_if_device(index, out):
+        """wait for the index's device if `out` is a device tensor: the search's own masks are closed next, it has to have run"""
+        if hasattr(out, "cpu"):
+            import torch
+            torch.cuda.synchronize(index.device)
 
     # ---- filter programs (any boolean shape on the device; DESIGN.md section 18) ---------------------------------------------------
     FILTER_ON_DEVICE = True   # False: section 17's two shapes keep section 17's call, every other expression takes the host route (tests compare the routes' bits)
@@ -725,7 +777,7 @@ class MilvusService:
     @classmethod
     def _query_window(cls, limit, offset):
         for name, v, least in (("limit", limit, 1), ("offset", offset, 0)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+            if not cls._int_in(v, least):
                 raise ValueError(f"{name}={v!r}: an int >= {least}")
         if int(offset) + int(limit) > cls.QUERY_WINDOW:
             raise ValueError(f"offset + limit = {int(offset) + int(limit)} exceeds {cls.QUERY_WINDOW}")
@@ -757,9 +809,7 @@ class MilvusService:
         entry: a list of row lists. All masks come from ONE _masks_for call (one filter_masks launch for every device program of the
         batch, equal expressions share a mask), all rows from ONE select_rows call. with_totals: (lists, totals) - the number of
         rows every filter selects, counted by the same call."""
-        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
-            raise ValueError("filters: a list of filter expressions")
-        exprs = [self._query_expr(e) for e in filters]
+        exprs = self._filter_list(filters)
         nq = len(exprs)
         fields = self._query_fields(output_fields)
         offs = list(offset) if isinstance(offset, (list, tuple, np.ndarray)) else [offset] * nq
@@ -767,31 +817,23 @@ class MilvusService:
             raise ValueError(f"offset holds {len(offs)} entries for {nq} filters")
         offs = [self._query_window(limit, o)[1] for o in offs] if nq else []
         limit = self._query_window(limit, 0)[0]
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         if index is None or nq == 0:
             return ([[] for _ in exprs], [0] * nq) if with_totals else [[] for _ in exprs]
-        masks = self._masks_for(index, exprs, nq)
-        try:
+        with self._leased_masks(index, exprs, nq) as masks:
             ids, total, taken = self._select_rows(index, masks, limit, np.asarray(offs, np.int64))
-        finally:
-            self._release_masks(masks)
         lists = [self._rows_to_dicts(ids[q, :int(taken[q])], fields) for q in range(nq)]
         return (lists, [int(t) for t in total]) if with_totals else lists
 
     def count_batch(self, filters) -> List[int]:
         """the number of rows every filter of the list selects: one _masks_for call, one count pass over the masks"""
-        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
-            raise ValueError("filters: a list of filter expressions")
-        exprs = [self._query_expr(e) for e in filters]
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        exprs = self._filter_list(filters)
+        index = self._live_index()
         if index is None or not exprs:
             return [0] * len(exprs)
-        masks = self._masks_for(index, exprs, len(exprs))
-        try:
-            step = index.max_nq
+        step = index.max_nq
+        with self._leased_masks(index, exprs, len(exprs)) as masks:
             total = np.concatenate([index.count_rows(masks[s:s + step]) for s in range(0, len(masks), step)])
-        finally:
-            self._release_masks(masks)
         return [int(t) for t in total]
 
     def count(self, filter: str = "") -> int:   # noqa: A002
@@ -801,13 +843,13 @@ class MilvusService:
     # ---- facet counts (the terms aggregation over a filter's rows) ---------------------------------------------
     # How the rows a filter selects spread over the values of a field: the masks of _masks_for and the whole-store grouping of
     # _grouping, read together on the device (_native.IcdIndex.group_counts). Additive like the scalar query: bad arguments raise.
-    @staticmethod
-    def _facet_args(field, limit, min_count):
+    @classmethod
+    def _facet_args(cls, field, limit, min_count):
         if not isinstance(field, str) or field not in filter_expr.GROUP_FIELDS:
             raise ValueError(f"field={field!r}: not one of {', '.join(filter_expr.GROUP_FIELDS)}")
-        if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1):
+        if limit is not None and not cls._int_in(limit, 1):
             raise ValueError(f"limit={limit!r}: None or an int >= 1")
-        if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or min_count < 0:
+        if not cls._int_in(min_count, 0):
             raise ValueError(f"min_count={min_count!r}: an int >= 0")
         return None if limit is None else int(limit), int(min_count)
 
@@ -819,20 +861,15 @@ class MilvusService:
         call per max_nq masks. with_totals: (lists, totals) - the rows every filter selects, the sum of its counts before the cut.
         An empty or unloaded collection answers []. Bad arguments raise ValueError."""
         limit, min_count = self._facet_args(field, limit, min_count)
-        if isinstance(filters, str) or not isinstance(filters, (list, tuple)):
-            raise ValueError("filters: a list of filter expressions")
-        exprs = [self._query_expr(e) for e in filters]
+        exprs = self._filter_list(filters)
         nq = len(exprs)
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         if index is None or nq == 0:
             return ([[] for _ in exprs], [0] * nq) if with_totals else [[] for _ in exprs]
         grouping, values = self._grouping(field, index, None, None)
-        masks = self._masks_for(index, exprs, nq)
-        try:
-            step = index.max_nq
+        step = index.max_nq
+        with self._leased_masks(index, exprs, nq) as masks:
             counts = np.concatenate([index.group_counts(masks[s:s + step], grouping) for s in range(0, nq, step)])
-        finally:
-            self._release_masks(masks)
         lists = []
         for row in counts:
             order = np.argsort(-row.astype(np.int64), kind="stable")   # (stable: equal counts keep the values' order)
@@ -847,12 +884,12 @@ class MilvusService:
     def get(self, ids, output_fields=None) -> List[Dict[str, Any]]:
         """MilvusClient.get: the rows with these ids, in the order asked for; unknown ids are left out. Host only."""
         fields = self._query_fields(output_fields)
-        if isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+        if self._int_in(ids):
             ids = [ids]
         if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple, np.ndarray)):
             raise ValueError("ids: an int or a list of ints")
         for i in ids:
-            if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+            if not self._int_in(i):
                 raise ValueError(f"ids: {i!r} is not an int")
         if self.client is None or not self.client.exists():
             return []
@@ -894,7 +931,7 @@ class MilvusService:
 
     @staticmethod
     def _query_offset(offset) -> int:
-        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
+        if not MilvusService._int_in(offset, 0):
             raise ValueError(f"offset={offset!r}: an int >= 0")
         return int(offset)
 
@@ -905,11 +942,11 @@ class MilvusService:
         batch_size <= 16384. Bad arguments raise ValueError."""
         expr = self._query_expr(filter)
         fields = self._query_fields(output_fields)
-        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 1 <= batch_size <= self.QUERY_WINDOW:
+        if not self._int_in(batch_size, 1, self.QUERY_WINDOW):
             raise ValueError(f"batch_size={batch_size!r}: an int in 1 .. {self.QUERY_WINDOW}")
-        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or (limit < 0 and limit != -1):
+        if not self._int_in(limit, -1):
             raise ValueError("limit must be -1 (no limit) or a non-negative integer")
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         mask = None if index is None or expr is None else self._masks_for(index, [expr], 1)[0]
         client = self.client
         return QueryIterator(self, index, mask, int(batch_size), int(limit), fields, int(_start),
@@ -950,8 +987,7 @@ class MilvusService:
         radius, range_filter, offset, banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         if filter_mode not in self.FILTER_MODES:
             raise ValueError(f"filter_mode={filter_mode!r}: one of {self.FILTER_MODES}")
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_batch")
+        self._one_filter(filter, "a list of filters needs a batch: one expression (or None) per query of search_batch")
         masked = filter is not None and filter_mode == "mask"   # (a bad expression is logged below and gives [], as on the view path)
         if masked and group_by_field is not None:
             raise ValueError("filter_mode='mask' cannot be combined with group_by_field")
@@ -960,19 +996,7 @@ class MilvusService:
                 logger.error("集合 %s 不存在", self.collection_name)
                 return []
             rows = None
-            if masked:
-                index = self._ready_index()
-                if index is None:
-                    return []
-                query_vector.tolist  # noqa: B018
-                q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
-                pair = (index, self._masks_for(index, filter, 1))
-                try:
-                    adj, raw, ids, levels = range_search.search_band(pair, q, int(top_k), radius, range_filter, offset)
-                finally:
-                    self._release_masks(pair[1])
-                return self._hits_to_dicts(adj[0], raw[0], ids[0])
-            if filter is not None:
+            if filter is not None and not masked:
                 index, rows = self._filtered_index(filter)
             else:
                 index = self._ready_index()
@@ -982,22 +1006,32 @@ class MilvusService:
             #  an array's values arrive as float32 either way - converting through a Python list cost 35 us of a 130-us call)
             query_vector.tolist  # noqa: B018
             q = np.asarray(query_vector, dtype=np.float32).reshape(1, -1)
-            if group_by_field is not None and group_scorer is not None:
-                adj, raw, ids, levels, groups, values, (gsc, gid) = self._search_grouped(index, rows, filter, q, top_k, group_by_field, group_size,
-                                                                                         group_scorer)
-                hits = self._hits_to_dicts(adj[0], raw[0], ids[0], (group_by_field, groups[0], values))
-                return self._add_group_scores([hits], group_by_field, values, gsc, gid)[0]
-            if group_by_field is not None:
-                adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, q, top_k, group_by_field, group_size)
-                return self._hits_to_dicts(adj[0], raw[0], ids[0], (group_by_field, groups[0], values))
-            if banded:
-                adj, raw, ids, levels = range_search.search_band(index, q, int(top_k), radius, range_filter, offset)
+            band = (radius, range_filter, offset)
+            if masked:
+                out = self._search_masked(index, filter, 1, q, top_k, band)
             else:
-                adj, raw, ids, levels = index.search_reweighted(q, int(top_k))
-            return self._hits_to_dicts(adj[0], raw[0], ids[0])
+                out = self._search_tail(index, rows, filter, q, top_k, group_by_field, group_size, group_scorer, band if banded else None)
+            hits = self._hits_to_dicts(out[0][0], out[1][0], out[2][0], None if group_by_field is None else (group_by_field, out[4][0], out[5]))
+            return hits if group_scorer is None else self._add_group_scores([hits], group_by_field, out[5], *out[6])[0]
         except Exception as exc:
             logger.error("搜索失败: %s", exc)
             return []
+
+    def _search_masked(self, index, filter, nq: int, queries, top_k, band):   # noqa: A002
+        """the masked branch of `search` and `search_batch`: the filter's masks leased around ONE search of the (index, masks) pair
+        under band = (radius, range_filter, offset) -> (adj, raw, ids, levels)"""
+        with self._leased_masks(index, filter, nq) as masks:   # (closing a mask synchronises the device: the search has run)
+            return range_search.search_band((index, masks), queries, int(top_k), *band)
+
+    def _search_tail(self, index, rows, filter, queries, top_k, group_by_field, group_size, group_scorer, band):   # noqa: A002
+        """what `search` and `search_batch` run on the store's index or on a filter's view (`rows`: the view's): the grouped search
+        (_search_grouped's tuple, scored with a group_scorer), the banded one (band = (radius, range_filter, offset), or None) or
+        the plain one -> (adj, raw, ids, levels)"""
+        if group_by_field is not None:
+            return self._search_grouped(index, rows, filter, queries, top_k, group_by_field, group_size, group_scorer)
+        if band is not None:
+            return range_search.search_band(index, queries, int(top_k), *band)
+        return index.search_reweighted(queries, int(top_k))
 
     def _hit_lists(self, adj, raw, ids, group=None, extra=None) -> List[List[Dict[str, Any]]]:
         """as_dicts of a batch: [nq, k] arrays (device tensors are moved to the host) -> one _hits_to_dicts list per query. group:
@@ -1053,8 +1087,7 @@ class MilvusService:
         filter_mode="mask": the pages are those of the filter's row mask on the index itself (the same pages; the iterator keeps
         its own reference to the mask)."""
         radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("search_iterator takes one filter expression")
+        self._one_filter(filter, "search_iterator takes one filter expression")
         masked = self._check_filter_args(filter, filter_mode, None)
         if self.client is None or not self.client.exists():
             index = None
@@ -1107,15 +1140,10 @@ class MilvusService:
         if index is None:
             raise RuntimeError(f"collection {self.collection_name} is empty or missing")
         rows = None
+        band = (radius, range_filter, offset)
         if masked:
-            pair = (index, self._masks_for(index, filter, nq))
-            try:
-                adj, raw, ids, levels = range_search.search_band(pair, query_vectors, int(top_k), radius, range_filter, offset)
-            finally:
-                self._release_masks(pair[1])   # (closing synchronises the device: the search has run)
-            if not as_dicts:
-                return adj, raw, ids, levels
-            return self._hit_lists(adj, raw, ids)
+            adj, raw, ids, levels = self._search_masked(index, filter, nq, query_vectors, top_k, band)
+            return self._hit_lists(adj, raw, ids) if as_dicts else (adj, raw, ids, levels)
         if filter is not None:
             index, rows = self._filtered_index(filter)
             if index is None:   # nothing selected: no device call
@@ -1125,46 +1153,27 @@ class MilvusService:
                 if group_scorer is not None:
                     return empty + (empty[3] - 1, empty[1][:, :int(top_k)], (empty[3] - 1)[:, :int(top_k)])
                 return empty + (empty[3] - 1,)
-        if group_by_field is not None and group_scorer is not None:
-            adj, raw, ids, levels, groups, values, (gsc, gid) = self._search_grouped(index, rows, filter, query_vectors, top_k, group_by_field,
-                                                                                     group_size, group_scorer)
-            if not as_dicts:
-                return adj, raw, ids, levels, groups, gsc, gid
-            return self._add_group_scores(self._hit_lists(adj, raw, ids, (group_by_field, groups, values)), group_by_field, values, gsc, gid)
-        if group_by_field is not None:
-            adj, raw, ids, levels, groups, values = self._search_grouped(index, rows, filter, query_vectors, top_k, group_by_field, group_size)
-            if not as_dicts:
-                return adj, raw, ids, levels, groups
-            return self._hit_lists(adj, raw, ids, (group_by_field, groups, values))
         # (large batches on a corpus of tight families of near-identical rows - ICD sibling codes - are handled inside the
         #  library: a second coarse pass over the queries the first could not certify, and from the next large batch on the
         #  wider partition right away; include/icd_search.h icd_stats.last_second_pass / wide_mode)
-        if banded:
-            adj, raw, ids, levels = range_search.search_band(index, query_vectors, int(top_k), radius, range_filter, offset)
-        else:
-            adj, raw, ids, levels = index.search_reweighted(query_vectors, int(top_k))
+        out = self._search_tail(index, rows, filter, query_vectors, top_k, group_by_field, group_size, group_scorer, band if banded else None)
+        if group_by_field is None:
+            adj, raw, ids, levels = out
+            return self._hit_lists(adj, raw, ids) if as_dicts else (adj, raw, ids, levels)
+        adj, raw, ids, levels, groups, values = out[:6]
+        scores = () if group_scorer is None else tuple(out[6])   # (gsc, gid) of a scored search
         if not as_dicts:
-            return adj, raw, ids, levels
-        return self._hit_lists(adj, raw, ids)
+            return (adj, raw, ids, levels, groups) + scores
+        lists = self._hit_lists(adj, raw, ids, (group_by_field, groups, values))
+        return self._add_group_scores(lists, group_by_field, values, *scores) if scores else lists
 
     # ---- MMR search (a diverse top-k) ---------------------------------------------------------------------------
     MMR_MAX_FETCH = 128   # candidates per query (the hit list's slots)
 
-    def _mmr_for(self, index, nq: int):
-        """the cached IcdMmr of the store's index with room for `nq` queries (per store generation; regrown when short)"""
-        gen = self.client.generation
-        with self._views_lock:
-            hit = self._mmr
-            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_nq >= nq:
-                return hit[1]
-            mmr = index.mmr(min(index.max_nq, max(int(nq), 64)))
-            self._mmr = (index, mmr, gen)
-        return mmr
-
     def _mmr_args(self, top_k, fetch_k, lambda_mult, radius, range_filter, search_params):
         """(top_k, fetch_k or None, lambda, radius, range_filter) checked without a store: ValueError on a bad one"""
         def whole(name, v):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            if not self._int_in(v):
                 raise ValueError(f"{name}={v!r}: an int")
             return int(v)
         top_k = whole("top_k", top_k)
@@ -1195,12 +1204,9 @@ class MilvusService:
         as_dicts=True a list of `search`-shaped hit lists whose hits carry "mmr_score", the value the hit was picked with.
         An empty or unloaded collection answers [] per query ([] hits each). Bad arguments raise ValueError."""
         top_k, fetch_k, lam, radius, range_filter = self._mmr_args(top_k, fetch_k, lambda_mult, radius, range_filter, search_params)
-        shape = np.shape(query_vectors)
-        if len(shape) not in (1, 2):
-            raise ValueError("query_vectors: [nq, dim] (or one vector)")
-        nq = 1 if len(shape) == 1 else int(shape[0])
+        shape, nq = self._batch_size(query_vectors)
         self._check_filter_args(filter, "mask", None, nq)   # (a bad expression raises before anything is loaded)
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         if index is None:
             return [[] for _ in range(nq)]
         if shape[-1] != index.dim:
@@ -1210,15 +1216,11 @@ class MilvusService:
             fetch_k = min(cap, max(20, 4 * top_k))
         if fetch_k > cap or top_k > fetch_k:
             raise ValueError(f"top_k={top_k}, fetch_k={fetch_k}: need top_k <= fetch_k <= {cap} (the store's max k)")
-        masks = None if filter is None else self._masks_for(index, filter, nq)
-        try:
-            adj, raw, ids, levels, mmr = index.search_mmr(query_vectors, top_k, fetch_k, lam, mmr=self._mmr_for(index, nq), masks=masks,
-                                                          radius=radius, range_filter=range_filter, reweighted=True)
-            if masks is not None and hasattr(adj, "cpu"):
-                import torch
-                torch.cuda.synchronize(index.device)   # (transient masks are closed below: the search has to have run)
-        finally:
-            self._release_masks(masks)
+        with self._leased_masks(index, filter, nq) as masks:
+            adj, raw, ids, levels, mmr = index.search_mmr(query_vectors, top_k, fetch_k, lam, mmr=self._workspace_for("mmr", index, nq),
+                                                          masks=masks, radius=radius, range_filter=range_filter, reweighted=True)
+            if masks is not None:
+                self._sync_if_device(index, adj)
         if not as_dicts:
             return adj, raw, ids, levels, mmr
         return self._hit_lists(adj, raw, ids, extra=("mmr_score", mmr))
@@ -1227,8 +1229,7 @@ class MilvusService:
                    filter: Optional[str] = None, radius: Optional[float] = None, range_filter: Optional[float] = None,   # noqa: A002
                    search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
         """the diverse hit list of ONE query (search_mmr_batch): `search`'s dicts in adjusted-score order, "mmr_score" added"""
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_mmr_batch")
+        self._one_filter(filter, "a list of filters needs a batch: one expression (or None) per query of search_mmr_batch")
         q = np.asarray(query_vector, dtype=np.float32)
         if q.ndim != 1:
             raise ValueError("query_vector: one vector")
@@ -1238,20 +1239,9 @@ class MilvusService:
     # ---- search by stored ids (Milvus 2.6's search by primary key) -------------------------------------------
     BY_IDS_MAX_K = 127   # the search runs at top_k + 1: the row's own hit takes a slot of the 128
 
-    def _byrows_for(self, index, nq: int):
-        """the cached IcdByRows of the store's index with room for `nq` ids (per store generation; regrown when short)"""
-        gen = self.client.generation
-        with self._views_lock:
-            hit = self._byrows
-            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_nq >= nq:
-                return hit[1]
-            ws = index.byrows(min(index.max_nq, max(int(nq), 64)))
-            self._byrows = (index, ws, gen)
-        return ws
-
     def _by_ids_args(self, top_k, include_self, radius, range_filter):
         """(top_k, radius, range_filter) checked without a store: ValueError on a bad one"""
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)):
+        if not self._int_in(top_k):
             raise ValueError(f"top_k={top_k!r}: an int")
         top = self.BY_IDS_MAX_K + (1 if include_self else 0)
         if not 1 <= int(top_k) <= top:
@@ -1261,7 +1251,7 @@ class MilvusService:
 
     @staticmethod
     def _id_list(ids) -> np.ndarray:
-        if isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+        if MilvusService._int_in(ids):
             ids = [ids]
         if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple, np.ndarray)):
             raise ValueError("ids: an int or a list of ints")
@@ -1272,15 +1262,11 @@ class MilvusService:
 
     def _search_by_rows(self, index, rows, top_k, filter, nq, radius, range_filter, include_self):   # noqa: A002
         """one library call (chunked by the workspace) with the filter's masks taken and released around it"""
-        masks = None if filter is None else self._masks_for(index, filter, nq)
-        try:
-            out = index.search_by_rows(rows, top_k, workspace=self._byrows_for(index, nq), masks=masks, radius=radius,
+        with self._leased_masks(index, filter, nq) as masks:
+            out = index.search_by_rows(rows, top_k, workspace=self._workspace_for("byrows", index, nq), masks=masks, radius=radius,
                                        range_filter=range_filter, include_self=include_self, reweighted=True)
-            if masks is not None and hasattr(out[0], "cpu"):
-                import torch
-                torch.cuda.synchronize(index.device)   # (transient masks are closed below: the search has to have run)
-        finally:
-            self._release_masks(masks)
+            if masks is not None:
+                self._sync_if_device(index, out[0])
         return out
 
     def search_by_ids(self, ids, top_k: int = 10, filter=None, radius: Optional[float] = None,   # noqa: A002
@@ -1299,7 +1285,7 @@ class MilvusService:
         rows = self._id_list(ids)
         nq = int(rows.size)
         self._check_filter_args(filter, "mask", None, nq)   # (a bad expression raises before anything is loaded)
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         if index is None:
             return [[] for _ in range(nq)]
         bad = rows[(rows < 0) | (rows >= index.n)]
@@ -1317,8 +1303,7 @@ class MilvusService:
         first): `search`'s dicts, the record itself left out. KeyError when the collection holds no such code."""
         if not isinstance(code, str) or not code or '"' in code or "\\" in code:
             raise ValueError("code: a non-empty string without quotes or backslashes")
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("similar_codes takes one filter expression")
+        self._one_filter(filter, "similar_codes takes one filter expression")
         top_k, _, _ = self._by_ids_args(top_k, False, None, None)
         self._check_filter_args(filter, "mask", None, 1)
         row = self._row_of_code(code)
@@ -1347,43 +1332,29 @@ class MilvusService:
         still gets neighbours). reweighted=True: `search`'s adjusted scores and order; False: the raw inner products, best
         first. An empty or unloaded collection answers two [0, top_k] arrays."""
         top_k, _, _ = self._by_ids_args(top_k, False, None, None)
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("knn_graph takes one filter expression")
+        self._one_filter(filter, "knn_graph takes one filter expression")
         self._check_filter_args(filter, "mask", None, 1)
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         if index is None:
             return np.zeros((0, top_k), np.int64), np.zeros((0, top_k), np.float64)
         if top_k + 1 > index.max_k:
             raise ValueError(f"top_k={top_k}: the search runs at {top_k + 1}, above the store's max k {index.max_k}")
         import torch
         n = int(index.n)
-        ws = self._byrows_for(index, min(n, index.max_nq))
+        ws = self._workspace_for("byrows", index, min(n, index.max_nq))
         step = min(ws.max_nq, index.max_nq)
         out_ids, out_scores = np.empty((n, top_k), np.int64), np.empty((n, top_k), np.float64)
-        mask = None if filter is None else self._masks_for(index, filter, 1)[0]
-        try:
+        with self._leased_masks(index, filter, 1) as masks:
+            mask = None if masks is None else masks[0]
             for r0 in range(0, n, step):
                 rows = torch.arange(r0, min(n, r0 + step), dtype=torch.int64, device=torch.device("cuda", index.device))
                 out = index.search_by_rows(rows, top_k, workspace=ws, masks=mask, reweighted=reweighted)
                 scores, hit_ids = (out[0], out[2]) if reweighted else (out[0], out[1])
                 out_ids[r0:r0 + len(rows)] = hit_ids.cpu().numpy()     # (the copy waits for the chunk: a mask is closed behind the loop)
                 out_scores[r0:r0 + len(rows)] = scores.cpu().numpy()
-        finally:
-            self._release_masks([mask])
         return out_ids, out_scores
 
     # ---- boosted search (Milvus 2.6's boost ranker; DESIGN.md section 22) ----------------------------------------------------------
-    def _boost_for(self, index, nq: int):
-        """the cached IcdBoost of the store's index with room for `nq` queries (per store generation; regrown when short)"""
-        gen = self.client.generation
-        with self._views_lock:
-            hit = self._boost
-            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_nq >= nq:
-                return hit[1]
-            ws = index.boost_workspace(min(index.max_nq, max(int(nq), 64)))
-            self._boost = (index, ws, gen)
-        return ws
-
     def _boosted_index(self, index, rankers, filter, nq: int):   # noqa: A002
         """(the BoostedIndex of a batch, every mask it uses): the boost filters and the queries' own filters take ONE _masks_for
         call - device filter programs, TEXT_MATCH masks and the mask cache; equal expressions share a mask. A boost filter that
@@ -1408,7 +1379,7 @@ class MilvusService:
                 row.append((m_, r.weight))
             pairs.append(row)
         masks = made[at:at + len(own)] if own else None
-        return boost_ranker.BoostedIndex(index, self._boost_for(index, nq), pairs, masks), made
+        return boost_ranker.BoostedIndex(index, self._workspace_for("boost", index, nq), pairs, masks), made
 
     def search_boosted_batch(self, query_vectors, top_k: int = 10, boosts=None, as_dicts: bool = False, filter=None,   # noqa: A002
                              radius: Optional[float] = None, range_filter: Optional[float] = None, offset: int = 0,
@@ -1421,28 +1392,21 @@ class MilvusService:
         radius / range_filter / offset / search_params as in `search`, on the boosted score and ranking. Returns (adjusted f64,
         raw f32, ids i64, levels i32), each [nq, top_k], or with as_dicts=True `search`-shaped hit lists. An empty or unloaded
         collection answers [] per query. Bad arguments raise ValueError before anything is loaded."""
-        shape = np.shape(query_vectors)
-        if len(shape) not in (1, 2):
-            raise ValueError("query_vectors: [nq, dim] (or one vector)")
-        nq = 1 if len(shape) == 1 else int(shape[0])
+        shape, nq = self._batch_size(query_vectors)
         rankers = boost_ranker.rankers_per_query(boosts, nq)
         radius, range_filter, offset, _ = self._check_band(top_k, None, radius, range_filter, offset, search_params)
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= range_search.PAGE:
+        if not self._int_in(top_k, 1, range_search.PAGE):
             raise ValueError(f"top_k={top_k!r}: 1 .. {range_search.PAGE}")
         self._check_filter_args(filter, "mask", None, nq)
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         if index is None:
             return [[] for _ in range(nq)]
         if shape[-1] != index.dim:
             raise ValueError(f"query dim {shape[-1]} != index dim {index.dim}")
         bi, made = self._boosted_index(index, rankers, filter, nq)
-        try:
+        with self._released(made):
             adj, raw, ids, levels = range_search.search_band(bi, query_vectors, int(top_k), radius, range_filter, offset)
-            if hasattr(adj, "cpu"):
-                import torch
-                torch.cuda.synchronize(index.device)   # (transient masks are closed below: the search has to have run)
-        finally:
-            self._release_masks(made)
+            self._sync_if_device(index, adj)
         if not as_dicts:
             return adj, raw, ids, levels
         return self._hit_lists(adj, raw, ids)
@@ -1451,8 +1415,7 @@ class MilvusService:
                        radius: Optional[float] = None, range_filter: Optional[float] = None, offset: int = 0,
                        search_params: Optional[Dict[str, Any]] = None) -> List[Dict[str, Any]]:
         """the boosted hit list of ONE query (search_boosted_batch): `search`'s dicts, `original_score` the boosted score"""
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("a list of filters needs a batch: one expression (or None) per query of search_boosted_batch")
+        self._one_filter(filter, "a list of filters needs a batch: one expression (or None) per query of search_boosted_batch")
         q = np.asarray(query_vector, dtype=np.float32)
         if q.ndim != 1:
             raise ValueError("query_vector: one vector")
@@ -1468,11 +1431,10 @@ class MilvusService:
         band, on the filter's selection), pages disjoint and exact at any depth - the cursor is a boosted score and an id. The
         iterator keeps its masks and the store generation it started on."""
         radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("search_boosted_iterator takes one filter expression")
+        self._one_filter(filter, "search_boosted_iterator takes one filter expression")
         rankers = boost_ranker.rankers_per_query(boosts, 1)
         self._check_filter_args(filter, "mask", None, 1)
-        index = self._ready_index() if self.client is not None and self.client.exists() else None
+        index = self._live_index()
         range_search.SearchIterator(None if index is None else index, query_vector, batch_size, limit, radius, range_filter, None,
                                     lambda: None).close()   # (its argument checks, before a mask is made)
         bi = None if index is None else self._boosted_index(index, rankers, filter, 1)[0]
@@ -1481,21 +1443,10 @@ class MilvusService:
                                            lambda: (id(self.client), None if client is None else (client.generation, client.count)))
 
     # ---- hybrid search (Milvus hybrid_search over dense requests) ------------------------------------------
-    def _fusion_for(self, index, total: int):
-        """the cached IcdFusion of the store's index with room for `total` sub-lists (per store generation; regrown when short)"""
-        gen = self.client.generation
-        with self._views_lock:
-            hit = self._fusion
-            if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and hit[1].max_total >= total:
-                return hit[1]
-            fusion = index.fusion(min(index.max_nq, max(int(total), 64)))
-            self._fusion = (index, fusion, gen)
-        return fusion
-
     def fusions(self) -> List[Dict[str, Any]]:
         """the cached hybrid-search workspace (at most one): sub-lists per call, HBM bytes"""
         with self._views_lock:
-            hit = self._fusion
+            hit = self._workspaces.get("fusion")
         if hit is None or hit[1].closed:
             return []
         st = hit[1].stats()
@@ -1568,7 +1519,7 @@ class MilvusService:
             filter_expr.check_grouping(group_by_field, top_k, group_size)
         elif group_size != 1:
             raise ValueError("group_size needs group_by_field")
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 128:
+        if not self._int_in(top_k, 1, 128):
             raise ValueError(f"top_k={top_k!r}: an int in 1 .. 128")
         nq = len(np.asarray(q_off).reshape(-1)) - 1
         if nq < 0:
@@ -1624,9 +1575,8 @@ class MilvusService:
             raise ValueError("group_size needs group_by_field")
         if not isinstance(text, str):
             raise ValueError("text: a string")
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("a list of filters needs a batch: search_sparse_batch")
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= 128:
+        self._one_filter(filter, "a list of filters needs a batch: search_sparse_batch")
+        if not self._int_in(top_k, 1, 128):
             raise ValueError(f"top_k={top_k!r}: an int in 1 .. 128")
         radius, range_filter, offset, _banded = self._check_band(top_k, group_by_field, radius, range_filter, offset, search_params)
         _sp, tx = self._sparse_index()
@@ -1645,12 +1595,11 @@ class MilvusService:
         radius, range_filter = range_search.check_bounds(radius, range_filter, search_params)
         if not isinstance(text, str):
             raise ValueError("text: a string")
-        if isinstance(filter, (list, tuple)):
-            raise ValueError("search_text_iterator takes one filter expression")
+        self._one_filter(filter, "search_text_iterator takes one filter expression")
         if filter is not None:
             filter_expr.compile(filter)
         band, query = None, None
-        if self.client is not None and self.client.exists() and self._ready_index() is not None:
+        if self._live_index() is not None:
             sp, tx = self._sparse_index()
             index = self._index
             query = tx.encode_queries([text])
@@ -1703,7 +1652,7 @@ class MilvusService:
         per = [self._filter_mask(index, r.expr) for r in sparse]
         s_raw, s_ids, _lv = self._sparse_lists(index, sp, *csr, ls, per * nq if any(m is not None for m in per) else None, False)
         put("sparse", s_raw, s_ids, ls)
-        return index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, **self._ranker_kw(ranker)), nq, R
+        return index.fuse_lists(self._workspace_for("fusion", index, nq * R), scores, ids, [r.limit for r in reqs], limit, **self._ranker_kw(ranker)), nq, R
 
     @staticmethod
     def _ranker_kw(ranker):
@@ -1783,7 +1732,7 @@ class MilvusService:
                      np.zeros((nq, kk), np.uint32), np.full((nq, kk), -1, np.int32)), nq, R, values)
         g_target = g_parent if target is index else self._grouping(field, target, rows, fkey)[0]
         if not sparse:
-            out = target.search_hybrid(qd, [r.limit for r in reqs], limit, self._fusion_for(target, nq * R), grouping=g_target, group_size=s, **self._ranker_kw(ranker))
+            out = target.search_hybrid(qd, [r.limit for r in reqs], limit, self._workspace_for("fusion", target, nq * R), grouping=g_target, group_size=s, **self._ranker_kw(ranker))
             return out, nq, R, values
         sp, tx = self._sparse_index()
         scores, ids, put = self._interleave_lists(index, reqs, nq, max(r.limit for r in reqs) * s)
@@ -1797,7 +1746,7 @@ class MilvusService:
         mask = self._filter_mask(index, expr)
         s_raw, s_ids, _lv, _g = self._sparse_lists(index, sp, *csr, ls, None if mask is None else [mask] * (nq * Rs), False, g_parent, s)
         put("sparse", s_raw, s_ids, ls * s)
-        out = index.fuse_lists(self._fusion_for(index, nq * R), scores, ids, [r.limit for r in reqs], limit, grouping=g_parent, group_size=s, **self._ranker_kw(ranker))
+        out = index.fuse_lists(self._workspace_for("fusion", index, nq * R), scores, ids, [r.limit for r in reqs], limit, grouping=g_parent, group_size=s, **self._ranker_kw(ranker))
         return out, nq, R, values
 
     def hybrid_search_batch(self, reqs, ranker, limit: int = 10, as_dicts: bool = False, group_by_field: Optional[str] = None,
@@ -1839,7 +1788,7 @@ class MilvusService:
             lo = np.array([-np.inf if r.radius is None else r.radius for r in reqs], np.float32)
         if any(r.range_filter is not None for r in reqs):
             hi = np.array([np.inf if r.range_filter is None else r.range_filter for r in reqs], np.float32)
-        out = index.search_hybrid(q, [r.limit for r in reqs], limit, self._fusion_for(index, nq * R), masks=masks, radius=lo,
+        out = index.search_hybrid(q, [r.limit for r in reqs], limit, self._workspace_for("fusion", index, nq * R), masks=masks, radius=lo,
                                   range_filter=hi, **self._ranker_kw(ranker))
         if not as_dicts:
             return out

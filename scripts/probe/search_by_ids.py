@@ -101,7 +101,7 @@ def main():
         {"by ids (knn_graph)": lambda: ms.knn_graph(K),
          "host route (host rows -> search_batch at k + 1 -> numpy)": lambda: host_route(ms, corpus, every)},
         lambda: (ms.knn_graph(K)[0], host_route(ms, corpus, every)[0]))
-    print(f"by-rows workspace: {ms._byrows[1].stats()['bytes'] / 2**20:.1f} MiB for {ms._byrows[1].max_nq} ids per call")
+    print(f"by-rows workspace: {ms._workspaces['byrows'][1].stats()['bytes'] / 2**20:.1f} MiB for {ms._workspaces['byrows'][1].max_nq} ids per call")
     ms.disconnect()
 
 

@@ -92,18 +92,16 @@ def check_routes(ms, world):
     # a workspace shorter than the slice: knn_graph walks in chunks, the same bytes
     index = ms._ready_index()
     short = index.byrows(64)
-    with ms._views_lock:
-        kept, ms._byrows = ms._byrows, (index, short, ms.client.generation)
-    real = ms._byrows_for
-    ms._byrows_for = lambda idx, nq: short
+    # (handed out in place of the cache's: the cache itself would regrow a workspace shorter than the n ids knn_graph asks room for)
+    real = ms._workspace_for
+    ms._workspace_for = lambda kind, idx, need: short if kind == "byrows" else real(kind, idx, need)
     try:
+        assert short.max_nq == 64 < world["n"]
         c_ids, c_scores = ms.knn_graph(K)
         assert c_ids.tobytes() == g_ids.tobytes() and c_scores.tobytes() == g_scores.tobytes()
     finally:
-        del ms._byrows_for
-        assert ms._byrows_for.__func__ is real.__func__
-        with ms._views_lock:
-            ms._byrows = kept
+        del ms._workspace_for
+        assert ms._workspace_for.__func__ is real.__func__
         short.close()
     # per-id filters, a TEXT_MATCH one among them; the same id under different filters; a band
     ids = np.array([3, 3, 3, 3, 3, 40, 41, 42, 43, 44, n - 1, 0], np.int64)
