@@ -845,6 +845,47 @@ int icd_index_search_by_rows(icd_index *idx, icd_byrows *ws, icd_rowmask *const 
                              int32_t *out_levels, int32_t out_on_device, void *stream);
 
 /*
+ * Rank-of search: where do given rows land in a query's exact ranking, and with what score? The opposite question to every search
+ * above - for evaluation (recall@k and MRR need the gold row's rank, also past ICD_MAX_K), for "why not this code?", and for
+ * tracking ranks across corpus or model updates. DESIGN.md section 26. Query q carries nt target ids, targets[q][0 .. nt), global
+ * ids as searches return them; a slot holding -1 is padding. Per (query, target):
+ *   rank      the number of rows of masks[q] that stand STRICTLY AHEAD of the target in the ranking icd_index_search_masked
+ *             (reweighted = 0, no band) walks: canonical score descending, the smaller id first among equal scores. If that search
+ *             returns id x at position j, the rank of x is j - for every j below its k and for every row behind. (The reweighted
+ *             form re-sorts the k hits it has: a position in it depends on k and is no rank.)
+ *   raw, adj  the target's canonical score and (double)raw * w[level]: the bits icd_index_search_masked reports for that row.
+ *   level     the target's level.
+ *   no rank   rank -1, raw and adj NaN, level 0: a padding slot, an id outside [id_base, id_base + n), a row outside masks[q].
+ *             A target whose canonical score is NaN has no rank either (no search returns it): rank -1, raw and adj NaN, its level.
+ * Per query: selected, the number of rows masks[q] admits (n without a mask). Rows whose score is NaN are never ahead of
+ * anything. The same target may appear any number of times in a query; each slot is answered.
+ *
+ * icd_rankof_create: the workspace of the rank-of calls of `idx` for up to max_nq queries per call: a host caller's queries, the
+ * targets, their keys and the outputs. Nothing is allocated in a call. The handle keeps no pointer into its index: it is compared,
+ * never followed, and either may be destroyed first. It serves one stream at a time, like the index it belongs to. A view has no
+ * rank-of search (ICD_ERR_UNSUPPORTED: mask the parent), nor has the row-sharded path, nor an index of 2^31 rows or more.
+ *
+ * icd_index_rank_of: two launches on `stream`: rankof_targets_kernel (the targets' canonical scores, keys and levels) and
+ * rankof_sweep_kernel (exact_topk_kernel's sweep with the select replaced by a count: one integer add per work-group, query and
+ * target - the same bytes on every run). queries: [nq][dim], host or (queries_on_device = 1) device. targets: HOST int64 [nq][nt],
+ * 1 <= nt <= ICD_RANKOF_MAX_TARGETS. masks: NULL, or icd_index_search_masked's HOST table of nq entries (NULL entry: every row).
+ * Outputs are HOST arrays, [nq][nt] and out_selected [nq]; every one but out_rank may be NULL. The call synchronises `stream` and
+ * is not graph-capturable (ICD_ERR_INVALID while capturing). Every check comes before the first device call. ICD_ERR_INVALID: nt
+ * out of range, nq above the workspace's max_nq (with masks: above the index's), a workspace or a mask of another index, NULL
+ * arrays. ICD_ERR_STATE: a destroyed index, workspace or mask. ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 does nothing. A
+ * refused call writes no output.
+ */
+#define ICD_RANKOF_MAX_TARGETS 16
+typedef struct icd_rankof icd_rankof;
+int icd_rankof_create(icd_index *idx, int64_t max_nq, icd_rankof **out);
+int icd_rankof_destroy(icd_rankof *ws);
+/* queries per call, device bytes held (either pointer may be NULL) */
+int icd_rankof_stats(icd_rankof *ws, int64_t *out_max_nq, int64_t *out_bytes);
+int icd_index_rank_of(icd_index *idx, icd_rankof *ws, const float *queries, int64_t nq, int32_t queries_on_device,
+                      const int64_t *targets /* host [nq][nt] */, int32_t nt, icd_rowmask *const *masks /* NULL or host [nq] */,
+                      int64_t *out_rank, double *out_adj, float *out_raw, int32_t *out_levels, int64_t *out_selected, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -49,10 +49,12 @@ EXPORTED_SYMBOLS = (
     "icd_mmr_create", "icd_mmr_destroy", "icd_mmr_stats", "icd_index_search_mmr",
     "icd_boost_create", "icd_boost_destroy", "icd_boost_stats", "icd_index_search_boosted",
     "icd_byrows_create", "icd_byrows_destroy", "icd_byrows_stats", "icd_index_search_by_rows",
+    "icd_rankof_create", "icd_rankof_destroy", "icd_rankof_stats", "icd_index_rank_of",
     "icd_grouping_prepare_scorers", "icd_index_search_grouped_scored",
     "icd_grouping_prepare_maxsim", "icd_index_search_maxsim",
 )
 MAXSIM_SCORERS = {"sum": 1, "mean": 2}   # include/icd_search.h ICD_MAXSIM_*: how an embedding list's per-vector maxima combine
+RANKOF_MAX_TARGETS = 16                  # ICD_RANKOF_MAX_TARGETS: targets of one query of a rank-of call
 MAXSIM_MAX_T = 64                        # ICD_MAXSIM_MAX_T: vectors of one list
 GROUP_SCORERS = {"max": 0, "sum": 1, "avg": 2}   # include/icd_search.h ICD_GROUP_SCORER_*: what a group of a grouped search ranks by
 MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
@@ -179,6 +181,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_byrows_destroy.argtypes = [vp]
     lib.icd_byrows_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_by_rows.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.icd_rankof_create.argtypes = [vp, i64, C.POINTER(vp)]
+    lib.icd_rankof_destroy.argtypes = [vp]
+    lib.icd_rankof_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_rank_of.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.icd_boost_create.argtypes = [vp, i64, C.POINTER(vp)]
     lib.icd_boost_destroy.argtypes = [vp]
     lib.icd_boost_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -1400,6 +1406,64 @@ class IcdByRows(_Workspace):
     (k + 1)-wide lists of max_nq queries and a host caller's ids and outputs. Independent of the index's lifetime: either may be
     closed first (a search with a closed partner raises)."""
     _prefix, _noun, _size_key, _destroy = "byrows", "by-rows workspace", "max_nq", "icd_byrows_destroy"
+
+
+class IcdRankOf(_Handle):
+    """The workspace of one IcdIndex's rank-of calls (icd_rankof_*) and the call itself: IcdRankOf(index, max_nq).rank_of(...). It
+    holds a host caller's queries, the targets of max_nq queries, their keys and the outputs. Independent of the index's lifetime:
+    either may be closed first (a call with a closed partner raises). It is made and asked like every sized workspace -
+    _Workspace's own constructor and stats(), not a copy of them."""
+    _prefix, _noun, _size_key, _destroy = "rankof", "rank-of workspace", "max_nq", "icd_rankof_destroy"
+    stats = _Workspace.stats
+
+    def __init__(self, index: "IcdIndex", max_nq: Optional[int] = None):
+        if index.closed:
+            raise IcdError(-5, "index is closed")
+        _Workspace.__init__(self, index, index.max_nq if max_nq is None else max_nq)
+        self._index = index
+
+    def rank_of(self, queries, targets, masks=None):
+        """The exact rank of given ids in every query's ranking (icd_index_rank_of). queries: [nq, dim], a numpy array or a torch
+        CUDA tensor; targets: int64 [nq, nt] global ids (or [nq]: one per query), 1 <= nt <= RANKOF_MAX_TARGETS, -1 = padding;
+        masks: None, one IcdRowMask for every query, or nq entries of IcdRowMask or None. Returns numpy arrays (rank i64 [nq, nt],
+        adj f64, raw f32, levels i32, selected i64 [nq]): rank = the rows of the query's mask that stand strictly ahead of the
+        target in search_masked's raw order (score desc, id asc) - the position search_masked(reweighted=False) returns the id
+        at, for any k and past it - adj / raw the bits the search reports for that row, selected the rows the mask admits. No
+        rank (-1, NaN scores): padding, an id outside the index, a row outside its mask; a NaN-scored target has rank -1 too.
+        A batch longer than the workspace's max_nq runs in chunks. The call synchronises."""
+        index = self._index
+        if index.closed or self.closed:
+            raise IcdError(-5, "index or rank-of workspace is closed")
+        q, q_dev = index._prep_queries(queries)
+        if q.ndim != 2 or q.shape[-1] != index.dim:
+            raise ValueError(f"queries must be [nq, {index.dim}], got {tuple(q.shape)}")
+        nq = int(q.shape[0])
+        if _is_torch_tensor(targets):
+            targets = targets.detach().cpu().numpy()
+        tg = np.asarray(targets)
+        if tg.dtype.kind not in "iu":
+            raise ValueError("targets: integer ids")
+        if tg.ndim <= 1:
+            tg = tg.reshape(nq, -1) if nq else tg.reshape(0, 1)
+        tg = np.ascontiguousarray(tg, dtype=np.int64)
+        if tg.ndim != 2 or tg.shape[0] != nq or not (1 <= tg.shape[1] <= RANKOF_MAX_TARGETS):
+            raise ValueError(f"targets must be [{nq}, 1 .. {RANKOF_MAX_TARGETS}], got {tuple(tg.shape)}")
+        nt = int(tg.shape[1])
+        table = None if masks is None else _mask_table(masks, nq, f"{nq} queries", "query")
+        qptr = _dev_ptr if q_dev else _host_ptr
+        stream = _current_stream_ptr(index.device) if q_dev else None
+
+        def call(qs, s0):
+            m = qs.shape[0]
+            rank, adj, raw, lv = (np.empty((m, nt), dt) for dt in (np.int64, np.float64, np.float32, np.int32))
+            sel = np.empty(m, np.int64)
+            if m:
+                _check(self._lib, self._lib.icd_index_rank_of(
+                    index._h, self._h, qptr(qs), m, 1 if q_dev else 0, tg[s0:s0 + m].ctypes.data, nt,
+                    None if table is None else table.ctypes.data + 8 * s0,
+                    rank.ctypes.data, adj.ctypes.data, raw.ctypes.data, lv.ctypes.data, sel.ctypes.data, stream))
+            return rank, adj, raw, lv, sel
+        return _chunked(q, self.max_nq if table is None else min(index.max_nq, self.max_nq), False, call)
 
 
 class IcdBoost(_Workspace):

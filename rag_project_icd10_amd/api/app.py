@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, POST /codes/rank, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -13,12 +13,13 @@ from __future__ import annotations
 import logging
 import os
 from contextlib import asynccontextmanager
-from typing import Optional
+from typing import List, Optional
 
 from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
-from .icd_models import (BoostedQueryRequest, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
+from ..services import rank_of as rank_search
+from .icd_models import (BoostedQueryRequest, CodeRankRequest, CodeRankResult, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
                          HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, SegmentsQueryRequest, SegmentsQueryResponse,
                          SimilarCodesResponse, convert_numpy_types)
 
@@ -377,6 +378,28 @@ async def codes_facets(request: FacetRequest):
     except Exception as exc:
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
     return FacetResponse(field=request.field, total=totals[0], facets=convert_numpy_types(lists[0]))
+
+
+@app.post("/codes/rank", response_model=List[CodeRankResult])
+async def codes_rank(request: CodeRankRequest):
+    """Where given codes land for one text, over the whole collection (services/rank_of.py, RankOf.rank_of): per code its
+    exact rank (0 = best, null where the filter leaves it out), adjusted and raw score, level, and the rows the filter admits. An
+    unknown code is a 404, bad arguments are a 400."""
+    if not embedding_service or not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        if not request.text:
+            raise ValueError("text: a non-empty string")
+        if not 1 <= len(request.codes) <= rank_search.MAX_CODES:
+            raise ValueError(f"codes: {len(request.codes)} codes, need 1 .. {rank_search.MAX_CODES}")
+        results = rank_search.RankOf(milvus_service).rank_of(request.text, list(request.codes), filter=request.filter or None)
+    except KeyError as exc:
+        raise HTTPException(status_code=404, detail=f"no record with code {exc.args[0] if exc.args else ''}")
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    return convert_numpy_types(results)
 
 
 @app.get("/codes/{code}/similar", response_model=SimilarCodesResponse)

@@ -325,6 +325,23 @@ class SimilarCodesResponse(BaseModel):
     candidates: List[Candidate] = Field(default_factory=list, description="the top_k closest codes, the code itself left out: adjusted-score order")
 
 
+class CodeRankRequest(BaseModel):
+    """POST /codes/rank: where given codes land in the exact ranking of one text (services/rank_of.py).
+    The ranges are checked by the route (a 400 with the reason), not by the model."""
+    text: str = Field(..., description="the diagnosis text the codes are ranked for")
+    codes: List[str] = Field(..., description="1 .. 16 codes")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields: the ranking is taken among those rows")
+
+
+class CodeRankResult(BaseModel):
+    code: str
+    rank: Optional[int] = Field(default=None, description="selected rows strictly ahead of the code (0 = best); null: the filter leaves the code out")
+    score: Optional[float] = Field(default=None, description="the level-adjusted score, as /query reports it")
+    raw_score: Optional[float] = Field(default=None, description="the raw inner product")
+    level: int = 0
+    selected: int = Field(..., description="rows the filter admits")
+
+
 class SegmentsQueryRequest(BaseModel):
     """POST /segments_query: the segments of ONE text as an embedding list (MilvusService.search_embedding_list; DESIGN.md section
     25). The ranges are checked by the route (a 400 with the reason), not by the model."""

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import contextlib
 import datetime
+import functools
 import logging
 import os
 import threading
@@ -32,7 +33,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..corpus_store import CorpusStore
-from . import boost_ranker, filter_expr, hybrid_search as hybrid, range_search, sparse_text
+from . import boost_ranker, filter_expr, hybrid_search as hybrid, range_search, rank_of, sparse_text
 
 logger = logging.getLogger(__name__)
 
@@ -277,17 +278,21 @@ class MilvusService:
 
     # kind -> (the IcdIndex method that makes one, the attribute of the handle that holds its size)
     _WORKSPACES = {"fusion": ("fusion", "max_total"), "mmr": ("mmr", "max_nq"), "boost": ("boost_workspace", "max_nq"), "byrows": ("byrows", "max_nq")}
+    # kinds whose workspace is made by a function (index, size) of their own module, not by a method of the index: the same cache,
+    # the same rule
+    _WORKSPACE_FACTORIES = {"rankof": (rank_of.make_workspace, "max_nq")}
 
     def _workspace_for(self, kind: str, index, need: int):
         """the cached workspace of `kind` of `index` (the store's, or a view) with room for `need` queries, ids or sub-lists: one per
         kind, kept while the index, the store generation and the handle hold and it is large enough, else made anew"""
         gen = self.client.generation
-        make, size = self._WORKSPACES[kind]
+        make, size = self._WORKSPACES.get(kind) or self._WORKSPACE_FACTORIES[kind]
+        make = getattr(index, make) if isinstance(make, str) else functools.partial(make, index)
         with self._views_lock:
             hit = self._workspaces.get(kind)
             if hit is not None and hit[0] is index and hit[2] == gen and not index.closed and not hit[1].closed and getattr(hit[1], size) >= need:
                 return hit[1]
-            ws = getattr(index, make)(min(index.max_nq, max(int(need), 64)))
+            ws = make(min(index.max_nq, max(int(need), 64)))
             self._workspaces[kind] = (index, ws, gen)
         return ws
 
