@@ -886,6 +886,55 @@ int icd_index_rank_of(icd_index *idx, icd_rankof *ws, const float *queries, int6
                       int64_t *out_rank, double *out_adj, float *out_raw, int32_t *out_levels, int64_t *out_selected, void *stream);
 
 /*
+ * Wide search: the exact ranks first .. first + k - 1 of every query's ranking, for first + k up to ICD_WIDE_MAX_K, in one call -
+ * a candidate list for a re-ranker, recall@1000, a deep offset, everything above a similarity floor. DESIGN.md section 27. Every
+ * search above stops at ICD_MAX_K hits. The contract, for a query q, its optional row mask masks[q], its optional band
+ * (lo[q], hi[q]) = (radius, range_filter), first >= 0 and k >= 1:
+ *   1. scores   the canonical ones: the fp32 fmaf chain over d ascending from +0.0f, the bits of icd_index_search in MODE_EXACT.
+ *   2. ranking  a row ranks iff the mask admits it, its score is not NaN and lo < score <= hi (plain float compares; an absent
+ *               bound makes no test, so without a radius a score of -inf ranks; a NaN device bound empties the band).
+ *   3. order    score descending, the smaller row first among equal score bits: the order of the exact searches.
+ *   4. raw      (reweighted = 0) ranks first .. first + k - 1 of that ranking, best first: out_raw f32, out_ids i64 (row +
+ *               id_base), out_levels i32, [nq][k]; padding -inf, -1, 0 behind. out_count[q] (i32): the real hits of the slice;
+ *               out_selected[q] (i64): the rows that rank - the total behind the page.
+ *   5. reweighted (reweighted = 1) adj = (double)raw * w[level], ONE stable descending sort of the returned slice (equal adj keeps
+ *               raw order): out_adj f64 and raw, id, level with it; padding -inf, -inf, -1, 0.
+ *   6. at k <= ICD_MAX_K and first = 0 both forms equal icd_index_search_masked / icd_index_search_range at the same k bit for
+ *               bit; at any k they equal the first k entries of the restricted full ranking.
+ *   7. the same bytes come back on every run.
+ *
+ * icd_wide_create: the workspace of the wide searches of `idx` for up to max_nq queries per call and first + k up to max_k: the
+ * score block, the candidate block, the threshold records and a host caller's queries, bounds and outputs. The score and
+ * candidate blocks hold as many queries as fit a fixed byte budget (256 MiB); a longer batch runs block by block inside the call.
+ * Nothing is allocated in a call. The handle keeps no pointer into its index: it is compared, never followed, and either may be
+ * destroyed first. It serves one stream at a time, like the index it belongs to. A view has no wide search (ICD_ERR_UNSUPPORTED:
+ * mask the parent), nor has the row-sharded path, nor an index of 2^31 rows or more, nor one whose single score run exceeds the
+ * budget.
+ *
+ * icd_index_search_wide: per score block four launches on `stream` (wide_scores_kernel, wide_threshold_kernel,
+ * wide_collect_kernel, wide_sort_emit_kernel). queries: [nq][dim], host or (queries_on_device = 1) device. masks: NULL, or
+ * icd_index_search_masked's HOST table of nq entries (NULL entry: every row). lo, hi: NULL (no bound) or [nq], host or
+ * (bounds_on_device = 1) device; host bounds are checked (no NaN, lo < hi). Outputs: [nq][k] and [nq], host or
+ * (outputs_on_device = 1) device; out_adj may be NULL unless reweighted. Device queries, device outputs, device or no bounds and
+ * no mask table: the call only enqueues and is graph-capturable. Anything else is staged on the host or synchronises `stream`
+ * and is refused while capturing (ICD_ERR_INVALID). Every check comes before the first device call. ICD_ERR_INVALID: k or first
+ * out of range, first + k above ICD_WIDE_MAX_K or the workspace's max_k, nq above the workspace's max_nq (with masks: above the
+ * index's), a workspace or a mask of another index, NULL arrays. ICD_ERR_STATE: a destroyed index, workspace or mask.
+ * ICD_ERR_UNSUPPORTED: a view as `idx`. nq = 0 does nothing. A refused call writes no output.
+ */
+#define ICD_WIDE_MAX_K 16384
+typedef struct icd_wide icd_wide;
+int icd_wide_create(icd_index *idx, int64_t max_nq, int32_t max_k, icd_wide **out);
+int icd_wide_destroy(icd_wide *ws);
+/* queries per call, first + k per call, device bytes held (any pointer may be NULL) */
+int icd_wide_stats(icd_wide *ws, int64_t *out_max_nq, int64_t *out_max_k, int64_t *out_bytes);
+int icd_index_search_wide(icd_index *idx, icd_wide *ws, icd_rowmask *const *masks /* NULL or host [nq] */, const float *queries,
+                          int64_t nq, int32_t k, int32_t first, int32_t queries_on_device, const float *lo /* NULL or [nq] */,
+                          const float *hi /* NULL or [nq] */, int32_t bounds_on_device, int32_t reweighted, double *out_adj,
+                          float *out_raw, int64_t *out_ids, int32_t *out_levels, int32_t *out_count, int64_t *out_selected,
+                          int32_t outputs_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -50,11 +50,13 @@ EXPORTED_SYMBOLS = (
     "icd_boost_create", "icd_boost_destroy", "icd_boost_stats", "icd_index_search_boosted",
     "icd_byrows_create", "icd_byrows_destroy", "icd_byrows_stats", "icd_index_search_by_rows",
     "icd_rankof_create", "icd_rankof_destroy", "icd_rankof_stats", "icd_index_rank_of",
+    "icd_wide_create", "icd_wide_destroy", "icd_wide_stats", "icd_index_search_wide",
     "icd_grouping_prepare_scorers", "icd_index_search_grouped_scored",
     "icd_grouping_prepare_maxsim", "icd_index_search_maxsim",
 )
 MAXSIM_SCORERS = {"sum": 1, "mean": 2}   # include/icd_search.h ICD_MAXSIM_*: how an embedding list's per-vector maxima combine
 RANKOF_MAX_TARGETS = 16                  # ICD_RANKOF_MAX_TARGETS: targets of one query of a rank-of call
+WIDE_MAX_K = 16384                       # ICD_WIDE_MAX_K: first + k of one wide search
 MAXSIM_MAX_T = 64                        # ICD_MAXSIM_MAX_T: vectors of one list
 GROUP_SCORERS = {"max": 0, "sum": 1, "avg": 2}   # include/icd_search.h ICD_GROUP_SCORER_*: what a group of a grouped search ranks by
 MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
@@ -185,6 +187,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_rankof_destroy.argtypes = [vp]
     lib.icd_rankof_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_rank_of.argtypes = [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.icd_wide_create.argtypes = [vp, i64, i32, C.POINTER(vp)]
+    lib.icd_wide_destroy.argtypes = [vp]
+    lib.icd_wide_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_index_search_wide.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.icd_boost_create.argtypes = [vp, i64, C.POINTER(vp)]
     lib.icd_boost_destroy.argtypes = [vp]
     lib.icd_boost_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -1464,6 +1470,67 @@ class IcdRankOf(_Handle):
                     rank.ctypes.data, adj.ctypes.data, raw.ctypes.data, lv.ctypes.data, sel.ctypes.data, stream))
             return rank, adj, raw, lv, sel
         return _chunked(q, self.max_nq if table is None else min(index.max_nq, self.max_nq), False, call)
+
+
+class IcdWide(_Handle):
+    """The workspace of one IcdIndex's wide searches (icd_wide_*) and the call itself: IcdWide(index, max_nq, max_k).search_wide(...).
+    It holds the score block, the candidate block, the threshold records and a host caller's queries, bounds and outputs for calls
+    of up to max_nq queries and first + k up to max_k. Independent of the index's lifetime: either may be closed first (a call
+    with a closed partner raises). IcdIndex's public surface is recorded and stays as it is, so - as with IcdRankOf - workspace
+    and call stand beside it."""
+    _destroy = "icd_wide_destroy"
+
+    def __init__(self, index: "IcdIndex", max_nq: Optional[int] = None, max_k: int = WIDE_MAX_K):
+        if index.closed:
+            raise IcdError(-5, "index is closed")
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        self.max_nq = int(index.max_nq if max_nq is None else max_nq)
+        self.max_k = int(max_k)
+        _check(self._lib, self._lib.icd_wide_create(index._h, self.max_nq, self.max_k, C.byref(self._h)))
+        self._index = index
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "wide-search workspace is closed")
+        q, k, b = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_wide_stats(self._h, C.byref(q), C.byref(k), C.byref(b)))
+        return {"max_nq": q.value, "max_k": k.value, "bytes": b.value}
+
+    def search_wide(self, queries, k: int, *, masks=None, radius=None, range_filter=None, first: int = 0, reweighted: bool = True):
+        """Ranks first .. first + k - 1 of every query's exact ranking, first + k <= WIDE_MAX_K (icd_index_search_wide). queries:
+        [nq, dim], a numpy array or a torch CUDA tensor; masks: None, one IcdRowMask for every query, or nq entries of IcdRowMask
+        or None; radius / range_filter: None, a scalar or one value per query (radius < score <= range_filter). Returns
+        (adj f64, raw f32, ids i64, levels i32) [nq, k], count i32 [nq] and selected i64 [nq]: reweighted=True in
+        search_reweighted's order (level weight, one stable re-sort of the slice); False: adj is None and the rest is in raw order
+        (score desc, id asc). Padding: -inf, id -1, level 0. count: the real hits of the slice; selected: the rows that rank
+        (mask, band, no NaN) - the total behind the page. Numpy in -> numpy out; device tensors in -> device tensors out on
+        torch's current stream. A batch longer than the workspace's max_nq runs in chunks."""
+        index = self._index
+        if index.closed or self.closed:
+            raise IcdError(-5, "index or wide-search workspace is closed")
+        q, on_dev = index._prep_queries(queries)
+        if q.ndim != 2 or q.shape[-1] != index.dim:
+            raise ValueError(f"queries must be [nq, {index.dim}], got {tuple(q.shape)}")
+        k, first = int(k), int(first)
+        if k < 1 or first < 0 or first + k > WIDE_MAX_K:
+            raise ValueError(f"k={k}, first={first}: need k >= 1, first >= 0 and first + k <= {WIDE_MAX_K}")
+        nq = int(q.shape[0])
+        bands = _Bands(masks, nq, f"{nq} queries", "query")
+        bands.bound(((radius, np.float32), (range_filter, np.float32)), on_dev, index.device)
+
+        def call(qs, s0):
+            m = qs.shape[0]
+            (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, index.device, (m, k), (np.float64, np.float32, np.int64, np.int32))
+            (count, sel), _p, _s, _d = _outputs(on_dev, index.device, (m,), (np.int32, np.int64))
+            if m:
+                p_mask, (p_lo, p_hi) = bands.at(s0, m, ptr)
+                _check(self._lib, self._lib.icd_index_search_wide(
+                    index._h, self._h, p_mask, ptr(qs), m, k, first, dev, p_lo, p_hi, dev, 1 if reweighted else 0,
+                    ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(count), ptr(sel), dev, stream))
+            return (adj, raw, ids, lv, count, sel)
+        out = _chunked(q, self.max_nq if bands.table is None else min(index.max_nq, self.max_nq), on_dev, call)
+        return out if reweighted else (None,) + tuple(out[1:])
 
 
 class IcdBoost(_Workspace):

@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, POST /codes/rank, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, POST /codes/rank, POST /wide_query, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -15,13 +15,15 @@ import os
 from contextlib import asynccontextmanager
 from typing import List, Optional
 
+import numpy as np
 from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
 from ..services import rank_of as rank_search
+from ..services import wide_search
 from .icd_models import (BoostedQueryRequest, CodeRankRequest, CodeRankResult, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
                          HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, SegmentsQueryRequest, SegmentsQueryResponse,
-                         SimilarCodesResponse, convert_numpy_types)
+                         SimilarCodesResponse, WideQueryRequest, WideQueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
 
@@ -400,6 +402,27 @@ async def codes_rank(request: CodeRankRequest):
     except Exception as exc:
         raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
     return convert_numpy_types(results)
+
+
+@app.post("/wide_query", response_model=WideQueryResponse)
+async def wide_query(request: WideQueryRequest):
+    """The exact top_k candidates of one text for top_k up to 16 384, in one device call (services/wide_search.py,
+    WideSearch.search_wide_batch), and `total`, the rows that rank inside the filter and the band. Bad
+    arguments are a 400."""
+    if not embedding_service or not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        if not request.text:
+            raise ValueError("text: a non-empty string")
+        vector = np.asarray(embedding_service.encode_query(request.text), dtype=np.float32).reshape(1, -1)
+        lists, totals = wide_search.WideSearch(milvus_service).search_wide_batch(
+            vector, request.top_k, filter=request.filter or None, radius=request.radius, range_filter=request.range_filter,
+            offset=request.offset, as_dicts=True, with_totals=True)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    return WideQueryResponse(candidates=convert_numpy_types(lists[0]), total=int(totals[0]))
 
 
 @app.get("/codes/{code}/similar", response_model=SimilarCodesResponse)

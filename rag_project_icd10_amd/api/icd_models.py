@@ -342,6 +342,22 @@ class CodeRankResult(BaseModel):
     selected: int = Field(..., description="rows the filter admits")
 
 
+class WideQueryRequest(BaseModel):
+    """POST /wide_query: the exact top_k candidates of one text for top_k up to 16 384 (services/wide_search.py; DESIGN.md section
+    27). The ranges are checked by the route (a 400 with the reason), not by the model."""
+    text: str = Field(..., description="the diagnosis text")
+    top_k: int = Field(default=1000, description="candidates returned (1 .. 16384, offset + top_k <= 16384)")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields: only those rows rank")
+    radius: Optional[float] = Field(default=None, description="only rows with raw score > radius rank")
+    range_filter: Optional[float] = Field(default=None, description="only rows with raw score <= range_filter rank")
+    offset: int = Field(default=0, description="ranks skipped in front of the candidates")
+
+
+class WideQueryResponse(BaseModel):
+    candidates: List[Dict[str, Any]] = Field(..., description="`/query`-shaped candidates: code, title, score, original_score, metadata")
+    total: int = Field(..., description="rows that rank: inside the filter and the band")
+
+
 class SegmentsQueryRequest(BaseModel):
     """POST /segments_query: the segments of ONE text as an embedding list (MilvusService.search_embedding_list; DESIGN.md section
     25). The ranges are checked by the route (a 400 with the reason), not by the model."""
