@@ -935,6 +935,67 @@ int icd_index_search_wide(icd_index *idx, icd_wide *ws, icd_rowmask *const *mask
                           int32_t outputs_on_device, void *stream);
 
 /*
+ * Recommend search: rank every row by a request's positive and negative examples - "more like these, less like those" - exact
+ * over the whole index, in one call. DESIGN.md section 28. A request has P positive and N negative examples, positives first;
+ * list order matters; 1 <= P + N <= ICD_RECOMMEND_MAX_EXAMPLES. An example is a stored row (example_rows[e] in [0, n)) or a
+ * caller's vector of dim floats (example_rows[e] = -1: example_vectors[e]). s(e, i) is the canonical score of example vector e
+ * and row i: the fp32 fmaf chain over d ascending from +0.0f. The combined score c(i) of a request:
+ *   ICD_RECOMMEND_BEST_SCORE      bp = the largest positive-example score, folded in list order from -inf by plain compares
+ *                                 (bp = s if s > bp), bn the same over the negatives; c = bp if bp > bn, else -(bn * bn): one
+ *                                 fp32 multiply, then the sign flip.
+ *   ICD_RECOMMEND_SUM_SCORES      acc = +0.0f; acc = acc + s over the positives in list order, then acc = acc - s over the
+ *                                 negatives in list order; plain fp32 adds, nothing reassociated.
+ *   ICD_RECOMMEND_AVERAGE_VECTOR  (P >= 1) one target vector t built on the device: per component mp = the positives summed in
+ *                                 list order from +0.0f, then ONE correctly rounded fp32 divide by (float)P; mn the same over
+ *                                 the negatives; t = mp + (mp - mn) when N > 0, else mp. c(i) = s(t, i).
+ * A row ranks iff the request's mask (if any) admits it, it is not one of the request's stored-row examples (a vector example
+ * excludes nothing; a bit-identical duplicate of an example row still ranks), no example score of the row is NaN, c is not NaN,
+ * and lo < c <= hi (an absent bound makes no test). The ranking is by (c descending, the smaller row first among equal bits).
+ * first, k, the raw and the reweighted form, padding, out_count and out_selected are icd_index_search_wide's, with c in place of
+ * the raw score. The same bytes come back on every run. One stored positive under BEST_SCORE equals icd_index_search_wide of
+ * that row's vector with the row masked out, bit for bit.
+ *
+ * icd_recommend_create: the workspace for calls of up to max_requests requests holding up to max_examples examples in all
+ * (max_requests <= max_examples <= 16 x max_requests) and first + k up to max_k: the example block, its scores, the request
+ * block, the candidate block, the request table and a host caller's vectors, bounds and outputs. The blocks hold as many whole
+ * requests as fit the wide search's byte budget (256 MiB); a longer batch runs block by block inside the call, a request's
+ * examples never straddling two. Nothing is allocated in a call. The handle keeps no pointer into its index and serves one
+ * stream at a time. A view has no recommend search (ICD_ERR_UNSUPPORTED: mask the parent), nor has the row-sharded path, nor an
+ * index of 2^31 rows or more.
+ *
+ * icd_index_recommend: per block six launches on `stream` (recommend_examples_kernel, wide_scores_kernel,
+ * recommend_combine_kernel, wide_threshold_kernel, wide_collect_kernel, wide_sort_emit_kernel). example_rows [ne],
+ * example_off [nr + 1] (from 0) and n_positive [nr] are HOST arrays, checked and staged at call time; example_vectors is NULL (no
+ * example is a vector) or [ne][dim], host or (inputs_on_device = 1) device - the entries of stored examples are not read. masks,
+ * lo, hi, the outputs and their flags: as in icd_index_search_wide, per request. The request table is staged on the host at call
+ * time, so the call is refused while `stream` is capturing (ICD_ERR_INVALID). Every check comes before the first device call; a
+ * refused call writes no output. ICD_ERR_INVALID: an unknown strategy, k or first out of range, first + k above the workspace's
+ * max_k, nr or the examples above the workspace's, a request of 0 or more than 16 examples, n_positive outside the request,
+ * AVERAGE_VECTOR without a positive, a row outside [0, n), a vector example without example_vectors, a workspace or mask of
+ * another index, NULL arrays. nr = 0 does nothing.
+ *
+ * icd_recommend_read_vectors: the first `count` vectors the last block of the last call left in the example block ([count][dim],
+ * to the host; synchronises): under AVERAGE_VECTOR the requests' targets, else the examples' vectors. For tests.
+ */
+#define ICD_RECOMMEND_MAX_EXAMPLES 16
+#define ICD_RECOMMEND_AVERAGE_VECTOR 0
+#define ICD_RECOMMEND_BEST_SCORE 1
+#define ICD_RECOMMEND_SUM_SCORES 2
+typedef struct icd_recommend icd_recommend;
+int icd_recommend_create(icd_index *idx, int64_t max_requests, int64_t max_examples, int32_t max_k, icd_recommend **out);
+int icd_recommend_destroy(icd_recommend *ws);
+/* requests per call, examples per call, first + k per call, device bytes held (any pointer may be NULL) */
+int icd_recommend_stats(icd_recommend *ws, int64_t *out_max_requests, int64_t *out_max_examples, int64_t *out_max_k, int64_t *out_bytes);
+int icd_recommend_read_vectors(icd_recommend *ws, int64_t count, float *out /* host [count][dim] */);
+int icd_index_recommend(icd_index *idx, icd_recommend *ws, icd_rowmask *const *masks /* NULL or host [nr] */,
+                        const int64_t *example_rows /* host [ne] */, const float *example_vectors /* NULL or [ne][dim] */,
+                        const int64_t *example_off /* host [nr + 1] */, const int32_t *n_positive /* host [nr] */, int64_t nr,
+                        int32_t strategy, int32_t k, int32_t first, const float *lo /* NULL or [nr] */, const float *hi /* NULL or [nr] */,
+                        int32_t bounds_on_device, int32_t reweighted, double *out_adj, float *out_raw, int64_t *out_ids,
+                        int32_t *out_levels, int32_t *out_count, int64_t *out_selected, int32_t inputs_on_device,
+                        int32_t outputs_on_device, void *stream);
+
+/*
  * Row-sharded search, step 2: merge `G` best-first lists per query (layout [G][nq][k], as produced by
  * all-gathering the outputs of icd_index_search on every shard, together with the level of every
  * hit) into the global top-k, then reweight + stable re-sort as above. Device pointers only;

@@ -51,12 +51,15 @@ EXPORTED_SYMBOLS = (
     "icd_byrows_create", "icd_byrows_destroy", "icd_byrows_stats", "icd_index_search_by_rows",
     "icd_rankof_create", "icd_rankof_destroy", "icd_rankof_stats", "icd_index_rank_of",
     "icd_wide_create", "icd_wide_destroy", "icd_wide_stats", "icd_index_search_wide",
+    "icd_recommend_create", "icd_recommend_destroy", "icd_recommend_stats", "icd_recommend_read_vectors", "icd_index_recommend",
     "icd_grouping_prepare_scorers", "icd_index_search_grouped_scored",
     "icd_grouping_prepare_maxsim", "icd_index_search_maxsim",
 )
 MAXSIM_SCORERS = {"sum": 1, "mean": 2}   # include/icd_search.h ICD_MAXSIM_*: how an embedding list's per-vector maxima combine
 RANKOF_MAX_TARGETS = 16                  # ICD_RANKOF_MAX_TARGETS: targets of one query of a rank-of call
 WIDE_MAX_K = 16384                       # ICD_WIDE_MAX_K: first + k of one wide search
+RECOMMEND_MAX_EXAMPLES = 16              # ICD_RECOMMEND_MAX_EXAMPLES: positive + negative examples of one request
+RECOMMEND_STRATEGIES = {"average_vector": 0, "best_score": 1, "sum_scores": 2}   # ICD_RECOMMEND_*
 MAXSIM_MAX_T = 64                        # ICD_MAXSIM_MAX_T: vectors of one list
 GROUP_SCORERS = {"max": 0, "sum": 1, "avg": 2}   # include/icd_search.h ICD_GROUP_SCORER_*: what a group of a grouped search ranks by
 MAX_BOOSTS = 4   # include/icd_search.h ICD_MAX_BOOSTS: (row mask, weight) pairs per query of a boosted search
@@ -191,6 +194,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.icd_wide_destroy.argtypes = [vp]
     lib.icd_wide_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.icd_index_search_wide.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.icd_recommend_create.argtypes = [vp, i64, i64, i32, C.POINTER(vp)]
+    lib.icd_recommend_destroy.argtypes = [vp]
+    lib.icd_recommend_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.icd_recommend_read_vectors.argtypes = [vp, i64, vp]
+    lib.icd_index_recommend.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     lib.icd_boost_create.argtypes = [vp, i64, C.POINTER(vp)]
     lib.icd_boost_destroy.argtypes = [vp]
     lib.icd_boost_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
@@ -1531,6 +1539,149 @@ class IcdWide(_Handle):
             return (adj, raw, ids, lv, count, sel)
         out = _chunked(q, self.max_nq if bands.table is None else min(index.max_nq, self.max_nq), on_dev, call)
         return out if reweighted else (None,) + tuple(out[1:])
+
+
+class IcdRecommend(_Handle):
+    """The workspace of one IcdIndex's recommend searches (icd_recommend_*) and the call itself:
+    IcdRecommend(index, max_requests, max_examples, max_k).recommend(...). It holds the example block and its scores, the request
+    block, the candidate block, the request table and a host caller's vectors, bounds and outputs for calls of up to max_requests
+    requests with up to max_examples examples in all (default: 16 per request) and first + k up to max_k. Independent of the
+    index's lifetime: either may be closed first (a call with a closed partner raises). IcdIndex's public surface is recorded and
+    stays as it is, so - as with IcdWide - workspace and call stand beside it."""
+    _destroy = "icd_recommend_destroy"
+
+    def __init__(self, index: "IcdIndex", max_requests: Optional[int] = None, max_examples: Optional[int] = None, max_k: int = 128):
+        if index.closed:
+            raise IcdError(-5, "index is closed")
+        self._lib = index._lib
+        self._h = C.c_void_p()
+        self.max_requests = int(index.max_nq if max_requests is None else max_requests)
+        self.max_examples = int(self.max_requests * RECOMMEND_MAX_EXAMPLES if max_examples is None else max_examples)
+        self.max_k = int(max_k)
+        _check(self._lib, self._lib.icd_recommend_create(index._h, self.max_requests, self.max_examples, self.max_k, C.byref(self._h)))
+        self._index = index
+
+    def stats(self) -> dict:
+        if self.closed:
+            raise IcdError(-5, "recommend workspace is closed")
+        r, e, k, b = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self._lib, self._lib.icd_recommend_stats(self._h, C.byref(r), C.byref(e), C.byref(k), C.byref(b)))
+        return {"max_requests": r.value, "max_examples": e.value, "max_k": k.value, "bytes": b.value}
+
+    def last_vectors(self, count: int) -> np.ndarray:
+        """the first `count` vectors the last call's last block built on the device (icd_recommend_read_vectors): under
+        "average_vector" the requests' targets, else the examples' vectors. float32 [count, dim]; synchronises. For tests."""
+        if self.closed:
+            raise IcdError(-5, "recommend workspace is closed")
+        out = np.empty((int(count), self._index.dim), np.float32)
+        _check(self._lib, self._lib.icd_recommend_read_vectors(self._h, int(count), out.ctypes.data))
+        return out
+
+    def _pack(self, positive, negative):
+        """the requests of a call in the C ABI's form: rows int64 [ne] (a stored example's row, -1 for a vector), off int64
+        [nr + 1], npos int32 [nr], the vector examples by their place in the example order, and whether they are CUDA tensors"""
+        index = self._index
+        positive = list(positive)
+        negative = [()] * len(positive) if negative is None else list(negative)
+        if len(negative) != len(positive):
+            raise ValueError(f"negative holds {len(negative)} entries for {len(positive)} requests")
+        rows, off, npos, vectors, on_dev = [], [0], [], {}, None
+        for r, (pos, neg) in enumerate(zip(positive, negative)):
+            pos, neg = list(pos), list(neg)
+            if not 1 <= len(pos) + len(neg) <= RECOMMEND_MAX_EXAMPLES:
+                raise ValueError(f"request {r} holds {len(pos) + len(neg)} examples: 1 .. {RECOMMEND_MAX_EXAMPLES}")
+            for ex in pos + neg:
+                if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
+                    row = int(ex) - index.id_base
+                    if not 0 <= row < index.n:
+                        raise ValueError(f"request {r}: id {int(ex)} is outside the index")
+                    rows.append(row)
+                    continue
+                dev = _is_torch_tensor(ex) and ex.is_cuda
+                if _is_torch_tensor(ex) and not dev:
+                    ex = ex.detach().numpy()
+                if not dev:
+                    ex = np.asarray(ex, np.float32)
+                if ex.ndim != 1 or ex.shape[0] != index.dim:
+                    raise ValueError(f"request {r}: an example is an int id or a vector of {index.dim} floats, got shape {tuple(ex.shape)}")
+                if on_dev is not None and on_dev != dev:
+                    raise ValueError("example vectors: numpy arrays or CUDA tensors, not both")
+                on_dev = dev
+                vectors[len(rows)] = ex
+                rows.append(-1)
+            off.append(len(rows))
+            npos.append(len(pos))
+        return np.asarray(rows, np.int64), np.asarray(off, np.int64), np.asarray(npos, np.int32), vectors, bool(on_dev)
+
+    def recommend(self, positive, negative, strategy: str, k: int, *, masks=None, radius=None, range_filter=None, first: int = 0,
+                  reweighted: bool = True):
+        """Ranks first .. first + k - 1 of every request's ranking by its examples, first + k <= WIDE_MAX_K (icd_index_recommend;
+        DESIGN.md section 28). positive, negative: one sequence of examples per request (negative may be None: no negatives), 1 ..
+        16 examples a request; an example is an int (a stored id) or a vector of dim floats (a numpy array or a torch CUDA
+        tensor). strategy: "average_vector" (needs a positive), "best_score" or "sum_scores". masks: None, one IcdRowMask for every
+        request, or one entry (IcdRowMask or None) per request; radius / range_filter: None, a scalar or one value per request
+        (radius < combined score <= range_filter). A request's stored examples never rank. Returns (adj f64, raw f32, ids i64,
+        levels i32) [nr, k], count i32 [nr] and selected i64 [nr] as search_wide does, raw being the combined score; reweighted=
+        False: adj is None and the rest is in raw order. Numpy in -> numpy out; example vectors as CUDA tensors -> device tensors
+        out on torch's current stream. A batch above the workspace's sizes runs in chunks of whole requests."""
+        index = self._index
+        if index.closed or self.closed:
+            raise IcdError(-5, "index or recommend workspace is closed")
+        if strategy not in RECOMMEND_STRATEGIES:
+            raise ValueError(f"strategy={strategy!r}: one of {sorted(RECOMMEND_STRATEGIES)}")
+        k, first = int(k), int(first)
+        if k < 1 or first < 0 or first + k > WIDE_MAX_K:
+            raise ValueError(f"k={k}, first={first}: need k >= 1, first >= 0 and first + k <= {WIDE_MAX_K}")
+        rows, off, npos, vectors, on_dev = self._pack(positive, negative)
+        nr = len(npos)
+        if strategy == "average_vector" and nr and int(npos.min()) < 1:
+            raise ValueError("average_vector needs a positive example in every request")
+        bands = _Bands(masks, nr, f"{nr} requests", "request")
+        bands.bound(((radius, np.float32), (range_filter, np.float32)), on_dev, index.device)
+        vec = None
+        if vectors:   # [ne, dim] in the example order; the entries of stored examples are not read
+            if on_dev:
+                import torch
+                vec = torch.zeros((len(rows), index.dim), dtype=torch.float32, device=torch.device("cuda", index.device))
+                at = torch.as_tensor(list(vectors), device=vec.device)
+                vec[at] = torch.stack([v.to(device=vec.device, dtype=torch.float32) for v in vectors.values()])
+            else:
+                vec = np.zeros((len(rows), index.dim), np.float32)
+                vec[list(vectors)] = np.stack(list(vectors.values()))
+        step_r = self.max_requests if bands.table is None else min(index.max_nq, self.max_requests)
+        code = RECOMMEND_STRATEGIES[strategy]
+
+        def call(r0, m):
+            (adj, raw, ids, lv), ptr, stream, dev = _outputs(on_dev, index.device, (m, k), (np.float64, np.float32, np.int64, np.int32))
+            (count, sel), _p, _s, _d = _outputs(on_dev, index.device, (m,), (np.int32, np.int64))
+            if m:
+                e0, e1 = int(off[r0]), int(off[r0 + m])
+                p_mask, (p_lo, p_hi) = bands.at(r0, m, ptr)
+                c_off = np.ascontiguousarray(off[r0:r0 + m + 1] - e0)
+                c_rows, c_npos = np.ascontiguousarray(rows[e0:e1]), np.ascontiguousarray(npos[r0:r0 + m])
+                c_vec = None if vec is None else vec[e0:e1]
+                _check(self._lib, self._lib.icd_index_recommend(
+                    index._h, self._h, p_mask, c_rows.ctypes.data, None if c_vec is None else ptr(c_vec), c_off.ctypes.data, c_npos.ctypes.data, m,
+                    code, k, first, p_lo, p_hi, dev, 1 if reweighted else 0,
+                    ptr(adj) if reweighted else None, ptr(raw), ptr(ids), ptr(lv), ptr(count), ptr(sel), dev, dev, stream))
+            return (adj, raw, ids, lv, count, sel)
+        outs, r0 = [], 0
+        while r0 < nr:   # chunks of whole requests inside the workspace's requests and examples
+            m = 1
+            while r0 + m < nr and m < step_r and off[r0 + m + 1] - off[r0] <= self.max_examples:
+                m += 1
+            outs.append(call(r0, m))
+            r0 += m
+        if not outs:
+            outs = [call(0, 0)]
+        if len(outs) == 1:
+            out = outs[0]
+        elif on_dev:
+            import torch
+            out = tuple(torch.cat([o[i] for o in outs]) for i in range(6))
+        else:
+            out = tuple(np.concatenate([o[i] for o in outs]) for i in range(6))
+        return tuple(out) if reweighted else (None,) + tuple(out[1:])
 
 
 class IcdBoost(_Workspace):

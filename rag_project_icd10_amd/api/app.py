@@ -1,4 +1,4 @@
-"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, POST /codes/rank, POST /wide_query, GET /health, GET /stats, GET /.
+"""FastAPI surface: POST /embed, POST /query, POST /segments_query, POST /hybrid_query, POST /diverse_query, POST /boosted_query, POST /codes/query, POST /codes/facets, GET /codes/{code}, GET /codes/{code}/similar, POST /codes/rank, POST /wide_query, POST /recommend, GET /health, GET /stats, GET /.
 
 Mirrors the reference's main.py for these routes: lifespan-owned service globals (:25-105), `/`
 (:250-258), `/health` (:261-289), `/query` (:292-363: candidates of all matches merged, sorted by score,
@@ -20,9 +20,10 @@ from fastapi import FastAPI, HTTPException
 
 from ..dotenv_lite import load_dotenv
 from ..services import rank_of as rank_search
+from ..services import recommend as recommend_search
 from ..services import wide_search
 from .icd_models import (BoostedQueryRequest, CodeRankRequest, CodeRankResult, DiagnosisMatch, DiverseQueryRequest, EmbeddingRequest, EmbeddingResponse, FacetRequest, FacetResponse, HealthCheckResponse,
-                         HybridQueryRequest, QueryRequest, QueryResponse, ScalarQueryRequest, ScalarQueryResponse, SegmentsQueryRequest, SegmentsQueryResponse,
+                         HybridQueryRequest, QueryRequest, QueryResponse, RecommendRequest, ScalarQueryRequest, ScalarQueryResponse, SegmentsQueryRequest, SegmentsQueryResponse,
                          SimilarCodesResponse, WideQueryRequest, WideQueryResponse, convert_numpy_types)
 
 load_dotenv()   # main.py:11 of the reference; existing environment variables win
@@ -418,6 +419,27 @@ async def wide_query(request: WideQueryRequest):
         lists, totals = wide_search.WideSearch(milvus_service).search_wide_batch(
             vector, request.top_k, filter=request.filter or None, radius=request.radius, range_filter=request.range_filter,
             offset=request.offset, as_dicts=True, with_totals=True)
+    except ValueError as exc:
+        raise HTTPException(status_code=400, detail=str(exc))
+    except Exception as exc:
+        raise HTTPException(status_code=500, detail=f"查询失败: {exc}")
+    return WideQueryResponse(candidates=convert_numpy_types(lists[0]), total=int(totals[0]))
+
+
+@app.post("/recommend", response_model=WideQueryResponse)
+async def recommend(request: RecommendRequest):
+    """The exact top_k candidates by positive and negative examples - stored codes, ids, texts or vectors - under one of three
+    strategies, in one device call (services/recommend.py, Recommend.recommend_batch), and `total`, the rows
+    that rank inside the filter and the band: `/wide_query`'s response shape. An id outside the collection is a 404, bad
+    arguments are a 400."""
+    if not milvus_service:
+        raise HTTPException(status_code=503, detail="服务未就绪")
+    try:
+        lists, totals = recommend_search.Recommend(milvus_service).recommend_batch(
+            [list(request.positive)], [list(request.negative)], request.strategy, request.top_k, filter=request.filter or None,
+            radius=request.radius, range_filter=request.range_filter, offset=request.offset, as_dicts=True, with_totals=True)
+    except KeyError as exc:
+        raise HTTPException(status_code=404, detail=f"no record with id {exc.args[0] if exc.args else ''}")
     except ValueError as exc:
         raise HTTPException(status_code=400, detail=str(exc))
     except Exception as exc:

@@ -358,6 +358,19 @@ class WideQueryResponse(BaseModel):
     total: int = Field(..., description="rows that rank: inside the filter and the band")
 
 
+class RecommendRequest(BaseModel):
+    """POST /recommend: the exact top_k candidates by positive and negative examples (services/recommend.py).
+    The ranges are checked by the route (a 400 with the reason), not by the model."""
+    positive: List[Any] = Field(default_factory=list, description="examples to be close to: stored codes, int ids, texts or vectors")
+    negative: List[Any] = Field(default_factory=list, description="examples to stay away from; positive + negative hold 1 .. 16")
+    strategy: str = Field(default="average_vector", description="'average_vector', 'best_score' or 'sum_scores'")
+    top_k: int = Field(default=10, description="candidates returned (1 .. 16384, offset + top_k <= 16384)")
+    filter: Optional[str] = Field(default=None, description="Milvus filter expression over the scalar fields: only those rows rank")
+    radius: Optional[float] = Field(default=None, description="only rows with combined score > radius rank")
+    range_filter: Optional[float] = Field(default=None, description="only rows with combined score <= range_filter rank")
+    offset: int = Field(default=0, description="ranks skipped in front of the candidates")
+
+
 class SegmentsQueryRequest(BaseModel):
     """POST /segments_query: the segments of ONE text as an embedding list (MilvusService.search_embedding_list; DESIGN.md section
     25). The ranges are checked by the route (a 400 with the reason), not by the model."""

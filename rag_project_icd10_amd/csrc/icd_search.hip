@@ -33,6 +33,7 @@
 #include "byrows_kernel.hpp"
 #include "rankof_kernel.hpp"
 #include "wide_select_kernel.hpp"
+#include "recommend_kernel.hpp"
 #include "hier_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "stream_kernel.hpp"
@@ -1984,5 +1985,6 @@ int icd_index_last_profile(icd_index *idx, icd_profile *out) {
 #include "icd_byrows.hpp"     // search by stored rows: gather, the masked search at k + 1, drop the row's own hit
 #include "icd_rankof.hpp"     // rank-of search: the targets' scores, then a counting sweep
 #include "icd_wide.hpp"       // wide search: ordered scores, radix threshold, ordered collect, sort and emit
+#include "icd_recommend.hpp"  // recommend search: example vectors, the wide sweep over them, the fold, the wide select
 // the small-input sentence encoder (icd_encoder_*): its own file, this translation unit (fail(), HIP_TRY, packed_attention_kernel)
 #include "icd_encoder.hpp"

@@ -33,7 +33,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..corpus_store import CorpusStore
-from . import boost_ranker, filter_expr, hybrid_search as hybrid, range_search, rank_of, sparse_text, wide_search
+from . import boost_ranker, filter_expr, hybrid_search as hybrid, range_search, rank_of, recommend, sparse_text, wide_search
 
 logger = logging.getLogger(__name__)
 
@@ -280,7 +280,8 @@ class MilvusService:
     _WORKSPACES = {"fusion": ("fusion", "max_total"), "mmr": ("mmr", "max_nq"), "boost": ("boost_workspace", "max_nq"), "byrows": ("byrows", "max_nq")}
     # kinds whose workspace is made by a function (index, size) of their own module, not by a method of the index: the same cache,
     # the same rule
-    _WORKSPACE_FACTORIES = {"rankof": (rank_of.make_workspace, "max_nq"), "wide": (wide_search.make_workspace, "max_nq")}
+    _WORKSPACE_FACTORIES = {"rankof": (rank_of.make_workspace, "max_nq"), "wide": (wide_search.make_workspace, "max_nq"),
+                            "recommend": (recommend.make_workspace, "max_requests")}
 
     def _workspace_for(self, kind: str, index, need: int):
         """the cached workspace of `kind` of `index` (the store's, or a view) with room for `need` queries, ids or sub-lists: one per
