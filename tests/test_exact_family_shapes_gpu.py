@@ -240,7 +240,7 @@ def test_general_streaming_form_at_k16_without_the_single_launch(oracle, kind):
 DIM_NQ = 70
 
 
-def _dim_setup(dim, oracle):
+def _dim_setup(dim, oracle, id_base=0):
     n = 700 if dim == 4096 else 2500
     x = unit_rows(n, dim, 40 + dim)
     x[501:560:2] = x[500:560:2]                                     # a block of duplicated rows
@@ -248,7 +248,7 @@ def _dim_setup(dim, oracle):
     q = x[rng.integers(0, n, DIM_NQ - 10)] + (0.3 / np.sqrt(dim)) * rng.standard_normal((DIM_NQ - 10, dim)).astype(np.float32)
     q = np.ascontiguousarray(np.concatenate([x[500:520:2], q]), dtype=np.float32)   # queries 0 .. 9 ARE duplicated rows
     levels = icd_levels(n, dim)
-    s_all, i_all = oracle.flat_ip_topk(x, q, n)
+    s_all, i_all = oracle.flat_ip_topk(x, q, n, id_base=id_base)
     return x, levels, q, s_all, i_all
 
 
