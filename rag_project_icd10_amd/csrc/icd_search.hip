@@ -1237,7 +1237,14 @@ int search_device(icd_index *x, const float *dq, int nq, int k, int mode, const 
     rec(x, 0, s);
     const SearchCtx c = make_search_ctx(x, dq, nq, k, use_fast, o, s, band, mask, boost);
     // (k > 16 needs the 64-entry lists of the streaming kernel, ~0.9 ms per 16 queries: the coarse pass is faster there)
-    if (c.stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE)) return search_tiny(c);
+    const bool tiny = c.stream_ok && nq <= (use_fast ? (k <= 16 ? 16 : 0) : ST_MAX_ACTIVE);
+    if ((tiny || !use_fast) && (x->pol.last_narrow_large || x->pol.p2_eval_pending)) {
+        // every path but search_auto overwrites the counters the last planned search left (search_policy.hpp): judged now or never
+        const bool arrived = !x->capturing && x->h_nflag && x->ev_nflag && hipEventQuery(x->ev_nflag) == hipSuccess;
+        const SearchCounters left = arrived ? search_counters(x->h_nflag) : SearchCounters{};
+        policy_unplanned_search(x->pol, arrived ? &left : nullptr);
+    }
+    if (tiny) return search_tiny(c);
     { const int rcq = stage_host_query(c); if (rcq) return rcq; }
     { const int rcb = stage_host_bands(c); if (rcb) return rcb; }
     if (!band && !use_fast && c.kpx > 32 && x->opt_exact_narrow && nq > ST_MAX_ACTIVE && c.row_tiles >= 64) {

@@ -63,9 +63,15 @@ struct SearchPolicy {
 // pass had to take in a quarter of the queries and certified most of them, the corpus is one of tight families (ICD sibling
 // codes): large batches then start with the second pass's list count (1.5 instead of 2.2 ms per 10 000 queries there; 7 %
 // slower on Gaussian data, which is why it is not the default).
+inline void policy_take_verdicts(SearchPolicy &p, const SearchCounters &c);
 inline void policy_take_counters(SearchPolicy &p, const SearchCounters &c) {
     if (p.sparse_disarmed && c.clean_run < p.sparse_need) p.sparse_need = std::min(p.sparse_need * 2, SPARSE_NEED_MAX);   // an incident
     p.sparse_run_seen = c.clean_run;
+    policy_take_verdicts(p, c);
+}
+
+// ... its two verdicts on the search the counters belong to: was the second pass needed, is the corpus one of families
+inline void policy_take_verdicts(SearchPolicy &p, const SearchCounters &c) {
     if (p.p2_eval_pending) {
         p.p2_clean = c.f0 > PASS2_SKIP ? 0 : std::min(p.p2_clean + 1, 1 << 20);
         p.p2_eval_pending = false;
@@ -78,6 +84,19 @@ inline void policy_take_counters(SearchPolicy &p, const SearchCounters &c) {
         }
         p.last_narrow_large = false;
     }
+}
+
+// A search that is not planned here (MODE_EXACT, a banded search, k above the fast path's, the few-query streaming forms) clears
+// counter [0] and leaves the counters behind itself like every search: whoever reads them next reads ITS zero, not what the last
+// planned search flagged. Unjudged, a narrow large batch followed by one MODE_EXACT or one-query call never switched the index to
+// wide mode, and a narrow re-probe followed by one switched a family corpus OUT of it (20 * 0 <= n). Called before such a search
+// is enqueued: `arrived` the counters in host memory if the last search has completed (they are the planned search's, any
+// unplanned one in between came through here), else nullptr and the two verdicts are dropped. The streaming pair's run length
+// [4] passes through unplanned searches untouched and is taken in by the next planned one.
+inline void policy_unplanned_search(SearchPolicy &p, const SearchCounters *arrived) {
+    if (arrived) policy_take_verdicts(p, *arrived);
+    p.last_narrow_large = false;
+    p.p2_eval_pending = false;
 }
 
 // This search's plan. Every WIDE_REPROBE-th large search in wide mode runs narrow again and decides anew. (Also called while

@@ -6,7 +6,7 @@
 // every 64th wide search narrow; 4 clean searches of at most 24 flagged queries disarm the second pass; 96 clean searches
 // disarm the streaming pair, doubling up to 65536; a second pass applies below 320 first-pass candidates per query) - none
 // is computed from the header's own constants.
-// `search_policy_check GROUP` runs one group (wide, pass2, sparse, capturing, reset); no argument: all of them.
+// `search_policy_check GROUP` runs one group (wide, pass2, sparse, capturing, reset, unplanned); no argument: all of them.
 #include <cstdio>
 #include <cstring>
 
@@ -240,10 +240,69 @@ static void group_reset() {
     }
 }
 
+// a search that does not go through the plan (MODE_EXACT, a one-query call): search_device hands over the counters the last
+// planned search left if they have arrived; the unplanned search then leaves f0 = 0 behind itself
+static void unplanned(SearchPolicy &p, bool arrived, SearchCounters left) { policy_unplanned_search(p, arrived ? &left : nullptr); }
+
+static void group_unplanned() {
+    Knobs kn; Search s; s.nq = 2048; s.cand = 14 * 16;
+    {   // narrow large batch, MODE_EXACT, large batch: the narrow batch's own counters decide, not the zeros behind the exact search
+        SearchPolicy p;
+        search(p, kn, s, {0, 0, 0});
+        CHECK(p.last_narrow_large && p.p2_eval_pending);
+        unplanned(p, true, {2000, 0, 0});
+        CHECK(p.wide_mode && p.wide_runs == 0 && !p.last_narrow_large && !p.p2_eval_pending && p.p2_clean == 0);
+        CHECK(search(p, kn, s, {0, 0, 0}).wide_now && p.wide_mode);
+    }
+    {   // the narrow re-probe of a family corpus, then MODE_EXACT: wide mode stays (it left: 20 * 0 <= n)
+        SearchPolicy p; p.wide_mode = true; p.wide_runs = 63;
+        CHECK(!search(p, kn, s, {0, 0, 0}).wide_now && p.last_narrow_large);
+        unplanned(p, true, {2000, 0, 0});
+        CHECK(p.wide_mode);
+        CHECK(search(p, kn, s, {0, 0, 0}).wide_now && p.wide_mode && p.wide_runs == 65);
+    }
+    {   // ... and a re-probe that certified 95 % leaves it, judged at the unplanned search
+        SearchPolicy p; p.wide_mode = true; p.wide_runs = 63;
+        search(p, kn, s, {0, 0, 0});
+        unplanned(p, true, {102, 0, 0});       // 20 * 102 <= 2048
+        CHECK(!p.wide_mode);
+    }
+    {   // counters that have not arrived (or a capture): both verdicts are dropped, the zeros are never judged
+        SearchPolicy p; p.wide_mode = true; p.wide_runs = 63;
+        search(p, kn, s, {0, 0, 0});
+        unplanned(p, false, {0, 0, 0});
+        CHECK(p.wide_mode && !p.last_narrow_large && !p.p2_eval_pending);
+        CHECK(search(p, kn, s, {0, 0, 0}).wide_now && p.wide_mode && p.p2_clean == 0);
+    }
+    {   // the second pass's clean count: a batch that flagged 25 is not clean because an exact search followed it
+        SearchPolicy p; p.p2_clean = 3;
+        search(p, kn, s, {0, 0, 0});           // (nothing pending before it)
+        CHECK(p.p2_clean == 3);
+        unplanned(p, true, {25, 0, 0});
+        CHECK(p.p2_clean == 0);
+        search(p, kn, s, {0, 0, 0});           // the exact search's zeros: nothing pending, nothing counted
+        CHECK(p.p2_clean == 0 && p.pass2_armed());
+    }
+    {   // the streaming pair's run length is not taken in here (the next planned search does, once)
+        SearchPolicy p; p.sparse_disarmed = true;
+        search(p, kn, s, {0, 0, 96});
+        const int need = p.sparse_need, seen = p.sparse_run_seen;
+        unplanned(p, true, {0, 0, 0});
+        CHECK(p.sparse_need == need && p.sparse_run_seen == seen);
+    }
+    {   // nothing pending: nothing changes
+        SearchPolicy p; p.wide_mode = true; p.wide_runs = 5; p.p2_clean = 2;
+        const SearchPolicy before = p;
+        unplanned(p, true, {0, 0, 0});
+        CHECK(same(p, before));
+    }
+}
+
 int main(int argc, char **argv) {
     const char *only = argc > 1 ? argv[1] : nullptr;
     struct { const char *name; void (*run)(); } groups[] = {
-        {"wide", group_wide}, {"pass2", group_pass2}, {"sparse", group_sparse}, {"capturing", group_capturing}, {"reset", group_reset}};
+        {"wide", group_wide}, {"pass2", group_pass2}, {"sparse", group_sparse}, {"capturing", group_capturing}, {"reset", group_reset},
+        {"unplanned", group_unplanned}};
     int ran = 0;
     for (auto &g : groups)
         if (!only || !strcmp(only, g.name)) { g.run(); ++ran; }

@@ -1,7 +1,8 @@
 """CPU check of the adaptive rules of the AUTO search path (rag_project_icd10_amd/csrc/search_policy.hpp): plain C++ shared
 by search_device and the corpus-shape probe of icd_index_create, compiled here with g++ and run. The checker
 (tests/search_policy_check.cpp) drives the state the way a search does and pins wide mode of large batches, the second
-pass's and the streaming pair's disarm rules, graph capture and the probe's reset; its expected values are literals taken
+pass's and the streaming pair's disarm rules, graph capture, the probe's reset and the searches that are not planned (MODE_EXACT,
+one-query calls) between two planned ones; its expected values are literals taken
 from the rules as the library stated them before they moved into the header."""
 import os
 import subprocess
@@ -18,7 +19,7 @@ def build_checker(out_dir):
     return exe
 
 
-@pytest.mark.parametrize("group", ["wide", "pass2", "sparse", "capturing", "reset"])
+@pytest.mark.parametrize("group", ["wide", "pass2", "sparse", "capturing", "reset", "unplanned"])
 def test_search_policy(tmp_path, group):
     exe = build_checker(tmp_path)
     out = subprocess.run([exe, group], capture_output=True, text=True)
